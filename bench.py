@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """End-to-end throughput bench: audio-seconds per wall-second (RTF^-1) of the text->waveform hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -26,11 +26,16 @@ only collective is the start-up weight broadcast over RCCL.
 Schedules (`--schedule`, default `auto`): consecutive steps may share the GPU on one stream, on two streams (front of step
 k+1 under the decoder of step k) or on two streams with complementary CU masks; `auto` times a few steps of the first two
 during the warm-up and runs the timed region on the faster -- MI355X boxes differ in how they co-schedule two queues (DESIGN.md
-section 6) -- and reports all of them in `config.schedules_ms_per_step`.  `other_configs` (N = 1, after the timed region of the
-default command): short legs (3 warm-up + 5 steps, autotuned, schedule calibrated) of BASELINE.json configs[2..4] and a B = 1 /
-10 s latency point, so that ONE driver run carries all five workloads; the headline fields stay configs[1].  `cpu_baseline` = the UNMODIFIED reference modules on
-the host cores (`kind: "reference"`; from /root/reference, or from oracle/_ref = the same modules as bytecode where only
-that travelled), the oracle port beside it.
+section 6) -- and reports all of them in `config.schedules_ms_per_step`.
+
+A plain run sets up (weights, operand-scale calibration, autotuned set-up step, schedule calibration), warms up, times --steps
+steps and prints the line.  `--full` adds everything else the bench measures or checks: the box fingerprint, per-launch conv
+events in the timed region (`roofline`), the un-overlapped conv classes, host issue and device -> host times, the bitwise
+check against one stream, and for the default config at N = 1 `other_configs` (short legs -- 3 warm-up + 5 steps, autotuned,
+schedule calibrated -- of BASELINE.json configs[2..4], real ragged text and a B = 1 / 10 s latency point; the headline fields
+stay configs[1]) and `cpu_baseline` = the UNMODIFIED reference modules on the host cores (`kind: "reference"`, from
+oracle/_ref = the same modules as bytecode when oracle/make_ref.py has built them), the oracle port beside it.
+`--dump-outputs DIR` writes the waveforms of the last timed step as .npy files; the timed steps draw from a fixed seed.
 """
 import argparse
 import json
@@ -91,6 +96,24 @@ def synthetic_inputs(B, seed):
     lengths = torch.full((B,), N_PHONEMES, dtype=torch.long)
     ref_s = torch.randn(B, 256, generator=g)  # style vector of the reference audio (style encoders run once per speaker)
     return tokens, lengths, noise, durations, ref_s
+
+
+DRAW_SEED = 4321  # torch's global generators, seeded right before the timed steps (their in-step draws; + rank)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what a caller of the timed path received from the last timed step, as float32 .npy files --
+    `waveform.npy` [B, 1, samples] (30.7 MB for 32 x 10 s), or for long-form `waveform_00.npy` ... one per sentence."""
+    import numpy as np
+    waves = {"waveform": out} if torch.is_tensor(out) else {"waveform_%02d" % i: w for i, w in enumerate(out)}
+    nbytes = sum(w.numel() * 4 for w in waves.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d B of outputs exceed the %d B bound" % (nbytes, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, w in waves.items():
+        np.save(os.path.join(path, name + ".npy"), w.detach().float().cpu().numpy())
+    log("outputs of the last timed step written to %s (%d arrays, %d B)" % (path, len(waves), nbytes))
 
 
 T0 = time.time()
@@ -803,13 +826,26 @@ def main():
                          "otherwise)")
     ap.add_argument("--other-configs", choices=["auto", "on", "off"], default="auto",
                     help="short legs of BASELINE.json configs[2..4] + a B = 1 latency point after the timed region (`auto`: "
-                         "on for the default config at N = 1)")
-    ap.add_argument("--no-box-probe", action="store_true", help="skip the box fingerprint / micro-probe (`box` in the line)")
-    ap.add_argument("--detail-out", default="bench_detail.json",
-                    help="side file for the full result object (the printed line is its < 8 KB summary); '' = none")
+                         "on with --full for the default config at N = 1)")
+    ap.add_argument("--no-box-probe", action="store_true", help="skip the box fingerprint / micro-probe (`box` in the line; "
+                                                                 "--full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: box probe, per-launch conv events in the timed region (roofline), "
+                         "un-overlapped conv classes, host issue and device -> host times, the bitwise check against one "
+                         "stream, other_configs and cpu_baseline.  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as float32 DIR/<name>.npy (the "
+                         "waveform batch; long-form: one waveform per sentence); the timed steps draw from a fixed seed")
+    ap.add_argument("--detail-out", default=None,
+                    help="side file for the full result object (the printed line is its < 8 KB summary); '' = none "
+                         "(default: bench_detail.json with --full, none without)")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / reduction path only (gloo on CPU, no "
                                                            "compute): what the CPU tests use to cover the N-rank launch")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.detail_out is None:
+        a.detail_out = "bench_detail.json" if a.full else ""
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: one process per GPU, spawned here (the driver's torch.distributed.run
@@ -874,7 +910,7 @@ def main():
     # micro-probe (matrix-pipe clock, cache-level latencies, weight-stream / HBM bandwidth, workgroup census), taken with
     # the GPU otherwise idle: the line of a run on a box nobody can log into must explain its own per-class conv times.
     box = None
-    if rank == 0 and not a.no_box_probe:
+    if rank == 0 and a.full and not a.no_box_probe:
         from benchdata import boxinfo
         try:
             box = boxinfo.fingerprint(local_rank, probe=True, level=0)
@@ -1076,7 +1112,7 @@ def main():
     lib = _lib.load()
     unoverlapped, front_ms_alone = None, None
     single_name = "single/healthy-CUs" if ("healthy" in active["name"] and "single/healthy-CUs" in sched) else "single"
-    if not longform and single_name in sched and active["name"] != single_name:
+    if a.full and not longform and single_name in sched and active["name"] != single_name:
         chosen = active["name"]
         try:
             active["name"] = single_name
@@ -1104,8 +1140,11 @@ def main():
         active["name"] = chosen
         torch.cuda.synchronize()
     first_chunk_ms.clear()
-    # roofline leg: per-launch HIP events around every split-f16 conv launch, by shape class
-    lib.st2_conv_timing(1)  # C-ABI hook: event pairs inside st2_conv1d_xs itself, so the C++ plans' launches are seen
+    # the draws the timed steps make (ADPM2 step noise, SineGen noise) start from a fixed seed, whatever the calibration above
+    # ran: the same arguments give the same inputs to every timed step (--dump-outputs compares builds output for output)
+    torch.manual_seed(DRAW_SEED + rank)
+    if a.full:  # roofline leg: per-launch HIP events around every split-f16 conv launch, by shape class
+        lib.st2_conv_timing(1)  # C-ABI hook: event pairs inside st2_conv1d_xs itself, so the C++ plans' launches are seen
     torch.cuda.synchronize()
     parallel.barrier()
     t0 = time.perf_counter()
@@ -1124,54 +1163,58 @@ def main():
     else:
         assert out.shape == (B, 1, int(AUDIO_S_PER_UTT * 24000)) and bool(torch.isfinite(out).all())
     ops.check_status()  # raises if a cooperative BiLSTM group timed out or a split-f16 operand left the f16 range
-    # host issue time of one step (outside the timed region): wall time until the call has queued everything, GPU idle
-    # at the start and not waited for
-    host_issue = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        out = step()
-        host_issue.append((time.perf_counter() - t1) * 1e3)
-    torch.cuda.synchronize()
-    # Waveform device -> pinned host memory (reported beside `value`, never part of it -- the boundary hands over
-    # device tensors): one step's output, best of 3.
-    d2h_ms = None
-    try:
-        src = torch.cat([w.reshape(-1) for w in out]) if longform else out
-        host_buf = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
-        ts_d2h = []
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
+    host_issue, d2h_ms, bitwise = [], None, None
+    if a.full:
+        # host issue time of one step (outside the timed region): wall time until the call has queued everything, GPU idle
+        # at the start and not waited for
         for _ in range(3):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            host_buf.copy_(src, non_blocking=True)
-            torch.cuda.synchronize()
-            ts_d2h.append((time.perf_counter() - t1) * 1e3)
-        d2h_ms = min(ts_d2h)
-        del host_buf, src
-    except Exception as e:  # pinned allocation refused: the line goes out without the figure
-        log("D2H measurement skipped: %r" % (e,))
-    fixed.update(_fixed_draws(dev, steps_d, LONGFORM_SENTENCES if longform else None, B))
-    bitwise = _bitwise_vs_single(step, lambda: step(sequential=True))
-    fixed.clear()
-    ops.check_status()
+            out = step()
+            host_issue.append((time.perf_counter() - t1) * 1e3)
+        torch.cuda.synchronize()
+        # Waveform device -> pinned host memory (reported beside `value`, never part of it -- the boundary
+        # hands over device tensors): one step's output, best of 3.
+        try:
+            src = torch.cat([w.reshape(-1) for w in out]) if longform else out
+            host_buf = torch.empty(src.shape, dtype=src.dtype, pin_memory=True)
+            ts_d2h = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                host_buf.copy_(src, non_blocking=True)
+                torch.cuda.synchronize()
+                ts_d2h.append((time.perf_counter() - t1) * 1e3)
+            d2h_ms = min(ts_d2h)
+            del host_buf, src
+        except Exception as e:  # pinned allocation refused: the line goes out without the figure
+            log("D2H measurement skipped: %r" % (e,))
+        fixed.update(_fixed_draws(dev, steps_d, LONGFORM_SENTENCES if longform else None, B))
+        bitwise = _bitwise_vs_single(step, lambda: step(sequential=True))
+        fixed.clear()
+        ops.check_status()
 
     if rank == 0:
-        by_class = _read_conv_classes(lib)
-        roof = roofline(by_class)
-        _attach_unoverlapped(roof, unoverlapped)
-        try:  # the probe's dependent-free MFMA loop on random operands on THIS box: what `peak` is at the clock the chip sustains
-            mf = (box or {}).get("probe", {}).get("mfma", {}).get("random", {})
-            if mf.get("tflops"):
-                roof["ceiling_live"] = {"mfma_tflops_random_operands": mf["tflops"], "clock_ghz": mf.get("clock_ghz"),
-                                        "frac_of_peak": mf["tflops"] / F16S_PRODUCTS / roof["peak"],
-                                        "kernel_frac_of_it": roof["frac"] * roof["peak"] * F16S_PRODUCTS / mf["tflops"]}
-        except Exception as e:  # a report, never in the way of the line
-            log("ceiling_live unavailable: %r" % (e,))
-        roof["conv_ms_per_step_all_classes"] = sum(sum(v) for v in by_class.values()) / max(a.steps, 1)
-        roof["conv_ms_note"] = ("decoder + prosody convs of the timed region; the front's token GEMMs are replayed from its "
-                                "hipGraph there and appear in `unoverlapped.classes` (eager front) only")
-        if front_ms_alone is not None:
-            roof["front_ms_alone"] = round(front_ms_alone, 3)
+        roof = None
+        if a.full:
+            by_class = _read_conv_classes(lib)
+            roof = roofline(by_class)
+            _attach_unoverlapped(roof, unoverlapped)
+            try:  # the probe's dependent-free MFMA loop on random operands on THIS box: what `peak` is at the clock the chip sustains
+                mf = (box or {}).get("probe", {}).get("mfma", {}).get("random", {})
+                if mf.get("tflops"):
+                    roof["ceiling_live"] = {"mfma_tflops_random_operands": mf["tflops"], "clock_ghz": mf.get("clock_ghz"),
+                                            "frac_of_peak": mf["tflops"] / F16S_PRODUCTS / roof["peak"],
+                                            "kernel_frac_of_it": roof["frac"] * roof["peak"] * F16S_PRODUCTS / mf["tflops"]}
+            except Exception as e:  # a report, never in the way of the line
+                log("ceiling_live unavailable: %r" % (e,))
+            roof["conv_ms_per_step_all_classes"] = sum(sum(v) for v in by_class.values()) / max(a.steps, 1)
+            roof["conv_ms_note"] = ("decoder + prosody convs of the timed region; the front's token GEMMs are replayed from its "
+                                    "hipGraph there and appear in `unoverlapped.classes` (eager front) only")
+            if front_ms_alone is not None:
+                roof["front_ms_alone"] = round(front_ms_alone, 3)
         name = active["name"]
         streams = {"single": "1", "two-stream": "2 (front of step k+1 overlaps decoder of step k)",
                    "partitioned": "2 on complementary CU masks (front %d CUs, decoder the rest)" % a.front_cus,
@@ -1202,13 +1245,15 @@ def main():
                                            "chosen": r["chosen_name"],
                                            "ms": {c["name"]: c["ms"] for c in r["candidates"]}} for r in tune_table]),
                        "operand_scales": calibration,
-                       "bitwise_vs_single": bitwise["equal"], "bitwise_check": bitwise,
-                       "plan": _hooks.plan, "lstm": a.lstm, "graphed_front": not a.eager_front,
-                       "host_issue_ms_per_step": None if longform else round(min(host_issue), 3),
-                       "d2h_ms_per_step": None if d2h_ms is None else round(d2h_ms, 3),
-                       "value_with_d2h": None if d2h_ms is None else round(audio_s * world / (dt / a.steps + d2h_ms * 1e-3), 1)},
-            "roofline": roof,
+                       "plan": _hooks.plan, "lstm": a.lstm, "graphed_front": not a.eager_front},
         }
+        if a.full:
+            res["config"].update({
+                "bitwise_vs_single": bitwise["equal"], "bitwise_check": bitwise,
+                "host_issue_ms_per_step": None if longform else round(min(host_issue), 3),
+                "d2h_ms_per_step": None if d2h_ms is None else round(d2h_ms, 3),
+                "value_with_d2h": None if d2h_ms is None else round(audio_s * world / (dt / a.steps + d2h_ms * 1e-3), 1)})
+            res["roofline"] = roof
         if cu_health is not None:
             if box is None:
                 box = {}
@@ -1230,9 +1275,9 @@ def main():
             res["config"]["first_chunk_latency_ms"] = {"mean": sum(first_chunk_ms) / max(len(first_chunk_ms), 1),
                                                        "min": min(first_chunk_ms) if first_chunk_ms else None}
             res["scaling"] = "weak"  # replicas only: a passage is sequential in its style vector
-        if world == 1 and (a.other_configs == "on" or (a.other_configs == "auto" and a.config == "ljspeech")):
+        if world == 1 and (a.other_configs == "on" or (a.other_configs == "auto" and a.full and a.config == "ljspeech")):
             res["other_configs"] = other_configs(a, dev, model, sampler, lf_front, skip=a.config)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(man, sds, cfg)
         _emit(res, a.detail_out)
     if healthy is not None:

@@ -94,7 +94,8 @@ def compact(res, detail_path=None, limit=LIMIT):
             big = [c for c in cls if c.get("total_ms", 0.0) / tot >= 0.02]
             big.sort(key=lambda c: c.get("frac") or 0.0)
             r["unoverlapped"]["lowest_frac_classes"] = [_class_row(c) for c in big[:4]]
-    out["roofline"] = r
+    if "roofline" in res:  # bench.py --full only
+        out["roofline"] = r
     if "cpu_baseline" in res:
         cb = res["cpu_baseline"] or {}
         c = _pick(cb, _CPU_KEEP)
@@ -141,7 +142,8 @@ def compact(res, detail_path=None, limit=LIMIT):
     if len(json.dumps(out)) >= limit:  # last resort: the contract's fields alone, strings cut
         out["config"] = {k: _short(v, 80) if isinstance(v, str) else v for k, v in out["config"].items()
                          if not isinstance(v, (dict, list))}
-        out["roofline"] = _pick(out["roofline"], ("bound", "achieved", "peak", "unit", "frac", "traffic"))
+        if "roofline" in out:
+            out["roofline"] = _pick(out["roofline"], ("bound", "achieved", "peak", "unit", "frac", "traffic"))
     return out
 
 

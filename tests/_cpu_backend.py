@@ -406,10 +406,48 @@ def install():
     return cbs, table
 
 
+_depth = [0]  # cpu_backend() blocks open right now
+_host_classes = {}
+
+
+def _destroy_on_host(e):
+    """Engines made under cpu_backend() hold HOST "device" memory, so they are destroyed through this backend whenever they
+    die.  Torn down through the HIP entry points they would hipFree host pointers and, on a GPU box, leave the runtime's last
+    error set for the next kernel launch of torch or the library to report as its own ("invalid argument")."""
+    if not getattr(e, "h", None):
+        return
+    if _depth[0]:
+        e.lib.st2_destroy(e.h)
+    else:
+        install()
+        try:
+            e.lib.st2_destroy(e.h)
+        finally:
+            _lib.load().st2_debug_set_backend(None, 0)
+    e.h = None
+
+
+def _host_del(self):
+    try:
+        _destroy_on_host(self)
+    except Exception:
+        pass
+
+
 @contextlib.contextmanager
 def cpu_backend():
+    from styletts2_amd import engine
+    before = set(engine.live_engines())
     keep = install()
+    _depth[0] += 1
     try:
         yield keep
     finally:
+        _depth[0] -= 1
+        for e in engine.live_engines():
+            if e not in before and not type(e).__name__.startswith("Host"):
+                cls = type(e)
+                if cls not in _host_classes:
+                    _host_classes[cls] = type("Host" + cls.__name__, (cls,), {"__del__": _host_del})
+                e.__class__ = _host_classes[cls]
         _lib.load().st2_debug_set_backend(None, 0)

@@ -77,3 +77,45 @@ def test_worst_case_still_fits_and_is_strict_json():
 def test_bench_py_prints_through_the_compactor():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "print(json.dumps(res)" not in src and "benchline.dumps(res" in src
+
+
+def test_plain_line_without_roofline():
+    """A plain `bench.py` run (no --full) has no per-launch conv events and so no `roofline`: the line leaves it out and keeps
+    the headline fields as they are."""
+    name, res = FAT[0]
+    res = json.loads(json.dumps(res))
+    for k in ("roofline", "box", "other_configs", "cpu_baseline"):
+        res.pop(k, None)
+    back = _strict(benchline.dumps(res))
+    assert "roofline" not in back and "detail" not in back
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert back[k] == (pytest.approx(res[k], rel=1e-4) if isinstance(res[k], float) else res[k]), k
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: the waveform batch as one array, long-form's per-sentence waveforms as one array each, float32."""
+    import numpy as np
+    import torch
+
+    import bench
+    w = torch.randn(2, 1, 600, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "batch"), w)
+    got = np.load(tmp_path / "batch" / "waveform.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 1, 600) and np.array_equal(got, w.numpy())
+    waves = [torch.randn(n) for n in (500, 700)]
+    bench.dump_outputs(str(tmp_path / "long"), waves)
+    for i, x in enumerate(waves):
+        got = np.load(tmp_path / "long" / ("waveform_%02d.npy" % i))
+        assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    assert sorted(os.listdir(tmp_path / "long")) == ["waveform_00.npy", "waveform_01.npy"]
+
+
+def test_bench_cli_full_dump_outputs_and_steps():
+    import subprocess
+    import sys
+    run = lambda *args: subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(args), capture_output=True,
+                                       text=True, timeout=120)
+    h = run("--help")
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    bad = run("--steps", "0")
+    assert bad.returncode == 2 and "--steps" in bad.stderr

@@ -9,7 +9,7 @@
 #                    busy cycles), tools/bin/xs_bench_{0,1,2,4,8,15} on the shape, per-workgroup timeline (xs_bench_64)
 #   tests[:FILES]    pytest -m gpu (all, or the comma-separated test files)
 #   smoke            __graft_entry__.smoke()
-#   bench[:ARGS]     the driver's command `python bench.py --gpus 1 --steps 20 --warmup 5` (+ comma-separated extra args)
+#   bench[:ARGS]     `python bench.py --full --gpus 1 --steps 20 --warmup 5` (+ comma-separated extra args)
 #   bench_ab         the same without the autotuner (--no-autotune), for the A/B on this box
 #   configs          one short bench line per other configuration (libritts_hifigan, libritts_istftnet, longform)
 #   stats[:SCHED]    rocprofv3 --kernel-trace --stats of a short bench on one schedule (default single): per-kernel table +
@@ -64,10 +64,10 @@ for st in "$@"; do
         [ -n "${ST2_HUNT_KIT:-}" ] && run_slowkit
         bash tools/gpu_visit.sh $TAG bench:--no-cpu-baseline
         # the same box without the healthy-CU streams, and the long-form configuration both ways
-        timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --cu-mask off --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_nomask.json 2> $OUT/${TAG}_bench_nomask.err
+        timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cu-mask off --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_nomask.json 2> $OUT/${TAG}_bench_nomask.err
         python tools/bench_summary.py $OUT/${TAG}_bench_nomask.json | head -8
         for m in auto off; do
-          timeout 600 python bench.py --config longform --cu-mask $m --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_longform_mask_$m.json 2> $OUT/${TAG}_bench_longform_mask_$m.err
+          timeout 600 python bench.py --full --config longform --cu-mask $m --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_longform_mask_$m.json 2> $OUT/${TAG}_bench_longform_mask_$m.err
           python tools/bench_summary.py $OUT/${TAG}_bench_longform_mask_$m.json | head -1
         done
       fi ;;
@@ -77,14 +77,14 @@ for st in "$@"; do
     smoke) timeout 600 python __graft_entry__.py smoke 2>&1 | tail -3 | tee $OUT/${TAG}_smoke.log ;;
     bench)
       extra=$(echo $arg | tr ',' ' ')
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 $extra > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+      timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 $extra > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
       tail -4 $OUT/${TAG}_bench.err; python tools/bench_summary.py $OUT/${TAG}_bench.json ;;
     bench_ab)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-autotune --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_noautotune.json 2> $OUT/${TAG}_bench_noautotune.err
+      timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-autotune --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_noautotune.json 2> $OUT/${TAG}_bench_noautotune.err
       python tools/bench_summary.py $OUT/${TAG}_bench_noautotune.json ;;
     configs)
       for c in libritts_hifigan libritts_istftnet longform; do
-        timeout 600 python bench.py --config $c --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err
+        timeout 600 python bench.py --full --config $c --no-cpu-baseline --no-box-probe > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err
         python tools/bench_summary.py $OUT/${TAG}_bench_$c.json
       done ;;
     stats)
