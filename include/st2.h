@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ST2_ABI_VERSION 22
+#define ST2_ABI_VERSION 23
 
 /* ---- library ---------------------------------------------------------------------- */
 int st2_abi_version(void);
@@ -141,6 +141,14 @@ typedef struct st2_conv_desc {
      needs st2_conv1d_f16s_splitk_bytes(d) bytes here (the slices are stored in the accumulator layout of whole tiles: ksplit * B *
      padded C_out * padded L_out * 4).  NULL / too small = no split. */
   void* splitk_ws; int64_t splitk_ws_bytes;
+  /* ABI v23, optional: per-row lengths of a ragged batch (int32 [B] on the device, NULL = every row is L_in / L_out long).
+     x_len[b] (st2_conv1d_f16s): row b of the input ends at x_len[b] <= L_in -- positions past it are the conv's zero padding
+     AFTER the prologue (a select: whatever the memory holds there is ignored).  The xs path gets the same from
+     st2_act_split_len.  y_len[b] (both kernels): row b of the output ends at y_len[b] <= L_out -- tiles wholly past it exit
+     before doing any work, nothing is stored at or past it, and the epilogue's partial sums cover only its columns
+     (st2_stats_finalize_len).  Outputs past y_len[b] are left as the memory held them.  Values above L_in / L_out are
+     clamped.  st2_conv1d (the exact-fp32 kernel) does not implement them and rejects a descriptor that sets either. */
+  const int32_t* x_len; const int32_t* y_len;
 } st2_conv_desc;
 
 int st2_conv1d(const st2_conv_desc* d, void* stream);
@@ -207,12 +215,22 @@ int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t
                   int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale,
                   void* xs, int32_t xs_cg, int32_t Lp, int32_t halo, void* stream);
 int st2_conv1d_xs(const st2_conv_desc* d, void* stream);
+/* Ragged rows (ABI v23): as st2_act_split, with row b ending at len[b] <= L (int32 [B] on the device; NULL = L): positions at or
+ * past it are written as zeros after the prologue.  Not defined for ST2_PRO_COLNORM. */
+int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
+                      int32_t pro, float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
+                      int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale,
+                      void* xs, int32_t xs_cg, int32_t Lp, int32_t halo, const int32_t* len, void* stream);
 /* Columns per partial-sum slot (128, 64 or 32) the launch described by *d would use when its caller opts into the small-grid
  * builds (d.part_cols): a function of the geometry alone -- every plan gets the same answer, results are reproducible bit for
  * bit.  k = 3 / 7 / 11 launches of up to three utterances: 32 below ~100 tiles of 128 x 128, 64 up to ~900 (k = 3) / 340 (k = 7,
  * 11); 128 otherwise (y is bitwise the same either way: st2_conv1d_xs_impl.h). */
 int st2_conv1d_xs_part_cols(const st2_conv_desc* d);
 int st2_stats_finalize(const float* part, int32_t rows, int32_t nt, int32_t L, float eps, float* stats, int32_t cols, void* stream);
+/* Ragged rows (ABI v23): row r covers len[r / len_div] <= L columns (len int32 on the device, NULL = L; len_div = channels per
+ * batch item).  Slots wholly past that end are not read; the last one counts only its valid columns. */
+int st2_stats_finalize_len(const float* part, int32_t rows, int32_t nt, int32_t L, float eps, float* stats, int32_t cols,
+                           const int32_t* len, int32_t len_div, void* stream);
 
 /* ---- small direct Conv1d (any stride, tiny C_in): noise convs, F0/N down-convs ------ *
  * y[b,co,l] = bias[co] + sum_{ci,t} w[co,ci,t] * x[b,ci, l*stride + t - pad]   (plain OIK weights)
@@ -224,6 +242,12 @@ int st2_conv1d_direct(const float* x, int64_t x_bs, int32_t x_cs,
                       float* y, int64_t y_bs, int32_t y_cs,
                       int32_t B, int32_t C_in, int32_t C_out, int32_t L_in, int32_t L_out,
                       int32_t ks, int32_t stride, int32_t pad, void* stream);
+/* Ragged rows (ABI v23): row b of the input ends (zero padding) at x_len[b] <= L_in, outputs at or past y_len[b] are written as
+ * exact zeros (int32 [B] on the device; either may be NULL). */
+int st2_conv1d_direct_len(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias,
+                          float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C_in, int32_t C_out, int32_t L_in,
+                          int32_t L_out, int32_t ks, int32_t stride, int32_t pad, const int32_t* x_len,
+                          const int32_t* y_len, void* stream);
 
 /* ---- polyphase split of a strided Conv1d input (kernel = 2*stride, the noise_convs of both vocoders) -------- *
  * xp[b][ci*stride + r][u] = x[b][ci][u*stride + r - pad]  for u in [0,Lu), r in [0,stride); 0 outside [0,L_in).
@@ -240,6 +264,10 @@ int st2_phase_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32
  */
 int st2_instnorm_stats(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
                        float eps, float* stats /* [B][C][2] */, void* stream);
+/* Ragged rows (ABI v23): row b covers its first len[b] <= L columns (int32 [B] on the device, NULL = L), reduced in an order
+ * that does not depend on the row's address. */
+int st2_instnorm_stats_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
+                           float eps, float* stats, const int32_t* len, void* stream);
 
 /* LayerNorm statistics over the CHANNEL axis of an NCL tensor: stats[b][l] = (mean, rstd) over c.
  * Replaces F.layer_norm's reduction, Modules/diffusion/modules.py:18-38,556-557. */
@@ -276,6 +304,15 @@ int st2_convt_interleave_stats(const float* phases, int64_t p_bs, int32_t p_cs, 
                                float* out, int64_t o_bs, int32_t o_cs,
                                int32_t B, int32_t C, int32_t stride, int32_t pad, int32_t L_raw,
                                int32_t reflect_left, float* part, int32_t part_nt, void* stream);
+/* Ragged rows (ABI v23): row b has q_len[b] <= Lq phase columns (the rest is the transposed conv's zero padding) and
+ * out_len[b] <= L_raw + reflect_left outputs; tiles wholly past out_len[b] exit, partial sums cover only its columns.  Both
+ * int32 [B] on the device, both NULL or both set. */
+int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs, int32_t p_cs, int32_t Lq,
+                                   const float* bias, const float* add, int64_t a_bs, int32_t a_cs,
+                                   float* out, int64_t o_bs, int32_t o_cs,
+                                   int32_t B, int32_t C, int32_t stride, int32_t pad, int32_t L_raw,
+                                   int32_t reflect_left, float* part, int32_t part_nt, const int32_t* q_len,
+                                   const int32_t* out_len, void* stream);
 
 /* ---- AdaIN + LeakyReLU + depthwise ConvTranspose1d(k3,s2,p1,op1) ("pool") ------------ *
  * Replaces Modules/istftnet.py:441-444 with upsample=True (weights w[c][3], bias[c]). */
@@ -284,6 +321,12 @@ int st2_adain_leaky_pool(const float* x, int64_t x_bs, int32_t x_cs,
                          float slope, const float* w, const float* bias,
                          float* y, int64_t y_bs, int32_t y_cs,
                          int32_t B, int32_t C, int32_t L, void* stream);
+/* Ragged rows (ABI v23): row b of the input ends (zero padding) at len[b] <= L; 2 * len[b] outputs are written. */
+int st2_adain_leaky_pool_len(const float* x, int64_t x_bs, int32_t x_cs,
+                             const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
+                             float slope, const float* w, const float* bias,
+                             float* y, int64_t y_bs, int32_t y_cs,
+                             int32_t B, int32_t C, int32_t L, const int32_t* len, void* stream);
 
 /* ---- harmonic source (SineGen + SourceModuleHnNSF) ---------------------------------- *
  * f0 [B][F] frame-rate F0 (Hz), U samples per frame, H harmonics (9).
@@ -296,18 +339,38 @@ int st2_har_source(const float* f0, int32_t B, int32_t F, int32_t U, int32_t H,
                    const float* noise, const float* lin_w, const float* lin_b,
                    float sine_amp, float noise_std, float voiced_threshold, float sample_rate,
                    float* phase_scratch, float* out, void* stream);
+/* Ragged rows (ABI v23): row b holds f_len[b] <= F frames (int32 [B] on the device, NULL = F) in the [B][F] / [B][F*U][H] /
+ * [B][F*U] layouts: its phase prefix sums, its interpolation boundary and the noise it reads end there; out is exactly 0 from
+ * f_len[b] * U on. */
+int st2_har_source_len(const float* f0, int32_t B, int32_t F, int32_t U, int32_t H,
+                       const float* noise, const float* lin_w, const float* lin_b,
+                       float sine_amp, float noise_std, float voiced_threshold, float sample_rate,
+                       float* phase_scratch, float* out, const int32_t* f_len, void* stream);
 
 /* ---- STFT of the harmonic source (n_fft = win = N, hop, periodic Hann, center/reflect) *
  * har[b][k][m] = |X_k|, har[b][N/2+1+k][m] = atan2(Im, Re), k in [0,N/2], m in [0, L/hop].
  * Replaces Modules/istftnet.py:91-97,355-357. */
 int st2_stft_mag_phase(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop,
                        float* har, int64_t har_bs, int32_t har_cs, void* stream);
+/* Ragged rows (ABI v23): row b is len[b] <= L samples of a row of L, reflect-padded at its own end; frames m > len[b] / hop
+ * are exact zeros. */
+int st2_stft_mag_phase_len(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop,
+                           float* har, int64_t har_bs, int32_t har_cs, const int32_t* len, void* stream);
 
 /* ---- iSTFT synthesis: spec/phase [B][N/2+1][M] each (spec = exp(.), phase = sin(.) already
  * applied by the conv_post epilogue) -> wave [B][hop*(M-1)].
  * Replaces Modules/istftnet.py:99-104,380. */
 int st2_istft(const float* sp, int64_t sp_bs, int32_t sp_cs, int32_t B, int32_t M,
               int32_t n_fft, int32_t hop, float* wave, int64_t wave_bs, void* stream);
+/* Ragged rows (ABI v23): row b has m_len[b] (2..M) frames: it emits hop * (m_len[b] - 1) samples normalised by the window sum
+ * of that length, and exact zeros up to hop * (M - 1). */
+int st2_istft_len(const float* sp, int64_t sp_bs, int32_t sp_cs, int32_t B, int32_t M,
+                  int32_t n_fft, int32_t hop, float* wave, int64_t wave_bs, const int32_t* m_len, void* stream);
+/* Per-row lengths of a ragged batch (ABI v23): out[i][b] = (coef[3i] * f_b + coef[3i + 1]) / coef[3i + 2] for i < n <= 16,
+ * f_b = frames[b] clamped to 1..T_max (integer arithmetic, floor division; coef on the HOST, copied at launch; frames / out
+ * int32 on the device). */
+int st2_ragged_lengths(const int32_t* frames, int32_t B, int32_t T_max, int32_t n, const int32_t* coef, int32_t* out,
+                       void* stream);
 
 /* ---- denoiser helpers (tokens channel-major: x[b][c][n]) ------------------------------ */
 /* Multi-head attention without mask: q,k,v [B][H*D][N] -> o [B][H*D][N], softmax(q^T k * scale) v.
@@ -429,6 +492,11 @@ int st2_duration_head(const float* x, int64_t x_bs, int32_t x_cs, const float* w
                       void* stream);
 int st2_expand_by_durations(const float* x, int64_t x_bs, int32_t x_cs, const int64_t* dur, int32_t B, int32_t C,
                             int32_t N, int32_t T, int32_t shift, float* y, int64_t y_bs, int32_t y_cs, void* stream);
+/* Ragged rows (ABI v23): row b's durations sum to len[b] <= T (int32 [B] on the device, NULL = T); columns from len[b] on
+ * are exact zeros. */
+int st2_expand_by_durations_len(const float* x, int64_t x_bs, int32_t x_cs, const int64_t* dur, int32_t B, int32_t C,
+                                int32_t N, int32_t T, int32_t shift, float* y, int64_t y_bs, int32_t y_cs, const int32_t* len,
+                                void* stream);
 
 /* ---- reference-audio style path (compute_style, Demo/Inference_LibriTTS.ipynb:100-111) ------------------------- *
  * The mel front-end (meldataset.py:58-66: torchaudio MelSpectrogram(n_mels 80, n_fft 2048, win 1200, hop 300) ->
@@ -532,6 +600,18 @@ int64_t st2_decoder_workspace_bytes(st2_engine* e, int32_t B, int32_t T);
 int st2_decoder_forward(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
                         const float* sine_noise, const float* har_inject, int32_t B, int32_t T, float* wave,
                         void* workspace, int64_t workspace_bytes, const st2_decoder_taps* taps, void* stream);
+/* Ragged batch (ABI v23): row b is an utterance of frames[b] (int32 [B] on the device, each in 1..T_max) frames in the T_max
+ * layout above (asr [B][dim_in][T_max], F0 / N [B][2 T_max], sine_noise [B][600 T_max][9], har_inject istftnet
+ * [B][n_fft+2][120 T_max+1] zero past 120 frames[b] + 1 columns, hifigan [B][600 T_max] zero past 600 frames[b]).  Row b of
+ * wave [B][600 T_max] equals st2_decoder_forward of that utterance alone at T = frames[b] (every convolution sees the zero
+ * padding of the row's own end, every InstanceNorm / AdaIN reduces over the row's own columns) and is exactly 0 from
+ * 600 frames[b] on.  Inputs past a row's end are never used (NaN there is harmless).  frames[b] outside 1..T_max is clamped
+ * there (not checked: that would need a host read).  Workspace: st2_decoder_workspace_bytes(B, T_max).  Taps: not supported
+ * (must be NULL).  Same stream / graph-capture contract. */
+int st2_decoder_forward_ragged(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
+                               const float* sine_noise, const float* har_inject, const int32_t* frames, int32_t B,
+                               int32_t T_max, float* wave, void* workspace, int64_t workspace_bytes,
+                               const st2_decoder_taps* taps, void* stream);
 
 /* Per-step scalars of the ADPM2 loop, all input independent (sampler.py:184-191, 490-495): for step i (sigma_i ->
  * sigma_{i+1}) row i of `table` holds 11 doubles
@@ -564,6 +644,12 @@ int64_t st2_prosody_workspace_bytes(st2_engine* e, int32_t B, int32_t N, int32_t
 int st2_prosody_forward(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations, const float* s,
                         int32_t B, int32_t N, int32_t T, int32_t shift, float* asr, float* f0, float* n, void* workspace,
                         int64_t workspace_bytes, void* stream);
+/* Ragged batch (ABI v23): as st2_prosody_forward with T = T_max, row b's durations summing to frames[b] (int32 [B] on the
+ * device, 1..T_max).  Row b equals st2_prosody_forward of that utterance alone at T = frames[b]; asr is exactly 0 from
+ * frames[b] on, f0 / n from 2 frames[b] on.  Workspace: st2_prosody_workspace_bytes(B, N, T_max). */
+int st2_prosody_forward_ragged(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
+                               const float* s, const int32_t* frames, int32_t B, int32_t N, int32_t T_max, int32_t shift,
+                               float* asr, float* f0, float* n, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* TextEncoder.forward (models.py:284-345): tokens int64 [B][N] (id 0 = pad), lengths int32 [B] or NULL ->
  * t_en [B][dim_in][N]: Embedding -> depth x [weight-norm Conv1d k5 -> LayerNorm over channels -> LeakyReLU(0.2) -> mask] ->
@@ -788,6 +874,11 @@ enum st2_backend_slot {
   ST2_BE_DEV_ALLOC,   /* void* (*)(int64_t bytes) */
   ST2_BE_DEV_FREE,    /* void (*)(void*) */
   ST2_BE_UPLOAD,      /* int (*)(void* dst, const void* src, int64_t bytes): synchronous host -> device copy */
+  ST2_BACKEND_ENTRIES_V22,  /* a table of this many entries (ABI <= 22) leaves the slots below on their HIP kernels */
+  /* ABI v23: the length-aware entry points of the ragged decoder / prosody plans */
+  ST2_BE_ACT_SPLIT_LEN = ST2_BACKEND_ENTRIES_V22, ST2_BE_INSTNORM_STATS_LEN, ST2_BE_STATS_FINALIZE_LEN,
+  ST2_BE_CONV1D_DIRECT_LEN, ST2_BE_ADAIN_LEAKY_POOL_LEN, ST2_BE_CONVT_INTERLEAVE_STATS_LEN, ST2_BE_HAR_SOURCE_LEN,
+  ST2_BE_STFT_MAG_PHASE_LEN, ST2_BE_ISTFT_LEN, ST2_BE_RAGGED_LENGTHS, ST2_BE_EXPAND_BY_DURATIONS_LEN,
   ST2_BACKEND_ENTRIES
 };
 int st2_debug_set_backend(void* const* table, int32_t entries);

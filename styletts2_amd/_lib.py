@@ -14,7 +14,7 @@ import torch  # noqa: F401,E402  (deliberately before the CDLL below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libst2_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 HEADROOM_COLS, CALIBRATION_COLS = 12, 5  # st2.h ST2_HEADROOM_COLS / ST2_CALIBRATION_COLS
 
 f32p = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
@@ -49,6 +49,7 @@ class ConvDesc(C.Structure):
         ("xs", f32p), ("xs_cg", C.c_int32), ("xs_lp", C.c_int32), ("xs_halo", C.c_int32),
         ("part", f32p), ("part_nt", C.c_int32), ("part_cols", C.c_int32),
         ("splitk_ws", f32p), ("splitk_ws_bytes", C.c_int64),
+        ("x_len", C.c_void_p), ("y_len", C.c_void_p),  # ABI v23: per-row lengths of a ragged batch (NULL = L_in / L_out)
     ]
 
 
@@ -94,6 +95,11 @@ BACKEND_SLOTS = ["conv1d_f16s", "conv1d_xs", "act_split", "stats_finalize", "con
                  "axpbypcz", "time_features", "tokens_to_channels", "broadcast_cols", "copy_ncl", "expand_by_durations",
                  "lstm_bidir", "colnorm_apply", "duration_head", "mask_tail", "embed_tokens", "dwconv3x3s2",
                  "avgpool2x2", "dev_alloc", "dev_free", "upload"]  # enum st2_backend_slot
+# ABI v23: the length-aware slots of the ragged plans, after the ones above.  st2_debug_set_backend takes a table of
+# len(BACKEND_SLOTS) entries (these keep their HIP kernels) or of len(BACKEND_SLOTS + BACKEND_SLOTS_RAGGED).
+BACKEND_SLOTS_RAGGED = ["act_split_len", "instnorm_stats_len", "stats_finalize_len", "conv1d_direct_len",
+                        "adain_leaky_pool_len", "convt_interleave_stats_len", "har_source_len", "stft_mag_phase_len",
+                        "istft_len", "ragged_lengths", "expand_by_durations_len"]
 
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -197,6 +203,37 @@ _SIGNATURES = {
     "st2_duration_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     "st2_duration_forward": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, f32p,
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_decoder_forward_ragged": (C.c_int, [C.c_void_p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_void_p, C.c_int32,
+                                             C.c_int32, f32p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "st2_prosody_forward_ragged": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_act_split_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                    f32p, f32p, f32p, C.c_int64, C.c_int32, C.c_int32, f32p, C.c_float, f32p, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_stats_finalize_len": (C.c_int, [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, f32p, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_void_p]),
+    "st2_instnorm_stats_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, f32p,
+                                         C.c_void_p, C.c_void_p]),
+    "st2_conv1d_direct_len": (C.c_int, [f32p, C.c_int64, C.c_int32, f32p, f32p, f32p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "st2_convt_interleave_stats_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_int64, C.c_int32,
+                                                 f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, f32p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "st2_adain_leaky_pool_len": (C.c_int, [f32p, C.c_int64, C.c_int32, f32p, f32p, f32p, C.c_int64, C.c_float, f32p,
+                                           f32p, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p]),
+    "st2_har_source_len": (C.c_int, [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, f32p, f32p, C.c_void_p, C.c_void_p]),
+    "st2_stft_mag_phase_len": (C.c_int, [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32,
+                                         C.c_void_p, C.c_void_p]),
+    "st2_istft_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int64,
+                                C.c_void_p, C.c_void_p]),
+    "st2_expand_by_durations_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_ragged_lengths": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
+                                     C.c_void_p]),
     "st2_prosody_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "st2_prosody_forward": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -26,6 +26,7 @@ struct ActArgs {
   const float* alpha;
   float x_scale;
   st2_h8* xs; int xs_cg, Lp, halo;
+  const int32_t* len;  // int32 [B] valid columns per row (ragged batch) or NULL = L
   int* status;  // sticky status word (st2_status), may be null
 };
 
@@ -39,7 +40,8 @@ __global__ __launch_bounds__(256) void act_split_kernel(const ActArgs a) {
   const int cg = blockIdx.y;
   const int b = blockIdx.z;
   const int l = pos - a.halo;
-  const bool lok = l >= 0 && l < a.L;
+  const int Lb = a.len ? a.len[b] : a.L;  // ragged rows: the row's own end is its zero padding (a select, never a multiply)
+  const bool lok = l >= 0 && l < Lb;
   const int lc = min(max(l, 0), a.L - 1);
   const float* xb = a.x + (int64_t)b * a.x_bs + lc;
   float v[8];
@@ -121,11 +123,15 @@ __global__ __launch_bounds__(256) void act_split_kernel(const ActArgs a) {
 // what its producer subtracted) follow the sums in the same buffer: part = float2 [rows][nt], then float [rows][nt].  Slot mean =
 // shift + s1 / n, slot M2 = s2 - s1^2 / n; the row's mean is the weighted mean of the slot means and its M2 = sum of slot M2 + sum
 // n_i (mean_i - mean)^2 (Chan et al.) -- two wave reductions over coalesced reads.
-__global__ __launch_bounds__(256) void stats_finalize_kernel(const float* __restrict__ part, int rows, int nt, int L,
-                                                             float eps, float* __restrict__ stats, int cols) {
+// Ragged rows (len != NULL): row r covers len[r / len_div] columns; slots wholly past that end were never written and are not
+// read (no zero-count terms), the last slot counts only its valid columns.
+__global__ __launch_bounds__(256) void stats_finalize_kernel(const float* __restrict__ part, int rows, int nt, int L_max,
+                                                             float eps, float* __restrict__ stats, int cols,
+                                                             const int32_t* __restrict__ len, int len_div) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  const int L = len ? min(max(len[row / len_div], 1), L_max) : L_max;
   const float2* p = reinterpret_cast<const float2*>(part) + (int64_t)row * nt;
   const float* sh = part + (int64_t)rows * nt * 2 + (int64_t)row * nt;
   const int ns = min(nt, (L + cols - 1) / cols);  // slots that hold columns
@@ -246,6 +252,14 @@ extern "C" int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t
                              float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
                              int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale, void* xs, int32_t xs_cg,
                              int32_t Lp, int32_t halo, void* stream) {
+  return st2_act_split_len(x, x_bs, x_cs, B, C, L, pro, slope, stats, gamma, beta, gb_bs, gb_seg, gamma_plus_one, alpha, x_scale,
+                           xs, xs_cg, Lp, halo, nullptr, stream);
+}
+
+extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L, int32_t pro,
+                                 float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
+                                 int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale, void* xs,
+                                 int32_t xs_cg, int32_t Lp, int32_t halo, const int32_t* len, void* stream) {
   ST2_REQUIRE(x && xs && B > 0 && C > 0 && L > 0, "st2_act_split: bad arguments");
   ST2_REQUIRE(B <= 65535 && xs_cg <= 65535, "st2_act_split: grid too large");
   ST2_REQUIRE(xs_cg * 8 >= C, "st2_act_split: xs_cg=%d groups cannot hold C=%d channels", xs_cg, C);
@@ -262,6 +276,8 @@ extern "C" int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t
   a.stats = stats; a.gamma = gamma; a.beta = beta; a.gb_bs = gb_bs; a.gb_seg = gb_seg; a.gamma_plus_one = gamma_plus_one;
   a.alpha = alpha; a.x_scale = x_scale;
   a.xs = reinterpret_cast<st2_h8*>(xs); a.xs_cg = xs_cg; a.Lp = Lp; a.halo = halo;
+  a.len = len;
+  ST2_REQUIRE(!len || pro != ST2_PRO_COLNORM, "st2_act_split_len: per-row lengths are not defined for ST2_PRO_COLNORM");
   a.status = st2_status_device_ptr();
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (pro) {
@@ -364,11 +380,19 @@ extern "C" int st2_debug_headroom_read(double* rows, int32_t cap_rows) {
 
 extern "C" int st2_stats_finalize(const float* part, int32_t rows, int32_t nt, int32_t L, float eps, float* stats, int32_t cols,
                                   void* stream) {
+  return st2_stats_finalize_len(part, rows, nt, L, eps, stats, cols, nullptr, 1, stream);
+}
+
+extern "C" int st2_stats_finalize_len(const float* part, int32_t rows, int32_t nt, int32_t L, float eps, float* stats,
+                                      int32_t cols, const int32_t* len, int32_t len_div, void* stream) {
   ST2_REQUIRE(part && stats && rows > 0 && nt > 0 && L > 0, "st2_stats_finalize: bad arguments");
+  ST2_REQUIRE(!len || (len_div > 0 && rows % len_div == 0), "st2_stats_finalize_len: len_div=%d does not divide rows=%d", len_div,
+              rows);
   ST2_REQUIRE(cols > 0 && (int64_t)nt * cols >= L, "st2_stats_finalize: %d slots of %d columns do not cover L=%d", nt, cols, L);
   ST2_REQUIRE((reinterpret_cast<uintptr_t>(part) & 7) == 0, "st2_stats_finalize: part must be 8-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(stats_finalize_kernel, dim3(st2_cdiv(rows, 4)), dim3(256), 0, s, part, rows, nt, L, eps, stats, cols);
+  hipLaunchKernelGGL(stats_finalize_kernel, dim3(st2_cdiv(rows, 4)), dim3(256), 0, s, part, rows, nt, L, eps, stats, cols, len,
+                     len_div);
   ST2_CHECK_LAUNCH("st2_stats_finalize");
   return 0;
 }

@@ -243,6 +243,7 @@ extern "C" int st2_conv1d(const st2_conv_desc* dp, void* stream) {
               "st2_conv1d: empty geometry B=%d C_in=%d C_out=%d L_in=%d L_out=%d", d.B, d.C_in, d.C_out,
               d.L_in, d.L_out);
   ST2_REQUIRE(d.x && d.wt && d.y, "st2_conv1d: null tensor pointer");
+  ST2_REQUIRE(!d.x_len && !d.y_len, "st2_conv1d: per-row lengths (x_len / y_len) are implemented by st2_conv1d_f16s / _xs only");
   ST2_REQUIRE(d.w_ld >= d.C_out && (d.w_ld & 3) == 0, "st2_conv1d: w_ld=%d must be >= C_out=%d and %%4==0",
               d.w_ld, d.C_out);
   ST2_REQUIRE((reinterpret_cast<uintptr_t>(d.wt) & 15) == 0, "st2_conv1d: wt must be 16-byte aligned");

@@ -124,6 +124,9 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
   // order and applies the epilogue
   const int b = blockIdx.z / ksplit;
   const int ksl = blockIdx.z - b * ksplit;
+  // ragged rows: a tile wholly past its row's end exits before any barrier; the row's input ends (zero padding) at x_len[b]
+  if (d.y_len && n0 >= d.y_len[b]) return;
+  const int L_in_b = d.x_len ? min(d.x_len[b], d.L_in) : d.L_in;
 
   const int XW = BN + (KS - 1) * d.dil;  // staged positions
   // LDS: [2 buffers][2 planes hi/lo][CG][XW] slots of 16 B, then the channel parameter table
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
       const int pos = sp0 + r * TPG;
       if (pos >= XW) continue;
       const int l = lin0 + pos;
-      const bool lok = l >= 0 && l < d.L_in;
+      const bool lok = l >= 0 && l < L_in_b;
       float cmean = 0.f, crstd = 1.f;
       if constexpr (PRO == ST2_PRO_COLNORM) {
         const float* st = d.stats + ((int64_t)b * d.L_in + min(max(l, 0), d.L_in - 1)) * 2;
@@ -438,7 +441,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const st2_conv_desc 
   const int by = tile / tiles_x, bx = tile - by * tiles_x;
   const int co = by * (128 / WN) + wm * 32 + l31;  // BM = 32 * WM, WM * WN = 4
   const int l0 = bx * (32 * TN * WN) + wn * (32 * TN) + (q >> 2) * 32 + 8 * (q & 3) + 4 * kg;
-  if (co >= d.C_out || l0 >= d.L_out) return;
+  const int Lo = d.y_len ? min(d.y_len[b], d.L_out) : d.L_out;  // ragged rows: that row's own end
+  if (co >= d.C_out || l0 >= Lo) return;
   const int64_t slice = (int64_t)d.B * gridDim.y * (TN * 4) * 256;  // float4 per slice
   const float4* p = reinterpret_cast<const float4*>(part) + (((int64_t)b * gridDim.y + tile) * (TN * 4) + q) * 256 + tid;
   float4 a4 = p[0];
@@ -451,7 +455,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const st2_conv_desc 
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int l = l0 + c;
-    if (l >= d.L_out) break;
+    if (l >= Lo) break;
     float v = av[c] + bias;
     if (d.res) v += d.res[(int64_t)b * d.res_bs + (int64_t)co * d.res_cs + (l >> d.res_shift)];
     if (d.res2) v = d.res2[(int64_t)b * d.res2_bs + (int64_t)co * d.res2_cs + l] + v;
@@ -557,6 +561,7 @@ template <int KS>
 inline bool ws_eligible(const st2_conv_desc& d) {
   if constexpr (KS != 3 && KS != 7 && KS != 11) return false;
   if (d.pro != ST2_PRO_ADAIN_SNAKE || g_variant == 1 || d.C_in > 256 || d.C_out > 64) return false;
+  if (d.x_len || d.y_len) return false;  // ragged rows: the one-role build (bitwise the same) carries the per-row ends
   if (ksplit_for_geometry(d) > 1) return false;
   if (g_variant == 2) return true;
   const int BM = d.C_out > 32 ? 64 : 32;

@@ -313,8 +313,11 @@ __device__ __forceinline__ void xs_tile_of(unsigned lin, unsigned nx, unsigned n
     unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;                                                         \
     if (flags & 1) xs_tile_of(bx + gridDim.x * (by + gridDim.y * bz), gridDim.x, gridDim.y, flags, bx, by, bz);         \
     const int n0 = (int)bx * (32 * TN * WN);                                                                            \
+    /* ragged rows (d.y_len): a tile wholly past its row's end exits before any barrier */                              \
+    const int Lrow = d.y_len ? min(d.y_len[bz], d.L_out) : d.L_out;                                                     \
+    if (n0 >= Lrow) return;                                                                                             \
     if constexpr (ST2_XS_ROWEND && WN == 1 && TN >= 4) {                                                                \
-      if (d.L_out - n0 <= 32 * (TN / 4)) { /* workgroup-uniform */                                                      \
+      if (Lrow - n0 <= 32 * (TN / 4)) { /* workgroup-uniform */                                                         \
         conv1d_xs_body<KS, CI_T, WM, WN, TN / 4>(d, n0, by, bz, threadIdx.x);                                           \
         return;                                                                                                         \
       }                                                                                                                 \

@@ -68,7 +68,9 @@ __device__ __forceinline__ void st2_conv_epilogue(const st2_conv_desc& d, st2_f3
   // seven (profiles/r04/r04h1_*, r04j_*: what rounds 1-3 knew as "the slow box class").  Now blocks [0, jn_full) take the
   // straight-line build, blocks past the row end are skipped, and only a block that STRADDLES the row end (none at L =
   // 8 000; one column's worth at L = 48 001) takes the generic code.  Same values, same order of the partial sums.
-  const int avail = d.L_out - (n0 + wn * (32 * TN));  // valid columns of this wave's part of the tile (may be <= 0)
+  // ragged rows (d.y_len): this row ends at its own length -- no stores, no partial sums past it
+  const int Lo = __builtin_amdgcn_readfirstlane(d.y_len ? min(d.y_len[b], d.L_out) : d.L_out);  // workgroup-uniform: kept in an SGPR
+  const int avail = Lo - (n0 + wn * (32 * TN));  // valid columns of this wave's part of the tile (may be <= 0)
   const int jn_full = avail >= 32 * TN ? TN : (avail > 0 ? avail / 32 : 0);
   const int j_strad = (jn_full < TN && avail > jn_full * 32) ? jn_full : -1;
   const bool rows_ok = m0 + BM <= d.C_out;
@@ -195,7 +197,7 @@ __device__ __forceinline__ void st2_conv_epilogue(const st2_conv_desc& d, st2_f3
         constexpr int idx = decltype(idx_tag)::value;
         constexpr int j = idx / 16, q = (idx % 16) / 4, e = idx % 4;
         const int l = lw + j * 32 + 8 * q + e;
-        const bool ok = rok && l < d.L_out && j >= j_lo && j < j_hi;
+        const bool ok = rok && l < Lo && j >= j_lo && j < j_hi;
         float t = fmaf(acc[j][4 * q + e], osc_r, bias_r);
         if (use_res) t += ok ? rb[ro + (l >> d.res_shift)] : 0.f;
         if (use_res2) t = (ok ? r2b[r2o + j * 32 + 8 * q + e] : 0.f) + t;

@@ -64,6 +64,18 @@ struct Backend {
   void* (*dev_alloc)(int64_t);
   void (*dev_free)(void*);
   int (*upload)(void*, const void*, int64_t);
+  // ABI v23: length-aware entry points of the ragged plans (slots after ST2_BACKEND_ENTRIES_V22)
+  decltype(&st2_act_split_len) act_split_len;
+  decltype(&st2_instnorm_stats_len) instnorm_stats_len;
+  decltype(&st2_stats_finalize_len) stats_finalize_len;
+  decltype(&st2_conv1d_direct_len) conv1d_direct_len;
+  decltype(&st2_adain_leaky_pool_len) adain_leaky_pool_len;
+  decltype(&st2_convt_interleave_stats_len) convt_interleave_stats_len;
+  decltype(&st2_har_source_len) har_source_len;
+  decltype(&st2_stft_mag_phase_len) stft_mag_phase_len;
+  decltype(&st2_istft_len) istft_len;
+  decltype(&st2_ragged_lengths) ragged_lengths;
+  decltype(&st2_expand_by_durations_len) expand_by_durations_len;
 };
 
 void* hip_alloc(int64_t n) {
@@ -102,7 +114,10 @@ const Backend kHipBackend = {st2_conv1d_f16s, st2_conv1d_xs, st2_act_split, st2_
                              st2_istft, st2_attention_keylen, st2_add_chanvec, st2_mean_tokens_len, st2_axpbypcz,
                              st2_time_features, st2_tokens_to_channels, st2_broadcast_cols, st2_copy_ncl,
                              st2_expand_by_durations, hip_lstm, st2_colnorm_apply, st2_duration_head, st2_mask_tail,
-                             st2_embed_tokens, st2_dwconv3x3s2, st2_avgpool2x2, hip_alloc, hip_free, hip_upload};
+                             st2_embed_tokens, st2_dwconv3x3s2, st2_avgpool2x2, hip_alloc, hip_free, hip_upload,
+                             st2_act_split_len, st2_instnorm_stats_len, st2_stats_finalize_len, st2_conv1d_direct_len,
+                             st2_adain_leaky_pool_len, st2_convt_interleave_stats_len, st2_har_source_len,
+                             st2_stft_mag_phase_len, st2_istft_len, st2_ragged_lengths, st2_expand_by_durations_len};
 Backend g_be = kHipBackend;
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -135,6 +150,7 @@ struct View {  // NCL view, strides in elements
   int64_t bs = 0;
   int cs = 0;
   int B = 0, C = 0, L = 0;
+  const int32_t* len = nullptr;  // ragged plans: int32 [B] valid columns per row on the device (NULL = L)
   View rows(int c0, int c1) const {
     View v = *this;
     v.p = p + (int64_t)c0 * cs;
@@ -142,6 +158,11 @@ struct View {  // NCL view, strides in elements
     return v;
   }
   bool ok() const { return p != nullptr; }
+  View with_len(const int32_t* l) const {
+    View v = *this;
+    v.len = l;
+    return v;
+  }
 };
 
 int pitch_of(int L) { return (L + 31) / 32 * 32; }  // rows of the big activations start 128-byte aligned
@@ -773,6 +794,21 @@ float x_scale_for(int pro) {
 }
 int xs_row_slots(int L) { return XS_HALO + (std::max(L, 1) + 1 + 511) / 512 * 512 + 96; }
 
+// InstanceNorm statistics of y from per-slot partial sums; ragged rows reduce over their own columns only
+void finalize_stats(Ctx& c, float* part, const View& y, int nt, float* stats, int cols) {
+  if (y.len)
+    RUN(c, g_be.stats_finalize_len(part, y.B * y.C, nt, y.L, 1e-5f, stats, cols, y.len, y.C, c.stream));
+  else
+    RUN(c, g_be.stats_finalize(part, y.B * y.C, nt, y.L, 1e-5f, stats, cols, c.stream));
+}
+
+void instnorm_stats(Ctx& c, const View& x, float* stats) {
+  if (x.len)
+    RUN(c, g_be.instnorm_stats_len(x.p, x.bs, x.cs, x.B, x.C, x.L, 1e-5f, stats, x.len, c.stream));
+  else
+    RUN(c, g_be.instnorm_stats(x.p, x.bs, x.cs, x.B, x.C, x.L, 1e-5f, stats, c.stream));
+}
+
 void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const View& y, const ConvOpt& o) {
   st2_conv_desc d;
   memset(&d, 0, sizeof(d));
@@ -788,6 +824,7 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
   if (o.res2.ok()) { d.res2 = o.res2.p; d.res2_bs = o.res2.bs; d.res2_cs = o.res2.cs; }
   d.div = o.div;
   d.act = o.act; d.act_split = o.act_split; d.act_slope = o.act_slope;
+  d.x_len = x.len; d.y_len = y.len;  // ragged rows (NULL: today's launches)
   if (w.C_in != x.C || w.C_out != y.C) {
     if (c.rc == 0) { st2_set_error("engine: conv weight is %d->%d, call has %d->%d", w.C_in, w.C_out, x.C, y.C); c.rc = 1; }
     return;
@@ -801,8 +838,12 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
     const int cg = (x.C + 31) / 32 * 32 / 8;
     const int Lp = xs_row_slots(x.L);
     void* xs = c.a.alloc((int64_t)x.B * 2 * cg * Lp * 16);
-    RUN(c, g_be.act_split(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
-                          o.gamma_plus_one, o.alpha, d.x_scale, xs, cg, Lp, XS_HALO, c.stream));
+    if (x.len)
+      RUN(c, g_be.act_split_len(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
+                                o.gamma_plus_one, o.alpha, d.x_scale, xs, cg, Lp, XS_HALO, x.len, c.stream));
+    else
+      RUN(c, g_be.act_split(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
+                            o.gamma_plus_one, o.alpha, d.x_scale, xs, cg, Lp, XS_HALO, c.stream));
     d.xs = xs; d.xs_cg = cg; d.xs_lp = Lp; d.xs_halo = XS_HALO;
     float* part = nullptr;
     int nt = 0;
@@ -814,8 +855,7 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
       d.part = part; d.part_nt = nt; d.part_cols = pc;
     }
     RUN(c, g_be.conv1d_xs(&d, c.stream));
-    if (o.stats_out)
-      RUN(c, g_be.stats_finalize(part, y.B * y.C, nt, y.L, 1e-5f, o.stats_out, d.part_cols, c.stream));
+    if (o.stats_out) finalize_stats(c, part, y, nt, o.stats_out, d.part_cols);
   } else {
     if (o.gb_seg > 0) {
       if (c.rc == 0) { st2_set_error("engine: a per-segment affine (gb_seg) needs the act_split + xs path"); c.rc = 1; }
@@ -839,14 +879,16 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
       }
     }
     RUN(c, g_be.conv1d_f16s(&d, c.stream));
-    if (o.stats_out)
-      RUN(c, g_be.stats_finalize(part, y.B * y.C, nt, y.L, 1e-5f, o.stats_out, 128, c.stream));
+    if (o.stats_out) finalize_stats(c, part, y, nt, o.stats_out, 128);
   }
   c.a.off = mark;  // planes / partial sums are dead once the launches are queued (stream order protects reuse)
   if (!c.dry) st2_headroom_set_site(nullptr, -1);
 }
 
 float* new_stats(Ctx& c, int B, int C) { return c.a.f32((int64_t)B * C * 2); }
+
+// Arena bytes the per-row length table of a ragged plan (n int32 rows of B, allocated first) moves every later allocation by
+int64_t ragged_table_bytes(int B, int n) { return ((int64_t)n * B * 4 + 255) & ~(int64_t)255; }
 
 #include "st2_plan_decoder.inc"
 #include "st2_plan_sampler.inc"
@@ -866,8 +908,9 @@ extern "C" int st2_debug_set_backend(void* const* table, int32_t entries) {
     g_be = kHipBackend;
     return 0;
   }
-  ST2_REQUIRE(entries == ST2_BACKEND_ENTRIES, "st2_debug_set_backend: %d entries, expected %d", entries,
-              (int)ST2_BACKEND_ENTRIES);
+  ST2_REQUIRE(entries == ST2_BACKEND_ENTRIES || entries == ST2_BACKEND_ENTRIES_V22,
+              "st2_debug_set_backend: %d entries, expected %d (or %d: the slots before ABI v23)", entries,
+              (int)ST2_BACKEND_ENTRIES, (int)ST2_BACKEND_ENTRIES_V22);
   for (int i = 0; i < entries; ++i) ST2_REQUIRE(table[i] != nullptr, "st2_debug_set_backend: entry %d is null", i);
 #define SLOT(field, slot) g_be.field = reinterpret_cast<decltype(g_be.field)>(table[slot])
   SLOT(conv1d_f16s, ST2_BE_CONV1D_F16S); SLOT(conv1d_xs, ST2_BE_CONV1D_XS); SLOT(act_split, ST2_BE_ACT_SPLIT);
@@ -884,6 +927,20 @@ extern "C" int st2_debug_set_backend(void* const* table, int32_t entries) {
   SLOT(colnorm_apply, ST2_BE_COLNORM_APPLY); SLOT(duration_head, ST2_BE_DURATION_HEAD); SLOT(mask_tail, ST2_BE_MASK_TAIL);
   SLOT(embed_tokens, ST2_BE_EMBED_TOKENS); SLOT(dwconv3x3s2, ST2_BE_DWCONV3X3S2); SLOT(avgpool2x2, ST2_BE_AVGPOOL2X2);
   SLOT(dev_alloc, ST2_BE_DEV_ALLOC); SLOT(dev_free, ST2_BE_DEV_FREE); SLOT(upload, ST2_BE_UPLOAD);
+  const Backend& h = kHipBackend;  // an ABI <= 22 table keeps the length-aware slots on their HIP kernels
+  g_be.act_split_len = h.act_split_len; g_be.instnorm_stats_len = h.instnorm_stats_len;
+  g_be.stats_finalize_len = h.stats_finalize_len; g_be.conv1d_direct_len = h.conv1d_direct_len;
+  g_be.adain_leaky_pool_len = h.adain_leaky_pool_len; g_be.convt_interleave_stats_len = h.convt_interleave_stats_len;
+  g_be.har_source_len = h.har_source_len; g_be.stft_mag_phase_len = h.stft_mag_phase_len; g_be.istft_len = h.istft_len;
+  g_be.ragged_lengths = h.ragged_lengths; g_be.expand_by_durations_len = h.expand_by_durations_len;
+  if (entries == ST2_BACKEND_ENTRIES) {
+    SLOT(act_split_len, ST2_BE_ACT_SPLIT_LEN); SLOT(instnorm_stats_len, ST2_BE_INSTNORM_STATS_LEN);
+    SLOT(stats_finalize_len, ST2_BE_STATS_FINALIZE_LEN); SLOT(conv1d_direct_len, ST2_BE_CONV1D_DIRECT_LEN);
+    SLOT(adain_leaky_pool_len, ST2_BE_ADAIN_LEAKY_POOL_LEN);
+    SLOT(convt_interleave_stats_len, ST2_BE_CONVT_INTERLEAVE_STATS_LEN); SLOT(har_source_len, ST2_BE_HAR_SOURCE_LEN);
+    SLOT(stft_mag_phase_len, ST2_BE_STFT_MAG_PHASE_LEN); SLOT(istft_len, ST2_BE_ISTFT_LEN);
+    SLOT(ragged_lengths, ST2_BE_RAGGED_LENGTHS); SLOT(expand_by_durations_len, ST2_BE_EXPAND_BY_DURATIONS_LEN);
+  }
 #undef SLOT
   return 0;
 }
@@ -1104,7 +1161,8 @@ extern "C" int64_t st2_decoder_workspace_bytes(st2_engine* e, int32_t B, int32_t
   c.dry = true;
   c.a.dry = true;
   decoder_plan(c, *e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr);
-  return c.a.peak + 256;
+  // + the per-row length table the ragged plan (st2_decoder_forward_ragged) puts in front of the same allocations
+  return c.a.peak + 256 + ragged_table_bytes(B, 16);
 }
 
 extern "C" int st2_decoder_forward(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
@@ -1120,6 +1178,28 @@ extern "C" int st2_decoder_forward(st2_engine* e, const float* asr, const float*
   c.a.cap = workspace_bytes;
   const int rc = decoder_plan(c, *e, asr, f0, n, s, sine_noise, har_inject, B, T, wave, taps);
   ST2_REQUIRE(!c.a.overflow, "st2_decoder_forward: workspace of %lld B is too small (need %lld B, see "
+              "st2_decoder_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
+  return rc;
+}
+
+extern "C" int st2_decoder_forward_ragged(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
+                                          const float* sine_noise, const float* har_inject, const int32_t* frames, int32_t B,
+                                          int32_t T_max, float* wave, void* workspace, int64_t workspace_bytes,
+                                          const st2_decoder_taps* taps, void* stream) {
+  ST2_REQUIRE(frames, "st2_decoder_forward_ragged: frames (int32 [B] on the device) is required");
+  ST2_REQUIRE(B > 0 && T_max > 0, "st2_decoder_forward_ragged: bad geometry B=%d T_max=%d", B, T_max);
+  ST2_REQUIRE(e && e->dec.ready, "st2_decoder_forward_ragged: decoder weights not finalized");
+  ST2_REQUIRE(asr && f0 && n && s && wave && workspace, "st2_decoder_forward_ragged: bad arguments");
+  ST2_REQUIRE(sine_noise || har_inject, "st2_decoder_forward_ragged: sine_noise (or har_inject) is required");
+  ST2_REQUIRE(!taps, "st2_decoder_forward_ragged: taps are not supported (pass NULL)");
+  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+              "st2_decoder_forward_ragged: workspace must be 256-byte aligned");
+  Ctx c;
+  c.stream = stream;
+  c.a.base = static_cast<char*>(workspace);
+  c.a.cap = workspace_bytes;
+  const int rc = decoder_plan(c, *e, asr, f0, n, s, sine_noise, har_inject, B, T_max, wave, taps, frames);
+  ST2_REQUIRE(!c.a.overflow, "st2_decoder_forward_ragged: workspace of %lld B is too small (need %lld B, see "
               "st2_decoder_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
   return rc;
 }
@@ -1286,7 +1366,8 @@ extern "C" int64_t st2_prosody_workspace_bytes(st2_engine* e, int32_t B, int32_t
   c.dry = true;
   c.a.dry = true;
   prosody_plan(c, *e, nullptr, nullptr, nullptr, nullptr, B, N, T, 0, nullptr, nullptr, nullptr);
-  return c.a.peak + 256;
+  // + the per-row length table of st2_prosody_forward_ragged, in front of the same allocations
+  return c.a.peak + 256 + ragged_table_bytes(B, 2);
 }
 
 extern "C" int st2_prosody_forward(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
@@ -1303,6 +1384,27 @@ extern "C" int st2_prosody_forward(st2_engine* e, const float* d_cm, const float
   c.a.cap = workspace_bytes;
   const int rc = prosody_plan(c, *e, d_cm, t_en, durations, s, B, N, T, shift, asr, f0, n);
   ST2_REQUIRE(!c.a.overflow, "st2_prosody_forward: workspace of %lld B is too small (need %lld B, see "
+              "st2_prosody_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
+  return rc;
+}
+
+extern "C" int st2_prosody_forward_ragged(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
+                                          const float* s, const int32_t* frames, int32_t B, int32_t N, int32_t T_max,
+                                          int32_t shift, float* asr, float* f0, float* n, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+  ST2_REQUIRE(frames, "st2_prosody_forward_ragged: frames (int32 [B] on the device) is required");
+  ST2_REQUIRE(B > 0 && N > 0 && T_max > 0, "st2_prosody_forward_ragged: bad geometry B=%d N=%d T_max=%d", B, N, T_max);
+  ST2_REQUIRE(e && e->pred.ready, "st2_prosody_forward_ragged: predictor weights not finalized");
+  ST2_REQUIRE(d_cm && t_en && durations && s && asr && f0 && n && workspace, "st2_prosody_forward_ragged: bad arguments");
+  ST2_REQUIRE(N <= 512, "st2_prosody_forward_ragged: N=%d tokens exceed the 512 of PL-BERT's position table", N);
+  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+              "st2_prosody_forward_ragged: workspace must be 256-byte aligned");
+  Ctx c;
+  c.stream = stream;
+  c.a.base = static_cast<char*>(workspace);
+  c.a.cap = workspace_bytes;
+  const int rc = prosody_plan(c, *e, d_cm, t_en, durations, s, B, N, T_max, shift, asr, f0, n, frames);
+  ST2_REQUIRE(!c.a.overflow, "st2_prosody_forward_ragged: workspace of %lld B is too small (need %lld B, see "
               "st2_prosody_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
   return rc;
 }

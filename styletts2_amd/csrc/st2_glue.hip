@@ -1,6 +1,8 @@
 // Glue kernels between the big ones: everything the launch plans used to do with PyTorch elementwise ops (layout
 // changes, broadcasts, the sampler's time features, the duration head and the duration -> alignment expansion), so that
 // a module forward is HIP launches only and can be issued from C++ (st2_engine.hip) as well as from Python.
+#include <string.h>
+
 #include "st2_common.h"
 
 namespace {
@@ -106,10 +108,12 @@ __global__ __launch_bounds__(64) void duration_head_kernel(const float* __restri
 // writes are coalesced along t).
 __global__ __launch_bounds__(256) void expand_by_durations_kernel(const float* __restrict__ x, int64_t x_bs, int x_cs,
                                                                   const long long* __restrict__ dur, int N, int C,
-                                                                  int T, int shift, float* __restrict__ y,
-                                                                  int64_t y_bs, int y_cs, int* status) {
+                                                                  int T_max, int shift, float* __restrict__ y,
+                                                                  int64_t y_bs, int y_cs, int* status,
+                                                                  const int32_t* __restrict__ len) {
   __shared__ int cum[512];
   const int b = blockIdx.y;
+  const int T = len ? min(len[b], T_max) : T_max;  // ragged rows: this row's frame count, exact zeros after it
   const long long* db = dur + (int64_t)b * N;
   if (threadIdx.x < 64) {  // sequential-in-chunks inclusive scan by one wave (N <= 512)
     int carry = 0;
@@ -129,7 +133,13 @@ __global__ __launch_bounds__(256) void expand_by_durations_kernel(const float* _
   if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.z == 0 && cum[N - 1] != T)
     st2_raise_status(status, ST2_STATUS_DURATION_SUM);  // the caller's durations do not sum to the frame count it gave
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= T) return;
+  if (t >= T_max) return;
+  if (t >= T) {
+    const int c_hi = min(C, (int)(blockIdx.z + 1) * 64);
+    float* yb = y + (int64_t)b * y_bs + t;
+    for (int c = blockIdx.z * 64; c < c_hi; ++c) yb[(int64_t)c * y_cs] = 0.f;
+    return;
+  }
   const int ts = shift ? max(t - 1, 0) : t;
   int lo = 0, hi = N;  // first n with cum[n] > ts
   while (lo < hi) {
@@ -141,6 +151,23 @@ __global__ __launch_bounds__(256) void expand_by_durations_kernel(const float* _
   float* yb = y + (int64_t)b * y_bs + t;
   const int c_hi = min(C, (int)(blockIdx.z + 1) * 64);
   for (int c = blockIdx.z * 64; c < c_hi; ++c) yb[(int64_t)c * y_cs] = xb[(int64_t)c * x_cs];
+}
+
+// out[i][b] = (mul_i * frames[b] + add_i) / div_i: every per-row length of a ragged plan in one launch
+struct RaggedCoef {
+  int c[16][3];
+};
+__global__ __launch_bounds__(64) void ragged_lengths_kernel(const int32_t* __restrict__ frames, int B, int T_max, int n,
+                                                            const RaggedCoef k, int32_t* __restrict__ out) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  // clamped to 1..T_max: a caller's out-of-range frame count gives wrong rows, never a length past the buffers it sizes
+  const long long f = min(max(frames[b], 1), T_max);
+  for (int i = 0; i < n; ++i) {
+    const long long v = (long long)k.c[i][0] * f + k.c[i][1];
+    const long long d = k.c[i][2];
+    out[(int64_t)i * B + b] = (int32_t)(v >= 0 ? v / d : -((-v + d - 1) / d));
+  }
 }
 
 // x[b][c][l] = 0 for l >= len[b]  (the masked_fill_ of the text-side modules, models.py:308-312, 547-556)
@@ -262,12 +289,34 @@ extern "C" int st2_duration_head(const float* x, int64_t x_bs, int32_t x_cs, con
 extern "C" int st2_expand_by_durations(const float* x, int64_t x_bs, int32_t x_cs, const int64_t* dur, int32_t B,
                                        int32_t C, int32_t N, int32_t T, int32_t shift, float* y, int64_t y_bs,
                                        int32_t y_cs, void* stream) {
+  return st2_expand_by_durations_len(x, x_bs, x_cs, dur, B, C, N, T, shift, y, y_bs, y_cs, nullptr, stream);
+}
+
+extern "C" int st2_expand_by_durations_len(const float* x, int64_t x_bs, int32_t x_cs, const int64_t* dur, int32_t B,
+                                           int32_t C, int32_t N, int32_t T, int32_t shift, float* y, int64_t y_bs,
+                                           int32_t y_cs, const int32_t* len, void* stream) {
   ST2_REQUIRE(x && dur && y && B > 0 && C > 0 && N > 0 && T > 0, "st2_expand_by_durations: bad arguments");
   ST2_REQUIRE(N <= 512, "st2_expand_by_durations: N=%d tokens exceed the 512 of PL-BERT's position table", N);
   ST2_REQUIRE(B <= 65535, "st2_expand_by_durations: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(expand_by_durations_kernel, dim3(st2_cdiv(T, 256), B, st2_cdiv(C, 64)), dim3(256), 0, s, x, x_bs, x_cs,
-                     reinterpret_cast<const long long*>(dur), N, C, T, shift, y, y_bs, y_cs, st2_status_device_ptr());
+                     reinterpret_cast<const long long*>(dur), N, C, T, shift, y, y_bs, y_cs, st2_status_device_ptr(),
+                     len);
   ST2_CHECK_LAUNCH("st2_expand_by_durations");
+  return 0;
+}
+
+extern "C" int st2_ragged_lengths(const int32_t* frames, int32_t B, int32_t T_max, int32_t n, const int32_t* coef, int32_t* out,
+                                  void* stream) {
+  ST2_REQUIRE(frames && coef && out && B > 0 && T_max > 0 && n > 0 && n <= 16, "st2_ragged_lengths: bad arguments");
+  RaggedCoef k;
+  memset(&k, 0, sizeof(k));
+  for (int i = 0; i < n; ++i) {
+    ST2_REQUIRE(coef[3 * i + 2] > 0, "st2_ragged_lengths: divisor %d of length %d", coef[3 * i + 2], i);
+    for (int j = 0; j < 3; ++j) k.c[i][j] = coef[3 * i + j];
+  }
+  hipLaunchKernelGGL(ragged_lengths_kernel, dim3(st2_cdiv(B, 64)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), frames, B,
+                     T_max, n, k, out);
+  ST2_CHECK_LAUNCH("st2_ragged_lengths");
   return 0;
 }

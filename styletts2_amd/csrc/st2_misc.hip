@@ -10,12 +10,19 @@ namespace {
 __global__ __launch_bounds__(256) void conv1d_direct_kernel(const float* __restrict__ x, int64_t x_bs, int x_cs,
                                                             const float* __restrict__ w,
                                                             const float* __restrict__ bias, float* __restrict__ y,
-                                                            int64_t y_bs, int y_cs, int C_in, int L_in, int L_out,
-                                                            int ks, int stride, int pad) {
+                                                            int64_t y_bs, int y_cs, int C_in, int L_in_max, int L_out,
+                                                            int ks, int stride, int pad, const int32_t* __restrict__ x_len,
+                                                            const int32_t* __restrict__ y_len) {
   const int l = blockIdx.x * 256 + threadIdx.x;
   const int co = blockIdx.y;
   const int b = blockIdx.z;
   if (l >= L_out) return;
+  // ragged rows: the input row ends (zero padding) at x_len[b]; outputs at or past y_len[b] are written as exact zeros
+  const int L_in = x_len ? min(x_len[b], L_in_max) : L_in_max;
+  if (y_len && l >= y_len[b]) {
+    y[(int64_t)b * y_bs + (int64_t)co * y_cs + l] = 0.f;
+    return;
+  }
   const float* xb = x + (int64_t)b * x_bs;
   const float* wc = w + (int64_t)co * C_in * ks;
   float acc = 0.f;
@@ -60,18 +67,23 @@ constexpr int CVT_TILE = 1024;
 // of the added tensor when the rows are aligned) and the divisions are by constants.
 template <int S>
 __global__ __launch_bounds__(256) void convt_interleave_kernel(const float* __restrict__ ph, int64_t p_bs, int p_cs,
-                                                               int Lq, const float* __restrict__ bias,
+                                                               const float* __restrict__ bias,
                                                                const float* __restrict__ add, int64_t a_bs, int a_cs,
                                                                float* __restrict__ out, int64_t o_bs, int o_cs, int C,
-                                                               int stride_rt, int pad, int L_raw, int reflect_left,
-                                                               float* __restrict__ part, int part_nt) {
+                                                               int stride_rt, int pad, int L_raw_max, int reflect_left,
+                                                               float* __restrict__ part, int part_nt, int Lq_max,
+                                                               const int32_t* __restrict__ q_len,
+                                                               const int32_t* __restrict__ out_len) {
   extern __shared__ float cvt_tile[];  // [stride][nqp]
   __shared__ float red[2][4];
   const int stride = S ? S : stride_rt;
   const int co = blockIdx.y;
   const int b = blockIdx.z;
-  const int L_out = L_raw + reflect_left;
+  // ragged rows: row b has q_len[b] phase columns and out_len[b] outputs; tiles wholly past them exit before any barrier
+  const int L_out = out_len ? min(out_len[b], L_raw_max + reflect_left) : L_raw_max + reflect_left;
+  const int Lq = q_len ? min(q_len[b], Lq_max) : Lq_max;
   const int o0 = blockIdx.x * CVT_TILE;
+  if (o0 >= L_out) return;
   const int nq = CVT_TILE / stride + 3;
   const int nqp = nq | 1;  // odd row pitch: the de-interleaving reads spread over the banks
   // raw positions this tile touches: l in [l_lo, l_lo + CVT_TILE] (one extra on the left for the reflected sample)
@@ -177,10 +189,13 @@ __global__ __launch_bounds__(256) void adain_leaky_pool_kernel(const float* __re
                                                                const float* __restrict__ beta, int64_t gb_bs,
                                                                float slope, const float* __restrict__ w,
                                                                const float* __restrict__ bias, float* __restrict__ y,
-                                                               int64_t y_bs, int y_cs, int C, int L) {
+                                                               int64_t y_bs, int y_cs, int C, int L_max,
+                                                               const int32_t* __restrict__ len) {
   const int lo = blockIdx.x * 256 + threadIdx.x;
   const int c = blockIdx.y;
   const int b = blockIdx.z;
+  // ragged rows: the input row ends (the pool's zero padding) at len[b]; outputs past 2 * len[b] are not written
+  const int L = len ? min(len[b], L_max) : L_max;
   if (lo >= 2 * L) return;
   const float mean = stats[((int64_t)b * C + c) * 2 + 0];
   const float rstd = stats[((int64_t)b * C + c) * 2 + 1];
@@ -248,12 +263,20 @@ extern "C" int st2_conv1d_direct(const float* x, int64_t x_bs, int32_t x_cs, con
                                  float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C_in, int32_t C_out,
                                  int32_t L_in, int32_t L_out, int32_t ks, int32_t stride, int32_t pad,
                                  void* stream) {
+  return st2_conv1d_direct_len(x, x_bs, x_cs, w, bias, y, y_bs, y_cs, B, C_in, C_out, L_in, L_out, ks, stride, pad, nullptr,
+                               nullptr, stream);
+}
+
+extern "C" int st2_conv1d_direct_len(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias,
+                                     float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C_in, int32_t C_out,
+                                     int32_t L_in, int32_t L_out, int32_t ks, int32_t stride, int32_t pad,
+                                     const int32_t* x_len, const int32_t* y_len, void* stream) {
   ST2_REQUIRE(x && w && y && B > 0 && C_in > 0 && C_out > 0 && L_in > 0 && L_out > 0 && ks > 0 && stride > 0,
               "st2_conv1d_direct: bad arguments");
   ST2_REQUIRE(C_out <= 65535 && B <= 65535, "st2_conv1d_direct: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(conv1d_direct_kernel, dim3(st2_cdiv(L_out, 256), C_out, B), dim3(256), 0, s, x, x_bs, x_cs, w,
-                     bias, y, y_bs, y_cs, C_in, L_in, L_out, ks, stride, pad);
+                     bias, y, y_bs, y_cs, C_in, L_in, L_out, ks, stride, pad, x_len, y_len);
   ST2_CHECK_LAUNCH("st2_conv1d_direct");
   return 0;
 }
@@ -284,6 +307,16 @@ extern "C" int st2_convt_interleave_stats(const float* phases, int64_t p_bs, int
                                           int64_t o_bs, int32_t o_cs, int32_t B, int32_t C, int32_t stride, int32_t pad,
                                           int32_t L_raw, int32_t reflect_left, float* part, int32_t part_nt,
                                           void* stream) {
+  return st2_convt_interleave_stats_len(phases, p_bs, p_cs, Lq, bias, add, a_bs, a_cs, out, o_bs, o_cs, B, C, stride, pad, L_raw,
+                                        reflect_left, part, part_nt, nullptr, nullptr, stream);
+}
+
+extern "C" int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs, int32_t p_cs, int32_t Lq,
+                                              const float* bias, const float* add, int64_t a_bs, int32_t a_cs, float* out,
+                                              int64_t o_bs, int32_t o_cs, int32_t B, int32_t C, int32_t stride, int32_t pad,
+                                              int32_t L_raw, int32_t reflect_left, float* part, int32_t part_nt,
+                                              const int32_t* q_len, const int32_t* out_len, void* stream) {
+  ST2_REQUIRE(!q_len == !out_len, "st2_convt_interleave_stats_len: q_len and out_len go together");
   ST2_REQUIRE(phases && out && B > 0 && C > 0 && stride > 0 && L_raw > 0 && Lq > 0,
               "st2_convt_interleave: bad arguments");
   ST2_REQUIRE(reflect_left == 0 || (reflect_left == 1 && L_raw >= 2), "st2_convt_interleave: bad reflect_left");
@@ -297,8 +330,8 @@ extern "C" int st2_convt_interleave_stats(const float* phases, int64_t p_bs, int
   const int nq = CVT_TILE / stride + 3;
   const size_t smem = (size_t)stride * (nq | 1) * sizeof(float);
 #define ST2_CVT_LAUNCH(SV)                                                                                              \
-  hipLaunchKernelGGL((convt_interleave_kernel<SV>), dim3(nt, C, B), dim3(256), smem, s, phases, p_bs, p_cs, Lq, bias, add, \
-                     a_bs, a_cs, out, o_bs, o_cs, C, stride, pad, L_raw, reflect_left, part, part_nt)
+  hipLaunchKernelGGL((convt_interleave_kernel<SV>), dim3(nt, C, B), dim3(256), smem, s, phases, p_bs, p_cs, bias, add, \
+                     a_bs, a_cs, out, o_bs, o_cs, C, stride, pad, L_raw, reflect_left, part, part_nt, Lq, q_len, out_len)
   switch (stride) {  // the up-sampling rates of the two vocoders as compile-time constants, anything else generic
     case 2: ST2_CVT_LAUNCH(2); break;
     case 3: ST2_CVT_LAUNCH(3); break;
@@ -316,11 +349,19 @@ extern "C" int st2_adain_leaky_pool(const float* x, int64_t x_bs, int32_t x_cs, 
                                     const float* gamma, const float* beta, int64_t gb_bs, float slope, const float* w,
                                     const float* bias, float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C,
                                     int32_t L, void* stream) {
+  return st2_adain_leaky_pool_len(x, x_bs, x_cs, stats, gamma, beta, gb_bs, slope, w, bias, y, y_bs, y_cs, B, C, L, nullptr,
+                                  stream);
+}
+
+extern "C" int st2_adain_leaky_pool_len(const float* x, int64_t x_bs, int32_t x_cs, const float* stats,
+                                        const float* gamma, const float* beta, int64_t gb_bs, float slope, const float* w,
+                                        const float* bias, float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C,
+                                        int32_t L, const int32_t* len, void* stream) {
   ST2_REQUIRE(x && stats && gamma && beta && w && y && B > 0 && C > 0 && L > 0,
               "st2_adain_leaky_pool: bad arguments");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(adain_leaky_pool_kernel, dim3(st2_cdiv(2 * L, 256), C, B), dim3(256), 0, s, x, x_bs, x_cs,
-                     stats, gamma, beta, gb_bs, slope, w, bias, y, y_bs, y_cs, C, L);
+                     stats, gamma, beta, gb_bs, slope, w, bias, y, y_bs, y_cs, C, L, len);
   ST2_CHECK_LAUNCH("st2_adain_leaky_pool");
   return 0;
 }

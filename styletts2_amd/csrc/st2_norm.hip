@@ -7,10 +7,13 @@ namespace {
 // One workgroup per (b, c) row.  Rows are up to 48 001 samples (generator) or 400/800 (decoder front).
 template <int NT>
 __global__ __launch_bounds__(NT) void instnorm_stats_kernel(const float* __restrict__ x, int64_t x_bs, int x_cs,
-                                                            int C, int L, float eps, float* __restrict__ stats) {
+                                                            int C, int L_max, float eps, float* __restrict__ stats,
+                                                            const int32_t* __restrict__ len) {
   const int row = blockIdx.x;
   const int b = row / C;
   const int c = row % C;
+  // ragged rows: the row's own valid columns only (len int32 [B], NULL = L_max)
+  const int L = len ? min(max(len[b], 1), L_max) : L_max;
   const float* xr = x + (int64_t)b * x_bs + (int64_t)c * x_cs;
   double s = 0.0, ss = 0.0;
   if ((reinterpret_cast<uintptr_t>(xr) & 15) == 0) {
@@ -25,6 +28,26 @@ __global__ __launch_bounds__(NT) void instnorm_stats_kernel(const float* __restr
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const double d = (double)v[e];
+        a[e] += d;
+        q[e] += d * d;
+      }
+    }
+    s = (a[0] + a[1]) + (a[2] + a[3]);
+    ss = (q[0] + q[1]) + (q[2] + q[3]);
+    for (int l = 4 * L4 + threadIdx.x; l < L; l += NT) {
+      const double v = (double)xr[l];
+      s += v;
+      ss += v * v;
+    }
+  } else if (len) {
+    // length-aware entry: the aligned path's order with scalar loads, so that a row's statistics do not depend on where the
+    // batch layout puts it (a ragged row and the same row of a uniform batch at its own length reduce in one order)
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    const int L4 = L >> 2;
+    for (int i = threadIdx.x; i < L4; i += NT) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)xr[4 * i + e];
         a[e] += d;
         q[e] += d * d;
       }
@@ -244,13 +267,18 @@ extern "C" int st2_colnorm_apply(const float* x, int64_t x_bs, int32_t x_cs, con
 
 extern "C" int st2_instnorm_stats(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
                                   float eps, float* stats, void* stream) {
+  return st2_instnorm_stats_len(x, x_bs, x_cs, B, C, L, eps, stats, nullptr, stream);
+}
+
+extern "C" int st2_instnorm_stats_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
+                                      float eps, float* stats, const int32_t* len, void* stream) {
   ST2_REQUIRE(x && stats && B > 0 && C > 0 && L > 0, "st2_instnorm_stats: bad arguments");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int rows = B * C;
   if (L <= 2048)
-    hipLaunchKernelGGL((instnorm_stats_kernel<64>), dim3(rows), dim3(64), 0, s, x, x_bs, x_cs, C, L, eps, stats);
+    hipLaunchKernelGGL((instnorm_stats_kernel<64>), dim3(rows), dim3(64), 0, s, x, x_bs, x_cs, C, L, eps, stats, len);
   else
-    hipLaunchKernelGGL((instnorm_stats_kernel<256>), dim3(rows), dim3(256), 0, s, x, x_bs, x_cs, C, L, eps, stats);
+    hipLaunchKernelGGL((instnorm_stats_kernel<256>), dim3(rows), dim3(256), 0, s, x, x_bs, x_cs, C, L, eps, stats, len);
   ST2_CHECK_LAUNCH("st2_instnorm_stats");
   return 0;
 }

@@ -78,39 +78,62 @@ int pack_predictor(st2_engine& e, Blob& blob, std::string* err) {
 // asr[B][dim_in][T] = expand(t_en), (F0, N)[B][2T] = F0Ntrain(expand(d), s); d_cm [B][pred_hidden + style_dim][N] is the
 // duration encoder's output channel-major, dur int64 [B][N] with rows summing to T
 int prosody_plan(Ctx& c, const st2_engine& e, const float* d_cm, const float* t_en, const int64_t* dur, const float* s_p,
-                 int B, int N, int T, int shift, float* asr, float* f0, float* nn) {
+                 int B, int N, int T, int shift, float* asr, float* f0, float* nn, const int32_t* frames = nullptr) {
   const st2_model_config& cfg = e.cfg;
   const PPredictor& p = e.pred;
   const int dh = cfg.pred_hidden, Cd = dh + cfg.style_dim, Ct = cfg.dim_in;
-  View en = new_ncl(c, B, Cd, T, false);
-  RUN(c, g_be.expand_by_durations(d_cm, (int64_t)Cd * N, N, dur, B, Cd, N, T, shift, en.p, en.bs, en.cs, c.stream));
-  RUN(c, g_be.expand_by_durations(t_en, (int64_t)Ct * N, N, dur, B, Ct, N, T, shift, asr, (int64_t)Ct * T, T, c.stream));
+  // ragged rows: T_b = frames[b] and 2 T_b (after the up-sampling block) per row
+  const int32_t* lenT = nullptr;
+  const int32_t* len2T = nullptr;
+  if (frames) {
+    const int32_t coef[6] = {1, 0, 1, 2, 0, 1};
+    int32_t* tab = static_cast<int32_t*>(c.a.alloc((int64_t)2 * B * 4));
+    RUN(c, g_be.ragged_lengths(frames, B, T, 2, coef, tab, c.stream));
+    lenT = tab;
+    len2T = tab + B;
+  }
+  View en = new_ncl(c, B, Cd, T, false).with_len(lenT);
+  if (frames) {  // exact zeros past T_b
+    RUN(c, g_be.expand_by_durations_len(d_cm, (int64_t)Cd * N, N, dur, B, Cd, N, T, shift, en.p, en.bs, en.cs, lenT, c.stream));
+    RUN(c, g_be.expand_by_durations_len(t_en, (int64_t)Ct * N, N, dur, B, Ct, N, T, shift, asr, (int64_t)Ct * T, T, lenT,
+                                        c.stream));
+  } else {
+    RUN(c, g_be.expand_by_durations(d_cm, (int64_t)Cd * N, N, dur, B, Cd, N, T, shift, en.p, en.bs, en.cs, c.stream));
+    RUN(c, g_be.expand_by_durations(t_en, (int64_t)Ct * N, N, dur, B, Ct, N, T, shift, asr, (int64_t)Ct * T, T, c.stream));
+  }
   // shared BiLSTM: input projection of every frame as one k = 1 conv, then the recurrence
   const int H = p.shared.H;
-  View G = new_ncl(c, B, 8 * H, T, false);
+  View G = new_ncl(c, B, 8 * H, T, false).with_len(lenT);
   {
     ConvOpt o;
     o.bias = e.F(p.shared.bias);
     conv(c, e, en, p.shared.w_ih, G, o);
   }
-  View y = new_ncl(c, B, 2 * H, T, false);
+  View y = new_ncl(c, B, 2 * H, T, false).with_len(lenT);
   const int64_t sb = st2_lstm_coop_scratch_bytes(B);
   void* scratch = sb > 0 ? c.a.alloc(sb) : nullptr;
-  RUN(c, g_be.lstm_bidir(G.p, G.bs, G.cs, e.F(p.shared.whh_t), nullptr, B, H, T, y.p, y.bs, y.cs, scratch, sb, c.stream));
+  // packed-sequence semantics: row b's recurrence runs over its own T_b frames (frames = the lengths; NULL = T)
+  RUN(c, g_be.lstm_bidir(G.p, G.bs, G.cs, e.F(p.shared.whh_t), lenT, B, H, T, y.p, y.bs, y.cs, scratch, sb, c.stream));
   float* h = c.a.f32((int64_t)B * p.J);
   RUN(c, g_be.style_fc(s_p, B, cfg.style_dim, e.F(p.bank_wt), e.F(p.bank_b), p.J, ST2_ACT_NONE, h, c.stream));
   DecRun r{c, e, h, p.J};
+  r.lenT = lenT;
+  r.len2T = len2T;
   for (int path = 0; path < 2; ++path) {
     const PAdainResBlk* blks = path ? p.n : p.f0;
     View t = y;
     for (int i = 0; i < 3; ++i) {
       View out = new_ncl(c, B, blks[i].dim_out, blks[i].upsample ? 2 * t.L : t.L, false);
       run_adain_resblk(r, blks[i], t, out);
-      t = out;
+      t = out.with_len(t.len && blks[i].upsample ? len2T : t.len);
     }
     float* dst = path ? nn : f0;
-    RUN(c, g_be.conv1d_direct(t.p, t.bs, t.cs, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), dst,
-                              (int64_t)t.L, t.L, B, t.C, 1, t.L, t.L, 1, 1, 0, c.stream));
+    if (frames)  // F0 / N: exact zeros past 2 T_b
+      RUN(c, g_be.conv1d_direct_len(t.p, t.bs, t.cs, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), dst,
+                                    (int64_t)t.L, t.L, B, t.C, 1, t.L, t.L, 1, 1, 0, t.len, t.len, c.stream));
+    else
+      RUN(c, g_be.conv1d_direct(t.p, t.bs, t.cs, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), dst,
+                                (int64_t)t.L, t.L, B, t.C, 1, t.L, t.L, 1, 1, 0, c.stream));
   }
   return c.rc;
 }

@@ -23,15 +23,18 @@ __device__ __forceinline__ float torch_remainder1(float x) {
 // dependent fp64 add and a store per iteration -- 250 us of pure latency per decoder call.)  The fp64 sums are exact to
 // ~1e-13 relative whatever the association (<= 2^10 terms of 24-bit values), far below the fp32 rounding of a prefix, so the
 // stored phases are those of the sequential scan.
-__global__ __launch_bounds__(64) void sinegen_phase_kernel(const float* __restrict__ f0, int B, int F, int U, int H,
-                                                           float sample_rate, float* __restrict__ phase_f) {
+// Ragged rows (f_len != NULL): row b holds f_len[b] frames in a row of F_max; only those are read and scanned.
+__global__ __launch_bounds__(64) void sinegen_phase_kernel(const float* __restrict__ f0, int B, int F_max, int U, int H,
+                                                           float sample_rate, float* __restrict__ phase_f,
+                                                           const int32_t* __restrict__ f_len) {
   const int row = blockIdx.x;  // (b, h)
   const int lane = threadIdx.x;
   const int b = row / H;
   const int h = row % H;
   const float mult = (float)(h + 1);
-  const float* f = f0 + (int64_t)b * F;
-  float* out = phase_f + ((int64_t)b * H + h) * F;
+  const int F = f_len ? min(f_len[b], F_max) : F_max;
+  const float* f = f0 + (int64_t)b * F_max;
+  float* out = phase_f + ((int64_t)b * H + h) * F_max;
   const float two_pi_part = 3.14159274101257324219f;  // (float)np.pi
   const float fu = (float)U;
   const int chunk = (F + 63) / 64;
@@ -59,17 +62,24 @@ __global__ __launch_bounds__(64) void sinegen_phase_kernel(const float* __restri
 }
 
 // ---- pass 2: sample-rate sines, U/V mix, noise, 9->1 linear, tanh ------------------------------
-__global__ __launch_bounds__(256) void har_source_kernel(const float* __restrict__ f0, int F, int U, int H,
+__global__ __launch_bounds__(256) void har_source_kernel(const float* __restrict__ f0, int F_max, int U, int H,
                                                          const float* __restrict__ noise,
                                                          const float* __restrict__ lin_w,
                                                          const float* __restrict__ lin_b, float sine_amp,
                                                          float noise_std, float voiced_threshold,
                                                          const float* __restrict__ phase_f,
-                                                         float* __restrict__ out) {
-  const int L = F * U;
+                                                         float* __restrict__ out, const int32_t* __restrict__ f_len) {
+  const int L_max = F_max * U;
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
-  if (t >= L) return;
+  if (t >= L_max) return;
+  // ragged rows: F frames / F * U samples of their own (the interpolation boundary is the row's end), exact zeros after
+  const int F = f_len ? min(f_len[b], F_max) : F_max;
+  const int L = F * U;
+  if (t >= L) {
+    out[(int64_t)b * L_max + t] = 0.f;
+    return;
+  }
   // F.interpolate(scale_factor=U, mode='linear', align_corners=False) source index, ATen-CPU form
   const float rs = (float)(1.0 / (double)U);
   float src = fmaf(rs, (float)t + 0.5f, -0.5f);
@@ -79,26 +89,29 @@ __global__ __launch_bounds__(256) void har_source_kernel(const float* __restrict
   const float w1 = src - (float)i0;
   const float w0 = 1.0f - w1;
 
-  const float f0v = f0[(int64_t)b * F + t / U];  // nearest x U up-sampling (istftnet.py:314,352)
+  const float f0v = f0[(int64_t)b * F_max + t / U];  // nearest x U up-sampling (istftnet.py:314,352)
   const float uv = f0v > voiced_threshold ? 1.0f : 0.0f;
   const float noise_amp = uv * noise_std + ((1.0f - uv) * sine_amp) / 3.0f;  // istftnet.py:241
 
-  const float* nz = noise + ((int64_t)b * L + t) * H;
+  const float* nz = noise + ((int64_t)b * L_max + t) * H;
   float acc = 0.f;
   for (int h = 0; h < H; ++h) {
-    const float* pf = phase_f + ((int64_t)b * H + h) * F;
+    const float* pf = phase_f + ((int64_t)b * H + h) * F_max;
     const float ph = fmaf(w0, pf[i0], w1 * pf[i1]);
     const float sine = sinf(ph) * sine_amp;
     const float sw = sine * uv + noise_amp * nz[h];
     acc = fmaf(lin_w[h], sw, acc);
   }
-  out[(int64_t)b * L + t] = tanhf(acc + lin_b[0]);
+  out[(int64_t)b * L_max + t] = tanhf(acc + lin_b[0]);
 }
 
 // ---- STFT: one thread per frame, N-point DFT by table (N <= 32) ---------------------------------
 constexpr int MAXN = 32;
-__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, int L, int N, int hop,
-                                                   float* __restrict__ har, int64_t har_bs, int har_cs) {
+// Ragged rows (len != NULL): row b is len[b] samples of a row of L_max, reflect-padded at its own end; its frames past
+// len[b] / hop + 1 are written as exact zeros.
+__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, int L_max, int N, int hop,
+                                                   float* __restrict__ har, int64_t har_bs, int har_cs,
+                                                   const int32_t* __restrict__ len) {
   __shared__ float tw_c[MAXN], tw_s[MAXN], win[MAXN];
   if (threadIdx.x < N) {
     // cospi/sinpi are exact at multiples of 1/2: the DC and Nyquist bins then have an exactly zero
@@ -109,11 +122,18 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
     win[threadIdx.x] = (float)(0.5 - 0.5 * cospi(a));
   }
   __syncthreads();
-  const int M = L / hop + 1;
   const int m = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
-  if (m >= M) return;
-  const float* xb = x + (int64_t)b * L;
+  if (m >= L_max / hop + 1) return;
+  const int L = len ? min(len[b], L_max) : L_max;
+  const int M = L / hop + 1;
+  const int NB = N / 2 + 1;
+  float* hb = har + (int64_t)b * har_bs + m;
+  if (m >= M) {
+    for (int k = 0; k < 2 * NB; ++k) hb[(int64_t)k * har_cs] = 0.f;
+    return;
+  }
+  const float* xb = x + (int64_t)b * L_max;
   float fr[MAXN];
   const int pad = N / 2;
 #pragma unroll
@@ -127,8 +147,6 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
       fr[n] = 0.f;
     }
   }
-  const int NB = N / 2 + 1;
-  float* hb = har + (int64_t)b * har_bs + m;
   for (int k = 0; k < NB; ++k) {
     float re = 0.f, im = 0.f;
     int idx = 0;
@@ -151,8 +169,11 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
 // done ONCE per (frame, bin) into LDS ([bin][frame], frames along the lanes): per sample it was repeated for every one
 // of the N/hop overlapping frames and N bins -- 20 x the sincos work at n_fft = 20, hop = 5.  Same values, same
 // accumulation order: the waveform is bitwise unchanged.
-__global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ sp, int64_t sp_bs, int sp_cs, int M,
-                                                    int N, int hop, float* __restrict__ wave, int64_t wave_bs, int FRP) {
+// Ragged rows (m_len != NULL): row b has m_len[b] frames of M_max; it emits hop * (m_len[b] - 1) samples normalised by the
+// window sum of that length, and exact zeros up to hop * (M_max - 1).
+__global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ sp, int64_t sp_bs, int sp_cs, int M_max,
+                                                    int N, int hop, float* __restrict__ wave, int64_t wave_bs, int FRP,
+                                                    const int32_t* __restrict__ m_len) {
   __shared__ float tw_c[MAXN], tw_s[MAXN], win[MAXN];
   extern __shared__ float ri[];  // [2][NB][FRP]: re, im of the frames m_base .. m_base + FR - 1
   if (threadIdx.x < N) {
@@ -163,9 +184,10 @@ __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ sp
     tw_s[threadIdx.x] = (float)sinpi(a);
     win[threadIdx.x] = (float)(0.5 - 0.5 * cospi(a));
   }
-  const int Lw = hop * (M - 1);
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
+  const int M = m_len ? min(max(m_len[b], 2), M_max) : M_max;
+  const int Lw = hop * (M - 1);
   const int NB = N / 2 + 1;
   const float* sb = sp + (int64_t)b * sp_bs;
   {  // frames touched by this workgroup's samples t0 .. t0 + 255
@@ -185,7 +207,10 @@ __global__ __launch_bounds__(256) void istft_kernel(const float* __restrict__ sp
     }
   }
   __syncthreads();
-  if (t >= Lw) return;
+  if (t >= Lw) {
+    if (t < hop * (M_max - 1)) wave[(int64_t)b * wave_bs + t] = 0.f;
+    return;
+  }
   const int tp = t + N / 2;  // position in the un-trimmed overlap-add buffer
   const int tp0 = (int)blockIdx.x * 256 + N / 2;  // (int: blockIdx is unsigned, tp0 - N + 1 must be able to go negative)
   const int m_base = (tp0 - N + 1 <= 0) ? 0 : (tp0 - N + hop) / hop;
@@ -227,33 +252,51 @@ extern "C" int st2_har_source(const float* f0, int32_t B, int32_t F, int32_t U, 
                               const float* lin_w, const float* lin_b, float sine_amp, float noise_std,
                               float voiced_threshold, float sample_rate, float* phase_scratch, float* out,
                               void* stream) {
+  return st2_har_source_len(f0, B, F, U, H, noise, lin_w, lin_b, sine_amp, noise_std, voiced_threshold, sample_rate,
+                            phase_scratch, out, nullptr, stream);
+}
+
+extern "C" int st2_har_source_len(const float* f0, int32_t B, int32_t F, int32_t U, int32_t H, const float* noise,
+                                  const float* lin_w, const float* lin_b, float sine_amp, float noise_std,
+                                  float voiced_threshold, float sample_rate, float* phase_scratch, float* out,
+                                  const int32_t* f_len, void* stream) {
   ST2_REQUIRE(f0 && noise && lin_w && lin_b && phase_scratch && out, "st2_har_source: null pointer");
   ST2_REQUIRE(B > 0 && F > 0 && U > 0 && H > 0 && H <= 64, "st2_har_source: bad geometry");
   ST2_REQUIRE((int64_t)F * U < (1LL << 31), "st2_har_source: utterance too long");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(sinegen_phase_kernel, dim3(B * H), dim3(64), 0, s, f0, B, F, U, H, sample_rate,
-                     phase_scratch);
+                     phase_scratch, f_len);
   ST2_CHECK_LAUNCH("st2_har_source(phase)");
   hipLaunchKernelGGL(har_source_kernel, dim3(st2_cdiv((int64_t)F * U, 256), B), dim3(256), 0, s, f0, F, U, H, noise,
-                     lin_w, lin_b, sine_amp, noise_std, voiced_threshold, phase_scratch, out);
+                     lin_w, lin_b, sine_amp, noise_std, voiced_threshold, phase_scratch, out, f_len);
   ST2_CHECK_LAUNCH("st2_har_source");
   return 0;
 }
 
 extern "C" int st2_stft_mag_phase(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop, float* har,
                                   int64_t har_bs, int32_t har_cs, void* stream) {
+  return st2_stft_mag_phase_len(x, B, L, n_fft, hop, har, har_bs, har_cs, nullptr, stream);
+}
+
+extern "C" int st2_stft_mag_phase_len(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop, float* har,
+                                      int64_t har_bs, int32_t har_cs, const int32_t* len, void* stream) {
   ST2_REQUIRE(x && har && B > 0 && L > 0, "st2_stft_mag_phase: bad arguments");
   ST2_REQUIRE(n_fft >= 2 && n_fft <= MAXN && (n_fft % 2) == 0 && hop > 0 && L > n_fft / 2,
               "st2_stft_mag_phase: n_fft=%d hop=%d L=%d unsupported", n_fft, hop, L);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int M = L / hop + 1;
-  hipLaunchKernelGGL(stft_kernel, dim3(st2_cdiv(M, 256), B), dim3(256), 0, s, x, L, n_fft, hop, har, har_bs, har_cs);
+  hipLaunchKernelGGL(stft_kernel, dim3(st2_cdiv(M, 256), B), dim3(256), 0, s, x, L, n_fft, hop, har, har_bs, har_cs, len);
   ST2_CHECK_LAUNCH("st2_stft_mag_phase");
   return 0;
 }
 
 extern "C" int st2_istft(const float* sp, int64_t sp_bs, int32_t sp_cs, int32_t B, int32_t M, int32_t n_fft,
                          int32_t hop, float* wave, int64_t wave_bs, void* stream) {
+  return st2_istft_len(sp, sp_bs, sp_cs, B, M, n_fft, hop, wave, wave_bs, nullptr, stream);
+}
+
+extern "C" int st2_istft_len(const float* sp, int64_t sp_bs, int32_t sp_cs, int32_t B, int32_t M, int32_t n_fft,
+                             int32_t hop, float* wave, int64_t wave_bs, const int32_t* m_len, void* stream) {
   ST2_REQUIRE(sp && wave && B > 0 && M > 1, "st2_istft: bad arguments");
   ST2_REQUIRE(n_fft >= 2 && n_fft <= MAXN && (n_fft % 2) == 0 && hop > 0 && (n_fft % hop) == 0,
               "st2_istft: n_fft=%d hop=%d unsupported", n_fft, hop);
@@ -262,7 +305,7 @@ extern "C" int st2_istft(const float* sp, int64_t sp_bs, int32_t sp_cs, int32_t 
   const int FRP = (256 / hop + n_fft / hop + 3) | 1;  // frames a 256-sample tile can touch, odd pitch
   const size_t smem = (size_t)2 * (n_fft / 2 + 1) * FRP * sizeof(float);
   hipLaunchKernelGGL(istft_kernel, dim3(st2_cdiv(Lw, 256), B), dim3(256), smem, s, sp, sp_bs, sp_cs, M, n_fft, hop, wave,
-                     wave_bs, FRP);
+                     wave_bs, FRP, m_len);
   ST2_CHECK_LAUNCH("st2_istft");
   return 0;
 }

@@ -338,11 +338,12 @@ class Decoder(nn.Module):
         return pk
 
     @torch.no_grad()
-    def forward(self, asr, F0_curve, N, s, noise=None, har=None, taps=None):
+    def forward(self, asr, F0_curve, N, s, noise=None, har=None, taps=None, frames=None):
         """`noise` [B, 600*T, 9] replaces the reference's in-forward `torch.randn_like` draw
         (Modules/istftnet.py:242) so parity runs can replay the oracle's tensor; `har` injects the
         harmonic STFT features (tap-point protocol); `taps` (dict) collects
-        intermediates."""
+        intermediates.  `frames` (int32 device tensor or list of B ints): a ragged batch padded to T, every row
+        computed as if alone (C++ engine only)."""
         if self.training:
             raise RuntimeError("the MI355X engine is inference-only; call .eval() (reference: istftnet.py:500-508 "
                                "is the training-only F0/N smoothing)")
@@ -354,7 +355,10 @@ class Decoder(nn.Module):
             if eng is None or not engine.same_device(eng, dev):
                 engine.replaced(eng, "decoder")
                 eng = self._eng = engine.build_decoder_engine(self, dev)
-            return eng.decoder_forward(asr, F0_curve, N, s, noise=noise, har=har, taps=taps)
+            return eng.decoder_forward(asr, F0_curve, N, s, noise=noise, har=har, taps=taps, frames=frames)
+        if frames is not None:
+            raise RuntimeError("Decoder.forward(frames=...): the ragged decoder exists only in the C++ engine "
+                               "(plan_mode 'engine', f16s convs on a HIP device)")
         pk = self._pk if (self._pk is not None and self._pk.device == dev) else self._prepare(dev)
         bank = pk.bank
         asr = asr.float().contiguous()

@@ -45,6 +45,21 @@ def live_engines():
     return [e for e in _LIVE if getattr(e, "h", None)]
 
 
+def ragged_frames(frames, B, T, dev):
+    """Per-row frame counts of a ragged call as an int32 [B] tensor on `dev` (None stays None).  A list is checked and
+    uploaded here, once, before the call is issued; a tensor is used as it is (no host read: legal under graph capture)."""
+    if frames is None:
+        return None
+    if isinstance(frames, torch.Tensor):
+        if frames.shape != (B,):
+            raise ValueError("frames must have shape (%d,), got %s" % (B, tuple(frames.shape)))
+        return frames.to(device=dev, dtype=torch.int32).contiguous()
+    frames = [int(f) for f in frames]
+    if len(frames) != B or not all(1 <= f <= T for f in frames):
+        raise ValueError("frames must be %d ints in 1..%d, got %r" % (B, T, frames))
+    return torch.tensor(frames, dtype=torch.int32).to(dev)
+
+
 def norm_device(dev):
     """torch.device with its index filled in: 'cuda', 'cuda:0', torch.device('cuda') and a tensor's .device all name the
     same engine (advisor, round 5: a cache keyed on the caller's spelling rebuilt the engine -- a full repack and upload --
@@ -146,9 +161,15 @@ class Engine:
         self.device = device
 
     # -- decoder ---------------------------------------------------------------------------------------------------
-    def decoder_forward(self, asr, F0, N, s, noise=None, har=None, taps=None):
+    def decoder_forward(self, asr, F0, N, s, noise=None, har=None, taps=None, frames=None):
+        """wave [B, 1, 600 T] = Decoder(asr [B, dim_in, T], F0 / N [B, 2T], s).  `frames` (int32 device tensor or list of
+        B ints in 1..T, optional): a ragged batch -- row b is the utterance of frames[b] frames padded to T, computed as if
+        alone (`st2_decoder_forward_ragged`), its wave exactly 0 from 600 frames[b] on."""
         B, Cin, T = asr.shape
         dev = asr.device
+        frames = ragged_frames(frames, B, T, dev)
+        if frames is not None and taps is not None:
+            raise ValueError("decoder_forward: taps are not supported with frames= (ragged batch)")
         cfg = self.cfg
         rates = [cfg.upsample_rates[i] for i in range(cfg.n_upsamples)]
         up = math.prod(rates) * (cfg.gen_istft_hop if cfg.decoder_kind == 0 else 1)
@@ -191,11 +212,19 @@ class Engine:
                 else:
                     setattr(tp, k, v.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_decoder_forward(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(),
-                                                0 if noise is None else noise.data_ptr(),
-                                                0 if har is None else har.data_ptr(), B, T, wave.data_ptr(),
-                                                ws_ptr, nbytes, None if tp is None else C.byref(tp), stream),
-                   "st2_decoder_forward")
+        if frames is None:
+            _lib.check(self.lib.st2_decoder_forward(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(),
+                                                    0 if noise is None else noise.data_ptr(),
+                                                    0 if har is None else har.data_ptr(), B, T, wave.data_ptr(),
+                                                    ws_ptr, nbytes, None if tp is None else C.byref(tp), stream),
+                       "st2_decoder_forward")
+        else:
+            _lib.check(self.lib.st2_decoder_forward_ragged(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(),
+                                                           0 if noise is None else noise.data_ptr(),
+                                                           0 if har is None else har.data_ptr(), frames.data_ptr(), B, T,
+                                                           wave.data_ptr(), ws_ptr, nbytes,
+                                                           None, stream),
+                       "st2_decoder_forward_ragged")
         if taps is not None:
             taps.update(bufs)
             if cfg.decoder_kind == 0:
@@ -205,11 +234,14 @@ class Engine:
         return wave
 
     # -- prosody (alignment expansion + F0Ntrain) --------------------------------------------------------------------
-    def prosody_forward(self, d_cm, t_en, durations, s, T, shift=False):
+    def prosody_forward(self, d_cm, t_en, durations, s, T, shift=False, frames=None):
         """d_cm [B, d_hid + sty, N], t_en [B, dim_in, N], durations int64 [B, N] (rows summing to T), s [B, sty] ->
-        (asr [B, dim_in, T], F0 [B, 2T], N [B, 2T]): one `st2_prosody_forward` call."""
+        (asr [B, dim_in, T], F0 [B, 2T], N [B, 2T]): one `st2_prosody_forward` call.  `frames` (int32 device tensor or
+        list of B ints in 1..T, optional): a ragged batch whose row b's durations sum to frames[b]; each row is computed
+        as if alone (`st2_prosody_forward_ragged`), asr exactly 0 from frames[b] on, F0 / N from 2 frames[b] on."""
         B, Cd, N = d_cm.shape
         dev = d_cm.device
+        frames = ragged_frames(frames, B, T, dev)
         d_cm, t_en, s = (t.float().contiguous() for t in (d_cm, t_en, s))
         durations = durations.long().contiguous()
         assert t_en.shape == (B, self.cfg.dim_in, N) and durations.shape == (B, N)
@@ -223,9 +255,15 @@ class Engine:
         ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
         ws_ptr = (ws.data_ptr() + 255) & ~255
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_prosody_forward(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(), s.data_ptr(),
-                                                B, N, T, 1 if shift else 0, asr.data_ptr(), f0.data_ptr(), nn_.data_ptr(),
-                                                ws_ptr, nbytes, stream), "st2_prosody_forward")
+        if frames is None:
+            _lib.check(self.lib.st2_prosody_forward(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(),
+                                                    s.data_ptr(), B, N, T, 1 if shift else 0, asr.data_ptr(), f0.data_ptr(),
+                                                    nn_.data_ptr(), ws_ptr, nbytes, stream), "st2_prosody_forward")
+        else:
+            _lib.check(self.lib.st2_prosody_forward_ragged(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(),
+                                                           s.data_ptr(), frames.data_ptr(), B, N, T, 1 if shift else 0,
+                                                           asr.data_ptr(), f0.data_ptr(), nn_.data_ptr(), ws_ptr, nbytes,
+                                                           stream), "st2_prosody_forward_ragged")
         return asr, f0, nn_
 
     # -- text encoder --------------------------------------------------------------------------------------------------

@@ -324,7 +324,8 @@ class GraphedFront:
 @torch.no_grad()
 def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
             ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, lj_tail=None, s_prev=None, t=0.7,
-            taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False):
+            taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False,
+            ragged_decode=False):
     """Everything in front of the decoder: text encoder, PL-BERT, style diffusion, style mixing, duration and
     prosody prediction, alignment expansion.  Returns the decoder's inputs {asr, F0, N, ref} plus the mixed style
     vector `s_pred` [B, 256] (what LFinference hands to the next sentence) and the durations.
@@ -348,7 +349,12 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
 
     `carry`: the rows are consecutive sentences of one passage (`_front_core`); `s_prev` is then [1, 256] or None.
     `group_events`: every entry of `groups` also carries `ready`, an event recorded on the current stream behind that group's
-    last kernel (a consumer on another stream starts on group 0 while the later groups are still being expanded)."""
+    last kernel (a consumer on another stream starts on group 0 while the later groups are still being expanded).
+
+    `ragged_decode` (with `allow_ragged`, C++ engine path): utterances of different frame counts are NOT split into groups;
+    ONE ragged prosody call (`st2_prosody_forward_ragged`) returns {asr, F0, N, ref} padded to the longest utterance plus
+    `frames` (int32 [B] on the device) and `frames_host` (list), which `model.decoder(..., frames=)` decodes in one call, every
+    row as if alone."""
     dev = tokens.device
     B, N = tokens.shape
     ops.check_status() if dev.type == "cuda" else None  # device-side conditions raised by the previous call's kernels
@@ -422,6 +428,16 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     if not allow_ragged:
         raise ValueError("utterances of one call must have equal total duration; bucket them, pass `durations`, or "
                          "use inference() which decodes per frame count (frames per utterance: %s)" % tot)
+    if ragged_decode:
+        if not _engine_path(dev, taps):
+            raise ValueError("ragged_decode needs the C++ engine path (HIP device, plan_mode 'engine', no taps)")
+        T_max = int(max(tot))
+        frames_host = [int(v) for v in tot]
+        frames = torch.tensor(frames_host, dtype=torch.int32).to(dev)  # once per batch, before the prosody call is issued
+        asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d_cm, t_en, durations, s, T_max, shift=hifigan,
+                                                                         frames=frames)
+        out.update(asr=asr, F0=F0_pred, N=N_pred, frames=frames, frames_host=frames_host)
+        return out
     groups = {}
     for b, T in enumerate(tot):
         groups.setdefault(int(T), []).append(b)
@@ -435,10 +451,31 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     return out
 
 
+def _decode_ragged(model, p, sine_noise=None, noise_rows=None):
+    """One ragged decoder call over prepare(ragged_decode=True)'s padded batch -> list of [1, 600 T_b] waveforms.
+    `sine_noise`: per-utterance SineGen draws (each >= 600 T_b samples), zero-padded here to the batch's T_max."""
+    tot = p["frames_host"]
+    T_max = p["asr"].shape[-1]
+    sn = None
+    if sine_noise is not None and noise_rows is None and torch.is_tensor(sine_noise) and sine_noise.dim() == 3 \
+            and sine_noise.shape[0] == len(tot) and sine_noise.shape[1] >= 600 * T_max:
+        sn = sine_noise[:, :600 * T_max]  # the batch's own rows: a view (the decoder reads each only up to 600 T_b)
+    elif sine_noise is not None:
+        rows = [sine_noise[b] for b in range(len(tot))] if noise_rows is None else noise_rows
+        # rows of different lengths (one per sentence): stacked into the T_max layout; past 600 T_b nothing is read, so
+        # the buffer is not cleared
+        sn = torch.empty((len(tot), 600 * T_max, rows[0].shape[-1]), device=p["asr"].device, dtype=torch.float32)
+        for b, n in enumerate(rows):
+            sn[b, :600 * tot[b]] = n[:600 * tot[b]]
+    w = model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sn, frames=p["frames"])
+    return [w[b, :, :600 * tot[b]] for b in range(len(tot))]
+
+
 @torch.no_grad()
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
-              taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None):
+              taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
+              ragged_decode=False):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -463,11 +500,15 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     on the current one; the current stream waits for all of them before the call returns.  One utterance's decoder launches
     grids of 2 x 23 tiles for 256 CUs: two or three of them fill each other's idle CUs (the long-form path does the same,
     `synthesize_long(decode_streams=)`).  Bitwise the sequential result.
+
+    `ragged_decode=True`: a batch of different frame counts takes ONE ragged prosody call and ONE ragged decoder call
+    (`prepare(ragged_decode=True)`) instead of one pair per frame count; the waveforms come back as the
+    same list, each row sliced to its own 600 T_b samples (`decode_streams` is then moot).
     """
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
-              front=front)
+              front=front, ragged_decode=ragged_decode)
     if front_stream is None:
         p = prepare(model, sampler, tokens, **kw)
     else:
@@ -480,8 +521,10 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
             ready.record(front_stream)
         main.wait_event(ready)
         for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]):
-            for v in (g["asr"], g["F0"], g["N"], g["ref"]):
+            for v in (g["asr"], g["F0"], g["N"], g["ref"]) + ((g["frames"],) if "frames" in g else ()):
                 v.record_stream(main)  # allocated on the front stream, consumed on the main stream
+    if "frames" in p:
+        return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
         return model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sine_noise)
     waves = [None] * tokens.shape[0]
@@ -518,7 +561,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
 @torch.no_grad()
 def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, t=0.7, diffusion_steps=5,
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
-                    overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1):
+                    overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
+                    ragged_decode=False):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -554,6 +598,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     everywhere: packed-sequence BiLSTMs, key-padded attention, length-aware mean -- results are those of the un-padded
     sentence), so that a `GraphedSampler` (models.make_sampler(graph=True)) replays ONE captured hipGraph per bucket
     instead of capturing one per sentence length.
+
+    `ragged_decode=True`: every front group's sentences take ONE ragged prosody call and ONE ragged decoder call on the
+    caller's stream (`prepare(ragged_decode=True)`, DESIGN.md section 10) instead of one pair per distinct frame count;
+    `decode_streams` is then moot.
     """
     dev = sentences[0].device
     multispeaker = ref_s is not None
@@ -626,7 +674,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
         kw = dict(input_lengths=q["lengths"], noise=q["noise"], diffusion_steps=diffusion_steps,
                   embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta, lj_tail=False, s_prev=s_prev, t=t,
                   step_noise=q["step_noise"], durations=q["dur"], total_frames=q["frames"], lengths_dev=q["lens_dev"],
-                  front=front, carry=len(ids) > 1, allow_ragged=True, group_events=use_streams and len(ids) > 1)
+                  front=front, carry=len(ids) > 1, allow_ragged=True, group_events=use_streams and len(ids) > 1,
+                  ragged_decode=ragged_decode)
         if use_streams:
             with torch.cuda.stream(side):
                 p = prepare(model, sampler, q["tokens"], **kw)
@@ -635,6 +684,19 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
         else:
             p = prepare(model, sampler, q["tokens"], **kw)
         s_prev = p["s_pred"][-1:]
+        if "frames" in p:  # one ragged decoder call for the whole front group, on the caller's stream
+            if use_streams:
+                main.wait_event(ready)
+                for v in (p["asr"], p["F0"], p["N"], p["ref"], p["frames"]):
+                    v.record_stream(main)  # allocated on the side stream, consumed on the caller's
+            rows = None if sine_noises is None else [sine_noises[k].reshape(-1, sine_noises[k].shape[-1]) for k in ids]
+            ws = _decode_ragged(model, p, sine_noise=rows, noise_rows=rows)
+            for j, w in enumerate(ws):
+                wave = w.reshape(-1)
+                waves[ids[j]] = wave[:-trim] if trim else wave
+                done[ids[j]] = None
+            emitted = emit(emitted)
+            continue
         groups = p["groups"] if "groups" in p else [(list(range(len(ids))), p)]
         for idx, g in groups:  # one decoder call per distinct frame count, in the order of each group's first sentence
             ds = dec[n_dec % len(dec)] if dec else main
