@@ -216,7 +216,7 @@ int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t
                   void* xs, int32_t xs_cg, int32_t Lp, int32_t halo, void* stream);
 int st2_conv1d_xs(const st2_conv_desc* d, void* stream);
 /* Ragged rows (ABI v23): as st2_act_split, with row b ending at len[b] <= L (int32 [B] on the device; NULL = L): positions at or
- * past it are written as zeros after the prologue.  Not defined for ST2_PRO_COLNORM. */
+ * past it are written as zeros after the prologue; values above L are clamped.  Not defined for ST2_PRO_COLNORM. */
 int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L,
                       int32_t pro, float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
                       int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale,
@@ -305,8 +305,9 @@ int st2_convt_interleave_stats(const float* phases, int64_t p_bs, int32_t p_cs, 
                                int32_t B, int32_t C, int32_t stride, int32_t pad, int32_t L_raw,
                                int32_t reflect_left, float* part, int32_t part_nt, void* stream);
 /* Ragged rows (ABI v23): row b has q_len[b] <= Lq phase columns (the rest is the transposed conv's zero padding) and
- * out_len[b] <= L_raw + reflect_left outputs; tiles wholly past out_len[b] exit, partial sums cover only its columns.  Both
- * int32 [B] on the device, both NULL or both set. */
+ * out_len[b] <= L_raw + reflect_left outputs; tiles wholly past out_len[b] exit, partial sums cover only its columns, outputs
+ * past out_len[b] are left as the memory held them (st2_stats_finalize_len with len_div = C).  Both int32 [B] on the device,
+ * both NULL or both set. */
 int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs, int32_t p_cs, int32_t Lq,
                                    const float* bias, const float* add, int64_t a_bs, int32_t a_cs,
                                    float* out, int64_t o_bs, int32_t o_cs,
@@ -321,7 +322,8 @@ int st2_adain_leaky_pool(const float* x, int64_t x_bs, int32_t x_cs,
                          float slope, const float* w, const float* bias,
                          float* y, int64_t y_bs, int32_t y_cs,
                          int32_t B, int32_t C, int32_t L, void* stream);
-/* Ragged rows (ABI v23): row b of the input ends (zero padding) at len[b] <= L; 2 * len[b] outputs are written. */
+/* Ragged rows (ABI v23): row b of the input ends (zero padding) at len[b] <= L; 2 * len[b] outputs are written, the rest of
+ * the row is left as the memory held it. */
 int st2_adain_leaky_pool_len(const float* x, int64_t x_bs, int32_t x_cs,
                              const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
                              float slope, const float* w, const float* bias,
@@ -353,7 +355,8 @@ int st2_har_source_len(const float* f0, int32_t B, int32_t F, int32_t U, int32_t
 int st2_stft_mag_phase(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop,
                        float* har, int64_t har_bs, int32_t har_cs, void* stream);
 /* Ragged rows (ABI v23): row b is len[b] <= L samples of a row of L, reflect-padded at its own end; frames m > len[b] / hop
- * are exact zeros. */
+ * are exact zeros.  len[b] is clamped to n_fft / 2 + 1 .. L (the reflection needs more samples than n_fft / 2, as
+ * torch's reflect pad does): a shorter row gives the result of its first n_fft / 2 + 1 samples. */
 int st2_stft_mag_phase_len(const float* x, int32_t B, int32_t L, int32_t n_fft, int32_t hop,
                            float* har, int64_t har_bs, int32_t har_cs, const int32_t* len, void* stream);
 

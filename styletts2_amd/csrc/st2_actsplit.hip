@@ -40,7 +40,9 @@ __global__ __launch_bounds__(256) void act_split_kernel(const ActArgs a) {
   const int cg = blockIdx.y;
   const int b = blockIdx.z;
   const int l = pos - a.halo;
-  const int Lb = a.len ? a.len[b] : a.L;  // ragged rows: the row's own end is its zero padding (a select, never a multiply)
+  // ragged rows: the row's own end is its zero padding (a select, never a multiply); past L it is clamped, as the convs clamp
+  // x_len (unclamped, the tail up to Lp would hold copies of column L - 1)
+  const int Lb = a.len ? min(a.len[b], a.L) : a.L;
   const bool lok = l >= 0 && l < Lb;
   const int lc = min(max(l, 0), a.L - 1);
   const float* xb = a.x + (int64_t)b * a.x_bs + lc;

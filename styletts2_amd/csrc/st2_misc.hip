@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void convt_interleave_kernel(const float* __re
       for (int u = 0; u < SB; ++u) {
         const int e = min(e0 + u * 256, total - 1);
         const int r = e / nq, i = e - r * nq;
-        t[u] = pb[(int64_t)r * C * p_cs + min(q_lo + i, Lq - 1)];
+        t[u] = pb[(int64_t)r * C * p_cs + max(min(q_lo + i, Lq - 1), 0)];  // (q_len[b] = 0: column 0, selected away below)
       }
 #pragma unroll
       for (int u = 0; u < SB; ++u) {

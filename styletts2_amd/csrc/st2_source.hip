@@ -108,7 +108,8 @@ __global__ __launch_bounds__(256) void har_source_kernel(const float* __restrict
 // ---- STFT: one thread per frame, N-point DFT by table (N <= 32) ---------------------------------
 constexpr int MAXN = 32;
 // Ragged rows (len != NULL): row b is len[b] samples of a row of L_max, reflect-padded at its own end; its frames past
-// len[b] / hop + 1 are written as exact zeros.
+// len[b] / hop + 1 are written as exact zeros.  len[b] is clamped to N/2 + 1 .. L_max: the reflection of a frame that reaches
+// N/2 past the row's end stays inside the row only from N/2 + 1 samples on (torch's reflect pad needs pad < length too).
 __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, int L_max, int N, int hop,
                                                    float* __restrict__ har, int64_t har_bs, int har_cs,
                                                    const int32_t* __restrict__ len) {
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
   const int m = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (m >= L_max / hop + 1) return;
-  const int L = len ? min(len[b], L_max) : L_max;
+  const int L = len ? min(max(len[b], N / 2 + 1), L_max) : L_max;
   const int M = L / hop + 1;
   const int NB = N / 2 + 1;
   float* hb = har + (int64_t)b * har_bs + m;

@@ -89,6 +89,21 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _chk_len(t, name, n, like):
+    """Per-row lengths of a ragged batch (include/st2.h, ABI v23): int32 [n], contiguous, on the device of `like`.  Checked
+    before anything else of the call, so a bad one never reaches a launch.  Returns the device pointer (0 for None)."""
+    if t is None:
+        return 0
+    if not torch.is_tensor(t) or t.dtype != torch.int32:
+        raise _lib.St2Error("%s must be an int32 tensor (got %s)" % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.numel() != n or not t.is_contiguous():
+        raise _lib.St2Error("%s must be a contiguous tensor of %d entries (got shape %s)" % (name, n, tuple(t.shape)))
+    if not t.is_cuda or not torch.is_tensor(like) or t.device != like.device:
+        raise _lib.St2Error("%s must live on the device of the tensor it describes (%s, got %s)" % (
+            name, like.device if torch.is_tensor(like) else None, t.device))
+    return t.data_ptr()
+
+
 def _bs_cs(t):
     """(batch stride, channel stride) of an NCL view."""
     return t.stride(0), t.stride(1)
@@ -306,10 +321,15 @@ def xs_row_slots(L):
 
 
 def activate(x, *, pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, gamma_plus_one=False, alpha=None,
-              c_pad=32, gb_seg=0, x_scale=None):
+              c_pad=32, gb_seg=0, x_scale=None, lengths=None):
     """`st2_act_split`: x [B, C, L] fp32 -> XsTensor holding split_f16(x_scale * pro(x)) with the conv's zero padding
     (x_scale = x_scale_for(pro) unless the caller passes a calibrated power of two, `calibrated_x_scale`).  `gb_seg` > 0 (PRO_COLNORM on a token-merged view [1, C, G * gb_seg]): gamma / beta
-    are [G, C] and row l // gb_seg applies at position l (per-utterance AdaLayerNorm affine, include/st2.h)."""
+    are [G, C] and row l // gb_seg applies at position l (per-utterance AdaLayerNorm affine, include/st2.h).  `lengths` (int32 [B]
+    on the device, `st2_act_split_len`): row b ends at lengths[b], the positions past it are written as the conv's zero padding."""
+    if lengths is not None:
+        _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
+        if pro == PRO_COLNORM:
+            raise _lib.St2Error("activate: per-row lengths are not defined for PRO_COLNORM (st2_act_split_len)")
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, L = x.shape
@@ -335,6 +355,11 @@ def activate(x, *, pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, g
         _chk(alpha, "alpha", 1)
         assert alpha.numel() == Cc and alpha.is_contiguous()
     xsc = float(x_scale) if x_scale else x_scale_for(pro)
+    if lengths is not None:
+        _lib.check(lib.st2_act_split_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
+                                         _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
+                                         xsc, data.data_ptr(), cg, Lp, XS_HALO, lengths.data_ptr(), _stream()), "st2_act_split_len")
+        return XsTensor(data, Cc, L, XS_HALO, xsc)
     _lib.check(lib.st2_act_split(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
                                  _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
                                  xsc, data.data_ptr(), cg, Lp, XS_HALO, _stream()), "st2_act_split")
@@ -347,21 +372,34 @@ def new_part(B, C, nt, device):
     return torch.empty((B * C * nt * 3,), device=device, dtype=torch.float32)
 
 
-def stats_finalize(part, B, C, nt, L, cols=128, eps=1e-5, out=None):
+def stats_finalize(part, B, C, nt, L, cols=128, eps=1e-5, out=None, lengths=None, len_div=1):
     """`st2_stats_finalize`: the buffer of `new_part` filled by the producer of a [B, C, L] tensor (slots of `cols` columns) ->
-    stats [B, C, 2] (mean, rstd) of that tensor."""
+    stats [B, C, 2] (mean, rstd) of that tensor.  `lengths` (int32 [B * C / len_div] on the device, `st2_stats_finalize_len`):
+    row r of the B * C covers its first lengths[r // len_div] columns; slots past that end are not read."""
+    if lengths is not None:
+        if len_div <= 0 or (B * C) % len_div:
+            raise _lib.St2Error("stats_finalize: len_div=%d does not divide the %d rows" % (len_div, B * C))
+        _chk_len(lengths, "lengths", B * C // len_div, part)
     lib = _lib.load()
     assert part.numel() >= B * C * nt * 3 and part.is_contiguous()
     if out is None:
         out = torch.empty((B, C, 2), device=part.device, dtype=torch.float32)
+    if lengths is not None:
+        _lib.check(lib.st2_stats_finalize_len(part.data_ptr(), B * C, nt, L, eps, out.data_ptr(), int(cols), lengths.data_ptr(),
+                                              int(len_div), _stream()), "st2_stats_finalize_len")
+        return out
     _lib.check(lib.st2_stats_finalize(part.data_ptr(), B * C, nt, L, eps, out.data_ptr(), int(cols), _stream()), "st2_stats_finalize")
     return out
 
 
 def conv1d_xs(xs, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=None, res=None, res_shift=0,
-              res2=None, div=1.0, act=ACT_NONE, act_split=0, act_slope=0.0, want_stats=False, part_cols=None):
+              res2=None, div=1.0, act=ACT_NONE, act_split=0, act_slope=0.0, want_stats=False, part_cols=None, y_len=None):
     """`st2_conv1d_xs` on an XsTensor; with want_stats returns (out, stats [B, C_out, 2]) where the InstanceNorm
-    statistics of `out` come from the conv epilogue's per-tile partial sums + `st2_stats_finalize`."""
+    statistics of `out` come from the conv epilogue's per-tile partial sums + `st2_stats_finalize`.  `y_len` (int32 [B] on the
+    device, st2_conv_desc.y_len): row b of the output ends at y_len[b]; nothing is stored past it and the statistics cover
+    only its columns (the input's own ends come from `activate(lengths=)`)."""
+    if y_len is not None:
+        _chk_len(y_len, "y_len", xs.data.shape[0] if isinstance(xs, XsTensor) else -1, xs.data if isinstance(xs, XsTensor) else None)
     lib = _lib.load()
     assert isinstance(xs, XsTensor) and isinstance(wt, SplitConvWeight)
     B, C_in, L_in = xs.data.shape[0], xs.C, xs.L
@@ -382,6 +420,7 @@ def conv1d_xs(xs, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, ou
     _chk(bias, "bias", 1)
     d.bias = _ptr(bias)
     d.y, d.y_bs, d.y_cs = out.data_ptr(), out.stride(0), out.stride(1)
+    d.y_len = _ptr(y_len)
     _fill_epilogue(d, B, C_out, L_out, res, res_shift, res2, div, act, act_split, act_slope)
     part = None
     if want_stats:
@@ -392,7 +431,7 @@ def conv1d_xs(xs, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, ou
         d.part, d.part_nt, d.part_cols = part.data_ptr(), nt, pc
     _launch_conv(lib.st2_conv1d_xs, "st2_conv1d_xs", d)
     if want_stats:
-        return out, stats_finalize(part, B, C_out, nt, L_out, cols=d.part_cols or 128)
+        return out, stats_finalize(part, B, C_out, nt, L_out, cols=d.part_cols or 128, lengths=y_len, len_div=C_out)
     return out
 
 
@@ -416,12 +455,17 @@ def _launch_conv(fn, fname, d):
 def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=None,
            pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, gamma_plus_one=False, alpha=None,
            res=None, res_shift=0, res2=None, div=1.0, act=ACT_NONE, act_split=0, act_slope=0.0, want_stats=False,
-           gb_seg=0, x_scale=None):
+           gb_seg=0, x_scale=None, x_len=None, y_len=None):
     """Fused Conv1d, see `st2_conv1d` / `st2_conv1d_f16s` / `st2_conv1d_xs` in include/st2.h.  wt is either the
     packed K-major fp32 weight [C_in*ks, w_ld] of weights.pack_conv() (exact-fp32 MFMA kernel) or a
     weights.SplitConvWeight from weights.pack_conv_f16s() (split-f16 MFMA kernels, fp32-class accuracy at 5.3x the
     rate ceiling).  With a SplitConvWeight, a prologue and conv_path() == "xs" the call is issued as
-    st2_act_split + st2_conv1d_xs.  want_stats=True returns (out, InstanceNorm statistics of out [B, C_out, 2])."""
+    st2_act_split + st2_conv1d_xs.  want_stats=True returns (out, InstanceNorm statistics of out [B, C_out, 2]).  x_len / y_len
+    (int32 [B] on the device, st2_conv_desc): per-row ends of the input (zero padding after the prologue) and of the output
+    (nothing stored past it, statistics over its columns); split-f16 weights only (st2_conv1d rejects them)."""
+    nb = x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1
+    _chk_len(x_len, "x_len", nb, x)
+    _chk_len(y_len, "y_len", nb, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, C_in, L_in = x.shape
@@ -429,10 +473,10 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     if (split and pad_left <= XS_HALO and L_in >= XS_MIN_L and (pro != PRO_NONE or C_in >= XS_MIN_C_PLAIN)
             and conv_path() == "xs" and not prefer_fused(pro, C_in, ks)):
         xs = activate(x, pro=pro, slope=slope, stats=stats, gamma=gamma, beta=beta,
-                      gamma_plus_one=gamma_plus_one, alpha=alpha, gb_seg=gb_seg, x_scale=x_scale)
+                      gamma_plus_one=gamma_plus_one, alpha=alpha, gb_seg=gb_seg, x_scale=x_scale, lengths=x_len)
         return conv1d_xs(xs, wt, C_out, ks, dil=dil, pad_left=pad_left, L_out=L_out, bias=bias, out=out, res=res,
                          res_shift=res_shift, res2=res2, div=div, act=act, act_split=act_split, act_slope=act_slope,
-                         want_stats=want_stats)
+                         want_stats=want_stats, y_len=y_len)
     if gb_seg:
         raise _lib.St2Error("gb_seg (per-segment affine of a token-merged view) exists on the st2_act_split + "
                             "st2_conv1d_xs path only; this call routes to the fused kernel")
@@ -465,6 +509,7 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     _chk(bias, "bias", 1)
     d.bias = _ptr(bias)
     d.y, d.y_bs, d.y_cs = out.data_ptr(), out.stride(0), out.stride(1)
+    d.x_len, d.y_len = _ptr(x_len), _ptr(y_len)
     d.pro, d.slope = pro, slope
     if pro in (PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_COLNORM):
         _chk(stats, "stats", 3)
@@ -495,12 +540,19 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
             d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), nb
     _launch_conv(fn, fname, d)
     if want_stats:
-        return out, (stats_finalize(part, B, C_out, nt, L_out) if part is not None else instnorm_stats(out))
+        if part is not None:
+            return out, stats_finalize(part, B, C_out, nt, L_out, lengths=y_len, len_div=C_out)
+        return out, instnorm_stats(out, lengths=y_len)
     return out
 
 
-def conv1d_direct(x, w, bias, stride, pad, L_out=None, out=None):
-    """Plain-weight ([C_out, C_in, ks]) direct conv for strided / tiny-C_in layers (`st2_conv1d_direct`)."""
+def conv1d_direct(x, w, bias, stride, pad, L_out=None, out=None, x_len=None, y_len=None):
+    """Plain-weight ([C_out, C_in, ks]) direct conv for strided / tiny-C_in layers (`st2_conv1d_direct`).  x_len / y_len
+    (int32 [B] on the device, `st2_conv1d_direct_len`): the input row ends (zero padding) at x_len[b], outputs from y_len[b]
+    on are exact zeros."""
+    nb = x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1
+    _chk_len(x_len, "x_len", nb, x)
+    _chk_len(y_len, "y_len", nb, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(w, "w", 3)
@@ -514,6 +566,11 @@ def conv1d_direct(x, w, bias, stride, pad, L_out=None, out=None):
     if out is None:
         out = torch.empty((B, C_out, L_out), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
+    if x_len is not None or y_len is not None:
+        _lib.check(lib.st2_conv1d_direct_len(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), _ptr(bias), out.data_ptr(),
+                                             out.stride(0), out.stride(1), B, C_in, C_out, L_in, L_out, ks, stride, pad,
+                                             _ptr(x_len), _ptr(y_len), _stream()), "st2_conv1d_direct_len")
+        return out
     _lib.check(lib.st2_conv1d_direct(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), _ptr(bias),
                                      out.data_ptr(), out.stride(0), out.stride(1), B, C_in, C_out, L_in, L_out,
                                      ks, stride, pad, _stream()), "st2_conv1d_direct")
@@ -531,12 +588,19 @@ def phase_split(x, stride, pad, Lu):
     return xp
 
 
-def instnorm_stats(x, eps=1e-5, out=None):
+def instnorm_stats(x, eps=1e-5, out=None, lengths=None):
+    """`st2_instnorm_stats`: x [B, C, L] -> (mean, rstd) [B, C, 2]; `lengths` (int32 [B] on the device,
+    `st2_instnorm_stats_len`): row b over its first lengths[b] columns."""
+    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, L = x.shape
     if out is None:
         out = torch.empty((B, Cc, 2), device=x.device, dtype=torch.float32)
+    if lengths is not None:
+        _lib.check(lib.st2_instnorm_stats_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, eps, out.data_ptr(),
+                                              lengths.data_ptr(), _stream()), "st2_instnorm_stats_len")
+        return out
     _lib.check(lib.st2_instnorm_stats(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, eps, out.data_ptr(),
                                       _stream()), "st2_instnorm_stats")
     return out
@@ -574,9 +638,15 @@ CVT_TILE = 1024  # positions per st2_convt_interleave tile (= per entry of its p
 
 
 def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, reflect_left=False, out=None,
-                     want_stats=False):
+                     want_stats=False, q_len=None, out_len=None):
     """`st2_convt_interleave[_stats]`; with want_stats returns (out, InstanceNorm statistics of out [B, C_out, 2]) from
-    the kernel's per-tile partial sums + `st2_stats_finalize`."""
+    the kernel's per-tile partial sums + `st2_stats_finalize`.  q_len / out_len (int32 [B] on the device, both or neither,
+    `st2_convt_interleave_stats_len`): row b has q_len[b] phase columns and out_len[b] outputs."""
+    if (q_len is None) != (out_len is None):
+        raise _lib.St2Error("convt_interleave: q_len and out_len go together")
+    nb = phases.shape[0] if torch.is_tensor(phases) and phases.dim() == 3 else -1
+    _chk_len(q_len, "q_len", nb, phases)
+    _chk_len(out_len, "out_len", nb, phases)
     lib = _lib.load()
     _chk(phases, "phases", 3)
     _chk(bias, "bias", 1)
@@ -593,6 +663,14 @@ def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, ref
     if want_stats:
         nt = (L_out + CVT_TILE - 1) // CVT_TILE
         part = new_part(B, C_out, nt, phases.device)
+    if q_len is not None:
+        _lib.check(lib.st2_convt_interleave_stats_len(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
+                                                      _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
+                                                      C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
+                                                      q_len.data_ptr(), out_len.data_ptr(), _stream()), "st2_convt_interleave_len")
+        if want_stats:
+            return out, stats_finalize(part, B, C_out, nt, L_out, cols=CVT_TILE, lengths=out_len, len_div=C_out)
+        return out
     _lib.check(lib.st2_convt_interleave_stats(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
                                               _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
                                               C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
@@ -602,7 +680,10 @@ def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, ref
     return out
 
 
-def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None):
+def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None, lengths=None):
+    """`st2_adain_leaky_pool`: x [B, C, L] -> [B, C, 2L]; `lengths` (int32 [B] on the device, `st2_adain_leaky_pool_len`): the
+    input row ends (zero padding) at lengths[b], 2 * lengths[b] outputs are written and the rest of the row is left as it was."""
+    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(stats, "stats", 3)
@@ -614,6 +695,12 @@ def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None):
     assert w.shape == (Cc, 3) and w.is_contiguous() and gamma.stride(0) == beta.stride(0)
     if out is None:
         out = torch.empty((B, Cc, 2 * L), device=x.device, dtype=torch.float32)
+    if lengths is not None:
+        _lib.check(lib.st2_adain_leaky_pool_len(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
+                                                beta.data_ptr(), gamma.stride(0), slope, w.data_ptr(), _ptr(bias),
+                                                out.data_ptr(), out.stride(0), out.stride(1), B, Cc, L, lengths.data_ptr(),
+                                                _stream()), "st2_adain_leaky_pool_len")
+        return out
     _lib.check(lib.st2_adain_leaky_pool(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
                                         beta.data_ptr(), gamma.stride(0), slope, w.data_ptr(), _ptr(bias),
                                         out.data_ptr(), out.stride(0), out.stride(1), B, Cc, L, _stream()),
@@ -622,8 +709,10 @@ def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None):
 
 
 def har_source(f0, U, noise, lin_w, lin_b, sine_amp=0.1, noise_std=0.003, voiced_threshold=10.0,
-               sample_rate=24000.0):
-    """f0 [B, F] -> har_source [B, F*U]; noise [B, F*U, H] standard-normal draws."""
+               sample_rate=24000.0, f_len=None, out=None):
+    """f0 [B, F] -> har_source [B, F*U]; noise [B, F*U, H] standard-normal draws.  `f_len` (int32 [B] on the device,
+    `st2_har_source_len`): row b holds f_len[b] frames, its output is exactly 0 from f_len[b] * U on."""
+    _chk_len(f_len, "f_len", f0.shape[0] if torch.is_tensor(f0) and f0.dim() == 2 else -1, f0)
     lib = _lib.load()
     _chk(f0, "f0", 2)
     _chk(noise, "noise", 3)
@@ -634,32 +723,58 @@ def har_source(f0, U, noise, lin_w, lin_b, sine_amp=0.1, noise_std=0.003, voiced
     assert f0.is_contiguous() and noise.is_contiguous() and noise.shape == (B, F * U, H)
     assert lin_w.numel() == H and lin_w.is_contiguous()
     scratch = torch.empty((B, H, F), device=f0.device, dtype=torch.float32)
-    out = torch.empty((B, F * U), device=f0.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, F * U), device=f0.device, dtype=torch.float32)
+    _chk(out, "out", 2)
+    assert out.shape == (B, F * U) and out.is_contiguous()
+    if f_len is not None:
+        _lib.check(lib.st2_har_source_len(f0.data_ptr(), B, F, U, H, noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
+                                          sine_amp, noise_std, voiced_threshold, sample_rate, scratch.data_ptr(),
+                                          out.data_ptr(), f_len.data_ptr(), _stream()), "st2_har_source_len")
+        return out
     _lib.check(lib.st2_har_source(f0.data_ptr(), B, F, U, H, noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
                                   sine_amp, noise_std, voiced_threshold, sample_rate, scratch.data_ptr(),
                                   out.data_ptr(), _stream()), "st2_har_source")
     return out
 
 
-def stft_mag_phase(x, n_fft, hop):
+def stft_mag_phase(x, n_fft, hop, lengths=None, out=None):
+    """x [B, L] -> (|X|, angle X) [B, n_fft + 2, L // hop + 1] (`st2_stft_mag_phase`).  `lengths` (int32 [B] on the device,
+    `st2_stft_mag_phase_len`): row b is its first lengths[b] samples (clamped to n_fft / 2 + 1 .. L), reflect-padded at its
+    own end; frames past lengths[b] // hop are exact zeros."""
+    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else -1, x)
     lib = _lib.load()
     _chk(x, "x", 2)
     assert x.is_contiguous()
     B, L = x.shape
     M = L // hop + 1
-    har = torch.empty((B, n_fft + 2, M), device=x.device, dtype=torch.float32)
+    har = out if out is not None else torch.empty((B, n_fft + 2, M), device=x.device, dtype=torch.float32)
+    _chk(har, "out", 3)
+    assert har.shape == (B, n_fft + 2, M)
+    if lengths is not None:
+        _lib.check(lib.st2_stft_mag_phase_len(x.data_ptr(), B, L, n_fft, hop, har.data_ptr(), har.stride(0), har.stride(1),
+                                              lengths.data_ptr(), _stream()), "st2_stft_mag_phase_len")
+        return har
     _lib.check(lib.st2_stft_mag_phase(x.data_ptr(), B, L, n_fft, hop, har.data_ptr(), har.stride(0), har.stride(1),
                                       _stream()), "st2_stft_mag_phase")
     return har
 
 
-def istft(sp, n_fft, hop):
-    """sp [B, n_fft+2, M] = cat(spec, phase) -> wave [B, 1, hop*(M-1)]."""
+def istft(sp, n_fft, hop, m_len=None, out=None):
+    """sp [B, n_fft+2, M] = cat(spec, phase) -> wave [B, 1, hop*(M-1)].  `m_len` (int32 [B] on the device, `st2_istft_len`):
+    row b has m_len[b] frames (clamped to 2..M) and emits hop * (m_len[b] - 1) samples, exact zeros after them."""
+    _chk_len(m_len, "m_len", sp.shape[0] if torch.is_tensor(sp) and sp.dim() == 3 else -1, sp)
     lib = _lib.load()
     _chk(sp, "sp", 3)
     B, Cc, M = sp.shape
     assert Cc == n_fft + 2
-    wave = torch.empty((B, 1, hop * (M - 1)), device=sp.device, dtype=torch.float32)
+    wave = out if out is not None else torch.empty((B, 1, hop * (M - 1)), device=sp.device, dtype=torch.float32)
+    _chk(wave, "out", 3)
+    assert wave.shape == (B, 1, hop * (M - 1))
+    if m_len is not None:
+        _lib.check(lib.st2_istft_len(sp.data_ptr(), sp.stride(0), sp.stride(1), B, M, n_fft, hop, wave.data_ptr(),
+                                     wave.stride(0), m_len.data_ptr(), _stream()), "st2_istft_len")
+        return wave
     _lib.check(lib.st2_istft(sp.data_ptr(), sp.stride(0), sp.stride(1), B, M, n_fft, hop, wave.data_ptr(),
                              wave.stride(0), _stream()), "st2_istft")
     return wave
@@ -889,8 +1004,10 @@ def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False):
     return (dur, sums) if want_sums else dur
 
 
-def expand_by_durations(x, dur, T, shift=False, out=None):
-    """`st2_expand_by_durations`: x [B, C, N], dur int64 [B, N] (rows sum to T) -> [B, C, T]."""
+def expand_by_durations(x, dur, T, shift=False, out=None, lengths=None):
+    """`st2_expand_by_durations`: x [B, C, N], dur int64 [B, N] (rows sum to T) -> [B, C, T].  `lengths` (int32 [B] on the
+    device, `st2_expand_by_durations_len`): row b's durations sum to lengths[b], its columns from there on are exact zeros."""
+    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, N = x.shape
@@ -898,9 +1015,27 @@ def expand_by_durations(x, dur, T, shift=False, out=None):
     if out is None:
         out = torch.empty((B, Cc, T), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
+    if lengths is not None:
+        _lib.check(lib.st2_expand_by_durations_len(x.data_ptr(), x.stride(0), x.stride(1), dur.data_ptr(), B, Cc, N, T,
+                                                   1 if shift else 0, out.data_ptr(), out.stride(0), out.stride(1),
+                                                   lengths.data_ptr(), _stream()), "st2_expand_by_durations_len")
+        return out
     _lib.check(lib.st2_expand_by_durations(x.data_ptr(), x.stride(0), x.stride(1), dur.data_ptr(), B, Cc, N, T,
                                            1 if shift else 0, out.data_ptr(), out.stride(0), out.stride(1), _stream()),
                "st2_expand_by_durations")
+    return out
+
+
+def ragged_lengths(frames, T_max, coef):
+    """`st2_ragged_lengths`: frames int32 [B] on the device, coef = [(mul, add, div), ...] (at most 16, div > 0) -> int32
+    [len(coef), B] with out[i][b] = (mul_i * f_b + add_i) // div_i (floor division), f_b = frames[b] clamped to 1..T_max."""
+    B = frames.numel() if torch.is_tensor(frames) else -1
+    _chk_len(frames, "frames", B, frames)
+    lib = _lib.load()
+    n = len(coef)
+    flat = (C.c_int32 * (3 * max(n, 1)))(*[int(v) for t in coef for v in t])
+    out = torch.empty((n, B), device=frames.device, dtype=torch.int32)
+    _lib.check(lib.st2_ragged_lengths(frames.data_ptr(), B, int(T_max), n, flat, out.data_ptr(), _stream()), "st2_ragged_lengths")
     return out
 
 

@@ -61,8 +61,8 @@ def _row_desc(d, b, L_in, L_out):
 def _conv_rows(d, x_of_row, cols):
     xl, yl = _lens(d.x_len, d.B), _lens(d.y_len, d.B)
     for b in range(d.B):
-        Li = xl[b] if xl else d.L_in
-        Lo = yl[b] if yl else d.L_out
+        Li = min(xl[b], d.L_in) if xl else d.L_in  # values above L_in / L_out are clamped (include/st2.h)
+        Lo = min(yl[b], d.L_out) if yl else d.L_out
         r = _row_desc(d, b, Li, Lo)
         y = R._conv1d(x_of_row(r, b, Li), _weight(d), d.C_out, d.ks, **_epilogue_kwargs(r))
         if d.part:
@@ -186,6 +186,7 @@ def har_source_len(f0, B, Fr, U, H, noise, lin_w, lin_b, sine_amp, noise_std, vt
 def stft_mag_phase_len(x, B, L, n_fft, hop, har, har_bs, har_cs, length, stream):
     h = _ncl(har, har_bs, har_cs, B, n_fft + 2, L // hop + 1)
     for b, n in enumerate(_lens(length, B)):
+        n = min(max(n, n_fft // 2 + 1), L)  # clamped as the kernel clamps it (include/st2.h)
         M = n // hop + 1
         h[b, :, :M] = R.stft_mag_phase(_t(x + b * L * 4, (1, n), (L, 1)), n_fft, hop)[0]
         h[b, :, M:] = 0.0

@@ -6,6 +6,7 @@ import math
 import pytest
 import torch
 
+from _util import make_conv_case, rel_err
 from oracle import ops_ref as R
 from styletts2_amd import _hooks, ops, weights
 
@@ -15,44 +16,6 @@ DEV = "cuda"
 
 def g(t):
     return None if t is None else t.to(DEV)
-
-
-def rel_err(a, b):
-    a = a.detach().cpu().double()
-    b = b.detach().cpu().double()
-    return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
-
-
-def make_conv_case(seed, B, C_in, C_out, L, ks, dil, pro, act=R.ACT_NONE, res=False, res2=False, res_shift=0,
-                   div=1.0, pad_left=None, L_out=None, bias=True, sliced=False):
-    gen = torch.Generator().manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=gen)
-    x = r(B, C_in, L) * 1.5 + 0.3
-    w = r(C_out, C_in, ks) / math.sqrt(C_in * ks)
-    kw = dict(dil=dil, pad_left=(ks - 1) * dil // 2 if pad_left is None else pad_left, L_out=L_out,
-              bias=r(C_out) if bias else None, pro=pro, div=div, act=act)
-    Lo = L if L_out is None else L_out
-    if pro in (R.PRO_LEAKY, R.PRO_ADAIN_LEAKY):
-        kw["slope"] = 0.2
-    if pro in (R.PRO_ADAIN_LEAKY, R.PRO_ADAIN_SNAKE):
-        kw["stats"] = R.instnorm_stats(x)
-        h = r(B, 2 * C_in + 3) * 0.5
-        kw["gamma"], kw["beta"] = h[:, 1:1 + C_in], h[:, 1 + C_in:1 + 2 * C_in]
-    if pro == R.PRO_COLNORM:
-        kw["stats"] = R.colnorm_stats(x)
-        kw["gamma"], kw["beta"] = r(1, C_in), r(1, C_in)
-    if pro in (R.PRO_ADAIN_SNAKE, R.PRO_SNAKE):
-        kw["alpha"] = torch.rand(C_in, generator=gen) + 0.5
-    if res:
-        kw["res"] = r(B, C_out, (Lo + (1 << res_shift) - 1) >> res_shift)
-        kw["res_shift"] = res_shift
-    if res2:
-        kw["res2"] = r(B, C_out, Lo)
-    if act == R.ACT_EXP_SIN:
-        kw["act_split"] = C_out // 2
-    if act == R.ACT_LEAKY:
-        kw["act_slope"] = 0.1
-    return x, w, kw
 
 
 CONV_CASES = [
