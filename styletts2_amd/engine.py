@@ -10,6 +10,7 @@ plan tests substitute per-kernel contracts for the HIP wrappers; the real wrappe
 """
 import ctypes as C
 import math
+import warnings
 import weakref
 
 import torch
@@ -60,6 +61,24 @@ def ragged_frames(frames, B, T, dev):
     return torch.tensor(frames, dtype=torch.int32).to(dev)
 
 
+def _stream(dev):
+    """torch's current stream on a HIP device; the CPU backends of the plan tests take no stream."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+
+
+def _lengths(lengths, dev, B):
+    """Per-row token counts as the C ABI reads them: int32 [B], contiguous, on `dev` (None stays None)."""
+    if lengths is None:
+        return None
+    lengths = lengths.to(torch.int32).contiguous()
+    assert lengths.device == dev and lengths.numel() == B
+    return lengths
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
 def norm_device(dev):
     """torch.device with its index filled in: 'cuda', 'cuda:0', torch.device('cuda') and a tensor's .device all name the
     same engine (advisor, round 5: a cache keyed on the caller's spelling rebuilt the engine -- a full repack and upload --
@@ -80,7 +99,6 @@ def replaced(old, what):
     """Called when a cached engine is about to be rebuilt (weights reloaded or moved): a calibration table belongs to the
     weights it was measured on and does not travel -- but the caller must hear that it is gone."""
     if old is not None and getattr(old, "h", None) and any(old.calibration_scales()):
-        import warnings
         warnings.warn("the calibrated %s engine is being rebuilt (weights reloaded or moved): its per-layer operand scales are "
                       "dropped; run pipeline.calibrate / load_calibration_state again" % what, RuntimeWarning, stacklevel=3)
 
@@ -143,6 +161,14 @@ class Engine:
         except Exception:
             pass
 
+    def _workspace(self, dev, query, *args, what):
+        """(keep-alive tensor, 256-byte aligned pointer, size) of the workspace `query(handle, *args)` asks for, on `dev`."""
+        nbytes = getattr(self.lib, query)(self.h, *args)
+        if nbytes <= 0:
+            raise _lib.St2Error("%s failed (%s)" % (query, what))
+        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
+        return ws, (ws.data_ptr() + 255) & ~255, nbytes
+
     def load(self, name, t):
         t = t.detach().float().cpu().contiguous()
         shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
@@ -183,11 +209,7 @@ class Engine:
         if har is not None:
             har = har.float().contiguous()
         wave = torch.empty((B, 1, L), device=dev, dtype=torch.float32)
-        nbytes = self.lib.st2_decoder_workspace_bytes(self.h, B, T)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_decoder_workspace_bytes failed (weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_decoder_workspace_bytes", B, T, what="weights not finalized?")
         tp = None
         if taps is not None:
             tp = _lib.DecoderTaps()
@@ -211,20 +233,10 @@ class Engine:
                     tp.stage[int(k[5:])] = v.data_ptr()
                 else:
                     setattr(tp, k, v.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        if frames is None:
-            _lib.check(self.lib.st2_decoder_forward(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(),
-                                                    0 if noise is None else noise.data_ptr(),
-                                                    0 if har is None else har.data_ptr(), B, T, wave.data_ptr(),
-                                                    ws_ptr, nbytes, None if tp is None else C.byref(tp), stream),
-                       "st2_decoder_forward")
-        else:
-            _lib.check(self.lib.st2_decoder_forward_ragged(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(),
-                                                           0 if noise is None else noise.data_ptr(),
-                                                           0 if har is None else har.data_ptr(), frames.data_ptr(), B, T,
-                                                           wave.data_ptr(), ws_ptr, nbytes,
-                                                           None, stream),
-                       "st2_decoder_forward_ragged")
+        entry, fr = ("st2_decoder_forward", ()) if frames is None else ("st2_decoder_forward_ragged", (frames.data_ptr(),))
+        _lib.check(getattr(self.lib, entry)(self.h, asr.data_ptr(), F0.data_ptr(), N.data_ptr(), s.data_ptr(), _ptr(noise),
+                                            _ptr(har), *fr, B, T, wave.data_ptr(), ws_ptr, nbytes,
+                                            None if tp is None else C.byref(tp), _stream(dev)), entry)
         if taps is not None:
             taps.update(bufs)
             if cfg.decoder_kind == 0:
@@ -249,21 +261,11 @@ class Engine:
         asr = torch.empty((B, self.cfg.dim_in, T), device=dev, dtype=torch.float32)
         f0 = torch.empty((B, 2 * T), device=dev, dtype=torch.float32)
         nn_ = torch.empty((B, 2 * T), device=dev, dtype=torch.float32)
-        nbytes = self.lib.st2_prosody_workspace_bytes(self.h, B, N, T)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_prosody_workspace_bytes failed (predictor weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        if frames is None:
-            _lib.check(self.lib.st2_prosody_forward(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(),
-                                                    s.data_ptr(), B, N, T, 1 if shift else 0, asr.data_ptr(), f0.data_ptr(),
-                                                    nn_.data_ptr(), ws_ptr, nbytes, stream), "st2_prosody_forward")
-        else:
-            _lib.check(self.lib.st2_prosody_forward_ragged(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(),
-                                                           s.data_ptr(), frames.data_ptr(), B, N, T, 1 if shift else 0,
-                                                           asr.data_ptr(), f0.data_ptr(), nn_.data_ptr(), ws_ptr, nbytes,
-                                                           stream), "st2_prosody_forward_ragged")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_prosody_workspace_bytes", B, N, T, what="predictor weights not finalized?")
+        entry, fr = ("st2_prosody_forward", ()) if frames is None else ("st2_prosody_forward_ragged", (frames.data_ptr(),))
+        _lib.check(getattr(self.lib, entry)(self.h, d_cm.data_ptr(), t_en.data_ptr(), durations.data_ptr(), s.data_ptr(), *fr,
+                                            B, N, T, 1 if shift else 0, asr.data_ptr(), f0.data_ptr(), nn_.data_ptr(), ws_ptr,
+                                            nbytes, _stream(dev)), entry)
         return asr, f0, nn_
 
     # -- text encoder --------------------------------------------------------------------------------------------------
@@ -272,18 +274,11 @@ class Engine:
         B, N = tokens.shape
         dev = tokens.device
         tokens = tokens.long().contiguous()
-        if lengths is not None:
-            lengths = lengths.to(torch.int32).contiguous()
-            assert lengths.device == dev and lengths.numel() == B
+        lengths = _lengths(lengths, dev, B)
         t_en = torch.empty((B, self.cfg.dim_in, N), device=dev, dtype=torch.float32)
-        nbytes = self.lib.st2_text_workspace_bytes(self.h, B, N)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_text_workspace_bytes failed (text-encoder weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_text_forward(self.h, tokens.data_ptr(), 0 if lengths is None else lengths.data_ptr(), B, N,
-                                             t_en.data_ptr(), ws_ptr, nbytes, stream), "st2_text_forward")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_text_workspace_bytes", B, N, what="text-encoder weights not finalized?")
+        _lib.check(self.lib.st2_text_forward(self.h, tokens.data_ptr(), _ptr(lengths), B, N, t_en.data_ptr(), ws_ptr, nbytes,
+                                             _stream(dev)), "st2_text_forward")
         return t_en
 
     # -- reference-audio style encoders ---------------------------------------------------------------------------------------
@@ -293,15 +288,11 @@ class Engine:
         mel = mel.float().reshape(mel.shape[0], mel.shape[-2], mel.shape[-1]).contiguous()
         B, H, T = mel.shape
         dev = mel.device
-        nbytes = self.lib.st2_style_workspace_bytes(self.h, which, B, H, T)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_style_workspace_bytes failed (style-encoder weights not finalized, or not an 80 x >= 80 mel)")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_style_workspace_bytes", which, B, H, T,
+                                             what="style-encoder weights not finalized, or not an 80 x >= 80 mel")
         out = torch.empty((B, self.style_dims[which]), device=dev, dtype=torch.float32)
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_style_forward(self.h, which, mel.data_ptr(), B, H, T, out.data_ptr(), ws_ptr, nbytes, stream),
-                   "st2_style_forward")
+        _lib.check(self.lib.st2_style_forward(self.h, which, mel.data_ptr(), B, H, T, out.data_ptr(), ws_ptr, nbytes,
+                                              _stream(dev)), "st2_style_forward")
         return out
 
     # -- PL-BERT ---------------------------------------------------------------------------------------------------------
@@ -311,18 +302,11 @@ class Engine:
         B, N = tokens.shape
         dev = tokens.device
         tokens = tokens.long().contiguous()
-        if lengths is not None:
-            lengths = lengths.to(torch.int32).contiguous()
-            assert lengths.device == dev and lengths.numel() == B
+        lengths = _lengths(lengths, dev, B)
         out = torch.empty((B, self.cfg.dn_embedding, N), device=dev, dtype=torch.float32)
-        nbytes = self.lib.st2_bert_workspace_bytes(self.h, B, N)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_bert_workspace_bytes failed (PL-BERT weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_bert_forward(self.h, tokens.data_ptr(), 0 if lengths is None else lengths.data_ptr(), B, N,
-                                             out.data_ptr(), ws_ptr, nbytes, stream), "st2_bert_forward")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_bert_workspace_bytes", B, N, what="PL-BERT weights not finalized?")
+        _lib.check(self.lib.st2_bert_forward(self.h, tokens.data_ptr(), _ptr(lengths), B, N, out.data_ptr(), ws_ptr, nbytes,
+                                             _stream(dev)), "st2_bert_forward")
         return out.transpose(1, 2)
 
     # -- the whole front (tokens -> t_en, d, s, ref, durations) ---------------------------------------------------------------
@@ -343,9 +327,7 @@ class Engine:
         noise, step_noise, ref_s, s_prev = f(noise), f(step_noise), f(ref_s), f(s_prev)
         assert noise.numel() == B * C2 and step_noise.numel() == (steps - 1) * B * C2 and len(table) == (steps - 1) * 11
         assert s_prev is None or s_prev.numel() == (C2 if carry else B * C2)
-        if lengths is not None:
-            lengths = lengths.to(torch.int32).contiguous()
-            assert lengths.device == dev and lengths.numel() == B
+        lengths = _lengths(lengths, dev, B)
         new = lambda *shape, dtype=torch.float32: torch.empty(shape, device=dev, dtype=dtype)
         out = dict(t_en=new(B, cfg.dim_in, N), d_cm=new(B, cfg.pred_hidden + cfg.style_dim, N), s=new(B, cfg.style_dim),
                    ref=new(B, cfg.style_dim), s_pred=new(B, C2),
@@ -357,13 +339,9 @@ class Engine:
                            embedding_scale=float(embedding_scale), table=tab, sigma0=float(sigma0), alpha=float(alpha),
                            beta=float(beta), t=float(t), t_en=ptr(out["t_en"]), d_cm=ptr(out["d_cm"]), s=ptr(out["s"]),
                            ref=ptr(out["ref"]), s_pred_out=ptr(out["s_pred"]), durations=ptr(out["durations"]), carry=int(bool(carry)))
-        nbytes = self.lib.st2_front_workspace_bytes(self.h, C.byref(a))
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_front_workspace_bytes failed (a weight group is not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_front_forward(self.h, C.byref(a), ws_ptr, nbytes, stream), "st2_front_forward")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_front_workspace_bytes", C.byref(a),
+                                             what="a weight group is not finalized?")
+        _lib.check(self.lib.st2_front_forward(self.h, C.byref(a), ws_ptr, nbytes, _stream(dev)), "st2_front_forward")
         return out
 
     # -- duration stage (DurationEncoder + duration LSTM + head) -------------------------------------------------------
@@ -374,21 +352,14 @@ class Engine:
         dev = d_en.device
         d_en, s = d_en.float().contiguous(), s.float().contiguous()
         assert dh == self.cfg.pred_hidden and s.shape == (B, self.cfg.style_dim)
-        if lengths is not None:
-            lengths = lengths.to(torch.int32).contiguous()
-            assert lengths.device == dev and lengths.numel() == B
+        lengths = _lengths(lengths, dev, B)
         d_cm = torch.empty((B, dh + self.cfg.style_dim, N), device=dev, dtype=torch.float32)
         dur = torch.empty((B, N), device=dev, dtype=torch.int64) if want_durations else None
-        nbytes = self.lib.st2_duration_workspace_bytes(self.h, B, N)
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_duration_workspace_bytes failed (duration-encoder weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_duration_forward(self.h, d_en.data_ptr(), s.data_ptr(),
-                                                 0 if lengths is None else lengths.data_ptr(), B, N, int(tail),
-                                                 d_cm.data_ptr(), 0 if dur is None else dur.data_ptr(), ws_ptr, nbytes,
-                                                 stream), "st2_duration_forward")
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_duration_workspace_bytes", B, N,
+                                             what="duration-encoder weights not finalized?")
+        _lib.check(self.lib.st2_duration_forward(self.h, d_en.data_ptr(), s.data_ptr(), _ptr(lengths), B, N, int(tail),
+                                                 d_cm.data_ptr(), _ptr(dur), ws_ptr, nbytes, _stream(dev)),
+                   "st2_duration_forward")
         return d_cm, dur
 
     # -- sampler ---------------------------------------------------------------------------------------------------
@@ -404,19 +375,13 @@ class Engine:
         step_noise = step_noise.float().contiguous()
         assert step_noise.numel() == (steps - 1) * B * Cc and noise.numel() == B * Cc
         out = torch.empty((B, 1, Cc), device=dev, dtype=torch.float32)
-        nbytes = self.lib.st2_sampler_workspace_bytes(self.h, B, N, steps, float(scale))
-        if nbytes <= 0:
-            raise _lib.St2Error("st2_sampler_workspace_bytes failed (weights not finalized?)")
-        ws = torch.empty((nbytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
+        ws, ws_ptr, nbytes = self._workspace(dev, "st2_sampler_workspace_bytes", B, N, steps, float(scale),
+                                             what="weights not finalized?")
         st = torch.empty((steps - 1, B, 1, Cc), device=dev, dtype=torch.float32) if taps is not None else None
         tab = (C.c_double * len(table))(*table)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-        _lib.check(self.lib.st2_sampler_run(self.h, noise.data_ptr(), embedding.data_ptr(),
-                                            0 if features is None else features.data_ptr(), step_noise.data_ptr(),
-                                            0 if lengths is None else lengths.data_ptr(), B, N, steps, float(scale), tab,
-                                            float(sigma0), out.data_ptr(), ws_ptr, nbytes,
-                                            0 if st is None else st.data_ptr(), stream), "st2_sampler_run")
+        _lib.check(self.lib.st2_sampler_run(self.h, noise.data_ptr(), embedding.data_ptr(), _ptr(features),
+                                            step_noise.data_ptr(), _ptr(lengths), B, N, steps, float(scale), tab, float(sigma0),
+                                            out.data_ptr(), ws_ptr, nbytes, _ptr(st), _stream(dev)), "st2_sampler_run")
         if taps is not None:
             for i in range(steps - 1):
                 taps["step%d" % i] = st[i]

@@ -6,6 +6,8 @@ tensors.  PyTorch is plumbing here (allocation, streams); all arithmetic happens
 There is no CPU path: a tensor that is not on a HIP device raises.
 """
 import ctypes as C
+import json
+import warnings
 
 import torch
 
@@ -104,9 +106,50 @@ def _chk_len(t, name, n, like):
     return t.data_ptr()
 
 
+def _nb(t, ndim=3):
+    """Rows of the batch a lengths tensor describes: the leading extent of `t`, or -1 (no lengths tensor fits) when `t` is not
+    the `ndim`-D tensor the wrapper goes on to demand."""
+    return t.shape[0] if torch.is_tensor(t) and t.dim() == ndim else -1
+
+
 def _bs_cs(t):
     """(batch stride, channel stride) of an NCL view."""
     return t.stride(0), t.stride(1)
+
+
+_PRO_NORM = (PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_COLNORM)  # prologues that read stats / gamma / beta
+_PRO_SNAKE = (PRO_ADAIN_SNAKE, PRO_SNAKE)  # prologues that read alpha
+
+
+def _chk_prologue(pro, B, Cc, L, stats, gamma, beta, alpha, gb_seg):
+    """Operands of a conv prologue over x [B, Cc, L] (include/st2.h st2_act_split / st2_conv_desc): stats [B, Cc, 2] (AdaIN) or
+    [B, L, 2] (PRO_COLNORM), gamma / beta [1 or B, Cc] -- or [G, Cc] with `gb_seg` > 0, see `activate` -- and alpha [Cc]
+    (Snake).  Returns the batch stride of gamma / beta (0: one row for the whole batch)."""
+    gbs = 0
+    if pro in _PRO_NORM:
+        _chk(stats, "stats", 3)
+        _chk(gamma, "gamma", 2)
+        _chk(beta, "beta", 2)
+        want = (B, L, 2) if pro == PRO_COLNORM else (B, Cc, 2)
+        assert tuple(stats.shape) == want and stats.is_contiguous(), (stats.shape, want)
+        assert gamma.shape[1] == Cc and beta.shape[1] == Cc
+        gbs = gamma.stride(0) if gamma.shape[0] > 1 else 0
+        bbs = beta.stride(0) if beta.shape[0] > 1 else 0
+        if gb_seg:
+            assert pro == PRO_COLNORM and B == 1 and gamma.shape[0] * gb_seg >= L and beta.shape[0] == gamma.shape[0]
+            assert gbs == bbs
+        else:
+            assert gamma.shape[0] in (1, B) and beta.shape[0] == gamma.shape[0] and gbs == bbs
+    if pro in _PRO_SNAKE:
+        _chk(alpha, "alpha", 1)
+        assert alpha.numel() == Cc and alpha.is_contiguous()
+    return gbs
+
+
+def _chk_split_weight(wt, C_in, C_out, ks):
+    if (wt.C_in, wt.C_out, wt.ks) != (C_in, C_out, ks) or not wt.wq.is_cuda or not wt.wq.is_contiguous():
+        raise _lib.St2Error("split weight is for (C_in=%d, C_out=%d, ks=%d) on %s, call has (%d, %d, %d)" % (
+            wt.C_in, wt.C_out, wt.ks, wt.wq.device, C_in, C_out, ks))
 
 
 def x_scale_for(pro):
@@ -115,7 +158,7 @@ def x_scale_for(pro):
     range; un-normalised inputs (plain / LeakyReLU / Snake prologues: the decoder's `cat` buffer carries the F0 curve
     in Hz, generator stage outputs, FFN intermediates) take 1, i.e. the full +-65504 of f16 (the lo half is then exact
     to 2^-25 absolute through f16 subnormals).  Beyond the range the kernels clamp and raise STATUS_F16_RANGE."""
-    return F16S_X_SCALE if pro in (PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_COLNORM) else 1.0
+    return F16S_X_SCALE if pro in _PRO_NORM else 1.0
 
 
 def calibrated_x_scale(max_abs, margin_bits=3):
@@ -144,7 +187,6 @@ def check_status(ignore=0):
     if st > 0 and st & _lib.STATUS_LSTM_RECOVERED:  # informational: the outputs are valid, the call lost its latency advantage
         global lstm_recoveries
         lstm_recoveries += 1
-        import warnings
         warnings.warn("a cooperative BiLSTM group was not co-resident in time; the call was re-run on the single-CU kernel "
                       "in-stream (results valid; ST2_STATUS_LSTM_RECOVERED)", RuntimeWarning, stacklevel=2)
         st &= ~_lib.STATUS_LSTM_RECOVERED
@@ -200,10 +242,9 @@ def tune_variant_name(v):
 def conv_tune_table():
     """The autotuner's table for the current device: a list of dicts {ks, C_in, C_out, L, B, chosen, candidates: [{variant,
     name, ms}]} (ms = 0 for classes pinned by hand)."""
-    import ctypes
     lib = _lib.load()
     n = lib.st2_conv_tune_read(None, 0)
-    rows = (ctypes.c_double * (24 * max(n, 1)))()
+    rows = (C.c_double * (24 * max(n, 1)))()
     n = min(n, lib.st2_conv_tune_read(rows, n))
     out = []
     for i in range(n):
@@ -223,12 +264,10 @@ def conv_tune_set(ks, C_in, C_out, L_out, B, variant):
 def probe_cu_health():
     """(report dict, CU mask as a list of 32-bit words, number of excluded CUs) -- include/st2.h `st2_probe_cu_health`: which
     CUs of this box run the conv path's workgroups abnormally slowly, and the CU mask of the device without them."""
-    import ctypes
-    import json
-    buf = ctypes.create_string_buffer(16384)
-    mask = (ctypes.c_uint32 * 16)()
-    n = ctypes.c_int32(0)
-    _lib.check(_lib.load().st2_probe_cu_health(buf, len(buf), mask, 16, ctypes.byref(n)), "st2_probe_cu_health")
+    buf = C.create_string_buffer(16384)
+    mask = (C.c_uint32 * 16)()
+    n = C.c_int32(0)
+    _lib.check(_lib.load().st2_probe_cu_health(buf, len(buf), mask, 16, C.byref(n)), "st2_probe_cu_health")
     rep = json.loads(buf.value.decode())
     words = (rep["cus"] + 31) // 32
     return rep, [int(mask[i]) for i in range(words)], int(n.value)
@@ -249,13 +288,12 @@ class headroom:
         return self
 
     def __exit__(self, *exc):
-        import ctypes
         lib = _lib.load()
         torch.cuda.synchronize()
         _lib.check(lib.st2_debug_headroom(0), "st2_debug_headroom")
         n = lib.st2_debug_headroom_read(None, 0)
         W = _lib.HEADROOM_COLS
-        buf = (ctypes.c_double * (W * max(n, 1)))()
+        buf = (C.c_double * (W * max(n, 1)))()
         n = min(n, lib.st2_debug_headroom_read(buf, n))
         pro_names = ["none", "leaky", "adain+leaky", "adain+snake", "snake", "layernorm"]
         for i in range(max(n, 0)):
@@ -268,9 +306,7 @@ class headroom:
 
 def probe_box(level=0):
     """Micro-measurements of the current device as a dict (include/st2.h `st2_probe_box`; ~0.5 s, synchronises)."""
-    import ctypes
-    import json
-    buf = ctypes.create_string_buffer(16384)
+    buf = C.create_string_buffer(16384)
     _lib.check(_lib.load().st2_probe_box(buf, len(buf), level), "st2_probe_box")
     return json.loads(buf.value.decode())
 
@@ -326,43 +362,20 @@ def activate(x, *, pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, g
     (x_scale = x_scale_for(pro) unless the caller passes a calibrated power of two, `calibrated_x_scale`).  `gb_seg` > 0 (PRO_COLNORM on a token-merged view [1, C, G * gb_seg]): gamma / beta
     are [G, C] and row l // gb_seg applies at position l (per-utterance AdaLayerNorm affine, include/st2.h).  `lengths` (int32 [B]
     on the device, `st2_act_split_len`): row b ends at lengths[b], the positions past it are written as the conv's zero padding."""
-    if lengths is not None:
-        _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
-        if pro == PRO_COLNORM:
-            raise _lib.St2Error("activate: per-row lengths are not defined for PRO_COLNORM (st2_act_split_len)")
+    lp = _chk_len(lengths, "lengths", _nb(x), x)
+    if lengths is not None and pro == PRO_COLNORM:
+        raise _lib.St2Error("activate: per-row lengths are not defined for PRO_COLNORM (st2_act_split_len)")
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, L = x.shape
     cg = (Cc + c_pad - 1) // c_pad * c_pad // 8
     Lp = xs_row_slots(L)
     data = torch.empty((B, 2, cg, Lp, 8), device=x.device, dtype=torch.float16)
-    gbs = 0
-    if pro in (PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_COLNORM):
-        _chk(stats, "stats", 3)
-        _chk(gamma, "gamma", 2)
-        _chk(beta, "beta", 2)
-        want = (B, L, 2) if pro == PRO_COLNORM else (B, Cc, 2)
-        assert tuple(stats.shape) == want and stats.is_contiguous(), (stats.shape, want)
-        assert gamma.shape[1] == Cc and beta.shape[1] == Cc
-        gbs = gamma.stride(0) if gamma.shape[0] > 1 else 0
-        bbs = beta.stride(0) if beta.shape[0] > 1 else 0
-        if gb_seg:
-            assert pro == PRO_COLNORM and B == 1 and gamma.shape[0] * gb_seg >= L and beta.shape[0] == gamma.shape[0]
-            assert gbs == bbs
-        else:
-            assert gamma.shape[0] in (1, B) and beta.shape[0] == gamma.shape[0] and gbs == bbs
-    if pro in (PRO_ADAIN_SNAKE, PRO_SNAKE):
-        _chk(alpha, "alpha", 1)
-        assert alpha.numel() == Cc and alpha.is_contiguous()
+    gbs = _chk_prologue(pro, B, Cc, L, stats, gamma, beta, alpha, gb_seg)
     xsc = float(x_scale) if x_scale else x_scale_for(pro)
-    if lengths is not None:
-        _lib.check(lib.st2_act_split_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
-                                         _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
-                                         xsc, data.data_ptr(), cg, Lp, XS_HALO, lengths.data_ptr(), _stream()), "st2_act_split_len")
-        return XsTensor(data, Cc, L, XS_HALO, xsc)
-    _lib.check(lib.st2_act_split(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
-                                 _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
-                                 xsc, data.data_ptr(), cg, Lp, XS_HALO, _stream()), "st2_act_split")
+    _lib.check(lib.st2_act_split_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
+                                     _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
+                                     xsc, data.data_ptr(), cg, Lp, XS_HALO, lp, _stream()), "st2_act_split_len")
     return XsTensor(data, Cc, L, XS_HALO, xsc)
 
 
@@ -376,19 +389,17 @@ def stats_finalize(part, B, C, nt, L, cols=128, eps=1e-5, out=None, lengths=None
     """`st2_stats_finalize`: the buffer of `new_part` filled by the producer of a [B, C, L] tensor (slots of `cols` columns) ->
     stats [B, C, 2] (mean, rstd) of that tensor.  `lengths` (int32 [B * C / len_div] on the device, `st2_stats_finalize_len`):
     row r of the B * C covers its first lengths[r // len_div] columns; slots past that end are not read."""
-    if lengths is not None:
-        if len_div <= 0 or (B * C) % len_div:
-            raise _lib.St2Error("stats_finalize: len_div=%d does not divide the %d rows" % (len_div, B * C))
-        _chk_len(lengths, "lengths", B * C // len_div, part)
+    if lengths is None:
+        len_div = 1  # no lengths to share between rows: what `st2_stats_finalize` passes
+    elif len_div <= 0 or (B * C) % len_div:
+        raise _lib.St2Error("stats_finalize: len_div=%d does not divide the %d rows" % (len_div, B * C))
+    lp = _chk_len(lengths, "lengths", B * C // len_div, part)
     lib = _lib.load()
     assert part.numel() >= B * C * nt * 3 and part.is_contiguous()
     if out is None:
         out = torch.empty((B, C, 2), device=part.device, dtype=torch.float32)
-    if lengths is not None:
-        _lib.check(lib.st2_stats_finalize_len(part.data_ptr(), B * C, nt, L, eps, out.data_ptr(), int(cols), lengths.data_ptr(),
-                                              int(len_div), _stream()), "st2_stats_finalize_len")
-        return out
-    _lib.check(lib.st2_stats_finalize(part.data_ptr(), B * C, nt, L, eps, out.data_ptr(), int(cols), _stream()), "st2_stats_finalize")
+    _lib.check(lib.st2_stats_finalize_len(part.data_ptr(), B * C, nt, L, eps, out.data_ptr(), int(cols), lp, int(len_div),
+                                          _stream()), "st2_stats_finalize_len")
     return out
 
 
@@ -403,9 +414,7 @@ def conv1d_xs(xs, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, ou
     lib = _lib.load()
     assert isinstance(xs, XsTensor) and isinstance(wt, SplitConvWeight)
     B, C_in, L_in = xs.data.shape[0], xs.C, xs.L
-    if (wt.C_in, wt.C_out, wt.ks) != (C_in, C_out, ks) or not wt.wq.is_cuda or not wt.wq.is_contiguous():
-        raise _lib.St2Error("split weight is for (C_in=%d, C_out=%d, ks=%d) on %s, call has (%d, %d, %d)" % (
-            wt.C_in, wt.C_out, wt.ks, wt.wq.device, C_in, C_out, ks))
+    _chk_split_weight(wt, C_in, C_out, ks)
     if L_out is None:
         L_out = L_in
     if out is None:
@@ -463,9 +472,8 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     st2_act_split + st2_conv1d_xs.  want_stats=True returns (out, InstanceNorm statistics of out [B, C_out, 2]).  x_len / y_len
     (int32 [B] on the device, st2_conv_desc): per-row ends of the input (zero padding after the prologue) and of the output
     (nothing stored past it, statistics over its columns); split-f16 weights only (st2_conv1d rejects them)."""
-    nb = x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1
-    _chk_len(x_len, "x_len", nb, x)
-    _chk_len(y_len, "y_len", nb, x)
+    _chk_len(x_len, "x_len", _nb(x), x)
+    _chk_len(y_len, "y_len", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, C_in, L_in = x.shape
@@ -481,9 +489,7 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
         raise _lib.St2Error("gb_seg (per-segment affine of a token-merged view) exists on the st2_act_split + "
                             "st2_conv1d_xs path only; this call routes to the fused kernel")
     if split:
-        if (wt.C_in, wt.C_out, wt.ks) != (C_in, C_out, ks) or not wt.wq.is_cuda or not wt.wq.is_contiguous():
-            raise _lib.St2Error("split weight is for (C_in=%d, C_out=%d, ks=%d) on %s, call has (%d, %d, %d)" % (
-                wt.C_in, wt.C_out, wt.ks, wt.wq.device, C_in, C_out, ks))
+        _chk_split_weight(wt, C_in, C_out, ks)
     else:
         _chk(wt, "wt", 2)
         if wt.shape[0] != C_in * ks or not wt.is_contiguous():
@@ -511,21 +517,11 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     d.y, d.y_bs, d.y_cs = out.data_ptr(), out.stride(0), out.stride(1)
     d.x_len, d.y_len = _ptr(x_len), _ptr(y_len)
     d.pro, d.slope = pro, slope
-    if pro in (PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_COLNORM):
-        _chk(stats, "stats", 3)
-        _chk(gamma, "gamma", 2)
-        _chk(beta, "beta", 2)
-        want = (B, L_in, 2) if pro == PRO_COLNORM else (B, C_in, 2)
-        assert tuple(stats.shape) == want and stats.is_contiguous(), (stats.shape, want)
-        assert gamma.shape[1] == C_in and beta.shape[1] == C_in
-        gbs = gamma.stride(0) if gamma.shape[0] > 1 else 0
-        bbs = beta.stride(0) if beta.shape[0] > 1 else 0
-        assert gamma.shape[0] in (1, B) and beta.shape[0] == gamma.shape[0] and (gbs == bbs)
+    gbs = _chk_prologue(pro, B, C_in, L_in, stats, gamma, beta, alpha, 0)  # gb_seg was refused above
+    if pro in _PRO_NORM:
         d.stats, d.gamma, d.beta, d.gb_bs = stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), gbs
         d.gamma_plus_one = 1 if gamma_plus_one else 0
-    if pro in (PRO_ADAIN_SNAKE, PRO_SNAKE):
-        _chk(alpha, "alpha", 1)
-        assert alpha.numel() == C_in and alpha.is_contiguous()
+    if pro in _PRO_SNAKE:
         d.alpha = alpha.data_ptr()
     _fill_epilogue(d, B, C_out, L_out, res, res_shift, res2, div, act, act_split, act_slope)
     ws = part = None
@@ -550,9 +546,8 @@ def conv1d_direct(x, w, bias, stride, pad, L_out=None, out=None, x_len=None, y_l
     """Plain-weight ([C_out, C_in, ks]) direct conv for strided / tiny-C_in layers (`st2_conv1d_direct`).  x_len / y_len
     (int32 [B] on the device, `st2_conv1d_direct_len`): the input row ends (zero padding) at x_len[b], outputs from y_len[b]
     on are exact zeros."""
-    nb = x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1
-    _chk_len(x_len, "x_len", nb, x)
-    _chk_len(y_len, "y_len", nb, x)
+    xlp = _chk_len(x_len, "x_len", _nb(x), x)
+    ylp = _chk_len(y_len, "y_len", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(w, "w", 3)
@@ -566,14 +561,9 @@ def conv1d_direct(x, w, bias, stride, pad, L_out=None, out=None, x_len=None, y_l
     if out is None:
         out = torch.empty((B, C_out, L_out), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
-    if x_len is not None or y_len is not None:
-        _lib.check(lib.st2_conv1d_direct_len(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), _ptr(bias), out.data_ptr(),
-                                             out.stride(0), out.stride(1), B, C_in, C_out, L_in, L_out, ks, stride, pad,
-                                             _ptr(x_len), _ptr(y_len), _stream()), "st2_conv1d_direct_len")
-        return out
-    _lib.check(lib.st2_conv1d_direct(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), _ptr(bias),
-                                     out.data_ptr(), out.stride(0), out.stride(1), B, C_in, C_out, L_in, L_out,
-                                     ks, stride, pad, _stream()), "st2_conv1d_direct")
+    _lib.check(lib.st2_conv1d_direct_len(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), _ptr(bias), out.data_ptr(),
+                                         out.stride(0), out.stride(1), B, C_in, C_out, L_in, L_out, ks, stride, pad,
+                                         xlp, ylp, _stream()), "st2_conv1d_direct_len")
     return out
 
 
@@ -591,18 +581,14 @@ def phase_split(x, stride, pad, Lu):
 def instnorm_stats(x, eps=1e-5, out=None, lengths=None):
     """`st2_instnorm_stats`: x [B, C, L] -> (mean, rstd) [B, C, 2]; `lengths` (int32 [B] on the device,
     `st2_instnorm_stats_len`): row b over its first lengths[b] columns."""
-    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
+    lp = _chk_len(lengths, "lengths", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, L = x.shape
     if out is None:
         out = torch.empty((B, Cc, 2), device=x.device, dtype=torch.float32)
-    if lengths is not None:
-        _lib.check(lib.st2_instnorm_stats_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, eps, out.data_ptr(),
-                                              lengths.data_ptr(), _stream()), "st2_instnorm_stats_len")
-        return out
-    _lib.check(lib.st2_instnorm_stats(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, eps, out.data_ptr(),
-                                      _stream()), "st2_instnorm_stats")
+    _lib.check(lib.st2_instnorm_stats_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, eps, out.data_ptr(), lp,
+                                          _stream()), "st2_instnorm_stats_len")
     return out
 
 
@@ -644,9 +630,8 @@ def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, ref
     `st2_convt_interleave_stats_len`): row b has q_len[b] phase columns and out_len[b] outputs."""
     if (q_len is None) != (out_len is None):
         raise _lib.St2Error("convt_interleave: q_len and out_len go together")
-    nb = phases.shape[0] if torch.is_tensor(phases) and phases.dim() == 3 else -1
-    _chk_len(q_len, "q_len", nb, phases)
-    _chk_len(out_len, "out_len", nb, phases)
+    qlp = _chk_len(q_len, "q_len", _nb(phases), phases)
+    olp = _chk_len(out_len, "out_len", _nb(phases), phases)
     lib = _lib.load()
     _chk(phases, "phases", 3)
     _chk(bias, "bias", 1)
@@ -663,27 +648,19 @@ def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, ref
     if want_stats:
         nt = (L_out + CVT_TILE - 1) // CVT_TILE
         part = new_part(B, C_out, nt, phases.device)
-    if q_len is not None:
-        _lib.check(lib.st2_convt_interleave_stats_len(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
-                                                      _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
-                                                      C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
-                                                      q_len.data_ptr(), out_len.data_ptr(), _stream()), "st2_convt_interleave_len")
-        if want_stats:
-            return out, stats_finalize(part, B, C_out, nt, L_out, cols=CVT_TILE, lengths=out_len, len_div=C_out)
-        return out
-    _lib.check(lib.st2_convt_interleave_stats(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
-                                              _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
-                                              C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
-                                              _stream()), "st2_convt_interleave")
+    _lib.check(lib.st2_convt_interleave_stats_len(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
+                                                  _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
+                                                  C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
+                                                  qlp, olp, _stream()), "st2_convt_interleave_stats_len")
     if want_stats:
-        return out, stats_finalize(part, B, C_out, nt, L_out, cols=CVT_TILE)
+        return out, stats_finalize(part, B, C_out, nt, L_out, cols=CVT_TILE, lengths=out_len, len_div=C_out)
     return out
 
 
 def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None, lengths=None):
     """`st2_adain_leaky_pool`: x [B, C, L] -> [B, C, 2L]; `lengths` (int32 [B] on the device, `st2_adain_leaky_pool_len`): the
     input row ends (zero padding) at lengths[b], 2 * lengths[b] outputs are written and the rest of the row is left as it was."""
-    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
+    lp = _chk_len(lengths, "lengths", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(stats, "stats", 3)
@@ -695,16 +672,10 @@ def adain_leaky_pool(x, stats, gamma, beta, slope, w, bias, out=None, lengths=No
     assert w.shape == (Cc, 3) and w.is_contiguous() and gamma.stride(0) == beta.stride(0)
     if out is None:
         out = torch.empty((B, Cc, 2 * L), device=x.device, dtype=torch.float32)
-    if lengths is not None:
-        _lib.check(lib.st2_adain_leaky_pool_len(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
-                                                beta.data_ptr(), gamma.stride(0), slope, w.data_ptr(), _ptr(bias),
-                                                out.data_ptr(), out.stride(0), out.stride(1), B, Cc, L, lengths.data_ptr(),
-                                                _stream()), "st2_adain_leaky_pool_len")
-        return out
-    _lib.check(lib.st2_adain_leaky_pool(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
-                                        beta.data_ptr(), gamma.stride(0), slope, w.data_ptr(), _ptr(bias),
-                                        out.data_ptr(), out.stride(0), out.stride(1), B, Cc, L, _stream()),
-               "st2_adain_leaky_pool")
+    _lib.check(lib.st2_adain_leaky_pool_len(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
+                                            beta.data_ptr(), gamma.stride(0), slope, w.data_ptr(), _ptr(bias),
+                                            out.data_ptr(), out.stride(0), out.stride(1), B, Cc, L, lp, _stream()),
+               "st2_adain_leaky_pool_len")
     return out
 
 
@@ -712,7 +683,7 @@ def har_source(f0, U, noise, lin_w, lin_b, sine_amp=0.1, noise_std=0.003, voiced
                sample_rate=24000.0, f_len=None, out=None):
     """f0 [B, F] -> har_source [B, F*U]; noise [B, F*U, H] standard-normal draws.  `f_len` (int32 [B] on the device,
     `st2_har_source_len`): row b holds f_len[b] frames, its output is exactly 0 from f_len[b] * U on."""
-    _chk_len(f_len, "f_len", f0.shape[0] if torch.is_tensor(f0) and f0.dim() == 2 else -1, f0)
+    lp = _chk_len(f_len, "f_len", _nb(f0, 2), f0)
     lib = _lib.load()
     _chk(f0, "f0", 2)
     _chk(noise, "noise", 3)
@@ -727,14 +698,9 @@ def har_source(f0, U, noise, lin_w, lin_b, sine_amp=0.1, noise_std=0.003, voiced
         out = torch.empty((B, F * U), device=f0.device, dtype=torch.float32)
     _chk(out, "out", 2)
     assert out.shape == (B, F * U) and out.is_contiguous()
-    if f_len is not None:
-        _lib.check(lib.st2_har_source_len(f0.data_ptr(), B, F, U, H, noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
-                                          sine_amp, noise_std, voiced_threshold, sample_rate, scratch.data_ptr(),
-                                          out.data_ptr(), f_len.data_ptr(), _stream()), "st2_har_source_len")
-        return out
-    _lib.check(lib.st2_har_source(f0.data_ptr(), B, F, U, H, noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
-                                  sine_amp, noise_std, voiced_threshold, sample_rate, scratch.data_ptr(),
-                                  out.data_ptr(), _stream()), "st2_har_source")
+    _lib.check(lib.st2_har_source_len(f0.data_ptr(), B, F, U, H, noise.data_ptr(), lin_w.data_ptr(), lin_b.data_ptr(),
+                                      sine_amp, noise_std, voiced_threshold, sample_rate, scratch.data_ptr(),
+                                      out.data_ptr(), lp, _stream()), "st2_har_source_len")
     return out
 
 
@@ -742,7 +708,7 @@ def stft_mag_phase(x, n_fft, hop, lengths=None, out=None):
     """x [B, L] -> (|X|, angle X) [B, n_fft + 2, L // hop + 1] (`st2_stft_mag_phase`).  `lengths` (int32 [B] on the device,
     `st2_stft_mag_phase_len`): row b is its first lengths[b] samples (clamped to n_fft / 2 + 1 .. L), reflect-padded at its
     own end; frames past lengths[b] // hop are exact zeros."""
-    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else -1, x)
+    lp = _chk_len(lengths, "lengths", _nb(x, 2), x)
     lib = _lib.load()
     _chk(x, "x", 2)
     assert x.is_contiguous()
@@ -751,19 +717,15 @@ def stft_mag_phase(x, n_fft, hop, lengths=None, out=None):
     har = out if out is not None else torch.empty((B, n_fft + 2, M), device=x.device, dtype=torch.float32)
     _chk(har, "out", 3)
     assert har.shape == (B, n_fft + 2, M)
-    if lengths is not None:
-        _lib.check(lib.st2_stft_mag_phase_len(x.data_ptr(), B, L, n_fft, hop, har.data_ptr(), har.stride(0), har.stride(1),
-                                              lengths.data_ptr(), _stream()), "st2_stft_mag_phase_len")
-        return har
-    _lib.check(lib.st2_stft_mag_phase(x.data_ptr(), B, L, n_fft, hop, har.data_ptr(), har.stride(0), har.stride(1),
-                                      _stream()), "st2_stft_mag_phase")
+    _lib.check(lib.st2_stft_mag_phase_len(x.data_ptr(), B, L, n_fft, hop, har.data_ptr(), har.stride(0), har.stride(1), lp,
+                                          _stream()), "st2_stft_mag_phase_len")
     return har
 
 
 def istft(sp, n_fft, hop, m_len=None, out=None):
     """sp [B, n_fft+2, M] = cat(spec, phase) -> wave [B, 1, hop*(M-1)].  `m_len` (int32 [B] on the device, `st2_istft_len`):
     row b has m_len[b] frames (clamped to 2..M) and emits hop * (m_len[b] - 1) samples, exact zeros after them."""
-    _chk_len(m_len, "m_len", sp.shape[0] if torch.is_tensor(sp) and sp.dim() == 3 else -1, sp)
+    lp = _chk_len(m_len, "m_len", _nb(sp), sp)
     lib = _lib.load()
     _chk(sp, "sp", 3)
     B, Cc, M = sp.shape
@@ -771,12 +733,8 @@ def istft(sp, n_fft, hop, m_len=None, out=None):
     wave = out if out is not None else torch.empty((B, 1, hop * (M - 1)), device=sp.device, dtype=torch.float32)
     _chk(wave, "out", 3)
     assert wave.shape == (B, 1, hop * (M - 1))
-    if m_len is not None:
-        _lib.check(lib.st2_istft_len(sp.data_ptr(), sp.stride(0), sp.stride(1), B, M, n_fft, hop, wave.data_ptr(),
-                                     wave.stride(0), m_len.data_ptr(), _stream()), "st2_istft_len")
-        return wave
-    _lib.check(lib.st2_istft(sp.data_ptr(), sp.stride(0), sp.stride(1), B, M, n_fft, hop, wave.data_ptr(),
-                             wave.stride(0), _stream()), "st2_istft")
+    _lib.check(lib.st2_istft_len(sp.data_ptr(), sp.stride(0), sp.stride(1), B, M, n_fft, hop, wave.data_ptr(),
+                                 wave.stride(0), lp, _stream()), "st2_istft_len")
     return wave
 
 
@@ -790,13 +748,12 @@ def attention(q, k, v, heads, scale, out=None, key_len=None):
     D = HD // heads
     assert k.shape == q.shape and v.shape == q.shape
     assert _bs_cs(q) == _bs_cs(k) == _bs_cs(v)
+    lp = _chk_len(key_len, "key_len", B, q)
     if out is None:
         out = torch.empty((B, HD, N), device=q.device, dtype=torch.float32)
-    if key_len is not None:
-        assert key_len.is_cuda and key_len.dtype == torch.int32 and key_len.numel() == B and key_len.is_contiguous()
     _lib.check(lib.st2_attention_keylen(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), q.stride(1),
-                                        out.data_ptr(), out.stride(0), out.stride(1), B, heads, D, N, scale,
-                                        0 if key_len is None else key_len.data_ptr(), _stream()), "st2_attention")
+                                        out.data_ptr(), out.stride(0), out.stride(1), B, heads, D, N, scale, lp, _stream()),
+               "st2_attention")
     return out
 
 
@@ -813,15 +770,13 @@ def colnorm_apply(x, stats, gamma, beta, *, gamma_plus_one=False, act=ACT_NONE, 
     assert gamma.shape[1] == Cc and beta.shape == gamma.shape and gamma.shape[0] in (1, B)
     gbs = gamma.stride(0) if gamma.shape[0] > 1 else 0
     assert (beta.stride(0) if beta.shape[0] > 1 else 0) == gbs and gamma.stride(1) == 1 and beta.stride(1) == 1
-    if lengths is not None:
-        assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+    lp = _chk_len(lengths, "lengths", B, x)
     if out is None:
         out = torch.empty((B, Cc, L), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
     _lib.check(lib.st2_colnorm_apply(x.data_ptr(), x.stride(0), x.stride(1), stats.data_ptr(), gamma.data_ptr(),
-                                     beta.data_ptr(), gbs, 1 if gamma_plus_one else 0, act, slope,
-                                     0 if lengths is None else lengths.data_ptr(), out.data_ptr(), out.stride(0),
-                                     out.stride(1), B, Cc, L, _stream()), "st2_colnorm_apply")
+                                     beta.data_ptr(), gbs, 1 if gamma_plus_one else 0, act, slope, lp, out.data_ptr(),
+                                     out.stride(0), out.stride(1), B, Cc, L, _stream()), "st2_colnorm_apply")
     return out
 
 
@@ -848,11 +803,9 @@ def lstm_bidir(G, whh_t, lengths=None, out=None):
     B, R, N = G.shape
     H = R // 8
     assert whh_t.shape == (2, H, 4 * H) and whh_t.is_contiguous()
-    if lengths is not None:
-        assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+    lp = _chk_len(lengths, "lengths", B, G)
     if out is None:
         out = torch.empty((B, 2 * H, N), device=G.device, dtype=torch.float32)
-    lp = 0 if lengths is None else lengths.data_ptr()
     nbytes = lib.st2_lstm_coop_scratch_bytes(B) if lstm_mode() == "coop" else 0
     if nbytes > 0:
         scratch = torch.empty((nbytes,), device=G.device, dtype=torch.uint8)
@@ -905,12 +858,11 @@ def mean_tokens(x, out=None, lengths=None):
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, N = x.shape
+    lp = _chk_len(lengths, "lengths", B, x)
     if out is None:
         out = torch.empty((B, Cc), device=x.device, dtype=torch.float32)
-    if lengths is not None:
-        assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
-    _lib.check(lib.st2_mean_tokens_len(x.data_ptr(), x.stride(0), x.stride(1), out.data_ptr(), out.stride(0), B, Cc,
-                                       N, 0 if lengths is None else lengths.data_ptr(), _stream()), "st2_mean_tokens")
+    _lib.check(lib.st2_mean_tokens_len(x.data_ptr(), x.stride(0), x.stride(1), out.data_ptr(), out.stride(0), B, Cc, N, lp,
+                                       _stream()), "st2_mean_tokens")
     return out
 
 
@@ -994,20 +946,18 @@ def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False):
     B, K, N = x.shape
     J = w.shape[0]
     assert w.shape[1] == K and w.is_contiguous() and bias.numel() == J
-    if lengths is not None:
-        assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.numel() == B and lengths.is_contiguous()
+    lp = _chk_len(lengths, "lengths", B, x)
     dur = torch.empty((B, N), device=x.device, dtype=torch.int64)
     sums = torch.empty((B, N), device=x.device, dtype=torch.float32) if want_sums else None
     _lib.check(lib.st2_duration_head(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), bias.data_ptr(), B, K, J, N,
-                                     0 if lengths is None else lengths.data_ptr(), int(tail), dur.data_ptr(),
-                                     _ptr(sums), _stream()), "st2_duration_head")
+                                     lp, int(tail), dur.data_ptr(), _ptr(sums), _stream()), "st2_duration_head")
     return (dur, sums) if want_sums else dur
 
 
 def expand_by_durations(x, dur, T, shift=False, out=None, lengths=None):
     """`st2_expand_by_durations`: x [B, C, N], dur int64 [B, N] (rows sum to T) -> [B, C, T].  `lengths` (int32 [B] on the
     device, `st2_expand_by_durations_len`): row b's durations sum to lengths[b], its columns from there on are exact zeros."""
-    _chk_len(lengths, "lengths", x.shape[0] if torch.is_tensor(x) and x.dim() == 3 else -1, x)
+    lp = _chk_len(lengths, "lengths", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, N = x.shape
@@ -1015,14 +965,9 @@ def expand_by_durations(x, dur, T, shift=False, out=None, lengths=None):
     if out is None:
         out = torch.empty((B, Cc, T), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
-    if lengths is not None:
-        _lib.check(lib.st2_expand_by_durations_len(x.data_ptr(), x.stride(0), x.stride(1), dur.data_ptr(), B, Cc, N, T,
-                                                   1 if shift else 0, out.data_ptr(), out.stride(0), out.stride(1),
-                                                   lengths.data_ptr(), _stream()), "st2_expand_by_durations_len")
-        return out
-    _lib.check(lib.st2_expand_by_durations(x.data_ptr(), x.stride(0), x.stride(1), dur.data_ptr(), B, Cc, N, T,
-                                           1 if shift else 0, out.data_ptr(), out.stride(0), out.stride(1), _stream()),
-               "st2_expand_by_durations")
+    _lib.check(lib.st2_expand_by_durations_len(x.data_ptr(), x.stride(0), x.stride(1), dur.data_ptr(), B, Cc, N, T,
+                                               1 if shift else 0, out.data_ptr(), out.stride(0), out.stride(1), lp, _stream()),
+               "st2_expand_by_durations_len")
     return out
 
 
