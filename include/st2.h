@@ -55,12 +55,18 @@ int st2_device_info(int dev, char* name, int cap);
  *                            repairs the call in-stream and raises ST2_STATUS_LSTM_RECOVERED instead);
  *   ST2_STATUS_DURATION_SUM  a row of the durations handed to st2_expand_by_durations does not sum to T (caller-supplied
  *                            durations with a wrong `total_frames`): frames past the sum repeat the last phoneme.
+ *   ST2_STATUS_FRAME_CAPACITY  (added under ABI 23, additive) a row of the durations handed to st2_frames_from_durations
+ *                            sums to more than the capacity T_cap: its frame count was clamped to T_cap and the row is
+ *                            synthesised TRUNCATED to its first T_cap frames (st2_expand_by_durations_len then raises
+ *                            ST2_STATUS_DURATION_SUM for the same row).  Both bits mean "this row is not its solo run;
+ *                            retry with a larger capacity"; every other row of the batch is unaffected.
  * st2_status(clear != 0) returns the word and atomically clears it.  Returns < 0 if no HIP device is usable. */
 #define ST2_STATUS_F16_RANGE 1
 #define ST2_STATUS_LSTM_TIMEOUT 2
 #define ST2_STATUS_DURATION_SUM 4
 #define ST2_STATUS_LSTM_RECOVERED 8  /* informational: a cooperative BiLSTM group timed out and st2_lstm_bidir_coop_recovering
                                         re-ran the call on the single-CU kernel -- the outputs are VALID, latency was lost */
+#define ST2_STATUS_FRAME_CAPACITY 16 /* informational-but-reported: a row was truncated to the caller's frame capacity */
 int st2_status(int clear);
 
 /* ---- fused Conv1d (implicit GEMM on v_mfma_f32_32x32x2_f32, exact fp32) ------------ *
@@ -500,6 +506,36 @@ int st2_expand_by_durations(const float* x, int64_t x_bs, int32_t x_cs, const in
 int st2_expand_by_durations_len(const float* x, int64_t x_bs, int32_t x_cs, const int64_t* dur, int32_t B, int32_t C,
                                 int32_t N, int32_t T, int32_t shift, float* y, int64_t y_bs, int32_t y_cs, const int32_t* len,
                                 void* stream);
+
+/* ---- sync-free synthesis: device frame counts and packed PCM (added under ABI 23, additive: two kernel-level entry
+ * points, no new backend-table slot, no struct change) ------------------------------------------------------------- *
+ * A caller that states a frame CAPACITY T_cap (the longest utterance it accepts) needs no host read of the predicted
+ * durations: the frame counts stay on the device from the duration head to the packed samples.
+ *
+ * st2_frames_from_durations: frames[b] = clamp(sum_{n < len[b]} dur[b][n], 1, T_cap)  (dur int64 [B][N], N <= 512; len int32
+ * [B] on the device, clamped to 0..N, NULL = N; frames int32 [B]).  A row whose sum exceeds T_cap raises
+ * ST2_STATUS_FRAME_CAPACITY; that row is then synthesised truncated to its first T_cap frames (st2_expand_by_durations_len
+ * clamps the same way and raises ST2_STATUS_DURATION_SUM).  One launch, no allocation, no synchronisation.  NULL dur /
+ * frames, B <= 0, N <= 0, N > 512 or T_cap <= 0 return non-zero before any launch. */
+int st2_frames_from_durations(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, int32_t T_cap, int32_t* frames,
+                              void* stream);
+
+/* st2_wave_pack: the valid samples of a ragged batch of waveforms as ONE contiguous buffer.  Row b (at wave + b * w_bs,
+ * w_bs >= samples_per_frame * T_cap) contributes n_b = max(0, samples_per_frame * f_b - trim) samples, f_b = frames[b]
+ * clamped to 0..T_cap (a row of no frames contributes nothing); offsets (int64 [B + 1], device) receives the exclusive prefix sum of n_b,
+ * offsets[B] the total; out[offsets[b] + i] = cvt(wave[b][i]) for i < n_b:
+ *   ST2_PACK_F32  a bit copy (out is float);
+ *   ST2_PACK_S16  (int16_t) rint(clamp(x, -1, 1) * 32767.0f), round-to-nearest-even; a NaN sample gives 0 (out is int16_t).
+ * `out_capacity` is in SAMPLES: nothing at or past min(offsets[B], out_capacity) is written (offsets still describes the
+ * untruncated layout), and nothing of `wave` at or past samples_per_frame * f_b is read -- the ragged decoder's tails may
+ * hold anything.  trim: samples dropped from every row's end (the notebooks' HiFi-GAN tail).  Two launches (scan, move), no
+ * allocation, no synchronisation; the move stores 16 bytes per lane on the aligned body of every row and peels head and
+ * tail.  Bad arguments (NULL wave / frames / out / offsets, B <= 0 or > 65535, T_cap <= 0, samples_per_frame <= 0, trim < 0,
+ * out_capacity < 0, unknown fmt, w_bs too small) return non-zero before any launch. */
+enum st2_pack_format { ST2_PACK_F32 = 0, ST2_PACK_S16 = 1 };
+int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                  int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets,
+                  void* stream);
 
 /* ---- reference-audio style path (compute_style, Demo/Inference_LibriTTS.ipynb:100-111) ------------------------- *
  * The mel front-end (meldataset.py:58-66: torchaudio MelSpectrogram(n_mels 80, n_fft 2048, win 1200, hop 300) ->

@@ -21,6 +21,8 @@ f32p = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 
 PRO_NONE, PRO_LEAKY, PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_SNAKE, PRO_COLNORM = range(6)
 STATUS_F16_RANGE, STATUS_LSTM_TIMEOUT, STATUS_DURATION_SUM, STATUS_LSTM_RECOVERED = 1, 2, 4, 8
+STATUS_FRAME_CAPACITY = 16  # added under ABI 23: a row was truncated to the caller's frame capacity
+PACK_F32, PACK_S16 = 0, 1  # enum st2_pack_format
 ACT_NONE, ACT_GELU, ACT_EXP_SIN, ACT_TANH, ACT_LEAKY, ACT_GELU_TANH = range(6)
 
 
@@ -234,6 +236,9 @@ _SIGNATURES = {
                                               C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "st2_ragged_lengths": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
                                      C.c_void_p]),
+    "st2_frames_from_durations": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_wave_pack": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                C.c_int64, C.c_void_p, C.c_void_p]),
     "st2_prosody_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "st2_prosody_forward": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -174,13 +174,19 @@ def status(clear=False):
 
 
 lstm_recoveries = 0  # check_status() calls that found ST2_STATUS_LSTM_RECOVERED (bench.py reports it)
+frame_capacity_hits = 0  # check_status() calls that found ST2_STATUS_FRAME_CAPACITY (a row truncated to `max_frames`)
 
 
 def check_status(ignore=0):
     """Raises St2Error if a kernel reported a device-side condition since the last check (and clears it).  Called by
     the pipeline at its existing host synchronisation points and at the start of every call for the previous one's
     kernels, so a failure is never silent and costs no extra synchronisation.  `ignore`: status bits the caller expects
-    (pipeline.calibrate provokes F16_RANGE on purpose); every other bit is still reported."""
+    (pipeline.calibrate provokes F16_RANGE on purpose); every other bit is still reported.
+
+    ST2_STATUS_FRAME_CAPACITY is a warning, not an exception, and takes ST2_STATUS_DURATION_SUM with it: the alignment expansion
+    reports the truncated row a second time under that bit.  The word is ONE per process, so a genuine DURATION_SUM (forced
+    durations with a wrong `total_frames` on another path) raised between the same two checks is reported as the capacity
+    warning too; a caller that mixes both kinds of call and needs them apart checks the status between them."""
     st = status(clear=True)
     if st > 0:
         st &= ~int(ignore)
@@ -190,6 +196,15 @@ def check_status(ignore=0):
         warnings.warn("a cooperative BiLSTM group was not co-resident in time; the call was re-run on the single-CU kernel "
                       "in-stream (results valid; ST2_STATUS_LSTM_RECOVERED)", RuntimeWarning, stacklevel=2)
         st &= ~_lib.STATUS_LSTM_RECOVERED
+    if st > 0 and st & _lib.STATUS_FRAME_CAPACITY:  # informational but reported: the call completed, one row is not its solo run
+        global frame_capacity_hits
+        frame_capacity_hits += 1
+        warnings.warn("an utterance needed more frames than the capacity given with the call (`max_frames`) and was synthesised "
+                      "truncated to it; the other rows of its batch are unaffected; retry that row with a larger capacity "
+                      "(ST2_STATUS_FRAME_CAPACITY)", RuntimeWarning, stacklevel=2)
+        # the alignment expansion reports the same row as ST2_STATUS_DURATION_SUM (its durations do not sum to the clamped frame
+        # count): with the capacity bit set that is the same event, not a caller's wrong `total_frames`
+        st &= ~(_lib.STATUS_FRAME_CAPACITY | _lib.STATUS_DURATION_SUM)
     if st <= 0:
         return
     msgs = []
@@ -982,6 +997,64 @@ def ragged_lengths(frames, T_max, coef):
     out = torch.empty((n, B), device=frames.device, dtype=torch.int32)
     _lib.check(lib.st2_ragged_lengths(frames.data_ptr(), B, int(T_max), n, flat, out.data_ptr(), _stream()), "st2_ragged_lengths")
     return out
+
+
+def _chk_dev(t, name, dtype, ndim):
+    """A non-fp32 device operand of the sync-free entry points: on a HIP device, of `dtype`, `ndim`-D and contiguous."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.St2Error("%s must live on a HIP device (got %s); the engine has no CPU path" % (
+            name, t.device if torch.is_tensor(t) else type(t).__name__))
+    if t.dtype != dtype or t.dim() != ndim or not t.is_contiguous():
+        raise _lib.St2Error("%s must be a contiguous %d-D %s tensor (got %s %s)" % (name, ndim, dtype, t.dtype, tuple(t.shape)))
+
+
+def frames_from_durations(dur, lengths_dev, T_cap):
+    """`st2_frames_from_durations`: dur int64 [B, N] on the device, lengths_dev int32 [B] on the device or None -> int32 [B]
+    with frames[b] = clamp(sum_{n < lengths[b]} dur[b][n], 1, T_cap), without a host read.  A row over capacity raises
+    ST2_STATUS_FRAME_CAPACITY (ops.check_status) and is synthesised truncated to T_cap frames."""
+    _chk_dev(dur, "dur", torch.int64, 2)
+    B, N = dur.shape
+    lp = _chk_len(lengths_dev, "lengths_dev", B, dur)
+    lib = _lib.load()
+    frames = torch.empty((B,), device=dur.device, dtype=torch.int32)
+    _lib.check(lib.st2_frames_from_durations(dur.data_ptr(), B, N, lp, int(T_cap), frames.data_ptr(), _stream()),
+               "st2_frames_from_durations")
+    return frames
+
+
+PACK_FORMATS = {"f32": (_lib.PACK_F32, torch.float32), "s16": (_lib.PACK_S16, torch.int16)}
+
+
+def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_per_frame=600):
+    """`st2_wave_pack`: wave [B, 1, L] or [B, L] (L a multiple of `samples_per_frame`: the batch's frame capacity), frames
+    int32 [B] on the device -> (packed, offsets): the first max(0, samples_per_frame * frames[b] - trim) samples of every row,
+    back to back, as int16 PCM ("s16": rint(clamp(x, -1, 1) * 32767), NaN -> 0) or fp32 ("f32": a copy), and their int64
+    [B + 1] exclusive prefix sum on the device (offsets[B] = the total).  `out` (1-D, of the format's dtype) bounds what is
+    written: nothing at or past min(offsets[B], out.numel()); by default it holds every row at capacity.  No host read."""
+    if fmt not in PACK_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(PACK_FORMATS), fmt))
+    code, dtype = PACK_FORMATS[fmt]
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf = int(samples_per_frame)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B * L,), device=wave.device, dtype=dtype)
+    _chk_dev(out, "out", dtype, 1)
+    if offsets is None:
+        offsets = torch.empty((B + 1,), device=wave.device, dtype=torch.int64)
+    _chk_dev(offsets, "offsets", torch.int64, 1)
+    if offsets.numel() != B + 1 or out.device != wave.device or offsets.device != wave.device:
+        raise _lib.St2Error("offsets must hold %d entries; out / offsets must live on the device of wave" % (B + 1))
+    _lib.check(lib.st2_wave_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), code, out.data_ptr(),
+                                 out.numel(), offsets.data_ptr(), _stream()), "st2_wave_pack")
+    return out, offsets
 
 
 # ---- reference-audio style path (st2_style.hip) ----------------------------------------------------------------------

@@ -224,6 +224,17 @@ def _front_core(model, sampler, tokens, lengths_host, lengths_dev, noise, step_n
     return dict(t_en=t_en, d=d, s=s, ref=ref, durations=dur)
 
 
+def _sampler_generation(sampler):
+    """Bumped by the denoiser whenever its packed weights are rebuilt: a recorded graph of an older generation is stale."""
+    return getattr(sampler.diffusion.net, "_pack_gen", 0)
+
+
+def _engine_changed(eng, recorded, calib_gen):
+    """Is a graph recorded over engine `recorded` at calibration generation `calib_gen` stale now that the model holds `eng`?
+    A rebuilt engine (reload, .to()) has other buffers; a re-calibrated one other operand scales, which are kernel arguments."""
+    return eng is not recorded or eng.calib_gen != calib_gen
+
+
 class GraphedFront:
     """hipGraph replay of `_front_core` (BASELINE.json configs[4]: latency-bound sentence-by-sentence synthesis).  The
     front of one sentence is ~600 launches of 5-40 us kernels issued from Python (~6 ms of host time against ~4 ms of
@@ -242,7 +253,7 @@ class GraphedFront:
         self._graphs = {}
 
     def _generation(self):
-        return getattr(self.sampler.diffusion.net, "_pack_gen", 0)
+        return _sampler_generation(self.sampler)
 
     def _pack_refs(self):
         """(module, packed-weight cache) of every front module as of now.  A graph keeps these references -- the device
@@ -264,7 +275,7 @@ class GraphedFront:
             if not self._engine_mode():
                 return True
             eng = _front_engine(self.model, dev)
-            return eng is not g["engine"] or eng.calib_gen != g["calib_gen"]  # the operand scales are kernel arguments
+            return _engine_changed(eng, g["engine"], g.get("calib_gen"))  # (a Python-front graph has neither)
         return any(getattr(m, "_pk", None) is not pk for m, pk in g["packs"])
 
     @torch.no_grad()
@@ -325,7 +336,7 @@ class GraphedFront:
 def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
             ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, lj_tail=None, s_prev=None, t=0.7,
             taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False,
-            ragged_decode=False):
+            ragged_decode=False, max_frames=None):
     """Everything in front of the decoder: text encoder, PL-BERT, style diffusion, style mixing, duration and
     prosody prediction, alignment expansion.  Returns the decoder's inputs {asr, F0, N, ref} plus the mixed style
     vector `s_pred` [B, 256] (what LFinference hands to the next sentence) and the durations.
@@ -354,14 +365,35 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     `ragged_decode` (with `allow_ragged`, C++ engine path): utterances of different frame counts are NOT split into groups;
     ONE ragged prosody call (`st2_prosody_forward_ragged`) returns {asr, F0, N, ref} padded to the longest utterance plus
     `frames` (int32 [B] on the device) and `frames_host` (list), which `model.decoder(..., frames=)` decodes in one call, every
-    row as if alone."""
+    row as if alone.
+
+    `max_frames` (int; implies `allow_ragged` and `ragged_decode`, C++ engine path, no taps): the sync-free path of DESIGN.md
+    section 11.  The caller states the capacity in decoder frames; the frame counts are computed on the device
+    (`ops.frames_from_durations`) and never read back, ONE ragged prosody call runs at T = max_frames, and the result carries
+    `frames` (device) and no `frames_host`.  The whole call is then legal under stream capture when every input is a device
+    tensor; a caller that passes `lengths_dev` gets the padded-batch semantics from it alone (`input_lengths` is not looked
+    at: a captured call serves other lengths at replay).  A row whose durations sum to more than `max_frames` is synthesised
+    truncated to it and raises ST2_STATUS_FRAME_CAPACITY (a warning at the next `ops.check_status()`).  Forced `durations`
+    take the same route (their rows are summed whole, pad tokens included, as on the other paths).  `allow_ragged` and
+    `ragged_decode` are implied whatever the caller passed; `total_frames` and `group_events` are refused."""
     dev = tokens.device
     B, N = tokens.shape
+    if max_frames is not None:
+        if int(max_frames) <= 0:
+            raise ValueError("max_frames must be a positive frame count, got %r" % (max_frames,))
+        if not _engine_path(dev, taps):
+            raise ValueError("max_frames needs the C++ engine path (HIP device, plan_mode 'engine', no taps)")
+        if total_frames is not None or group_events:
+            raise ValueError("max_frames: `total_frames` / `group_events` have no meaning on the capacity-bound path (the frame "
+                             "counts are computed on the device; there are no per-frame-count groups)")
     ops.check_status() if dev.type == "cuda" else None  # device-side conditions raised by the previous call's kernels
-    if input_lengths is None:
-        input_lengths = torch.full((B,), N, dtype=torch.long)
-    input_lengths = input_lengths.detach().cpu().long()
-    ragged_n = not bool((input_lengths == N).all())
+    if max_frames is not None and lengths_dev is not None:
+        ragged_n, input_lengths = True, None  # the device lengths are the truth: nothing on the host decides (stream capture)
+    else:
+        if input_lengths is None:
+            input_lengths = torch.full((B,), N, dtype=torch.long)
+        input_lengths = input_lengths.detach().cpu().long()
+        ragged_n = not bool((input_lengths == N).all())
     if ragged_n and lengths_dev is None:  # ONE host -> device copy of the lengths (none if the caller prepared it)
         lengths_dev = input_lengths.to(torch.int32).to(dev)
     if not ragged_n:
@@ -380,6 +412,20 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         f = _front_core(model, sampler, tokens, input_lengths, lengths_dev, noise, step_noise, ref_s, s_prev, taps=taps,
                         **ckw)
     t_en, d, s, ref = f["t_en"], f["d"], f["s"], f["ref"]
+    if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
+        T_cap = int(max_frames)
+        if durations is None:
+            durations, len_arg = f["durations"], lengths_dev
+            ops.check_status()  # the word is host-mapped: looking needs no synchronisation (whatever has completed is reported)
+        else:
+            durations, len_arg = durations.long().to(dev), None  # the caller's: pad-token frames count like any other
+        durations = durations.contiguous()
+        frames = ops.frames_from_durations(durations, len_arg, T_cap)
+        s_mixed = f.get("s_mixed")
+        asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d.transpose(-1, -2).contiguous(), t_en, durations, s,
+                                                                         T_cap, shift=hifigan, frames=frames)
+        return dict(ref=ref, s_pred=s_mixed if s_mixed is not None else torch.cat([ref, s], dim=-1), durations=durations,
+                    asr=asr, F0=F0_pred, N=N_pred, frames=frames, max_frames=T_cap)
     if durations is None:
         durations = f["durations"]
         tot = durations.sum(dim=1).tolist()  # the path's one data-dependent host sync: the frame counts
@@ -471,11 +517,163 @@ def _decode_ragged(model, p, sine_noise=None, noise_rows=None):
     return [w[b, :, :600 * tot[b]] for b in range(len(tot))]
 
 
+class SynthesisResult:
+    """What the capacity-bound path returns (`inference(max_frames=)`, `GraphedSynthesis`), all on the
+    device and none of it waited for:
+      wave     [B, 1, samples_per_frame * max_frames] fp32, exact zeros from row b's samples_per_frame * frames[b] on;
+      frames   int32 [B]: every row's frame count, clamped to 1..max_frames;
+      packed   (with `pack`) the rows' valid samples minus `trim` each, back to back: int16 PCM ("s16") or fp32 ("f32");
+      offsets  (with `pack`) int64 [B + 1]: row b is packed[offsets[b]:offsets[b + 1]].
+    `to_host()` is the one place that waits."""
+
+    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None):
+        self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
+        self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
+        self.samples_per_frame = wave.shape[-1] // self.max_frames
+        self._buf = buf  # offsets and packed are views of this one allocation: one copy takes both
+        self._host = None  # its pinned mirror, allocated by the first to_host()
+
+    def to_host(self):
+        """The list of per-utterance 1-D numpy arrays (int16 for "s16", else float32; `trim` applied): ONE device -> host copy
+        into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
+        copy has waited for every kernel of the call, so a row truncated to `max_frames` (ST2_STATUS_FRAME_CAPACITY) is
+        reported here, also on a graph replay, which runs no Python in between.  A result made without `pack` is packed as
+        fp32 first.  The pinned buffer is allocated once per result object (a pinned allocation costs milliseconds) and the
+        arrays are views of it: a `GraphedSynthesis` hands out the same result at every replay, so consume or copy them
+        before the next `to_host()`.  The copy takes the buffer at capacity, not at offsets[B]: sizing it by the total
+        would need a second wait."""
+        if self._buf is None:
+            self._buf, self.packed, self.offsets = _pack_into_one(self.wave, self.frames, self.trim, self.pack or "f32",
+                                                                  self.samples_per_frame)
+        if self._host is None or self._host.shape != self._buf.shape:
+            self._host = torch.empty(self._buf.shape, dtype=torch.uint8, pin_memory=True)
+        host = self._host
+        host.copy_(self._buf, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self._buf.device))
+        done.synchronize()
+        ops.check_status()
+        B = self.frames.numel()
+        hdr = self._buf.numel() - self.packed.numel() * self.packed.element_size()
+        offs = host[:8 * (B + 1)].view(torch.int64).tolist()
+        samples = host[hdr:].view(self.packed.dtype).numpy()
+        return [samples[offs[b]:offs[b + 1]] for b in range(B)]
+
+
+def _pack_into_one(wave, frames, trim, fmt, samples_per_frame):
+    """`ops.wave_pack` into ONE device allocation, [offsets int64 [B + 1] | pad to 16 bytes | samples at capacity], so that a
+    single copy brings both to the host.  Returns (the allocation as bytes, packed, offsets)."""
+    B, L = wave.shape[0], wave.shape[-1]
+    dtype = ops.PACK_FORMATS[fmt][1]
+    hdr = (8 * (B + 1) + 15) // 16 * 16
+    buf = torch.empty((hdr + B * L * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
+    packed, offsets = ops.wave_pack(wave, frames, trim=trim, fmt=fmt, out=buf[hdr:].view(dtype),
+                                    offsets=buf[:8 * (B + 1)].view(torch.int64), samples_per_frame=samples_per_frame)
+    return buf, packed, offsets
+
+
+def _decode_capacity(model, p, sine_noise, pack, trim):
+    """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
+    back, nothing is sliced on the host."""
+    T_cap, B = p["max_frames"], p["asr"].shape[0]
+    sn = None
+    if sine_noise is not None:
+        if not torch.is_tensor(sine_noise) or sine_noise.dim() != 3 or sine_noise.shape[0] != B \
+                or sine_noise.shape[1] < 600 * T_cap:
+            raise ValueError("sine_noise must be [B, >= 600 * max_frames, 9] on the capacity-bound path")
+        sn = sine_noise[:, :600 * T_cap]  # a view: the decoder reads row b only up to 600 frames[b]
+    w = model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sn, frames=p["frames"])
+    if trim is None:
+        trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
+    if pack is None:
+        return SynthesisResult(w, p["frames"], T_cap, trim=trim)
+    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, w.shape[-1] // T_cap)
+    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf)
+
+
+class GraphedSynthesis:
+    """tokens -> (packed) waveform as ONE hipGraph: `inference(max_frames=, lengths_dev=)` captured on
+    one stream -- the capture has no side stream, the graph is a linear chain -- over static input buffers
+
+        tokens int64 [B, N], lengths_dev int32 [B], noise [B, 1, 256], step_noise [steps - 1, B, 1, 256],
+        sine_noise [B, 600 max_frames, 9], ref_s [B, 256] (multi-speaker models)
+
+    which `__call__` fills from whatever the caller hands in (anything left out keeps its previous contents; the `static` dict
+    gives direct access) before it replays.  The returned `SynthesisResult` refers to the graph's own output buffers: consume
+    it (`to_host()`) before the next replay.  Recorded on the first call; recorded again when the front's or the decoder's
+    engine was rebuilt or re-calibrated (the operand scales are kernel arguments), by the rule `GraphedFront` follows."""
+
+    def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
+                 embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None):
+        from .diffusion import GraphedSampler
+        self.model = model
+        self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
+        dev = torch.device(device) if device is not None else next(model.decoder.parameters()).device
+        if not _engine_path(dev):
+            raise ValueError("GraphedSynthesis needs the C++ engine path (HIP device, plan_mode 'engine')")
+        if pack is not None and pack not in ops.PACK_FORMATS:
+            raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.PACK_FORMATS), pack))
+        self.device, self.max_frames, self.steps = dev, int(max_frames), int(diffusion_steps)
+        self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
+                       max_frames=self.max_frames, pack=pack, trim=trim)
+        z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
+        self.static = dict(tokens=torch.zeros((B, N), device=dev, dtype=torch.int64),
+                           lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=z(B, 1, 256),
+                           step_noise=z(max(self.steps - 1, 0), B, 1, 256), sine_noise=z(B, 600 * self.max_frames, 9),
+                           ref_s=None if ref_s is None else ref_s.detach().to(dev, torch.float32).reshape(-1, 256)
+                           .expand(B, -1).contiguous())
+        self._g = None
+
+    def _run(self):
+        st = self.static
+        return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
+                         sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"], **self.kw)
+
+    def _engines(self):
+        engs = model_engines(self.model, self.device)
+        return [engs["front"], engs["decoder"]]
+
+    def _record(self):
+        dev = self.device
+        cur = torch.cuda.current_stream(dev)
+        side = ops.aux_stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            self._run()  # eager warm-up outside the capture: weight packing, kernel attributes, the status word, the allocator
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self._run()
+        engs = self._engines()
+        return dict(graph=graph, out=out, gen=_sampler_generation(self.sampler), engines=[(e, e.calib_gen) for e in engs])
+
+    @torch.no_grad()
+    def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None):
+        st = self.static
+        for name, val in (("tokens", tokens), ("lengths_dev", lengths), ("noise", noise), ("step_noise", step_noise),
+                          ("sine_noise", sine_noise), ("ref_s", ref_s)):
+            if val is not None:
+                if st[name] is None:
+                    raise ValueError("this graph was built without %s" % name)
+                if name == "sine_noise":
+                    val = val[:, :st[name].shape[1]]
+                st[name].copy_(val.reshape(st[name].shape), non_blocking=True)
+        g = self._g
+        if g is not None and (g["gen"] != _sampler_generation(self.sampler)
+                              or any(_engine_changed(e, rec, gen) for e, (rec, gen) in zip(self._engines(), g["engines"]))):
+            g = None
+        if g is None:
+            g = self._g = self._record()
+        g["graph"].replay()
+        return g["out"]
+
+
 @torch.no_grad()
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
-              ragged_decode=False):
+              ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -504,11 +702,30 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     `ragged_decode=True`: a batch of different frame counts takes ONE ragged prosody call and ONE ragged decoder call
     (`prepare(ragged_decode=True)`) instead of one pair per frame count; the waveforms come back as the
     same list, each row sliced to its own 600 T_b samples (`decode_streams` is then moot).
+
+    `max_frames` (int): the sync-free path (`prepare(max_frames=)`): the caller states the capacity in
+    decoder frames, the host reads nothing back, ONE ragged prosody and ONE ragged decoder call run at T = max_frames, and the
+    return value is a `SynthesisResult`: `wave` [B, 1, 600 max_frames] with exact zeros past each row's 600 frames[b] samples
+    and `frames` (int32 [B] on the device).  `sine_noise`, if given, is [B, >= 600 max_frames, 9] (handed over as a view; each
+    row is read up to 600 frames[b] only); absent, it is drawn on the device at capacity.  `pack` ("s16" / "f32"): the result also
+    carries `packed` (every row's valid samples back to back: 16-bit PCM or fp32, `ops.wave_pack`) and `offsets` (int64 [B + 1],
+    device); `trim` samples are dropped from every row's end -- by default the notebooks' rule, 50 for a HiFi-GAN decoder and 0
+    for iSTFTNet.  `result.to_host()` is the one place that waits.  `lengths_dev` (int32 [B] on the device): the token counts of
+    a right-padded batch without any host copy (stream capture, `GraphedSynthesis`).  `decode_streams` and `total_frames` are
+    refused with `max_frames`.
     """
+    if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
+        raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
+    if pack is not None and pack not in ops.PACK_FORMATS:
+        raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.PACK_FORMATS), pack))
+    if max_frames is not None and decode_streams:
+        raise ValueError("max_frames: there is ONE decoder call, on the current stream; `decode_streams` has no meaning here")
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
               front=front, ragged_decode=ragged_decode)
+    if max_frames is not None:
+        kw.update(max_frames=max_frames, lengths_dev=lengths_dev)
     if front_stream is None:
         p = prepare(model, sampler, tokens, **kw)
     else:
@@ -523,6 +740,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]):
             for v in (g["asr"], g["F0"], g["N"], g["ref"]) + ((g["frames"],) if "frames" in g else ()):
                 v.record_stream(main)  # allocated on the front stream, consumed on the main stream
+    if max_frames is not None:
+        return _decode_capacity(model, p, sine_noise, pack, trim)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
