@@ -771,6 +771,49 @@ int64_t st2_style_workspace_bytes(st2_engine* e, int32_t which, int32_t B, int32
 int st2_style_forward(st2_engine* e, int32_t which, const float* mel, int32_t B, int32_t n_mels, int32_t T, float* style,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- length-aware reference-audio style path (additive under ABI 23) ------------------------------------- *
+ * A batch of B reference clips of unequal length in one [B][L_cap] buffer: row b of every result equals the clip processed
+ * alone at its own length.  Masking is a select throughout: nothing at or past a row's own end is ever used, those
+ * positions may hold NaN bit patterns.  Lengths are int32 [B] on the device and are CLAMPED where they are read (a caller's
+ * bad length gives a wrong row, never a read or a store outside the buffers the capacities size).
+ *
+ *   st2_stft_frames_len  st2_stft_frames with the reflection about the row's own [0, L_b), L_b = len[b] clamped to
+ *                        [L_min, L]; frame columns at or past M_b = L_b / hop + 1 are exact zeros, so the windowed-DFT and
+ *                        filter-bank convs behind it need no lengths.  m_len (int32 [B], may be NULL) receives M_b.
+ *   st2_log_norm_len     st2_log_norm on rows x[b][c][0 .. M), columns at or past len[b] written as exact 0.
+ *   st2_dwconv3x3s2_len / st2_avgpool2x2_len   the maps of clip b are w_len[b] <= W wide (clamped to 1 .. W): zero padding /
+ *                        the odd-width replicate at the row's own end, outputs [0, (w_len[b] + 1) / 2); outputs past that
+ *                        width are left as the memory held them.
+ *   st2_style_lengths    one launch: every per-row length of st2_style_forward_ragged from mel_len [B] (clamped to
+ *                        [T_min, T_cap]).  With W_0 = mel_len and W_{i+1} = (W_i + 1) / 2 the table holds, in this order,
+ *                        W_i[b] for i = 0 .. stages (B entries each), W_stages[b] - 4 (B entries), then for i = 0 .. stages
+ *                        the per-stacked-row table of the H >> i high map: B ((H >> i) + 2) - 2 entries, entry r = W_i[b]
+ *                        when padded row r + 1 of the [B][(H >> i) + 2] stack is an image row of clip b, 0 when it is one
+ *                        of the zero rows between clips (a "seam": the conv tiles of that row exit without storing).
+ *                        st2_style_lengths_count returns the number of entries (-1 on bad arguments). */
+int st2_stft_frames_len(const float* wave, int64_t w_bs, int32_t B, int32_t L, int32_t n_win, int32_t hop, int32_t shift,
+                        float* frames, int64_t f_bs, int32_t f_cs, const int32_t* len, int32_t L_min, int32_t* m_len,
+                        void* stream);
+int st2_log_norm_len(float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t M, float eps, float mean, float stdv,
+                     const int32_t* len, void* stream);
+int st2_dwconv3x3s2_len(const float* x, int64_t x_bs, int64_t x_hs, int32_t x_cs, const float* w, const float* bias, int32_t B,
+                        int32_t C, int32_t H, int32_t W, float* y, int64_t y_bs, int64_t y_hs, int32_t y_cs,
+                        const int32_t* w_len, void* stream);
+int st2_avgpool2x2_len(const float* x, int64_t x_bs, int64_t x_hs, int32_t x_cs, int32_t B, int32_t C, int32_t H, int32_t W,
+                       float* y, int64_t y_bs, int64_t y_hs, int32_t y_cs, const int32_t* w_len, void* stream);
+int64_t st2_style_lengths_count(int32_t B, int32_t H, int32_t stages);
+int st2_style_lengths(const int32_t* mel_len, int32_t B, int32_t T_min, int32_t T_cap, int32_t H, int32_t stages, int32_t* out,
+                      void* stream);
+/* StyleEncoder.forward on a ragged batch: mel [B][80][T_cap], row b valid on its first mel_len[b] frames (int32 [B] on the
+ * device, clamped to [80, T_cap]) -> style [B][style_dim], row b as st2_style_forward gives it for that clip alone.  Every
+ * Conv2d is ONE launch over the B (h + 2) - 2 stacked rows of the padded [B][h + 2][c][w] maps with per-row x_len / y_len
+ * (seam rows: 0), so the number of launches does not depend on B; the split-K decision of each conv is the one the per-clip
+ * launch of st2_style_forward takes, so a batch whose rows are all T_cap long gives st2_style_forward's bits.  No host read,
+ * no allocation: legal under stream capture. */
+int64_t st2_style_workspace_bytes_ragged(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T_cap);
+int st2_style_forward_ragged(st2_engine* e, int32_t which, const float* mel, const int32_t* mel_len, int32_t B, int32_t n_mels,
+                             int32_t T_cap, float* style, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- measurement hook (bench.py's roofline leg) ------------------------------------------------------------------- *
  * st2_conv_timing(1) clears and starts, (0) stops recording a HIP event pair around every st2_conv1d_xs launch (C_in >=
  * 64, L_out >= 256) on its launch stream, whichever plan issues it.  st2_conv_timing_read (after stopping) waits for the
@@ -898,8 +941,9 @@ int st2_stream_create_cu_mask(const uint32_t* mask, int32_t n_words, void** stre
 int st2_stream_destroy(void* stream);
 
 /* ---- testing hook ---------------------------------------------------------------------------------------------- *
- * Replaces the kernel / memory entry points the launch plans call by the caller's (an array of ST2_BACKEND_ENTRIES
- * function pointers in the order of `enum st2_backend_slot`; NULL restores the HIP kernels).  tests/ uses it to run the
+ * Replaces the kernel / memory entry points the launch plans call by the caller's (an array of ST2_BACKEND_ENTRIES,
+ * ST2_BACKEND_ENTRIES_RAGGED or ST2_BACKEND_ENTRIES_V22 function pointers in the order of `enum st2_backend_slot`: a shorter
+ * table leaves the later slots on their HIP kernels; NULL restores the HIP kernels).  tests/ uses it to run the
  * C++ plans on HOST memory against per-kernel CPU contracts, i.e. to validate plan wiring, packing and workspace
  * aliasing without a GPU.  Never used by the product path. */
 enum st2_backend_slot {
@@ -918,6 +962,9 @@ enum st2_backend_slot {
   ST2_BE_ACT_SPLIT_LEN = ST2_BACKEND_ENTRIES_V22, ST2_BE_INSTNORM_STATS_LEN, ST2_BE_STATS_FINALIZE_LEN,
   ST2_BE_CONV1D_DIRECT_LEN, ST2_BE_ADAIN_LEAKY_POOL_LEN, ST2_BE_CONVT_INTERLEAVE_STATS_LEN, ST2_BE_HAR_SOURCE_LEN,
   ST2_BE_STFT_MAG_PHASE_LEN, ST2_BE_ISTFT_LEN, ST2_BE_RAGGED_LENGTHS, ST2_BE_EXPAND_BY_DURATIONS_LEN,
+  ST2_BACKEND_ENTRIES_RAGGED,  /* a table of this many entries leaves the slots below on their HIP kernels */
+  /* the length-aware entry points of the ragged style plan (st2_style_forward_ragged) */
+  ST2_BE_DWCONV3X3S2_LEN = ST2_BACKEND_ENTRIES_RAGGED, ST2_BE_AVGPOOL2X2_LEN, ST2_BE_STYLE_LENGTHS,
   ST2_BACKEND_ENTRIES
 };
 int st2_debug_set_backend(void* const* table, int32_t entries);

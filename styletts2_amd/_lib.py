@@ -102,6 +102,8 @@ BACKEND_SLOTS = ["conv1d_f16s", "conv1d_xs", "act_split", "stats_finalize", "con
 BACKEND_SLOTS_RAGGED = ["act_split_len", "instnorm_stats_len", "stats_finalize_len", "conv1d_direct_len",
                         "adain_leaky_pool_len", "convt_interleave_stats_len", "har_source_len", "stft_mag_phase_len",
                         "istft_len", "ragged_lengths", "expand_by_durations_len"]
+# The length-aware slots of the ragged style plan (st2_style_forward_ragged), after the two lists above: a third table size.
+BACKEND_SLOTS_STYLE = ["dwconv3x3s2_len", "avgpool2x2_len", "style_lengths"]
 
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -278,6 +280,20 @@ _SIGNATURES = {
     "st2_avgpool2x2": (C.c_int, [f32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
                                  C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "st2_axpbypcz": (C.c_int, [f32p, C.c_float, f32p, C.c_float, f32p, C.c_float, f32p, C.c_int64, C.c_void_p]),
+    "st2_stft_frames_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                      C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_log_norm_len": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                   C.c_float, C.c_void_p, C.c_void_p]),
+    "st2_dwconv3x3s2_len": (C.c_int, [f32p, C.c_int64, C.c_int64, C.c_int32, f32p, f32p, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_avgpool2x2_len": (C.c_int, [f32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                     C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "st2_style_lengths_count": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "st2_style_lengths": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
+    "st2_style_workspace_bytes_ragged": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "st2_style_forward_ragged": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                           C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -10,6 +10,11 @@ int st2_stream_cu_count(void* stream);  // st2_api.hip: CUs of a stream made by 
 // st2_actsplit.hip: the engine's conv() names the conv site (st2_calibration_read's index) of the launches it is about to issue on
 // this thread, so that the headroom records (st2_debug_headroom) can be folded into per-site operand scales; (null, -1) = none.
 void st2_headroom_set_site(const void* engine, int site);
+// st2_conv1d_f16s.hip: the next st2_conv1d_f16s / st2_conv1d_f16s_splitk_bytes calls of this thread take their split-K decision
+// as a launch of `rows` batch rows would (0 = the descriptor's own B).  The ragged style plan stacks the per-clip launches of
+// the uniform plan into one and keeps each clip's split -- and with it its bits -- this way.
+void st2_conv1d_f16s_split_as(int rows);
+int st2_conv1d_f16s_slices(const st2_conv_desc* d);  // K slices st2_conv1d_f16s runs *d in when given its split-K workspace (>= 1)
 int* st2_status_device_ptr();  // st2_api.hip: device view of the sticky status word (nullptr without a device)
 
 // Kernel side: raise status bit `bit` (ST2_STATUS_*).  Every bit has its own 32-bit slot in the host-mapped block so

@@ -15,6 +15,8 @@ int st2_headroom_of_fused_conv(const st2_conv_desc& d, hipStream_t s);  // st2_a
 
 extern "C" void st2_conv1d_f16s_set_variant(int v) { st2f16s::g_variant = (v == 1 || v == 2) ? v : 0; }
 int st2f16s::g_splitk_max = 8, st2f16s::g_splitk_min_chunks = 4;
+thread_local int st2f16s::g_split_rows = 0;
+void st2_conv1d_f16s_split_as(int rows) { st2f16s::g_split_rows = rows > 0 ? rows : 0; }
 extern "C" void st2_conv1d_f16s_set_splitk(int max_slices, int min_chunks) {
   st2f16s::g_splitk_max = max_slices >= 1 && max_slices <= 32 ? max_slices : 8;
   st2f16s::g_splitk_min_chunks = min_chunks >= 1 && min_chunks <= 16 ? min_chunks : 4;
@@ -23,6 +25,11 @@ extern "C" void st2_conv1d_f16s_set_splitk(int max_slices, int min_chunks) {
 extern "C" int st2_conv1d_f16s_chunk(int ks) { return ks <= 3 ? 32 : 16; }
 
 extern "C" int st2_conv1d_f16s_co_block(int C_out) { return C_out > 64 ? 128 : (C_out > 32 ? 64 : 32); }
+
+int st2_conv1d_f16s_slices(const st2_conv_desc* dp) {
+  if (!dp || dp->B <= 0 || dp->C_in <= 0 || dp->C_out <= 0 || dp->L_out <= 0) return 1;
+  return ksplit_for_geometry(*dp);
+}
 
 extern "C" int64_t st2_conv1d_f16s_splitk_bytes(const st2_conv_desc* dp) {
   if (!dp || dp->B <= 0 || dp->C_in <= 0 || dp->C_out <= 0 || dp->L_out <= 0) return 0;

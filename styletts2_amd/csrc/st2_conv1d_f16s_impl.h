@@ -32,6 +32,7 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef st2_f32x16 f32x16;
 
 namespace st2f16s {
+extern thread_local int g_split_rows;  // st2_conv1d_f16s_split_as (st2_common.h): 0 = the descriptor's B
 extern int g_splitk_max, g_splitk_min_chunks;  // st2_conv1d_f16s_set_splitk (st2_conv1d_f16s.hip): 8 slices of >= 4 chunks by default
 }
 
@@ -481,7 +482,8 @@ inline int ksplit_for_geometry(const st2_conv_desc& d) {
   const int BM = d.C_out > 64 ? 128 : (d.C_out > 32 ? 64 : 32);
   const int BN = d.C_out > 64 ? 128 : (d.C_out > 32 ? 256 : 512);
   const int nchunk = (d.C_in + CI_T - 1) / CI_T;
-  const int64_t wgs = (int64_t)st2_cdiv(d.L_out, BN) * st2_cdiv(d.C_out, BM) * d.B;
+  const int rows = st2f16s::g_split_rows > 0 ? st2f16s::g_split_rows : d.B;
+  const int64_t wgs = (int64_t)st2_cdiv(d.L_out, BN) * st2_cdiv(d.C_out, BM) * rows;
   // measured (profiles/archive/r02/r02v_*, r02w_*): with 256 workgroups (B = 32 x 8 co-blocks) a 4-way split LOSES 4-6 % on the
   // LibriTTS configurations (the reduction re-reads 4 x the output), with 8-16 (B = 1) an 8-way split takes the
   // long-form passage from 181 to 118 ms -- so only launches below half a round of the chip are split, up to ~256 slices

@@ -76,6 +76,10 @@ struct Backend {
   decltype(&st2_istft_len) istft_len;
   decltype(&st2_ragged_lengths) ragged_lengths;
   decltype(&st2_expand_by_durations_len) expand_by_durations_len;
+  // length-aware entry points of the ragged style plan (slots after ST2_BACKEND_ENTRIES_RAGGED)
+  decltype(&st2_dwconv3x3s2_len) dwconv3x3s2_len;
+  decltype(&st2_avgpool2x2_len) avgpool2x2_len;
+  decltype(&st2_style_lengths) style_lengths;
 };
 
 void* hip_alloc(int64_t n) {
@@ -117,7 +121,8 @@ const Backend kHipBackend = {st2_conv1d_f16s, st2_conv1d_xs, st2_act_split, st2_
                              st2_embed_tokens, st2_dwconv3x3s2, st2_avgpool2x2, hip_alloc, hip_free, hip_upload,
                              st2_act_split_len, st2_instnorm_stats_len, st2_stats_finalize_len, st2_conv1d_direct_len,
                              st2_adain_leaky_pool_len, st2_convt_interleave_stats_len, st2_har_source_len,
-                             st2_stft_mag_phase_len, st2_istft_len, st2_ragged_lengths, st2_expand_by_durations_len};
+                             st2_stft_mag_phase_len, st2_istft_len, st2_ragged_lengths, st2_expand_by_durations_len,
+                             st2_dwconv3x3s2_len, st2_avgpool2x2_len, st2_style_lengths};
 Backend g_be = kHipBackend;
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -787,6 +792,7 @@ struct ConvOpt {
   int act = ST2_ACT_NONE, act_split = 0;
   float act_slope = 0.f;
   float* stats_out = nullptr;  // want_stats: [B][C_out][2]
+  int split_rows = 0;  // > 0: split-K as a launch of this many batch rows decides it (stacked launches of the ragged style plan)
 };
 
 float x_scale_for(int pro) {
@@ -872,6 +878,15 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
       part = c.a.f32((int64_t)y.B * y.C * nt * 3);
       d.part = part; d.part_nt = nt;
     } else {
+      st2_conv1d_f16s_split_as(o.split_rows);
+      // a stacked launch splits as its per-clip launch would: the grid (rows x slices) is checked here, dry runs included, so
+      // that a batch too large for it is refused by the workspace query and before the first launch of the forward
+      if ((int64_t)d.B * st2_conv1d_f16s_slices(&d) > 65535) {
+        if (c.rc == 0) { st2_set_error("engine: %d conv rows x %d K slices exceed the 65535 grid rows of one launch", d.B, st2_conv1d_f16s_slices(&d)); c.rc = 1; }
+        st2_conv1d_f16s_split_as(0);
+        c.a.off = mark;
+        return;
+      }
       const int64_t skb = st2_conv1d_f16s_splitk_bytes(&d);  // skinny layers run split-K inside the workspace
       if (skb > 0) {
         d.splitk_ws = c.a.alloc(skb);
@@ -879,6 +894,7 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
       }
     }
     RUN(c, g_be.conv1d_f16s(&d, c.stream));
+    st2_conv1d_f16s_split_as(0);
     if (o.stats_out) finalize_stats(c, part, y, nt, o.stats_out, 128);
   }
   c.a.off = mark;  // planes / partial sums are dead once the launches are queued (stream order protects reuse)
@@ -908,9 +924,9 @@ extern "C" int st2_debug_set_backend(void* const* table, int32_t entries) {
     g_be = kHipBackend;
     return 0;
   }
-  ST2_REQUIRE(entries == ST2_BACKEND_ENTRIES || entries == ST2_BACKEND_ENTRIES_V22,
-              "st2_debug_set_backend: %d entries, expected %d (or %d: the slots before ABI v23)", entries,
-              (int)ST2_BACKEND_ENTRIES, (int)ST2_BACKEND_ENTRIES_V22);
+  ST2_REQUIRE(entries == ST2_BACKEND_ENTRIES || entries == ST2_BACKEND_ENTRIES_RAGGED || entries == ST2_BACKEND_ENTRIES_V22,
+              "st2_debug_set_backend: %d entries, expected %d (or %d: without the ragged style slots, or %d: the slots before "
+              "ABI v23)", entries, (int)ST2_BACKEND_ENTRIES, (int)ST2_BACKEND_ENTRIES_RAGGED, (int)ST2_BACKEND_ENTRIES_V22);
   for (int i = 0; i < entries; ++i) ST2_REQUIRE(table[i] != nullptr, "st2_debug_set_backend: entry %d is null", i);
 #define SLOT(field, slot) g_be.field = reinterpret_cast<decltype(g_be.field)>(table[slot])
   SLOT(conv1d_f16s, ST2_BE_CONV1D_F16S); SLOT(conv1d_xs, ST2_BE_CONV1D_XS); SLOT(act_split, ST2_BE_ACT_SPLIT);
@@ -933,13 +949,18 @@ extern "C" int st2_debug_set_backend(void* const* table, int32_t entries) {
   g_be.adain_leaky_pool_len = h.adain_leaky_pool_len; g_be.convt_interleave_stats_len = h.convt_interleave_stats_len;
   g_be.har_source_len = h.har_source_len; g_be.stft_mag_phase_len = h.stft_mag_phase_len; g_be.istft_len = h.istft_len;
   g_be.ragged_lengths = h.ragged_lengths; g_be.expand_by_durations_len = h.expand_by_durations_len;
-  if (entries == ST2_BACKEND_ENTRIES) {
+  g_be.dwconv3x3s2_len = h.dwconv3x3s2_len; g_be.avgpool2x2_len = h.avgpool2x2_len; g_be.style_lengths = h.style_lengths;
+  if (entries >= ST2_BACKEND_ENTRIES_RAGGED) {
     SLOT(act_split_len, ST2_BE_ACT_SPLIT_LEN); SLOT(instnorm_stats_len, ST2_BE_INSTNORM_STATS_LEN);
     SLOT(stats_finalize_len, ST2_BE_STATS_FINALIZE_LEN); SLOT(conv1d_direct_len, ST2_BE_CONV1D_DIRECT_LEN);
     SLOT(adain_leaky_pool_len, ST2_BE_ADAIN_LEAKY_POOL_LEN);
     SLOT(convt_interleave_stats_len, ST2_BE_CONVT_INTERLEAVE_STATS_LEN); SLOT(har_source_len, ST2_BE_HAR_SOURCE_LEN);
     SLOT(stft_mag_phase_len, ST2_BE_STFT_MAG_PHASE_LEN); SLOT(istft_len, ST2_BE_ISTFT_LEN);
     SLOT(ragged_lengths, ST2_BE_RAGGED_LENGTHS); SLOT(expand_by_durations_len, ST2_BE_EXPAND_BY_DURATIONS_LEN);
+  }
+  if (entries == ST2_BACKEND_ENTRIES) {
+    SLOT(dwconv3x3s2_len, ST2_BE_DWCONV3X3S2_LEN); SLOT(avgpool2x2_len, ST2_BE_AVGPOOL2X2_LEN);
+    SLOT(style_lengths, ST2_BE_STYLE_LENGTHS);
   }
 #undef SLOT
   return 0;
@@ -1278,6 +1299,45 @@ extern "C" int st2_style_forward(st2_engine* e, int32_t which, const float* mel,
   const int rc = style_plan(c, *e, e->style[which], mel, B, n_mels, T, style);
   ST2_REQUIRE(!c.a.overflow, "st2_style_forward: workspace of %lld B is too small (need %lld B, see st2_style_workspace_bytes)",
               (long long)workspace_bytes, (long long)c.a.peak);
+  return rc;
+}
+
+extern "C" int64_t st2_style_workspace_bytes_ragged(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T_cap) {
+  if (!e || which < 0 || which > 1 || !e->style[which].ready || B <= 0 || n_mels != 80 || T_cap < 80) return -1;
+  if ((int64_t)B * (n_mels + 2) - 2 > 65535) return -1;
+  Ctx c;
+  c.dry = true;
+  c.a.dry = true;
+  if (style_plan_ragged(c, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr) != 0) return -1;  // batch too large
+  return c.a.peak + 256;
+}
+
+extern "C" int st2_style_forward_ragged(st2_engine* e, int32_t which, const float* mel, const int32_t* mel_len, int32_t B,
+                                        int32_t n_mels, int32_t T_cap, float* style, void* workspace, int64_t workspace_bytes,
+                                        void* stream) {
+  // the geometry first: nothing of `e` is touched, nothing is launched, before the batch itself is known to be sane
+  ST2_REQUIRE(mel_len, "st2_style_forward_ragged: mel_len is NULL (int32 [B] frame counts on the device; st2_style_forward takes "
+              "a uniform batch)");
+  ST2_REQUIRE(B > 0, "st2_style_forward_ragged: B=%d clips, need at least one", B);
+  ST2_REQUIRE(n_mels == 80 && T_cap >= 80, "st2_style_forward_ragged: T_cap=%d frames x n_mels=%d: needs an 80-bin mel with room for "
+              ">= 80 frames (four halvings, then the 5x5 valid conv)", T_cap, n_mels);
+  ST2_REQUIRE((int64_t)B * (n_mels + 2) - 2 <= 65535, "st2_style_forward_ragged: B=%d clips stack to more than 65535 conv rows", B);
+  ST2_REQUIRE(e && which >= 0 && which <= 1 && e->style[which].ready, "st2_style_forward_ragged: style-encoder weights not finalized");
+  ST2_REQUIRE(mel && style && workspace, "st2_style_forward_ragged: bad arguments");
+  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_style_forward_ragged: workspace must be 256-byte aligned");
+  {  // the plan once without launches: a batch one of its stacked launches cannot hold fails here, with nothing queued
+    Ctx dry;
+    dry.dry = true;
+    dry.a.dry = true;
+    if (style_plan_ragged(dry, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr) != 0) return 1;
+  }
+  Ctx c;
+  c.stream = stream;
+  c.a.base = static_cast<char*>(workspace);
+  c.a.cap = workspace_bytes;
+  const int rc = style_plan_ragged(c, *e, e->style[which], mel, mel_len, B, n_mels, T_cap, style);
+  ST2_REQUIRE(!c.a.overflow, "st2_style_forward_ragged: workspace of %lld B is too small (need %lld B, see "
+              "st2_style_workspace_bytes_ragged)", (long long)workspace_bytes, (long long)c.a.peak);
   return rc;
 }
 

@@ -172,6 +172,119 @@ int style_plan(Ctx& c, const st2_engine& e, const PStyleEnc& s, const float* mel
   return c.rc;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// ragged style plan == style_plan on B clips of unequal width in one [B][H][W] buffer (W = the capacity), row b as the clip
+// alone: every Conv2d ONE launch over the B (h + 2) - 2 stacked rows of the padded maps.  Three consecutive padded rows are a
+// conv's input channels whichever clip they belong to; a stacked row whose centre is an image row of clip b gets
+// x_len = y_len = that clip's width, one whose centre is a zero row between two clips (a seam) gets 0: its tiles exit before
+// any barrier and store nothing, so the zero rows stay zero.  Buffers the uniform plan keeps unpadded (S, R1, SC) take the
+// padded row stride here, so that one base pointer and one row stride describe the whole batch.
+// ------------------------------------------------------------------------------------------------------------------
+int style_plan_ragged(Ctx& c, const st2_engine& e, const PStyleEnc& s, const float* mel, const int32_t* mel_len, int B, int H,
+                      int W, float* out) {
+  constexpr int S = 4;  // down-sampling stages (pack_style checks the block count)
+  // length tables (st2.h st2_style_lengths): per clip W_0 .. W_4 and W_4 - 4, then one per-stacked-row table per stage
+  const int64_t n_tab = st2_style_lengths_count(B, H, S);
+  int32_t* tab = static_cast<int32_t*>(c.a.alloc(n_tab * 4));
+  RUN(c, g_be.style_lengths(mel_len, B, 80, W, H, S, tab, c.stream));
+  const int32_t* wlen[S + 2];
+  const int32_t* rlen[S + 1];
+  for (int i = 0; i < S + 2; ++i) wlen[i] = tab + (int64_t)i * B;
+  {
+    int64_t off = (int64_t)(S + 2) * B;
+    for (int i = 0; i <= S; ++i) {
+      rlen[i] = tab + off;
+      off += (int64_t)B * ((H >> i) + 2) - 2;
+    }
+  }
+  auto new_map = [&](int h, int ch, int w) -> float* {  // as in style_plan: rows 0 and h + 1 of every clip are zero
+    float* p = c.a.f32((int64_t)B * (h + 2) * ch * w);
+    for (int r : {0, h + 1})
+      RUN(c, g_be.broadcast_cols(e.F(e.zeros), 0, p + (int64_t)r * ch * w, (int64_t)(h + 2) * ch * w, w, B, ch, w, c.stream));
+    return p;
+  };
+  // padded rows r0 + r .. r0 + r + k - 1 of the whole [B (h + 2)][ch][w] stack as the channels of stacked row r:
+  // k = 3 from row 0 (a 3x3 conv's input) and k = 1 from row 1 (its output, a 1x1 conv's input) have the same centre row r + 1
+  auto stack = [&](float* P, int h, int ch, int w, int k, int r0, const int32_t* len) {
+    View v;
+    v.p = P + (int64_t)r0 * ch * w;
+    v.B = B * (h + 2) - 2; v.C = k * ch; v.L = w; v.bs = (int64_t)ch * w; v.cs = w; v.len = len;
+    return v;
+  };
+  float* m0 = new_map(H, 1, W);
+  RUN(c, g_be.copy_ncl(mel, (int64_t)H * W, W, m0 + W, (int64_t)(H + 2) * W, W, B, H, W, c.stream));
+  int C = s.c0;
+  float* P = new_map(H, C, W);
+  {
+    const View x = stack(m0, H, 1, W, 3, 0, rlen[0]);
+    RUN(c, g_be.conv1d_direct_len(x.p, x.bs, x.cs, e.F(s.w0), e.F(s.b0), P + (int64_t)C * W, (int64_t)C * W, W, x.B, 3, C, W, W, 3,
+                                  1, 1, rlen[0], rlen[0], c.stream));
+  }
+  int st = 0;
+  for (const PStyleBlk& blk : s.blocks) {
+    const int Co = blk.c_out, Ho = H / 2, Wo = (W + 1) / 2;
+    const int32_t* rl = rlen[st];
+    const int32_t* rlo = rlen[st + 1];
+    // shortcut: 1x1 conv at full resolution, then the 2x2 average (models.py:118-123)
+    float* SC = c.a.f32((int64_t)B * (Ho + 2) * Co * Wo);
+    if (blk.has_sc) {
+      float* Sm = c.a.f32((int64_t)B * (H + 2) * Co * W);
+      ConvOpt o;
+      o.split_rows = H;
+      conv(c, e, stack(P, H, C, W, 1, 1, rl), blk.wsc, stack(Sm, H, Co, W, 1, 1, rl), o);
+      RUN(c, g_be.avgpool2x2_len(Sm + (int64_t)Co * W, (int64_t)(H + 2) * Co * W, (int64_t)Co * W, W, B, Co, H, W,
+                                 SC + (int64_t)Co * Wo, (int64_t)(Ho + 2) * Co * Wo, (int64_t)Co * Wo, Wo, wlen[st], c.stream));
+    } else {
+      RUN(c, g_be.avgpool2x2_len(P + (int64_t)C * W, (int64_t)(H + 2) * C * W, (int64_t)C * W, W, B, C, H, W,
+                                 SC + (int64_t)Co * Wo, (int64_t)(Ho + 2) * Co * Wo, (int64_t)Co * Wo, Wo, wlen[st], c.stream));
+    }
+    // residual: leaky -> conv1 3x3 -> depthwise stride-2 3x3 -> leaky -> conv2 3x3 (models.py:125-135)
+    float* R1 = c.a.f32((int64_t)B * (H + 2) * C * W);
+    {
+      ConvOpt o;
+      o.pad_left = 1; o.bias = e.F(blk.b1); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = H;
+      conv(c, e, stack(P, H, C, W, 3, 0, rl), blk.w1, stack(R1, H, C, W, 1, 1, rl), o);
+    }
+    float* P2 = new_map(Ho, C, Wo);
+    RUN(c, g_be.dwconv3x3s2_len(R1 + (int64_t)C * W, (int64_t)(H + 2) * C * W, (int64_t)C * W, W, e.F(blk.wd), e.F(blk.bd), B, C, H,
+                                W, P2 + (int64_t)C * Wo, (int64_t)(Ho + 2) * C * Wo, (int64_t)C * Wo, Wo, wlen[st], c.stream));
+    float* Pn = new_map(Ho, Co, Wo);
+    {  // (shortcut + residual) / sqrt(2) in the epilogue
+      ConvOpt o;
+      o.pad_left = 1; o.bias = e.F(blk.b2); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = Ho;
+      o.res = stack(SC, Ho, Co, Wo, 1, 1, nullptr); o.div = (float)sqrt(2.0);
+      conv(c, e, stack(P2, Ho, C, Wo, 3, 0, rlo), blk.w2, stack(Pn, Ho, Co, Wo, 1, 1, rlo), o);
+    }
+    P = Pn; H = Ho; W = Wo; C = Co;
+    ++st;
+  }
+  // LeakyReLU -> 5x5 valid conv -> global average over the clip's own W_4 - 4 columns -> LeakyReLU -> Linear (models.py:151-163)
+  const int Cl = s.c_last, Wf = W - 4;
+  float* Fm = c.a.f32((int64_t)B * Cl * Wf);
+  {
+    View x;
+    x.p = P + (int64_t)C * W;
+    x.B = B; x.C = 5 * C; x.L = W; x.bs = (int64_t)(H + 2) * C * W; x.cs = W; x.len = wlen[S];
+    View y;
+    y.p = Fm;
+    y.B = B; y.C = Cl; y.L = Wf; y.bs = (int64_t)Cl * Wf; y.cs = Wf; y.len = wlen[S + 1];
+    ConvOpt o;
+    o.bias = e.F(s.b5); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = 1;
+    conv(c, e, x, s.w5, y, o);
+  }
+  float* m = c.a.f32((int64_t)B * Cl);
+  RUN(c, g_be.mean_tokens_len(Fm, (int64_t)Cl * Wf, Wf, m, Cl, B, Cl, Wf, wlen[S + 1], c.stream));
+  {
+    View x, y;
+    x.p = m; x.B = B; x.C = Cl; x.L = 1; x.bs = Cl; x.cs = 1;
+    y.p = out; y.B = B; y.C = s.style_dim; y.L = 1; y.bs = s.style_dim; y.cs = 1;
+    ConvOpt o;
+    o.bias = e.F(s.bl); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f;
+    conv(c, e, x, s.wl, y, o);
+  }
+  return c.rc;
+}
+
 bool check_cfg(const st2_model_config& c) {
   return c.n_upsamples >= 1 && c.n_upsamples <= 4 && c.n_resblock_kernels >= 1 && c.n_resblock_kernels <= 4 &&
          (c.decoder_kind == 0 || c.decoder_kind == 1) && c.dim_in > 0 && c.style_dim > 0 && c.dn_layers >= 0;

@@ -88,6 +88,122 @@ __global__ __launch_bounds__(256) void avgpool2x2_kernel(const float* __restrict
   y[(int64_t)b * y_bs + (int64_t)ho * y_hs + (int64_t)c * y_cs + wo] = s * 0.25f;
 }
 
+// ---- length-aware twins (ragged batch of reference clips): row b is the clip / map of its own length, whatever the memory
+// past that length holds is never read (a select), and a workgroup whose chunk lies wholly past the row's end leaves at once ----
+
+// st2_stft_frames with the reflection about the row's own [0, L_b), L_b = len[b] clamped to [L_min, L]; frame columns at or past
+// M_b = L_b / hop + 1 are written as exact zeros (the k = 1 DFT and filter-bank convs behind it then never see the tail).
+// m_len (optional): M_b per row, for the passes behind the convs.
+__global__ __launch_bounds__(256) void stft_frames_len_kernel(const float* __restrict__ wave, int64_t w_bs, int L, int L_min,
+                                                              int n_win, int hop, int shift, int M,
+                                                              const int32_t* __restrict__ len, float* __restrict__ fr,
+                                                              int64_t f_bs, int f_cs, int32_t* __restrict__ m_len) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  const int b = blockIdx.z;
+  const int Lb = min(max(len[b], L_min), L);
+  const int Mb = Lb / hop + 1;
+  if (m_len && blockIdx.x == 0 && c == 0 && threadIdx.x == 0) m_len[b] = Mb;
+  if (m >= M) return;
+  float v = 0.f;
+  if (m < Mb) {
+    int i = m * hop + c - shift;
+    if (i < 0) i = -i;
+    if (i >= Lb) i = 2 * (Lb - 1) - i;
+    v = wave[(int64_t)b * w_bs + min(max(i, 0), Lb - 1)];  // the clamp never moves an index the entry point admitted
+  }
+  fr[(int64_t)b * f_bs + (int64_t)c * f_cs + m] = v;
+}
+
+// x[b][c][m] = m < len[b] ? (log(eps + x[b][c][m]) - mean) / std : 0  in place
+__global__ __launch_bounds__(256) void log_norm_len_kernel(float* __restrict__ x, int64_t x_bs, int x_cs, int M, float eps,
+                                                           float mean, float stdv, const int32_t* __restrict__ len) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  const int b = blockIdx.z;
+  if (m >= M) return;
+  float* p = x + (int64_t)b * x_bs + (int64_t)c * x_cs + m;
+  *p = m < len[b] ? (logf(eps + *p) - mean) / stdv : 0.f;
+}
+
+// dwconv3x3s2_kernel on rows of width W_b = w_len[b] (clamped to 1 .. W): zero padding at the row's own right end, outputs
+// [0, (W_b + 1) / 2), nothing stored past them.  Same arithmetic, in the same order, as dwconv3x3s2_kernel.
+__global__ __launch_bounds__(256) void dwconv3x3s2_len_kernel(const float* __restrict__ x, int64_t x_bs, int64_t x_hs,
+                                                              int x_cs, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, int H, int Wmax, int Ho,
+                                                              const int32_t* __restrict__ w_len, float* __restrict__ y,
+                                                              int64_t y_bs, int64_t y_hs, int y_cs) {
+  const int b = blockIdx.z / Ho, ho = blockIdx.z % Ho;
+  const int W = min(max(w_len[b], 1), Wmax);
+  const int Wo = (W + 1) / 2;
+  if ((int)blockIdx.x * 256 >= Wo) return;
+  const int wo = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  if (wo >= Wo) return;
+  const float* wc = w + c * 9;
+  float acc = bias ? bias[c] : 0.f;
+#pragma unroll
+  for (int dh = 0; dh < 3; ++dh) {
+    const int h = 2 * ho + dh - 1;
+    if (h < 0 || h >= H) continue;
+    const float* xr = x + (int64_t)b * x_bs + (int64_t)h * x_hs + (int64_t)c * x_cs;
+#pragma unroll
+    for (int dw = 0; dw < 3; ++dw) {
+      const int ww = 2 * wo + dw - 1;
+      if (ww >= 0 && ww < W) acc += wc[dh * 3 + dw] * xr[ww];
+    }
+  }
+  y[(int64_t)b * y_bs + (int64_t)ho * y_hs + (int64_t)c * y_cs + wo] = acc;
+}
+
+// avgpool2x2_kernel on rows of width W_b = w_len[b] (clamped to 1 .. W): the row's own last column is replicated when W_b is odd
+__global__ __launch_bounds__(256) void avgpool2x2_len_kernel(const float* __restrict__ x, int64_t x_bs, int64_t x_hs, int x_cs,
+                                                             int Wmax, int Ho, const int32_t* __restrict__ w_len,
+                                                             float* __restrict__ y, int64_t y_bs, int64_t y_hs, int y_cs) {
+  const int b = blockIdx.z / Ho, ho = blockIdx.z % Ho;
+  const int W = min(max(w_len[b], 1), Wmax);
+  const int Wo = (W + 1) / 2;
+  if ((int)blockIdx.x * 256 >= Wo) return;
+  const int wo = blockIdx.x * 256 + threadIdx.x;
+  const int c = blockIdx.y;
+  if (wo >= Wo) return;
+  const float* r0 = x + (int64_t)b * x_bs + (int64_t)(2 * ho) * x_hs + (int64_t)c * x_cs;
+  const float* r1 = r0 + x_hs;
+  const int w0 = 2 * wo, w1 = min(2 * wo + 1, W - 1);
+  const float s = ((r0[w0] + r0[w1]) + r1[w0]) + r1[w1];
+  y[(int64_t)b * y_bs + (int64_t)ho * y_hs + (int64_t)c * y_cs + wo] = s * 0.25f;
+}
+
+// Every per-row length of the ragged style plan from mel_len [B] (layout: st2.h st2_style_lengths).  One thread per entry.
+__global__ __launch_bounds__(64) void style_lengths_kernel(const int32_t* __restrict__ mel_len, int B, int T_min, int T_cap,
+                                                           int H, int S, int32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  int b, stage, v_sub = 0;
+  bool seam = false;
+  if (i < (S + 2) * B) {  // per-clip tables: W_0 .. W_S, then W_S - 4
+    stage = min(i / B, S);
+    b = i % B;
+    if (i / B == S + 1) v_sub = 4;
+  } else {  // per-stacked-row tables of stage 0 .. S: B (h + 2) - 2 rows each, centre = padded row r + 1
+    int j = i - (S + 2) * B;
+    stage = 0;
+    int h = H;
+    while (stage < S && j >= B * (h + 2) - 2) {
+      j -= B * (h + 2) - 2;
+      ++stage;
+      h >>= 1;
+    }
+    const int r = (j + 1) % (h + 2);
+    b = min((j + 1) / (h + 2), B - 1);
+    seam = r == 0 || r == h + 1;
+  }
+  // clamped: a caller's out-of-range count gives a wrong row, never a length past the buffers T_cap sizes
+  int w = min(max(mel_len[b], T_min), T_cap);
+  for (int k = 0; k < stage; ++k) w = (w + 1) / 2;
+  out[i] = seam ? 0 : w - v_sub;
+}
+
 }  // namespace
 
 extern "C" int st2_stft_frames(const float* wave, int64_t w_bs, int32_t B, int32_t L, int32_t n_win, int32_t hop,
@@ -144,5 +260,80 @@ extern "C" int st2_avgpool2x2(const float* x, int64_t x_bs, int64_t x_hs, int32_
   hipLaunchKernelGGL(avgpool2x2_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x_bs, x_hs, x_cs, W, Ho, Wo, y, y_bs,
                      y_hs, y_cs);
   ST2_CHECK_LAUNCH("st2_avgpool2x2");
+  return 0;
+}
+
+extern "C" int st2_stft_frames_len(const float* wave, int64_t w_bs, int32_t B, int32_t L, int32_t n_win, int32_t hop,
+                                   int32_t shift, float* frames, int64_t f_bs, int32_t f_cs, const int32_t* len,
+                                   int32_t L_min, int32_t* m_len, void* stream) {
+  ST2_REQUIRE(wave && frames && len && B > 0 && L > 1 && n_win > 0 && hop > 0, "st2_stft_frames_len: bad arguments");
+  ST2_REQUIRE(B <= 65535 && n_win <= 65535, "st2_stft_frames_len: grid too large");
+  // Every admitted row length L_b in [L_min, L] must keep the single reflection inside [0, L_b): the last frame reads up to
+  // (L_b / hop) * hop + n_win - 1 - shift <= L_b + n_win - 1 - shift, which must not pass 2 (L_b - 1); the first one shift - 0.
+  ST2_REQUIRE(L_min >= 2 && L_min <= L && shift >= 0 && shift < L_min && (int64_t)L_min + n_win - 1 - shift <= 2 * (int64_t)(L_min - 1),
+              "st2_stft_frames_len: reflection reaches past the shortest admitted row (L_min=%d, L=%d, n_win=%d, hop=%d, shift=%d)",
+              L_min, L, n_win, hop, shift);
+  const int M = L / hop + 1;
+  dim3 grid(st2_cdiv(M, 256), n_win, B);
+  hipLaunchKernelGGL(stft_frames_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, wave, w_bs, L, L_min, n_win, hop, shift,
+                     M, len, frames, f_bs, f_cs, m_len);
+  ST2_CHECK_LAUNCH("st2_stft_frames_len");
+  return 0;
+}
+
+extern "C" int st2_log_norm_len(float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t M, float eps, float mean,
+                                float stdv, const int32_t* len, void* stream) {
+  ST2_REQUIRE(x && len && B > 0 && C > 0 && M > 0 && stdv != 0.f, "st2_log_norm_len: bad arguments");
+  ST2_REQUIRE(B <= 65535 && C <= 65535, "st2_log_norm_len: grid too large");
+  hipLaunchKernelGGL(log_norm_len_kernel, dim3(st2_cdiv(M, 256), C, B), dim3(256), 0, (hipStream_t)stream, x, x_bs, x_cs, M,
+                     eps, mean, stdv, len);
+  ST2_CHECK_LAUNCH("st2_log_norm_len");
+  return 0;
+}
+
+extern "C" int st2_dwconv3x3s2_len(const float* x, int64_t x_bs, int64_t x_hs, int32_t x_cs, const float* w,
+                                   const float* bias, int32_t B, int32_t C, int32_t H, int32_t W, float* y, int64_t y_bs,
+                                   int64_t y_hs, int32_t y_cs, const int32_t* w_len, void* stream) {
+  ST2_REQUIRE(x && w && y && w_len && B > 0 && C > 0 && H > 0 && W > 0, "st2_dwconv3x3s2_len: bad arguments");
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  ST2_REQUIRE((int64_t)B * Ho <= 65535 && C <= 65535, "st2_dwconv3x3s2_len: grid too large");
+  dim3 grid(st2_cdiv(Wo, 256), C, B * Ho);
+  hipLaunchKernelGGL(dwconv3x3s2_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x_bs, x_hs, x_cs, w, bias, H, W, Ho,
+                     w_len, y, y_bs, y_hs, y_cs);
+  ST2_CHECK_LAUNCH("st2_dwconv3x3s2_len");
+  return 0;
+}
+
+extern "C" int st2_avgpool2x2_len(const float* x, int64_t x_bs, int64_t x_hs, int32_t x_cs, int32_t B, int32_t C, int32_t H,
+                                  int32_t W, float* y, int64_t y_bs, int64_t y_hs, int32_t y_cs, const int32_t* w_len,
+                                  void* stream) {
+  ST2_REQUIRE(x && y && w_len && B > 0 && C > 0 && H > 1 && W > 0, "st2_avgpool2x2_len: bad arguments");
+  ST2_REQUIRE(H % 2 == 0, "st2_avgpool2x2_len: odd height %d (the reference pads the width only, models.py:72-75)", H);
+  const int Ho = H / 2, Wo = (W + 1) / 2;
+  ST2_REQUIRE((int64_t)B * Ho <= 65535 && C <= 65535, "st2_avgpool2x2_len: grid too large");
+  dim3 grid(st2_cdiv(Wo, 256), C, B * Ho);
+  hipLaunchKernelGGL(avgpool2x2_len_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x_bs, x_hs, x_cs, W, Ho, w_len, y,
+                     y_bs, y_hs, y_cs);
+  ST2_CHECK_LAUNCH("st2_avgpool2x2_len");
+  return 0;
+}
+
+extern "C" int64_t st2_style_lengths_count(int32_t B, int32_t H, int32_t stages) {
+  if (B <= 0 || H <= 0 || stages < 0 || stages > 8 || (H >> stages) < 1) return -1;
+  int64_t n = (int64_t)(stages + 2) * B;
+  for (int i = 0; i <= stages; ++i) n += (int64_t)B * ((H >> i) + 2) - 2;
+  return n;
+}
+
+extern "C" int st2_style_lengths(const int32_t* mel_len, int32_t B, int32_t T_min, int32_t T_cap, int32_t H, int32_t stages,
+                                 int32_t* out, void* stream) {
+  const int64_t n = st2_style_lengths_count(B, H, stages);
+  ST2_REQUIRE(mel_len && out && n > 0 && n < ((int64_t)1 << 30) && T_min >= 1 && T_cap >= T_min,
+              "st2_style_lengths: bad arguments");
+  ST2_REQUIRE(((T_min - 1) >> stages) + 1 > 4, "st2_style_lengths: T_min=%d leaves no column for the 5-wide valid conv after %d "
+              "halvings", T_min, stages);
+  hipLaunchKernelGGL(style_lengths_kernel, dim3(st2_cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, mel_len, B, T_min, T_cap, H,
+                     stages, out, (int)n);
+  ST2_CHECK_LAUNCH("st2_style_lengths");
   return 0;
 }

@@ -282,17 +282,34 @@ class Engine:
         return t_en
 
     # -- reference-audio style encoders ---------------------------------------------------------------------------------------
-    def style_forward(self, which, mel):
+    def style_forward(self, which, mel, frames=None):
         """mel [B, 1, 80, T] or [B, 80, T] (normalised log-mel, T >= 80) -> [B, style_dim]: one `st2_style_forward` call;
-        which = 0 `style_encoder`, 1 `predictor_encoder`."""
+        which = 0 `style_encoder`, 1 `predictor_encoder`.  `frames` (int32 device tensor or list of B ints in 80..T,
+        optional): a ragged batch -- row b is the mel of frames[b] frames padded to T (whatever the padding holds) and comes
+        out as if encoded alone (`st2_style_forward_ragged`).  A list is validated here; a device tensor is used as it is
+        (no host read: legal under graph capture) and clamped to 80..T on the device."""
         mel = mel.float().reshape(mel.shape[0], mel.shape[-2], mel.shape[-1]).contiguous()
         B, H, T = mel.shape
         dev = mel.device
-        ws, ws_ptr, nbytes = self._workspace(dev, "st2_style_workspace_bytes", which, B, H, T,
+        if frames is not None:
+            if isinstance(frames, torch.Tensor):
+                if frames.dtype != torch.int32 or frames.numel() != B or not frames.is_contiguous() or frames.device != dev:
+                    raise _lib.St2Error("frames must be a contiguous int32 tensor of %d entries on %s (got %s %s on %s)"
+                                        % (B, dev, frames.dtype, tuple(frames.shape), frames.device))
+            else:
+                frames = [int(f) for f in frames]
+                if len(frames) != B or not all(80 <= f <= T for f in frames):
+                    raise _lib.St2Error("frames must be %d ints in 80..%d (four halvings, then the 5x5 valid conv), got %r"
+                                        % (B, T, frames))
+                frames = torch.tensor(frames, dtype=torch.int32).to(dev)
+        query, entry = ("st2_style_workspace_bytes", "st2_style_forward") if frames is None else \
+            ("st2_style_workspace_bytes_ragged", "st2_style_forward_ragged")
+        ws, ws_ptr, nbytes = self._workspace(dev, query, which, B, H, T,
                                              what="style-encoder weights not finalized, or not an 80 x >= 80 mel")
         out = torch.empty((B, self.style_dims[which]), device=dev, dtype=torch.float32)
-        _lib.check(self.lib.st2_style_forward(self.h, which, mel.data_ptr(), B, H, T, out.data_ptr(), ws_ptr, nbytes,
-                                              _stream(dev)), "st2_style_forward")
+        fr = () if frames is None else (frames.data_ptr(),)
+        _lib.check(getattr(self.lib, entry)(self.h, which, mel.data_ptr(), *fr, B, H, T, out.data_ptr(), ws_ptr, nbytes,
+                                            _stream(dev)), entry)
         return out
 
     # -- PL-BERT ---------------------------------------------------------------------------------------------------------

@@ -1058,16 +1058,30 @@ def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_p
 
 
 # ---- reference-audio style path (st2_style.hip) ----------------------------------------------------------------------
-def stft_frames(wave, n_win, hop, shift):
-    """`st2_stft_frames`: wave [B, L] -> frames [B, n_win, L // hop + 1] (reflect-padded frame columns of torch.stft)."""
+def stft_frames(wave, n_win, hop, shift, lengths=None, min_length=None, want_frames=False):
+    """`st2_stft_frames`: wave [B, L] -> frames [B, n_win, L // hop + 1] (reflect-padded frame columns of torch.stft).
+    `lengths` (int32 [B] on the device, `st2_stft_frames_len`): row b is the clip of lengths[b] samples (clamped to
+    [min_length, L]; min_length defaults to the shortest length whose reflection stays inside the clip) -- reflected about its
+    own end, frame columns from lengths[b] // hop + 1 on exact zeros, nothing of `wave` at or past lengths[b] read.
+    want_frames: also return those frame counts (int32 [B] on the device)."""
+    lp = _chk_len(lengths, "lengths", _nb(wave, 2), wave)
     lib = _lib.load()
     _chk(wave, "wave", 2)
     B, L = wave.shape
     M = L // hop + 1
     fr = torch.empty((B, n_win, M), device=wave.device, dtype=torch.float32)
-    _lib.check(lib.st2_stft_frames(wave.data_ptr(), wave.stride(0), B, L, n_win, hop, shift, fr.data_ptr(), fr.stride(0),
-                                   fr.stride(1), _stream()), "st2_stft_frames")
-    return fr
+    if lengths is None:
+        if want_frames or min_length is not None:
+            raise _lib.St2Error("stft_frames: min_length / want_frames need lengths")
+        _lib.check(lib.st2_stft_frames(wave.data_ptr(), wave.stride(0), B, L, n_win, hop, shift, fr.data_ptr(), fr.stride(0),
+                                       fr.stride(1), _stream()), "st2_stft_frames")
+        return fr
+    if min_length is None:
+        min_length = min(L, max(shift + 1, n_win + 1 - shift, 2))
+    m_len = torch.empty((B,), device=wave.device, dtype=torch.int32) if want_frames else None
+    _lib.check(lib.st2_stft_frames_len(wave.data_ptr(), wave.stride(0), B, L, n_win, hop, shift, fr.data_ptr(), fr.stride(0),
+                                       fr.stride(1), lp, int(min_length), _ptr(m_len), _stream()), "st2_stft_frames_len")
+    return (fr, m_len) if want_frames else fr
 
 
 def power_spectrum(y):
@@ -1082,12 +1096,20 @@ def power_spectrum(y):
     return p
 
 
-def log_norm_(x, eps, mean, std):
-    """`st2_log_norm`: x = (log(eps + x) - mean) / std in place (x contiguous)."""
+def log_norm_(x, eps, mean, std, lengths=None):
+    """`st2_log_norm`: x = (log(eps + x) - mean) / std in place (x contiguous).  `lengths` (int32 [B] on the device,
+    `st2_log_norm_len`; x [B, C, M]): columns of row b from lengths[b] on are written as exact 0 instead."""
+    lp = _chk_len(lengths, "lengths", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x")
     assert x.is_contiguous()
-    _lib.check(lib.st2_log_norm(x.data_ptr(), x.numel(), eps, mean, std, _stream()), "st2_log_norm")
+    if lengths is None:
+        _lib.check(lib.st2_log_norm(x.data_ptr(), x.numel(), eps, mean, std, _stream()), "st2_log_norm")
+        return x
+    _chk(x, "x", 3)
+    B, Cc, M = x.shape
+    _lib.check(lib.st2_log_norm_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, M, eps, mean, std, lp, _stream()),
+               "st2_log_norm_len")
     return x
 
 
@@ -1095,8 +1117,11 @@ def _chk_map(t, name):
     _chk(t, name, 4)  # [B, H, C, W] view, W contiguous
 
 
-def dwconv3x3s2(x, w, bias, out):
-    """`st2_dwconv3x3s2`: x [B, H, C, W] (any strides, W contiguous), w [C, 3, 3], bias [C] -> out [B, Ho, C, Wo]."""
+def dwconv3x3s2(x, w, bias, out, lengths=None):
+    """`st2_dwconv3x3s2`: x [B, H, C, W] (any strides, W contiguous), w [C, 3, 3], bias [C] -> out [B, Ho, C, Wo].  `lengths`
+    (int32 [B] on the device, `st2_dwconv3x3s2_len`): the maps of item b are lengths[b] <= W wide -- zero padding at their own
+    end, outputs [0, (lengths[b] + 1) // 2), `out` past them left as it was."""
+    lp = _chk_len(lengths, "lengths", _nb(x, 4), x)
     lib = _lib.load()
     _chk_map(x, "x")
     _chk_map(out, "out")
@@ -1105,19 +1130,29 @@ def dwconv3x3s2(x, w, bias, out):
     B, H, Cc, Wd = x.shape
     assert w.shape == (Cc, 3, 3) and w.is_contiguous()
     assert out.shape == (B, (H - 1) // 2 + 1, Cc, (Wd - 1) // 2 + 1), (out.shape, x.shape)
-    _lib.check(lib.st2_dwconv3x3s2(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), w.data_ptr(), _ptr(bias), B, Cc,
-                                   H, Wd, out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), _stream()),
-               "st2_dwconv3x3s2")
+    args = (x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), w.data_ptr(), _ptr(bias), B, Cc, H, Wd, out.data_ptr(),
+            out.stride(0), out.stride(1), out.stride(2))
+    if lengths is None:
+        _lib.check(lib.st2_dwconv3x3s2(*args, _stream()), "st2_dwconv3x3s2")
+    else:
+        _lib.check(lib.st2_dwconv3x3s2_len(*args, lp, _stream()), "st2_dwconv3x3s2_len")
     return out
 
 
-def avgpool2x2(x, out):
-    """`st2_avgpool2x2`: x [B, H, C, W] -> out [B, H/2, C, (W+1)/2] (odd widths replicate their last column)."""
+def avgpool2x2(x, out, lengths=None):
+    """`st2_avgpool2x2`: x [B, H, C, W] -> out [B, H/2, C, (W+1)/2] (odd widths replicate their last column).  `lengths`
+    (int32 [B] on the device, `st2_avgpool2x2_len`): the maps of item b are lengths[b] <= W wide -- their own last column is
+    the one replicated, outputs [0, (lengths[b] + 1) // 2), `out` past them left as it was."""
+    lp = _chk_len(lengths, "lengths", _nb(x, 4), x)
     lib = _lib.load()
     _chk_map(x, "x")
     _chk_map(out, "out")
     B, H, Cc, Wd = x.shape
     assert out.shape == (B, H // 2, Cc, (Wd + 1) // 2), (out.shape, x.shape)
-    _lib.check(lib.st2_avgpool2x2(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), B, Cc, H, Wd, out.data_ptr(),
-                                  out.stride(0), out.stride(1), out.stride(2), _stream()), "st2_avgpool2x2")
+    args = (x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), B, Cc, H, Wd, out.data_ptr(), out.stride(0), out.stride(1),
+            out.stride(2))
+    if lengths is None:
+        _lib.check(lib.st2_avgpool2x2(*args, _stream()), "st2_avgpool2x2")
+    else:
+        _lib.check(lib.st2_avgpool2x2_len(*args, lp, _stream()), "st2_avgpool2x2_len")
     return out

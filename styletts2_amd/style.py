@@ -39,10 +39,19 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .layers import transient_state
-from . import _hooks, ops
+from . import _hooks, _lib, ops
 from . import weights as W
 
 MEL_MEAN, MEL_STD = -4.0, 4.0  # meldataset.py:60
+HOP = 300
+# shortest reference clip of a ragged batch: 80 mel frames (four halvings, then the 5x5 valid conv), M = 1 + L // HOP
+MIN_CLIP = 79 * HOP
+
+
+def _ragged_needs_engine_plan():
+    if _hooks.plan != "engine":
+        raise _lib.St2Error("lengths= (a ragged batch of reference clips) runs on the engine plan only: the per-kernel Python "
+                            "plan (_hooks.override(plan='python')) has no length-aware twin")
 
 
 class _SNConv2d(nn.Module):
@@ -160,13 +169,19 @@ class StyleEncoder(nn.Module):
         return pk
 
     @torch.no_grad()
-    def forward(self, x):
-        """mel [B, 1, 80, T] -> style [B, style_dim]: one `st2_style_forward` call into the C++ launch plan."""
+    def forward(self, x, lengths=None):
+        """mel [B, 1, 80, T] -> style [B, style_dim]: one `st2_style_forward` call into the C++ launch plan.  `lengths` (int32
+        [B] on the device, or a list of B ints in 80..T): a ragged batch, row b valid on its first lengths[b] frames and
+        encoded as if alone (`st2_style_forward_ragged`; engine plan only)."""
+        if lengths is not None:
+            _ragged_needs_engine_plan()
+            if x.device.type != "cuda":
+                raise _lib.St2Error("x must live on a HIP device (got %s); the engine has no CPU path" % (x.device,))
         if x.device.type == "cuda" and _hooks.plan == "engine":
             from . import engine
             from .text import _cached_engine
             eng = _cached_engine(self, "_engine", [self], lambda: engine.build_style_engine(self, None, x.device))
-            return eng.style_forward(0, x)
+            return eng.style_forward(0, x, frames=lengths)
         return self._forward_kernels(x)
 
     @torch.no_grad()
@@ -265,17 +280,54 @@ def _mel_pack(device, n_fft, win_length, n_mels):
     return pk
 
 
+def _clip_lengths(lengths, B, L_cap, dev):
+    """Per-clip sample counts of a ragged batch as int32 [B] on `dev`.  A host list is validated here (MIN_CLIP..L_cap) and
+    uploaded; a device tensor is used as it is -- no host read, legal under graph capture -- and clamped to the same range on
+    the device."""
+    if torch.is_tensor(lengths):
+        if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+            raise _lib.St2Error("lengths must be a contiguous int32 tensor of %d entries (got %s %s)"
+                                % (B, lengths.dtype, tuple(lengths.shape)))
+        if lengths.device != dev:
+            raise _lib.St2Error("lengths must live on the device of wave (%s, got %s)" % (dev, lengths.device))
+        return lengths
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != B:
+        raise _lib.St2Error("lengths must hold %d entries, got %d" % (B, len(lengths)))
+    bad = [v for v in lengths if not MIN_CLIP <= v <= L_cap]
+    if bad:
+        raise _lib.St2Error("reference clips must be %d..%d samples long (80 mel frames at least, the buffer's row at most), got %r"
+                            % (MIN_CLIP, L_cap, bad))
+    return torch.tensor(lengths, dtype=torch.int32).to(dev)
+
+
 @torch.no_grad()
-def mel_spectrogram_engine(wave, n_fft=2048, win_length=1200, hop_length=300, n_mels=80):
+def mel_spectrogram_engine(wave, n_fft=2048, win_length=1200, hop_length=HOP, n_mels=80, lengths=None, want_frames=False):
     """wave [B, L] (24 kHz) -> normalised log-mel [B, 80, 1 + L // 300]: (log(1e-5 + mel) + 4) / 4 (meldataset.py:58-66;
-    Demo/Inference_LibriTTS.ipynb `preprocess`) on the HIP kernels (module docstring)."""
+    Demo/Inference_LibriTTS.ipynb `preprocess`) on the HIP kernels (module docstring).  `lengths` (int32 [B] on the device, or
+    a list of B ints): row b is the clip of lengths[b] samples -- framed with the reflection about its own end, nothing of
+    `wave` at or past lengths[b] read -- and its mel is exact zeros from column 1 + lengths[b] // 300 on.  want_frames: also
+    return those frame counts (int32 [B] on the device)."""
+    if lengths is not None:
+        _ragged_needs_engine_plan()
     wave = wave.float().contiguous()
+    if lengths is not None:  # checked before anything is packed or launched
+        if wave.dim() != 2 or wave.shape[1] < 79 * hop_length:
+            raise _lib.St2Error("a ragged batch needs wave [B, L_cap >= %d], got %s" % (79 * hop_length, tuple(wave.shape)))
+        lengths = _clip_lengths(lengths, wave.shape[0], wave.shape[1], wave.device)
     dft_w, fb_w = _mel_pack(wave.device, n_fft, win_length, n_mels)
     K = n_fft // 2 + 1
-    frames = ops.stft_frames(wave, win_length, hop_length, n_fft // 2 - (n_fft - win_length) // 2)
+    shift = n_fft // 2 - (n_fft - win_length) // 2
+    m_len = None
+    if lengths is None:
+        frames = ops.stft_frames(wave, win_length, hop_length, shift)
+    else:
+        frames, m_len = ops.stft_frames(wave, win_length, hop_length, shift, lengths=lengths, min_length=79 * hop_length,
+                                        want_frames=True)
     spec = ops.conv1d(frames, dft_w, 2 * K, 1)
     mel = ops.conv1d(ops.power_spectrum(spec), fb_w, n_mels, 1)
-    return ops.log_norm_(mel, 1e-5, MEL_MEAN, MEL_STD)
+    mel = ops.log_norm_(mel, 1e-5, MEL_MEAN, MEL_STD) if m_len is None else ops.log_norm_(mel, 1e-5, MEL_MEAN, MEL_STD, lengths=m_len)
+    return (mel, m_len) if want_frames else mel
 
 
 def _style_engine(model, dev):
@@ -292,11 +344,31 @@ def _style_engine(model, dev):
 
 
 @torch.no_grad()
-def compute_style(model, wave):
+def compute_style(model, wave, lengths=None):
     """`compute_style` of Demo/Inference_LibriTTS.ipynb:100-111 minus the file I/O: wave [L] or [B, L] at 24 kHz
-    (already trimmed; the notebook trims with librosa.effects.trim(top_db=30) on the host) -> ref_s [B, 256]."""
+    (already trimmed; the notebook trims with librosa.effects.trim(top_db=30) on the host) -> ref_s [B, 256].
+
+    A ragged batch -- the clips of B zero-shot requests, no two of one length -- is one call too: `wave` [B, L_cap] with
+    `lengths` (int32 [B] on the device: no host read, legal under graph capture; or a list of B ints, validated here), or
+    simply a list of 1-D clips, which are copied into one buffer.  Row b equals the clip processed alone; whatever `wave`
+    holds at or past lengths[b] is never used.  Clips are MIN_CLIP (23 700) samples at least."""
+    if isinstance(wave, (list, tuple)):
+        if lengths is not None:
+            raise _lib.St2Error("compute_style: a list of clips carries its own lengths")
+        clips = [w.reshape(-1) for w in wave]
+        lengths = [int(w.numel()) for w in clips]
+        if not clips:
+            raise _lib.St2Error("compute_style: empty list of clips")
+        wave = torch.zeros((len(clips), max(max(lengths), MIN_CLIP)), device=clips[0].device, dtype=torch.float32)
+        for b, w in enumerate(clips):
+            wave[b, :lengths[b]] = w
     if wave.dim() == 1:
         wave = wave.unsqueeze(0)
+    if lengths is not None:
+        _ragged_needs_engine_plan()
+        mel, m_len = mel_spectrogram_engine(wave, lengths=lengths, want_frames=True)
+        eng = _style_engine(model, wave.device)
+        return torch.cat([eng.style_forward(0, mel, frames=m_len), eng.style_forward(1, mel, frames=m_len)], dim=1)
     mel = mel_spectrogram_engine(wave)
     if wave.device.type == "cuda" and _hooks.plan == "engine":  # both encoders as C++ launch plans (st2_style_forward)
         eng = _style_engine(model, wave.device)
