@@ -760,6 +760,60 @@ int st2_sizeof_front_args(void);
 int64_t st2_front_workspace_bytes(st2_engine* e, const st2_front_args* a);
 int st2_front_forward(st2_engine* e, const st2_front_args* a, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- per-request controls (added under ABI 23, additive: kernel-level entry points and one plan-level twin, no new
+ * backend-table slot, no change to an existing struct or signature) ------------------------------------------------ *
+ * What a request brings as a SETTING is a device row of fp32 [B], like its lengths are, so that one batch -- and one recorded
+ * graph -- serves any mix of requests.  A NULL row keeps the behaviour without it.  Rows are CLAMPED WHERE THEY ARE READ (a
+ * bad device value gives a clamped row, never a fault or a host read); hosts validate what they upload.
+ *
+ *   speed     dur[b][n] = max(1, rint(total[b][n] / speed[b])), total = the fp32 sigmoid sum of st2_duration_head: one
+ *             correctly rounded fp32 division behind the unchanged reduction, rint = round-half-even, 0 at pad tokens, `tail`
+ *             added afterwards, unscaled.  Clamped to [0.25, 4]; NaN -> 1.  x / 1 is exact: speed 1 gives st2_duration_head's
+ *             bits.
+ *   alpha, beta, t   the style mixing weights of st2_front_args with row b's own value.  Clamped to [0, 1]; NaN -> the
+ *             call's scalar.  The complement of a weight is (float)(1.0 - (double)w) and a mix is `v = a x; v += b y` (no
+ *             FMA), which is st2_axpbypcz's arithmetic: a row whose weight equals a scalar representable in fp32 gives the
+ *             bits of the scalar call.
+ *   f0_scale  F0[b][l] *= f0_scale[b] for l < 2 T_b.  Clamped to [0.5, 2]; NaN -> 1.
+ *   n_shift   N[b][l] += n_shift[b] for l < 2 T_b (N is a log-energy: a shift is a gain).  Clamped to [-2, 2]; NaN -> 0; a
+ *             shift of 0 keeps x itself (-0.0 survives).
+ *
+ * st2_duration_head_rate: st2_duration_head with `speed` (fp32 [B], device, not NULL).  Same reduction order; dsum (optional)
+ * receives the un-scaled sums.
+ * st2_style_mix_rows: the style mixing of st2_front_forward as ONE launch.  s_pred [B][2 style_dim] = the sampler's output;
+ * s_prev ([B][2 style_dim], or [1][2 style_dim] with carry != 0), ref_s [B][2 style_dim], t / alpha / beta (fp32 [B]) may each
+ * be NULL; a NULL weight row means the scalar t0 / alpha0 / beta0 (validated: in [0, 1]).  Outputs ref, s [B][style_dim] and
+ * (optional) s_pred_out [B][2 style_dim] = ref | s.  carry != 0: the rows are consecutive sentences of one passage and row k's
+ * s_prev is row k-1's mixed result (row 0 takes s_prev or nothing): ONE workgroup per 256 channels walks the rows, one channel
+ * per thread.  Same arithmetic, in the same order, as the st2_axpbypcz / st2_copy_ncl launches of the front plan it replaces.
+ * st2_prosody_controls: in place over f0, n [B][L] (row stride bs, L = 2 T of st2_prosody_forward[_ragged]'s outputs);
+ * frames (int32 [B], device, or NULL = every row is L long) bounds row b at 2 * frames[b] (clamped to 0..L): nothing at or past
+ * it is read or written, and a workgroup whose chunk lies there leaves at once.  A NULL f0_scale / n_shift leaves that curve
+ * alone; both NULL launches nothing.  One operation per element, never fused.
+ * All three: one launch, no allocation, no synchronisation, legal under stream capture; bad arguments return non-zero before
+ * any launch. */
+int st2_duration_head_rate(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias, int32_t B,
+                           int32_t K, int32_t J, int32_t N, const int32_t* len, int32_t tail, const float* speed,
+                           int64_t* dur, float* dsum, void* stream);
+int st2_style_mix_rows(const float* s_pred, const float* s_prev, const float* ref_s, const float* t, const float* alpha,
+                       const float* beta, double t0, double alpha0, double beta0, int32_t B, int32_t style_dim,
+                       int32_t carry, float* ref, float* s, float* s_pred_out, void* stream);
+int st2_prosody_controls(float* f0, float* n, int64_t bs, int32_t B, int32_t L, const float* f0_scale,
+                         const float* n_shift, const int32_t* frames, void* stream);
+
+/* st2_front_forward with per-row controls.  A NULL `ctl`, or one whose four members are NULL, issues exactly the launches of
+ * st2_front_forward.  With any of alpha / beta / t the style mixing is ONE st2_style_mix_rows launch (also in carry mode: the
+ * row scan runs inside it instead of as 5 B launches); with speed the duration head is st2_duration_head_rate (`durations`
+ * must then be non-NULL: there is nothing to scale otherwise).  With a non-empty `ctl` the scalar a->t / alpha / beta must lie
+ * in [0, 1] (they are what a NaN row falls back to).  Workspace: st2_front_workspace_bytes(a) suffices.  The CPU
+ * backends of st2_debug_set_backend have no slot for the two kernels: a non-empty `ctl` is refused while one is installed. */
+typedef struct st2_controls {
+  const float *speed, *alpha, *beta, *t;  /* each fp32 [B] on the device, or NULL */
+} st2_controls;
+int st2_sizeof_controls(void);
+int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* StyleEncoder.forward (models.py:139-164; `compute_style`, Demo/Inference_LibriTTS.ipynb:100-111): mel [B][80][T] (the
  * normalised log-mel of the reference recording, T >= 80 frames) -> style [B][style_dim].  which = 0: `style_encoder`
  * (acoustic half of ref_s), 1: `predictor_encoder` (prosodic half); ref_s = cat(which 0, which 1).  Conv2d layers run as

@@ -84,6 +84,11 @@ class FrontArgs(C.Structure):
                 ("s_pred_out", C.c_void_p), ("durations", C.c_void_p), ("carry", C.c_int32)]
 
 
+class ControlRows(C.Structure):
+    """Mirror of `st2_controls`: per-row controls of st2_front_forward_ctl, each fp32 [B] on the device or NULL."""
+    _fields_ = [("speed", C.c_void_p), ("alpha", C.c_void_p), ("beta", C.c_void_p), ("t", C.c_void_p)]
+
+
 class DecoderTaps(C.Structure):
     """Mirror of `st2_decoder_taps`."""
     _fields_ = [("encode", f32p), ("front", f32p), ("har_source", f32p), ("har", f32p), ("stage", f32p * 4),
@@ -241,6 +246,14 @@ _SIGNATURES = {
     "st2_frames_from_durations": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "st2_wave_pack": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_void_p, C.c_void_p]),
+    "st2_sizeof_controls": (C.c_int, []),
+    "st2_front_forward_ctl": (C.c_int, [C.c_void_p, C.POINTER(FrontArgs), C.POINTER(ControlRows), C.c_void_p, C.c_int64,
+                                        C.c_void_p]),
+    "st2_duration_head_rate": (C.c_int, [f32p, C.c_int64, C.c_int32, f32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int32, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "st2_style_mix_rows": (C.c_int, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                     C.c_int32, C.c_int32, f32p, f32p, f32p, C.c_void_p]),
+    "st2_prosody_controls": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_void_p, C.c_void_p]),
     "st2_prosody_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "st2_prosody_forward": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -331,6 +344,9 @@ def load():
     if lib.st2_sizeof_front_args() != C.sizeof(FrontArgs):
         raise St2Error("st2_front_args layout mismatch: library %d B, binding %d B"
                        % (lib.st2_sizeof_front_args(), C.sizeof(FrontArgs)))
+    if lib.st2_sizeof_controls() != C.sizeof(ControlRows):
+        raise St2Error("st2_controls layout mismatch: library %d B, binding %d B"
+                       % (lib.st2_sizeof_controls(), C.sizeof(ControlRows)))
     _lib = lib
     return lib
 

@@ -1375,6 +1375,11 @@ extern "C" int64_t st2_front_workspace_bytes(st2_engine* e, const st2_front_args
 
 extern "C" int st2_front_forward(st2_engine* e, const st2_front_args* a, void* workspace, int64_t workspace_bytes,
                                  void* stream) {
+  return st2_front_forward_ctl(e, a, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
   const char* why = front_ready(e);
   ST2_REQUIRE(!why, "st2_front_forward: %s", why);
   ST2_REQUIRE(a && a->tokens && a->noise && a->step_noise && a->table && a->t_en && a->d_cm && a->s && a->ref && workspace &&
@@ -1387,7 +1392,17 @@ extern "C" int st2_front_forward(st2_engine* e, const st2_front_args* a, void* w
   c.stream = stream;
   c.a.base = static_cast<char*>(workspace);
   c.a.cap = workspace_bytes;
-  const int rc = front_plan(c, *e, *a);
+  if (ctl && !(ctl->speed || ctl->alpha || ctl->beta || ctl->t)) ctl = nullptr;  // empty: st2_front_forward's launches
+  if (ctl) {
+    ST2_REQUIRE(!ctl->speed || a->durations, "st2_front_forward_ctl: speed with durations == NULL (forced durations): there is "
+                "nothing to scale");
+    const auto in01 = [](double w) { return w >= 0.0 && w <= 1.0; };
+    ST2_REQUIRE(in01(a->t) && in01(a->alpha) && in01(a->beta), "st2_front_forward_ctl: the scalar weights t=%g / alpha=%g / beta=%g "
+                "must lie in [0, 1]", a->t, a->alpha, a->beta);
+    ST2_REQUIRE(g_be.axpbypcz == kHipBackend.axpbypcz && g_be.duration_head == kHipBackend.duration_head,
+                "st2_front_forward_ctl: per-row controls have no slot in a debug backend (st2_debug_set_backend)");
+  }
+  const int rc = front_plan(c, *e, *a, ctl);
   ST2_REQUIRE(!c.a.overflow, "st2_front_forward: workspace of %lld B is too small (need %lld B, see "
               "st2_front_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
   return rc;

@@ -73,10 +73,19 @@ __global__ __launch_bounds__(256) void copy_ncl_kernel(const float* __restrict__
 //   logits[j] = bias[j] + sum_k W[j][k] * x[b][k][n]  (j < J = max_dur, k < K = 512; fp32, k ascending per lane then a
 //   fixed-order wave reduction),  dur = max(1, rint(sum_j sigmoid(logits[j]))),  0 at pad tokens (n >= len[b]),
 //   + tail on the utterance's own last token.  x is channel-major [B][K][N] (the duration LSTM's output layout).
+// RATE (st2_duration_head_rate): the sum is divided by the row's speaking rate before it is rounded -- one correctly rounded
+// fp32 division behind the unchanged reduction, so dsum and the RATE = false instantiation are what they were.
+__device__ __forceinline__ float rate_clamped(const float* __restrict__ speed, int b) {
+  const float s = speed[b];
+  return s != s ? 1.0f : fminf(fmaxf(s, 0.25f), 4.0f);  // a bad device value gives a clamped row, never a fault
+}
+
+template <bool RATE>
 __global__ __launch_bounds__(64) void duration_head_kernel(const float* __restrict__ x, int64_t x_bs, int x_cs,
                                                            const float* __restrict__ w, const float* __restrict__ bias,
                                                            int K, int J, int N, const int* __restrict__ len, int tail,
-                                                           long long* __restrict__ dur, float* __restrict__ dsum) {
+                                                           long long* __restrict__ dur, float* __restrict__ dsum,
+                                                           const float* __restrict__ speed) {
   const int n = blockIdx.x;
   const int b = blockIdx.y;
   const int lane = threadIdx.x;
@@ -92,7 +101,9 @@ __global__ __launch_bounds__(64) void duration_head_kernel(const float* __restri
     total += 1.0f / (1.0f + expf(-acc));
   }
   if (lane == 0) {
-    long long d = (long long)fmaxf(rintf(total), 1.0f);  // torch.round = round-half-even = rintf
+    float scaled = total;
+    if constexpr (RATE) scaled = total / rate_clamped(speed, b);  // x / 1 is exact: a neutral rate keeps the bits
+    long long d = (long long)fmaxf(rintf(scaled), 1.0f);  // torch.round = round-half-even = rintf
     if (n >= n_b) d = 0;
     if (n == n_b - 1) d += tail;
     dur[(int64_t)b * N + n] = d;
@@ -280,9 +291,23 @@ extern "C" int st2_duration_head(const float* x, int64_t x_bs, int32_t x_cs, con
   ST2_REQUIRE(x && w && bias && dur && B > 0 && K > 0 && J > 0 && N > 0, "st2_duration_head: bad arguments");
   ST2_REQUIRE(B <= 65535, "st2_duration_head: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(duration_head_kernel, dim3(N, B), dim3(64), 0, s, x, x_bs, x_cs, w, bias, K, J, N,
-                     reinterpret_cast<const int*>(len), tail, reinterpret_cast<long long*>(dur), dsum);
+  hipLaunchKernelGGL(duration_head_kernel<false>, dim3(N, B), dim3(64), 0, s, x, x_bs, x_cs, w, bias, K, J, N,
+                     reinterpret_cast<const int*>(len), tail, reinterpret_cast<long long*>(dur), dsum, nullptr);
   ST2_CHECK_LAUNCH("st2_duration_head");
+  return 0;
+}
+
+extern "C" int st2_duration_head_rate(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias,
+                                      int32_t B, int32_t K, int32_t J, int32_t N, const int32_t* len, int32_t tail,
+                                      const float* speed, int64_t* dur, float* dsum, void* stream) {
+  ST2_REQUIRE(x && w && bias && dur && speed, "st2_duration_head_rate: x / w / bias / speed / dur is NULL");
+  ST2_REQUIRE(B > 0 && K > 0 && J > 0 && N > 0 && tail >= 0, "st2_duration_head_rate: bad geometry (B=%d, K=%d, J=%d, N=%d, tail=%d)",
+              B, K, J, N, tail);
+  ST2_REQUIRE(B <= 65535, "st2_duration_head_rate: grid too large");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(duration_head_kernel<true>, dim3(N, B), dim3(64), 0, s, x, x_bs, x_cs, w, bias, K, J, N,
+                     reinterpret_cast<const int*>(len), tail, reinterpret_cast<long long*>(dur), dsum, speed);
+  ST2_CHECK_LAUNCH("st2_duration_head_rate");
   return 0;
 }
 

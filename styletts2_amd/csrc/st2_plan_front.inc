@@ -127,7 +127,7 @@ View bert_plan(Ctx& c, const st2_engine& e, const int64_t* tokens, const int32_t
   return X;
 }
 
-int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a) {
+int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_controls* ctl = nullptr) {
   const st2_model_config& cfg = e.cfg;
   const int B = a.B, N = a.N, sty = cfg.style_dim, C2 = cfg.dn_channels, dh = cfg.pred_hidden;
   text_plan(c, e, a.tokens, a.lengths, B, N, a.t_en);
@@ -147,6 +147,15 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a) {
                      a.sigma0, sp, nullptr) != 0 && c.rc == 0)
       c.rc = 1;
     c.a.off = mark;
+  }
+  const float* speed = ctl ? ctl->speed : nullptr;
+  if (ctl && (ctl->alpha || ctl->beta || ctl->t)) {
+    // per-row weights: the whole mixing -- in carry mode the row scan too -- is ONE launch (st2_controls.hip), the arithmetic of
+    // the launches below in their order
+    RUN(c, st2_style_mix_rows(sp, a.s_prev, a.ref_s, ctl->t, ctl->alpha, ctl->beta, a.t, a.alpha, a.beta, B, sty,
+                              a.carry && B > 1, a.ref, a.s, a.s_pred_out, c.stream));
+    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
+    return c.rc;
   }
   if (a.carry && B > 1) {
     // the rows are consecutive sentences of one passage: row k mixes with row k-1's MIXED style (the loop of LFinference,
@@ -177,7 +186,7 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a) {
     }
     RUN(c, g_be.copy_ncl(mixed, C2, sty, a.ref, sty, sty, B, 1, sty, c.stream));
     RUN(c, g_be.copy_ncl(mixed + sty, C2, sty, a.s, sty, sty, B, 1, sty, c.stream));
-    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations);
+    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
     return c.rc;
   }
   const float* cur = sp;
@@ -202,6 +211,6 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a) {
     RUN(c, g_be.copy_ncl(ref_src, C2, sty, a.s_pred_out, C2, sty, B, 1, sty, c.stream));
     RUN(c, g_be.copy_ncl(s_src, C2, sty, a.s_pred_out + sty, C2, sty, B, 1, sty, c.stream));
   }
-  duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations);
+  duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
   return c.rc;
 }

@@ -328,12 +328,14 @@ class Engine:
 
     # -- the whole front (tokens -> t_en, d, s, ref, durations) ---------------------------------------------------------------
     def front_forward(self, tokens, noise, step_noise, table, sigma0, *, lengths=None, ref_s=None, s_prev=None,
-                      embedding_scale=1.0, alpha=0.3, beta=0.7, t=0.7, predict=True, tail=0, carry=False):
+                      embedding_scale=1.0, alpha=0.3, beta=0.7, t=0.7, predict=True, tail=0, carry=False, controls=None):
         """One `st2_front_forward` call (== pipeline._front_core): tokens int64 [B, N], noise [B, 1, 256] or [B, 256],
         step_noise [steps-1, B, 1, 256]; (table, sigma0) = DiffusionSampler.step_table(steps).  Returns a dict with t_en
         [B, dim_in, N], d_cm [B, d_hid + sty, N], s, ref [B, sty], s_pred [B, 2 sty] (ref | s) and durations int64 [B, N]
         (None unless `predict`).  `carry`: the rows are consecutive sentences of one passage, row k's style is mixed with row
-        k-1's mixed style (`s_prev` [1, 2 sty] or None feeds row 0): st2.h st2_front_args.carry."""
+        k-1's mixed style (`s_prev` [1, 2 sty] or None feeds row 0): st2.h st2_front_args.carry.  `controls` (a dict of fp32
+        [B] device rows under "speed" / "alpha" / "beta" / "t", any subset): `st2_front_forward_ctl` -- row b's own speaking rate
+        and mixing weights; the mixing is then one launch."""
         cfg = self.cfg
         B, N = tokens.shape
         dev = tokens.device
@@ -358,7 +360,25 @@ class Engine:
                            ref=ptr(out["ref"]), s_pred_out=ptr(out["s_pred"]), durations=ptr(out["durations"]), carry=int(bool(carry)))
         ws, ws_ptr, nbytes = self._workspace(dev, "st2_front_workspace_bytes", C.byref(a),
                                              what="a weight group is not finalized?")
-        _lib.check(self.lib.st2_front_forward(self.h, C.byref(a), ws_ptr, nbytes, _stream(dev)), "st2_front_forward")
+        if not controls:
+            _lib.check(self.lib.st2_front_forward(self.h, C.byref(a), ws_ptr, nbytes, _stream(dev)), "st2_front_forward")
+            return out
+        rows = {}
+        for name, row in controls.items():
+            if name not in ("speed", "alpha", "beta", "t"):
+                raise ValueError("unknown front control %r" % (name,))
+            if not torch.is_tensor(row) or row.dtype != torch.float32 or row.dim() != 1 or row.numel() != B \
+                    or not row.is_contiguous() or row.device != dev:
+                raise _lib.St2Error("control %s must be a contiguous float32 [%d] tensor on %s" % (name, B, dev))
+            rows[name] = row.data_ptr()
+        if "speed" in rows and not predict:
+            raise ValueError("speed with forced durations: there is nothing to scale")
+        ctl = _lib.ControlRows(**rows)
+        _lib.check(self.lib.st2_front_forward_ctl(self.h, C.byref(a), C.byref(ctl), ws_ptr, nbytes, _stream(dev)),
+                   "st2_front_forward_ctl")
+        if rows.keys() & {"alpha", "beta", "t"}:
+            from . import ops
+            ops.style_mix_launches += 1
         return out
 
     # -- duration stage (DurationEncoder + duration LSTM + head) -------------------------------------------------------

@@ -951,9 +951,26 @@ def copy_ncl(x, out):
     return out
 
 
-def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False):
+def _chk_row(t, name, n, like):
+    """A per-row control (include/st2.h "per-request controls"): fp32 [n], contiguous, on the device of `like`.  Checked before
+    anything else of the call, as `_chk_len` checks lengths.  Returns the device pointer (0 for None)."""
+    if t is None:
+        return 0
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _lib.St2Error("%s must be a float32 tensor (got %s)" % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise _lib.St2Error("%s must be a contiguous 1-D tensor of %d entries (got shape %s)" % (name, n, tuple(t.shape)))
+    if not t.is_cuda or not torch.is_tensor(like) or t.device != like.device:
+        raise _lib.St2Error("%s must live on the device of the tensor it describes (%s, got %s)" % (
+            name, like.device if torch.is_tensor(like) else None, t.device))
+    return t.data_ptr()
+
+
+def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False, speed=None):
     """`st2_duration_head`: x [B, K, N] channel-major, w [J, K], bias [J] -> int64 durations [B, N] (and the un-rounded
-    sigmoid sums when want_sums)."""
+    sigmoid sums when want_sums).  `speed` (fp32 [B] on the device, `st2_duration_head_rate`): row b's sums are divided by
+    speed[b] (clamped to [0.25, 4], NaN -> 1) before they are rounded; the sums handed back stay un-scaled."""
+    sp = _chk_row(speed, "speed", _nb(x), x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(w, "w", 2)
@@ -964,9 +981,62 @@ def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False):
     lp = _chk_len(lengths, "lengths", B, x)
     dur = torch.empty((B, N), device=x.device, dtype=torch.int64)
     sums = torch.empty((B, N), device=x.device, dtype=torch.float32) if want_sums else None
-    _lib.check(lib.st2_duration_head(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), bias.data_ptr(), B, K, J, N,
-                                     lp, int(tail), dur.data_ptr(), _ptr(sums), _stream()), "st2_duration_head")
+    entry, rate = ("st2_duration_head", ()) if speed is None else ("st2_duration_head_rate", (sp,))
+    _lib.check(getattr(lib, entry)(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), bias.data_ptr(), B, K, J, N,
+                                   lp, int(tail), *rate, dur.data_ptr(), _ptr(sums), _stream()), entry)
     return (dur, sums) if want_sums else dur
+
+
+style_mix_launches = 0  # `st2_style_mix_rows` launches issued through the wrapper and the front (tests count them)
+
+
+def style_mix_rows(s_pred, s_prev=None, ref_s=None, t=None, alpha=None, beta=None, t0=0.7, alpha0=0.3, beta0=0.7, carry=False):
+    """`st2_style_mix_rows`: the front's style mixing as one launch.  s_pred [B, 2 sty] (the sampler's output), s_prev [B, 2 sty]
+    (or [1, 2 sty] with `carry`), ref_s [B, 2 sty], per-row weights t / alpha / beta fp32 [B] on the device -- any of them
+    None; a missing weight row means the scalar t0 / alpha0 / beta0.  Returns (ref [B, sty], s [B, sty], s_pred [B, 2 sty] =
+    ref | s).  `carry`: the rows are consecutive sentences, row k mixes with row k-1's mixed result."""
+    B = _nb(s_pred, 2)
+    rows = [_chk_row(v, n, B, s_pred) for v, n in ((t, "t"), (alpha, "alpha"), (beta, "beta"))]
+    lib = _lib.load()
+    _chk(s_pred, "s_pred", 2)
+    C2 = s_pred.shape[1]
+    if C2 % 2 or not s_pred.is_contiguous():
+        raise _lib.St2Error("s_pred must be a contiguous [B, 2 * style_dim] tensor (got %s)" % (tuple(s_pred.shape),))
+    for v, name, nb in ((s_prev, "s_prev", 1 if carry else B), (ref_s, "ref_s", B)):
+        _chk(v, name, 2)
+        if v is not None and (tuple(v.shape) != (nb, C2) or not v.is_contiguous() or v.device != s_pred.device):
+            raise _lib.St2Error("%s must be a contiguous [%d, %d] tensor on %s (got %s on %s)" % (
+                name, nb, C2, s_pred.device, tuple(v.shape), v.device))
+    for v, name in ((t0, "t0"), (alpha0, "alpha0"), (beta0, "beta0")):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError("%s=%r must lie in [0, 1]" % (name, v))
+    new = lambda n: torch.empty((B, n), device=s_pred.device, dtype=torch.float32)
+    ref, s, out = new(C2 // 2), new(C2 // 2), new(C2)
+    global style_mix_launches
+    style_mix_launches += 1
+    _lib.check(lib.st2_style_mix_rows(s_pred.data_ptr(), _ptr(s_prev), _ptr(ref_s), *rows, float(t0), float(alpha0),
+                                      float(beta0), B, C2 // 2, 1 if carry else 0, ref.data_ptr(), s.data_ptr(),
+                                      out.data_ptr(), _stream()), "st2_style_mix_rows")
+    return ref, s, out
+
+
+def prosody_controls(f0, n, f0_scale=None, n_shift=None, frames=None):
+    """`st2_prosody_controls`, in place: f0[b, l] *= f0_scale[b] and n[b, l] += n_shift[b] for l < 2 * frames[b] (every l
+    without `frames`); f0, n [B, L] fp32 of equal strides, f0_scale / n_shift fp32 [B] on the device (clamped to [0.5, 2] /
+    [-2, 2] where they are read; None leaves that curve alone), frames int32 [B] on the device.  Nothing at or past a row's
+    end is read or written.  Returns (f0, n)."""
+    B = _nb(f0, 2)
+    fp = _chk_len(frames, "frames", B, f0)
+    sc, sh = _chk_row(f0_scale, "f0_scale", B, f0), _chk_row(n_shift, "n_shift", B, f0)
+    lib = _lib.load()
+    _chk(f0, "f0", 2)
+    _chk(n, "n", 2)
+    if n.shape != f0.shape or n.stride() != f0.stride() or n.device != f0.device:
+        raise _lib.St2Error("f0 and n must have one shape, one layout and one device (got %s / %s)" % (
+            tuple(f0.shape), tuple(n.shape)))
+    _lib.check(lib.st2_prosody_controls(f0.data_ptr(), n.data_ptr(), f0.stride(0), B, f0.shape[1], sc, sh, fp, _stream()),
+               "st2_prosody_controls")
+    return f0, n
 
 
 def expand_by_durations(x, dur, T, shift=False, out=None, lengths=None):

@@ -140,6 +140,117 @@ def predict_durations(model, d, lj_tail=False, input_lengths=None):
                              lengths=lens, tail=5 if lj_tail else 0)  # LJSpeech notebook only: pred_dur[-1] += 5
 
 
+class Controls:
+    """Per-request controls of a batch (include/st2.h "per-request controls"): one fp32 device tensor of
+    six rows of [B] -- speed, alpha, beta, t, f0_scale, n_shift -- read per row by the kernels, so that one batch and one
+    recorded graph serve any mix of requests.
+
+        speed     durations = max(1, rint(sum / speed[b]))         [0.25, 4]   absent = 1
+        alpha, beta, t   row b's own style mixing weights           [0, 1]      absent = the call's scalar
+        f0_scale  F0[b] *= f0_scale[b]                              [0.5, 2]    absent = 1
+        n_shift   N[b] += n_shift[b]  (a log-energy: a gain)        [-2, 2]     absent = 0
+
+    Every control is a float (the whole batch), a sequence or a tensor of B values, or left out: an absent control keeps the
+    behaviour without it.  Host values are validated here (ValueError when out of range or not finite).  A tensor already on
+    the device is not read: it is clamped to the same range by the kernel that reads it (NaN = absent)."""
+    NAMES = ("speed", "alpha", "beta", "t", "f0_scale", "n_shift")
+    RANGES = {"speed": (0.25, 4.0), "alpha": (0.0, 1.0), "beta": (0.0, 1.0), "t": (0.0, 1.0), "f0_scale": (0.5, 2.0),
+              "n_shift": (-2.0, 2.0)}
+    # what an absent row holds: the device clamp's neutral value (NaN = "the call's scalar" for the mixing weights)
+    ABSENT = {"speed": 1.0, "alpha": float("nan"), "beta": float("nan"), "t": float("nan"), "f0_scale": 1.0, "n_shift": 0.0}
+
+    def __init__(self, B, speed=None, alpha=None, beta=None, t=None, f0_scale=None, n_shift=None, device=None):
+        B = int(B)
+        if B <= 0:
+            raise ValueError("Controls: B must be positive, got %r" % (B,))
+        given = dict(speed=speed, alpha=alpha, beta=beta, t=t, f0_scale=f0_scale, n_shift=n_shift)
+        on_dev = [v for v in given.values() if torch.is_tensor(v) and v.is_cuda]
+        if device is None:
+            device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        host = torch.empty((len(self.NAMES), B), dtype=torch.float32)
+        late = []
+        for i, name in enumerate(self.NAMES):
+            v = given[name]
+            host[i] = self.ABSENT[name]
+            if v is None:
+                continue
+            if torch.is_tensor(v) and v.is_cuda:  # never read: clamped where the kernels read it
+                if v.numel() != B:
+                    raise ValueError("Controls: %s must hold %d values, got shape %s" % (name, B, tuple(v.shape)))
+                late.append((i, v))
+                continue
+            row = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+            if row.numel() == 1:
+                row = row.expand(B)
+            if row.numel() != B:
+                raise ValueError("Controls: %s must be one value or %d values, got %d" % (name, B, row.numel()))
+            lo, hi = self.RANGES[name]
+            if not bool((torch.isfinite(row) & (row >= lo) & (row <= hi)).all()):
+                raise ValueError("Controls: %s must lie in [%g, %g], got %s" % (name, lo, hi, row.tolist()))
+            host[i] = row.to(torch.float32)
+        self.B = B
+        self.present = tuple(n for n in self.NAMES if given[n] is not None)
+        self.buf = host.to(device)  # ONE host -> device copy
+        for i, v in late:
+            self.buf[i].copy_(v.detach().reshape(B).to(torch.float32))
+
+    @classmethod
+    def neutral(cls, B, alpha=None, beta=None, t=None, device=None):
+        """All six rows present and neutral: speed 1, f0_scale 1, n_shift 0 and the given mixing weights (None = the call's
+        scalars).  Equals the call without controls bit for bit."""
+        c = cls(B, speed=1.0, alpha=alpha, beta=beta, t=t, f0_scale=1.0, n_shift=0.0, device=device)
+        c.present = cls.NAMES
+        return c
+
+    @property
+    def device(self):
+        return self.buf.device
+
+    def row(self, name):
+        """The fp32 [B] device row of a control, None when it is absent."""
+        return self.buf[self.NAMES.index(name)] if name in self.present else None
+
+    def front_rows(self):
+        """The present rows `st2_front_forward_ctl` reads (speed and the mixing weights)."""
+        return {n: self.row(n) for n in ("speed", "alpha", "beta", "t") if n in self.present}
+
+    def slice(self, i, j):
+        """Rows i .. j-1 of the batch as a Controls over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Controls)
+        c.B, c.present, c.buf = j - i, self.present, self.buf[:, i:j]
+        return c
+
+
+def _check_controls(controls, dev, B, taps, front, durations):
+    """What `controls=` cannot be combined with: refused before anything is launched."""
+    if not isinstance(controls, Controls):
+        raise ValueError("controls must be a pipeline.Controls, got %s" % type(controls).__name__)
+    if front is not None:
+        raise ValueError("controls cannot be combined with front= (a GraphedFront bakes the settings into its graphs); use "
+                         "GraphedSynthesis, which reads them from a static buffer")
+    if _hooks.plan != "engine":
+        raise ValueError("controls need the C++ engine plans: the per-kernel Python plans (plan='python') have no twin of the "
+                         "control kernels")
+    if dev.type != "cuda" or taps is not None:
+        raise ValueError("controls need the C++ engine path (HIP device, no taps)")
+    if controls.B != B or controls.device != dev:
+        raise ValueError("controls describe %d rows on %s, the batch has %d on %s" % (controls.B, controls.device, B, dev))
+    if durations is not None and "speed" in controls.present:
+        raise ValueError("controls.speed with forced durations: there is nothing to scale")
+
+
+def _prosody_controls(controls, F0, N, frames=None, sel=None):
+    """Row b's pitch scale / energy shift applied in place to the prosody call's curves (one launch; none when both are absent)."""
+    if controls is None:
+        return
+    rows = [controls.row("f0_scale"), controls.row("n_shift")]
+    if rows[0] is None and rows[1] is None:
+        return
+    if sel is not None:
+        rows = [None if v is None else sel(v).contiguous() for v in rows]
+    ops.prosody_controls(F0, N, rows[0], rows[1], frames=frames)
+
+
 @torch.no_grad()
 def _front_engine(model, dev):
     """The st2_engine handle of the front (text encoder, PL-BERT + bert_encoder, style denoiser, prosody predictor), packed
@@ -158,7 +269,7 @@ def _front_engine(model, dev):
 
 
 def _front_core(model, sampler, tokens, lengths_host, lengths_dev, noise, step_noise, ref_s, s_prev, *, diffusion_steps,
-                embedding_scale, alpha, beta, t, predict, lj_tail, carry=False, taps=None):
+                embedding_scale, alpha, beta, t, predict, lj_tail, carry=False, taps=None, controls=None):
     """The device-only part of the front: text encoder, PL-BERT, style diffusion, style mixing, duration encoder and
     (when `predict`) the duration head.  No host read of device data, no host -> device copy, no random draw: every
     input is a device tensor (`lengths_dev` int32 [B] for a right-padded batch, else None and `lengths_host` decides on
@@ -166,7 +277,8 @@ def _front_core(model, sampler, tokens, lengths_host, lengths_dev, noise, step_n
 
     `carry`: the B rows are consecutive sentences of ONE passage; row k's sampled style is mixed with row k-1's mixed style
     (`s_prev` [1, 256] or None feeds row 0) -- LFinference's loop as a row scan between the batched sampler and the batched
-    duration stages (st2.h st2_front_args.carry)."""
+    duration stages (st2.h st2_front_args.carry).  `controls` (a `Controls`, engine path only): row b's own speaking rate and
+    mixing weights (`st2_front_forward_ctl`)."""
     dev = tokens.device
     B, N = tokens.shape
     if _engine_path(dev, taps):  # ONE C-ABI call: st2_front_forward (csrc/st2_engine.hip front_plan)
@@ -179,7 +291,8 @@ def _front_core(model, sampler, tokens, lengths_host, lengths_dev, noise, step_n
         table, sigma0 = smp.step_table(diffusion_steps)
         o = _front_engine(model, dev).front_forward(tokens, noise, step_noise, table, sigma0, lengths=lengths_dev, ref_s=ref_s,
                                                     s_prev=s_prev, embedding_scale=embedding_scale, alpha=alpha, beta=beta,
-                                                    t=t, predict=predict, tail=5 if lj_tail else 0, carry=carry)
+                                                    t=t, predict=predict, tail=5 if lj_tail else 0, carry=carry,
+                                                    controls=None if controls is None else controls.front_rows())
         return dict(t_en=o["t_en"], d=o["d_cm"].transpose(1, 2), s=o["s"], ref=o["ref"], durations=o["durations"],
                     s_mixed=o["s_pred"])  # [B, 2 sty] = (ref | s), written by the plan: no torch.cat on the product path
     if lengths_dev is not None:  # mask built on the device; the modules take the device copy (text.py _device_lengths)
@@ -336,7 +449,7 @@ class GraphedFront:
 def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
             ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, lj_tail=None, s_prev=None, t=0.7,
             taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False,
-            ragged_decode=False, max_frames=None):
+            ragged_decode=False, max_frames=None, controls=None):
     """Everything in front of the decoder: text encoder, PL-BERT, style diffusion, style mixing, duration and
     prosody prediction, alignment expansion.  Returns the decoder's inputs {asr, F0, N, ref} plus the mixed style
     vector `s_pred` [B, 256] (what LFinference hands to the next sentence) and the durations.
@@ -375,9 +488,16 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     at: a captured call serves other lengths at replay).  A row whose durations sum to more than `max_frames` is synthesised
     truncated to it and raises ST2_STATUS_FRAME_CAPACITY (a warning at the next `ops.check_status()`).  Forced `durations`
     take the same route (their rows are summed whole, pad tokens included, as on the other paths).  `allow_ragged` and
-    `ragged_decode` are implied whatever the caller passed; `total_frames` and `group_events` are refused."""
+    `ragged_decode` are implied whatever the caller passed; `total_frames` and `group_events` are refused.
+
+    `controls` (a `Controls`; C++ engine path, no taps, no `front=`): per-row speaking rate, style mixing weights, pitch scale
+    and energy shift.  Rate and weights are read by the front (`st2_front_forward_ctl`: the mixing is
+    then one launch), pitch and energy are applied to F0 / N right behind every prosody call (`ops.prosody_controls`).  Nothing
+    of it is read on the host; None takes the code paths without it."""
     dev = tokens.device
     B, N = tokens.shape
+    if controls is not None:
+        _check_controls(controls, dev, B, taps, front, durations)
     if max_frames is not None:
         if int(max_frames) <= 0:
             raise ValueError("max_frames must be a positive frame count, got %r" % (max_frames,))
@@ -410,7 +530,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         f = front(tokens, input_lengths, lengths_dev, noise, step_noise, ref_s, s_prev, **ckw)
     else:
         f = _front_core(model, sampler, tokens, input_lengths, lengths_dev, noise, step_noise, ref_s, s_prev, taps=taps,
-                        **ckw)
+                        controls=controls, **ckw)
     t_en, d, s, ref = f["t_en"], f["d"], f["s"], f["ref"]
     if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
         T_cap = int(max_frames)
@@ -424,6 +544,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         s_mixed = f.get("s_mixed")
         asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d.transpose(-1, -2).contiguous(), t_en, durations, s,
                                                                          T_cap, shift=hifigan, frames=frames)
+        _prosody_controls(controls, F0_pred, N_pred, frames=frames)
         return dict(ref=ref, s_pred=s_mixed if s_mixed is not None else torch.cat([ref, s], dim=-1), durations=durations,
                     asr=asr, F0=F0_pred, N=N_pred, frames=frames, max_frames=T_cap)
     if durations is None:
@@ -459,6 +580,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         if _engine_path(dev, taps):  # alignment expansion + F0Ntrain as ONE C-ABI call (st2_prosody_forward)
             asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T,
                                                                              shift=hifigan)
+            _prosody_controls(controls, F0_pred, N_pred, sel=sel)
             return dict(asr=asr, F0=F0_pred, N=N_pred, ref=sel(ref), en=None)
         en = expand_by_durations(sel(d_cm), dur, T, shift=hifigan)                    # [b, 640, T]
         asr = expand_by_durations(sel(t_en), dur, T, shift=hifigan)                   # [b, 512, T]
@@ -482,6 +604,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         frames = torch.tensor(frames_host, dtype=torch.int32).to(dev)  # once per batch, before the prosody call is issued
         asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d_cm, t_en, durations, s, T_max, shift=hifigan,
                                                                          frames=frames)
+        _prosody_controls(controls, F0_pred, N_pred, frames=frames)
         out.update(asr=asr, F0=F0_pred, N=N_pred, frames=frames, frames_host=frames_host)
         return out
     groups = {}
@@ -601,7 +724,11 @@ class GraphedSynthesis:
     which `__call__` fills from whatever the caller hands in (anything left out keeps its previous contents; the `static` dict
     gives direct access) before it replays.  The returned `SynthesisResult` refers to the graph's own output buffers: consume
     it (`to_host()`) before the next replay.  Recorded on the first call; recorded again when the front's or the decoder's
-    engine was rebuilt or re-calibrated (the operand scales are kernel arguments), by the rule `GraphedFront` follows."""
+    engine was rebuilt or re-calibrated (the operand scales are kernel arguments), by the rule `GraphedFront` follows.
+
+    Per-request controls are one more static buffer, `static["controls"]` (a `Controls` with all six rows):
+    the graph is recorded over it holding the neutral values, `__call__(controls=)` copies the caller's rows in and a call
+    without them resets it to neutral.  Other controls never re-record."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None):
@@ -622,12 +749,15 @@ class GraphedSynthesis:
                            step_noise=z(max(self.steps - 1, 0), B, 1, 256), sine_noise=z(B, 600 * self.max_frames, 9),
                            ref_s=None if ref_s is None else ref_s.detach().to(dev, torch.float32).reshape(-1, 256)
                            .expand(B, -1).contiguous())
+        self.static["controls"] = Controls.neutral(B, device=dev)  # NaN weights: the call's own scalars
+        self._neutral = self.static["controls"].buf.clone()
         self._g = None
 
     def _run(self):
         st = self.static
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
-                         sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"], **self.kw)
+                         sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
+                         controls=st["controls"], **self.kw)
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -649,8 +779,14 @@ class GraphedSynthesis:
         return dict(graph=graph, out=out, gen=_sampler_generation(self.sampler), engines=[(e, e.calib_gen) for e in engs])
 
     @torch.no_grad()
-    def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None):
+    def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None):
         st = self.static
+        if controls is not None:
+            if not isinstance(controls, Controls) or controls.B != st["controls"].B:
+                raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
+            st["controls"].buf.copy_(controls.buf, non_blocking=True)  # an absent row holds its neutral value
+        else:
+            st["controls"].buf.copy_(self._neutral, non_blocking=True)
         for name, val in (("tokens", tokens), ("lengths_dev", lengths), ("noise", noise), ("step_noise", step_noise),
                           ("sine_noise", sine_noise), ("ref_s", ref_s)):
             if val is not None:
@@ -673,7 +809,7 @@ class GraphedSynthesis:
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
-              ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None):
+              ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -713,6 +849,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     for iSTFTNet.  `result.to_host()` is the one place that waits.  `lengths_dev` (int32 [B] on the device): the token counts of
     a right-padded batch without any host copy (stream capture, `GraphedSynthesis`).  `decode_streams` and `total_frames` are
     refused with `max_frames`.
+
+    `controls` (a `Controls`): per-row speaking rate, style mixing weights, pitch scale and energy shift, see `prepare`.
     """
     if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
         raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
@@ -723,7 +861,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
-              front=front, ragged_decode=ragged_decode)
+              front=front, ragged_decode=ragged_decode, controls=controls)
     if max_frames is not None:
         kw.update(max_frames=max_frames, lengths_dev=lengths_dev)
     if front_stream is None:
@@ -781,7 +919,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
 def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, t=0.7, diffusion_steps=5,
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
-                    ragged_decode=False):
+                    ragged_decode=False, controls=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -821,8 +959,14 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `ragged_decode=True`: every front group's sentences take ONE ragged prosody call and ONE ragged decoder call on the
     caller's stream (`prepare(ragged_decode=True)`, DESIGN.md section 10) instead of one pair per distinct frame count;
     `decode_streams` is then moot.
+
+    `controls` (a `Controls` of one row per SENTENCE): per-sentence speaking rate, mixing weights (`t` of row k weighs sentence
+    k-1's style into sentence k), pitch scale and energy shift.  A front group's carry-over is then ONE launch
+    (`st2_style_mix_rows`) instead of five per sentence.
     """
     dev = sentences[0].device
+    if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
+        raise ValueError("controls must be a pipeline.Controls of one row per sentence (%d)" % len(sentences))
     multispeaker = ref_s is not None
     if trim is None:
         trim = 100 if multispeaker else 0
@@ -894,7 +1038,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                   embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta, lj_tail=False, s_prev=s_prev, t=t,
                   step_noise=q["step_noise"], durations=q["dur"], total_frames=q["frames"], lengths_dev=q["lens_dev"],
                   front=front, carry=len(ids) > 1, allow_ragged=True, group_events=use_streams and len(ids) > 1,
-                  ragged_decode=ragged_decode)
+                  ragged_decode=ragged_decode, controls=None if controls is None else controls.slice(ids[0], ids[-1] + 1))
         if use_streams:
             with torch.cuda.stream(side):
                 p = prepare(model, sampler, q["tokens"], **kw)
