@@ -106,6 +106,22 @@ def _chk_len(t, name, n, like):
     return t.data_ptr()
 
 
+def _chk_out(t, name, shape, like):
+    """A caller-provided output view: float32, exactly `shape`, unit stride along its last axis, on the device of `like`.
+    Checked before anything else of the call (as `_chk_len`), so a bad one never reaches a launch."""
+    if t is None:
+        return
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _lib.St2Error("%s must be a float32 tensor (got %s)" % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if not torch.is_tensor(like) or tuple(t.shape) != tuple(shape):
+        raise _lib.St2Error("%s must have shape %s (got %s)" % (name, tuple(shape), tuple(t.shape)))
+    if t.device != like.device:
+        raise _lib.St2Error("%s must live on the device of the tensors it is computed from (%s, got %s)" % (
+            name, like.device, t.device))
+    if t.dim() > 0 and t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise _lib.St2Error("%s must have unit stride along its last axis" % name)
+
+
 def _nb(t, ndim=3):
     """Rows of the batch a lengths tensor describes: the leading extent of `t`, or -1 (no lengths tensor fits) when `t` is not
     the `ndim`-D tensor the wrapper goes on to demand."""
@@ -755,7 +771,9 @@ def istft(sp, n_fft, hop, m_len=None, out=None):
 
 def attention(q, k, v, heads, scale, out=None, key_len=None):
     """q, k, v: [B, heads*D, N] views with identical strides -> [B, heads*D, N].  key_len (int32 [B] on the device):
-    keys m >= key_len[b] are padding and excluded from the softmax (`st2_attention_keylen`)."""
+    keys m >= key_len[b] (clamped to 1..N) are padding: excluded from the softmax and never read (`st2_attention_keylen`).
+    `out`: a float32 [B, heads*D, N] view on q's device (any batch / channel stride, e.g. a channel slice of a wider buffer)."""
+    _chk_out(out, "out", q.shape if torch.is_tensor(q) else (), q)
     lib = _lib.load()
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _chk(t, n, 3)

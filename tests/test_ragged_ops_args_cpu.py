@@ -56,3 +56,20 @@ def test_convt_interleave_lengths_go_together():
 def test_stats_finalize_len_div_must_divide_the_rows():
     with pytest.raises(St2Error, match="len_div"):
         ops.stats_finalize(torch.zeros(B * 4 * 3), B, 4, 1, 16, lengths=torch.zeros(B, dtype=torch.int32), len_div=5)
+
+
+BAD_OUT = [(lambda: torch.zeros(B, 128, 15), "shape"),                        # one column short
+           (lambda: torch.zeros(B, 64, 16), "shape"),                         # half the channels
+           (lambda: torch.zeros(B * 128 * 16), "shape"),                      # flat
+           (lambda: torch.zeros(B, 128, 16, dtype=torch.float64), "float32"),  # dtype
+           (lambda: torch.zeros(B, 128, 16, dtype=torch.float16), "float32"),
+           (lambda: torch.zeros(B, 128, 16, device="meta"), "device"),        # not where q, k, v live
+           (lambda: torch.zeros(B, 128, 32)[:, :, ::2], "unit stride"),       # strided along the tokens
+           (lambda: [0.0], "float32")]                                        # not a tensor
+
+
+@pytest.mark.parametrize("make,what", BAD_OUT, ids=["%s%d" % (w.replace(" ", "_"), i) for i, (_, w) in enumerate(BAD_OUT)])
+def test_attention_out_is_checked_before_any_launch(make, what):
+    q = torch.zeros(B, 128, 16)
+    with pytest.raises(St2Error, match=what):
+        ops.attention(q, q, q, 2, 0.125, out=make())
