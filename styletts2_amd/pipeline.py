@@ -348,6 +348,39 @@ def _engine_changed(eng, recorded, calib_gen):
     return eng is not recorded or eng.calib_gen != calib_gen
 
 
+def _record_graph(run, dev):
+    """`run` once eagerly, then captured on the current stream of `dev` -> (graph, what the captured run returned).  The eager
+    run is the warm-up (weight packing, kernel attributes, the status word, the allocator) and goes onto the auxiliary stream,
+    ordered behind the current one and joined again, so that the capture starts on a drained device."""
+    cur = torch.cuda.current_stream(dev)
+    side = ops.aux_stream(dev)
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        run()
+    cur.wait_stream(side)
+    torch.cuda.synchronize(dev)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = run()
+    return graph, out
+
+
+def _hand_off(tensors, dst, wait=None):
+    """`tensors` (None entries skipped) were allocated on one stream and will be read on the stream `dst`: `dst` is first ordered
+    behind `wait` (an event, or the producing stream; None = the caller has ordered it already), then every tensor is marked
+    as in use on `dst`, so that the caching allocator does not hand its memory out again while `dst` still reads it."""
+    if wait is not None:
+        (dst.wait_event if isinstance(wait, torch.cuda.Event) else dst.wait_stream)(wait)
+    for v in tensors:
+        if v is not None:
+            v.record_stream(dst)
+
+
+def _decoder_inputs(g):
+    """What a prepared batch, or one frame-count group of it, hands to the decoder (`frames`: the ragged forms only)."""
+    return g["asr"], g["F0"], g["N"], g["ref"], g.get("frames")
+
+
 class GraphedFront:
     """hipGraph replay of `_front_core` (BASELINE.json configs[4]: latency-bound sentence-by-sentence synthesis).  The
     front of one sentence is ~600 launches of 5-40 us kernels issued from Python (~6 ms of host time against ~4 ms of
@@ -428,16 +461,7 @@ class GraphedFront:
                                st["step_noise"], st["ref_s"], st["s_prev"], **kw)
 
         dev = tokens.device
-        cur = torch.cuda.current_stream(dev)
-        side = ops.aux_stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            run()  # eager warm-up on a side stream: weight packing, kernel attributes, allocator warm-up
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = run()
+        graph, out = _record_graph(run, dev)
         # the graph's kernels read the packed weights: keep the Python caches / the C++ engine handle they live in alive,
         # and compare identities at replay (a reload or .to() rebuilds them)
         eng = _front_engine(self.model, dev) if self._engine_mode() else None
@@ -532,6 +556,18 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         f = _front_core(model, sampler, tokens, input_lengths, lengths_dev, noise, step_noise, ref_s, s_prev, taps=taps,
                         controls=controls, **ckw)
     t_en, d, s, ref = f["t_en"], f["d"], f["s"], f["ref"]
+    out = dict(ref=ref, s_pred=f["s_mixed"] if f.get("s_mixed") is not None else torch.cat([ref, s], dim=-1))
+    whole = lambda v: v
+
+    def prosody(sel, dur, T, frames):
+        """Alignment expansion + F0Ntrain of the rows `sel` picks as ONE C-ABI call (st2_prosody_forward; with `frames` its
+        ragged form, every row as if alone), then the rows' pitch / energy controls.  `d_cm` is the branch's: each makes the
+        channel-major copy where it always did.  hifigan: one-frame right shift, Demo/Inference_LibriTTS.ipynb:306-319."""
+        asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T, shift=hifigan,
+                                                                         frames=frames)
+        _prosody_controls(controls, F0_pred, N_pred, frames=frames, sel=sel)
+        return dict(asr=asr, F0=F0_pred, N=N_pred)
+
     if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
         T_cap = int(max_frames)
         if durations is None:
@@ -541,12 +577,8 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
             durations, len_arg = durations.long().to(dev), None  # the caller's: pad-token frames count like any other
         durations = durations.contiguous()
         frames = ops.frames_from_durations(durations, len_arg, T_cap)
-        s_mixed = f.get("s_mixed")
-        asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d.transpose(-1, -2).contiguous(), t_en, durations, s,
-                                                                         T_cap, shift=hifigan, frames=frames)
-        _prosody_controls(controls, F0_pred, N_pred, frames=frames)
-        return dict(ref=ref, s_pred=s_mixed if s_mixed is not None else torch.cat([ref, s], dim=-1), durations=durations,
-                    asr=asr, F0=F0_pred, N=N_pred, frames=frames, max_frames=T_cap)
+        d_cm = d.transpose(-1, -2).contiguous()
+        return dict(out, durations=durations, **prosody(whole, durations, T_cap, frames), frames=frames, max_frames=T_cap)
     if durations is None:
         durations = f["durations"]
         tot = durations.sum(dim=1).tolist()  # the path's one data-dependent host sync: the frame counts
@@ -562,26 +594,21 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     durations = durations.to(dev)
     if taps is not None:
         taps["durations"] = durations
-    s_mixed = f.get("s_mixed")
-    out = dict(ref=ref, s_pred=s_mixed if s_mixed is not None else torch.cat([ref, s], dim=-1), durations=durations)
+    out["durations"] = durations
     d_cm = d.transpose(-1, -2).contiguous()
 
     def expand(idx):
         """Alignment expansion + prosody for the utterances `idx` (all of one frame count T)."""
         T = int(tot[idx[0]])
         if len(idx) == B:
-            sel = lambda v: v
+            sel = whole
         elif idx == list(range(idx[0], idx[0] + len(idx))):  # consecutive utterances: a view, no index tensor (whose pageable
             sel = lambda v: v[idx[0]:idx[0] + len(idx)]      # host -> device copy would stall the host behind the stream)
         else:
             sel = lambda v: v[torch.as_tensor(idx, device=dev)]
         dur = sel(durations)
-        # hifigan: one-frame right shift, Demo/Inference_LibriTTS.ipynb:306-319
-        if _engine_path(dev, taps):  # alignment expansion + F0Ntrain as ONE C-ABI call (st2_prosody_forward)
-            asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T,
-                                                                             shift=hifigan)
-            _prosody_controls(controls, F0_pred, N_pred, sel=sel)
-            return dict(asr=asr, F0=F0_pred, N=N_pred, ref=sel(ref), en=None)
+        if _engine_path(dev, taps):
+            return dict(prosody(sel, dur, T, None), ref=sel(ref), en=None)
         en = expand_by_durations(sel(d_cm), dur, T, shift=hifigan)                    # [b, 640, T]
         asr = expand_by_durations(sel(t_en), dur, T, shift=hifigan)                   # [b, 512, T]
         F0_pred, N_pred = model.predictor.F0Ntrain(en, sel(s))
@@ -602,10 +629,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         T_max = int(max(tot))
         frames_host = [int(v) for v in tot]
         frames = torch.tensor(frames_host, dtype=torch.int32).to(dev)  # once per batch, before the prosody call is issued
-        asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(d_cm, t_en, durations, s, T_max, shift=hifigan,
-                                                                         frames=frames)
-        _prosody_controls(controls, F0_pred, N_pred, frames=frames)
-        out.update(asr=asr, F0=F0_pred, N=N_pred, frames=frames, frames_host=frames_host)
+        out.update(prosody(whole, durations, T_max, frames), frames=frames, frames_host=frames_host)
         return out
     groups = {}
     for b, T in enumerate(tot):
@@ -624,20 +648,30 @@ def _decode_ragged(model, p, sine_noise=None, noise_rows=None):
     """One ragged decoder call over prepare(ragged_decode=True)'s padded batch -> list of [1, 600 T_b] waveforms.
     `sine_noise`: per-utterance SineGen draws (each >= 600 T_b samples), zero-padded here to the batch's T_max."""
     tot = p["frames_host"]
-    T_max = p["asr"].shape[-1]
+    w = _decode_frames(model, p, sine_noise, noise_rows)
+    return [w[b, :, :600 * tot[b]] for b in range(len(tot))]
+
+
+def _decode_frames(model, p, sine_noise, noise_rows=None, strict=False):
+    """The ONE ragged decoder call of a prepared batch that carries `frames`, at the batch's width T (its longest row, or the
+    capacity).  The SineGen draws reach it as a [B, 600 T, 9] view of the caller's batch tensor where that is [B, >= 600 T, 9];
+    anything else is copied row by row (`noise_rows`, or sine_noise[b]) -- or, with `strict`, refused."""
+    B, T = p["asr"].shape[0], p["asr"].shape[-1]
     sn = None
     if sine_noise is not None and noise_rows is None and torch.is_tensor(sine_noise) and sine_noise.dim() == 3 \
-            and sine_noise.shape[0] == len(tot) and sine_noise.shape[1] >= 600 * T_max:
-        sn = sine_noise[:, :600 * T_max]  # the batch's own rows: a view (the decoder reads each only up to 600 T_b)
+            and sine_noise.shape[0] == B and sine_noise.shape[1] >= 600 * T:
+        sn = sine_noise[:, :600 * T]  # the batch's own rows: a view (the decoder reads row b only up to 600 frames[b])
+    elif sine_noise is not None and strict:
+        raise ValueError("sine_noise must be [B, >= 600 * max_frames, 9] on the capacity-bound path")
     elif sine_noise is not None:
-        rows = [sine_noise[b] for b in range(len(tot))] if noise_rows is None else noise_rows
+        tot = p["frames_host"]
+        rows = [sine_noise[b] for b in range(B)] if noise_rows is None else noise_rows
         # rows of different lengths (one per sentence): stacked into the T_max layout; past 600 T_b nothing is read, so
         # the buffer is not cleared
-        sn = torch.empty((len(tot), 600 * T_max, rows[0].shape[-1]), device=p["asr"].device, dtype=torch.float32)
+        sn = torch.empty((B, 600 * T, rows[0].shape[-1]), device=p["asr"].device, dtype=torch.float32)
         for b, n in enumerate(rows):
             sn[b, :600 * tot[b]] = n[:600 * tot[b]]
-    w = model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sn, frames=p["frames"])
-    return [w[b, :, :600 * tot[b]] for b in range(len(tot))]
+    return model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sn, frames=p["frames"])
 
 
 class SynthesisResult:
@@ -698,14 +732,8 @@ def _pack_into_one(wave, frames, trim, fmt, samples_per_frame):
 def _decode_capacity(model, p, sine_noise, pack, trim):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
     back, nothing is sliced on the host."""
-    T_cap, B = p["max_frames"], p["asr"].shape[0]
-    sn = None
-    if sine_noise is not None:
-        if not torch.is_tensor(sine_noise) or sine_noise.dim() != 3 or sine_noise.shape[0] != B \
-                or sine_noise.shape[1] < 600 * T_cap:
-            raise ValueError("sine_noise must be [B, >= 600 * max_frames, 9] on the capacity-bound path")
-        sn = sine_noise[:, :600 * T_cap]  # a view: the decoder reads row b only up to 600 frames[b]
-    w = model.decoder(p["asr"], p["F0"], p["N"], p["ref"], noise=sn, frames=p["frames"])
+    T_cap = p["max_frames"]
+    w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     if trim is None:
         trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
     if pack is None:
@@ -764,17 +792,7 @@ class GraphedSynthesis:
         return [engs["front"], engs["decoder"]]
 
     def _record(self):
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        side = ops.aux_stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            self._run()  # eager warm-up outside the capture: weight packing, kernel attributes, the status word, the allocator
-        cur.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self._run()
+        graph, out = _record_graph(self._run, self.device)
         engs = self._engines()
         return dict(graph=graph, out=out, gen=_sampler_generation(self.sampler), engines=[(e, e.calib_gen) for e in engs])
 
@@ -803,6 +821,42 @@ class GraphedSynthesis:
             g = self._g = self._record()
         g["graph"].replay()
         return g["out"]
+
+
+def _decode_groups(model, groups, dec, main, noise_of, ready=None, first=0):
+    """One decoder call per frame-count group `(idx, g)` of a prepared batch, in the groups' order -> (idx, wave [len(idx), 1,
+    600 T], event or None) per group.  `dec`: the auxiliary decoder streams (empty: every call runs on the current stream);
+    `main`: the caller's stream when streams are in play at all, else None (nothing is handed over); `noise_of(idx, g)`: the
+    group's SineGen draws.
+
+    * Group n of the CALL SEQUENCE goes to dec[n % len(dec)]: `first` is the number of groups decoded before these, so that the
+      round-robin runs on across the front calls of a passage.
+    * The decoder's stream waits for the group's own `ready` event where `prepare(group_events=True)` recorded one, else for
+      `ready` (the front call's); with neither the caller has ordered the streams already (`inference`: they wait for `main`).
+    * The noise rows are stacked on the stream that reads them, i.e. inside the stream block: stacked on the caller's stream
+      they raced the decoder (r05r).
+    * A wave made on a decoder stream is marked as in use on `main`, which takes it over behind the returned event.
+    * With decoder streams NOTHING is yielded before every decoder of `groups` has been queued, so the caller's stream takes its
+      per-group waits only after that.  A wait packet sits at the head of the caller's hardware queue until its decoder is
+      done, and HIP multiplexes streams onto ~4 such queues: an auxiliary stream that shares the caller's queue had its NEXT
+      decoder queued behind that wait -- the decoders serialised, and a passage took 74-114 ms instead of 52 depending on
+      which streams the process happened to get (rounds 5-6: "stream roulette").  Queued last, the waits block nothing.
+      Without decoder streams every group is yielded as soon as it is queued: a consumer (`on_chunk`) sees it at once."""
+    queued = []
+    for n, (idx, g) in enumerate(groups, first):
+        ds = dec[n % len(dec)] if dec else main
+        if main is not None:
+            _hand_off(_decoder_inputs(g), ds, g.get("ready", ready))
+        if not dec:
+            yield idx, model.decoder(g["asr"], g["F0"], g["N"], g["ref"], noise=noise_of(idx, g)), None
+            continue
+        with torch.cuda.stream(ds):
+            w = model.decoder(g["asr"], g["F0"], g["N"], g["ref"], noise=noise_of(idx, g))
+            ev = torch.cuda.Event()
+            ev.record(ds)
+        w.record_stream(main)
+        queued.append((idx, w, ev))
+    yield from queued
 
 
 @torch.no_grad()
@@ -874,10 +928,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
             p = prepare(model, sampler, tokens, **kw)
             ready = torch.cuda.Event()
             ready.record(front_stream)
-        main.wait_event(ready)
-        for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]):
-            for v in (g["asr"], g["F0"], g["N"], g["ref"]) + ((g["frames"],) if "frames" in g else ()):
-                v.record_stream(main)  # allocated on the front stream, consumed on the main stream
+        _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
+                  main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
         return _decode_capacity(model, p, sine_noise, pack, trim)
     if "frames" in p:
@@ -889,30 +941,37 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     main = torch.cuda.current_stream(tokens.device) if dec else None
     for st in dec:
         st.wait_stream(main)  # the front's outputs (and the caller's inputs) are ordered on the current stream
-    done = []
-    for n_dec, (idx, g) in enumerate(p["groups"]):
-        def run(idx=idx, g=g):
-            sn = None if sine_noise is None else [sine_noise[b] for b in idx]
-            if sn is not None:
-                sn = torch.stack([n[:g["F0"].shape[1] * 300] for n in sn])
-            return model.decoder(g["asr"], g["F0"], g["N"], g["ref"], noise=sn)
-        if dec:
-            ds = dec[n_dec % len(dec)]
-            for v in (g["asr"], g["F0"], g["N"], g["ref"]):
-                v.record_stream(ds)  # allocated on the current / front stream, consumed on the decoder's
-            with torch.cuda.stream(ds):
-                w = run()
-                ev = torch.cuda.Event()
-                ev.record(ds)
-            w.record_stream(main)
-            done.append(ev)
-        else:
-            w = run()
+    # every utterance's own draws, cut to the group's 600 T samples
+    noise_of = lambda idx, g: None if sine_noise is None else torch.stack([sine_noise[b][:g["F0"].shape[1] * 300] for b in idx])
+    for idx, w, ev in _decode_groups(model, p["groups"], dec, main, noise_of):
         for j, b in enumerate(idx):
             waves[b] = w[j]
-    for ev in done:
-        main.wait_event(ev)
+        if ev is not None:
+            main.wait_event(ev)
     return waves
+
+
+def _front_chunks(front_batch, K):
+    """`synthesize_long(front_batch=)` -> [(first sentence, one past the last)] per front call of a passage of K sentences: the
+    chunk sizes in turn, the last one repeating; 0 / None = everything that is left."""
+    sizes = list(front_batch) if isinstance(front_batch, (list, tuple)) else [front_batch]
+    starts, i = [], 0
+    while i < K:
+        n = sizes[min(len(starts), len(sizes) - 1)]
+        n = K - i if not n else max(1, min(int(n), K - i))
+        starts.append((i, i + n))
+        i += n
+    return starts
+
+
+def _decode_stream_list(decode_streams, use_streams, make):
+    """`synthesize_long(decode_streams=)` -> the auxiliary decoder streams: a sequence of two or more streams as given, a count
+    above 1 as that many of `make(0)`, `make(1)`, ...; none without `use_streams` or where one stream (the caller's) decodes."""
+    if use_streams and isinstance(decode_streams, (list, tuple)):
+        return list(decode_streams) if len(decode_streams) > 1 else []
+    if use_streams and decode_streams and int(decode_streams) > 1:
+        return [make(i) for i in range(int(decode_streams))]
+    return []
 
 
 @torch.no_grad()
@@ -975,17 +1034,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     side = (side_stream if side_stream is not None else ops.aux_stream(dev)) if use_streams else None  # (a caller may
     #                                                  hand in a CU-masked side stream: pipeline.MaskedStreams)
     K = len(sentences)
-    sizes = list(front_batch) if isinstance(front_batch, (list, tuple)) else [front_batch]
-    starts, i = [], 0
-    while i < K:  # chunk sizes in turn, the last one repeating; 0 / None = everything that is left
-        n = sizes[min(len(starts), len(sizes) - 1)]
-        n = K - i if not n else max(1, min(int(n), K - i))
-        starts.append((i, i + n))
-        i += n
     # per-call inputs are prepared (padded, stacked, moved to the device) BEFORE the streaming loop: a pageable
     # host -> device copy inside it would block the host until the issuing stream has drained
     prepped = []
-    for i, i_end in starts:
+    for i, i_end in _front_chunks(front_batch, K):
         ids = list(range(i, i_end))
         ns = [sentences[k].numel() for k in ids]
         npad = max(ns)
@@ -1009,19 +1061,13 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                             lens_dev=None if lengths is None else lengths.to(torch.int32).to(dev),
                             noise=cat(noises, 0), step_noise=cat(step_noises, 1),
                             ref_s=None if ref_s is None else ref_s.reshape(1, -1).expand(len(ids), -1).contiguous()))
-    dec = []
-    if use_streams and isinstance(decode_streams, (list, tuple)):
-        dec = list(decode_streams) if len(decode_streams) > 1 else []
-    elif use_streams and decode_streams and int(decode_streams) > 1:
-        dec = [ops.aux_stream(dev, 0, index=i + 1) for i in range(int(decode_streams))]
+    dec = _decode_stream_list(decode_streams, use_streams, lambda i: ops.aux_stream(dev, 0, index=i + 1))
     if use_streams:
         # weights and inputs produced on the caller's stream -- including the rows stacked just above -- are visible to the other streams
         for st in [side] + dec:
             st.wait_stream(main)
-        for q in prepped:
-            for v in q.values():
-                if torch.is_tensor(v) and v.is_cuda:
-                    v.record_stream(side)  # allocated on the caller's stream, read on the side stream
+        for q in prepped:  # allocated on the caller's stream, read on the side stream
+            _hand_off([v for v in q.values() if torch.is_tensor(v) and v.is_cuda], side)
     s_prev, waves, emitted, n_dec, done = None, [None] * K, 0, 0, {}
 
     def emit(emitted):
@@ -1045,53 +1091,26 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                 ready = torch.cuda.Event()
                 ready.record(side)
         else:
-            p = prepare(model, sampler, q["tokens"], **kw)
+            p, ready = prepare(model, sampler, q["tokens"], **kw), None
         s_prev = p["s_pred"][-1:]
         if "frames" in p:  # one ragged decoder call for the whole front group, on the caller's stream
             if use_streams:
-                main.wait_event(ready)
-                for v in (p["asr"], p["F0"], p["N"], p["ref"], p["frames"]):
-                    v.record_stream(main)  # allocated on the side stream, consumed on the caller's
+                _hand_off(_decoder_inputs(p), main, ready)  # allocated on the side stream, consumed on the caller's
             rows = None if sine_noises is None else [sine_noises[k].reshape(-1, sine_noises[k].shape[-1]) for k in ids]
-            ws = _decode_ragged(model, p, sine_noise=rows, noise_rows=rows)
-            for j, w in enumerate(ws):
-                wave = w.reshape(-1)
-                waves[ids[j]] = wave[:-trim] if trim else wave
-                done[ids[j]] = None
-            emitted = emit(emitted)
-            continue
-        groups = p["groups"] if "groups" in p else [(list(range(len(ids))), p)]
-        for idx, g in groups:  # one decoder call per distinct frame count, in the order of each group's first sentence
-            ds = dec[n_dec % len(dec)] if dec else main
-            n_dec += 1
-            if use_streams:
-                ds.wait_event(g.get("ready", ready))
-                for v in (g["asr"], g["F0"], g["N"], g["ref"]):
-                    v.record_stream(ds)  # allocated on the side stream, consumed on the decoder's stream
-            stack = lambda: None if sine_noises is None else torch.cat([sine_noises[ids[j]] for j in idx], dim=0)
-            if dec:
-                with torch.cuda.stream(ds):  # (the noise rows are stacked on the stream that reads them)
-                    w = model.decoder(g["asr"], g["F0"], g["N"], g["ref"], noise=stack())
-                    ev = torch.cuda.Event()
-                    ev.record(ds)
-                w.record_stream(main)  # handed to the caller's stream behind `ev`
-            else:
-                w, ev = model.decoder(g["asr"], g["F0"], g["N"], g["ref"], noise=stack()), None
+            decoded = [(list(range(len(ids))), _decode_ragged(model, p, sine_noise=rows, noise_rows=rows), None)]
+        else:  # one decoder call per distinct frame count, in the order of each group's first sentence
+            groups = p["groups"] if "groups" in p else [(list(range(len(ids))), p)]
+            noise_of = lambda idx, g: None if sine_noises is None else torch.cat([sine_noises[ids[j]] for j in idx], dim=0)
+            decoded = _decode_groups(model, groups, dec, main, noise_of, ready=ready, first=n_dec)
+            n_dec += len(groups)
+        for idx, w, ev in decoded:
             for j, b in enumerate(idx):
                 wave = w[j].reshape(-1)
                 waves[ids[b]] = wave[:-trim] if trim else wave
                 done[ids[b]] = ev
-            if not dec:
-                emitted = emit(emitted)
-        # Decoders on auxiliary streams: the caller's stream takes its per-sentence waits only AFTER every decoder of this front
-        # group has been queued.  A wait packet sits at the head of the caller's hardware queue until its decoder is done, and HIP
-        # multiplexes streams onto ~4 such queues: an auxiliary stream that shares the caller's queue had its NEXT decoder queued
-        # behind that wait -- the decoders serialised, and a passage took 74-114 ms instead of 52 depending on which streams the
-        # process happened to get (rounds 5-6: "stream roulette").  Queued last, the waits block nothing.
-        if dec:
-            emitted = emit(emitted)
-    if use_streams and s_prev is not None:
-        s_prev.record_stream(main)  # allocated on the side stream, handed to the caller's
+            emitted = emit(emitted)  # (with decoder streams every decoder of the front group is queued by now: _decode_groups)
+    if use_streams:
+        _hand_off((s_prev,), main)  # allocated on the side stream, handed to the caller's
     return waves, s_prev
 
 
