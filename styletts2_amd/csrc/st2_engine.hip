@@ -27,61 +27,6 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------
 // backend table
 // ------------------------------------------------------------------------------------------------------------------
-struct Backend {
-  decltype(&st2_conv1d_f16s) conv1d_f16s;
-  decltype(&st2_conv1d_xs) conv1d_xs;
-  decltype(&st2_act_split) act_split;
-  decltype(&st2_stats_finalize) stats_finalize;
-  decltype(&st2_conv1d_direct) conv1d_direct;
-  decltype(&st2_phase_split) phase_split;
-  decltype(&st2_instnorm_stats) instnorm_stats;
-  decltype(&st2_colnorm_stats) colnorm_stats;
-  decltype(&st2_style_fc) style_fc;
-  decltype(&st2_convt_interleave_stats) convt_interleave_stats;
-  decltype(&st2_adain_leaky_pool) adain_leaky_pool;
-  decltype(&st2_har_source) har_source;
-  decltype(&st2_stft_mag_phase) stft_mag_phase;
-  decltype(&st2_istft) istft;
-  decltype(&st2_attention_keylen) attention_keylen;
-  decltype(&st2_add_chanvec) add_chanvec;
-  decltype(&st2_mean_tokens_len) mean_tokens_len;
-  decltype(&st2_axpbypcz) axpbypcz;
-  decltype(&st2_time_features) time_features;
-  decltype(&st2_tokens_to_channels) tokens_to_channels;
-  decltype(&st2_broadcast_cols) broadcast_cols;
-  decltype(&st2_copy_ncl) copy_ncl;
-  decltype(&st2_expand_by_durations) expand_by_durations;
-  // bidirectional LSTM recurrence with a scratch buffer: the HIP entry tries the cooperative kernel and falls back to
-  // the single-CU one when the device cannot hold its workgroups co-resident (same policy as ops.lstm_bidir)
-  int (*lstm_bidir)(const float*, int64_t, int32_t, const float*, const int32_t*, int32_t, int32_t, int32_t, float*, int64_t,
-                    int32_t, void*, int64_t, void*);
-  decltype(&st2_colnorm_apply) colnorm_apply;
-  decltype(&st2_duration_head) duration_head;
-  decltype(&st2_mask_tail) mask_tail;
-  decltype(&st2_embed_tokens) embed_tokens;
-  decltype(&st2_dwconv3x3s2) dwconv3x3s2;
-  decltype(&st2_avgpool2x2) avgpool2x2;
-  void* (*dev_alloc)(int64_t);
-  void (*dev_free)(void*);
-  int (*upload)(void*, const void*, int64_t);
-  // ABI v23: length-aware entry points of the ragged plans (slots after ST2_BACKEND_ENTRIES_V22)
-  decltype(&st2_act_split_len) act_split_len;
-  decltype(&st2_instnorm_stats_len) instnorm_stats_len;
-  decltype(&st2_stats_finalize_len) stats_finalize_len;
-  decltype(&st2_conv1d_direct_len) conv1d_direct_len;
-  decltype(&st2_adain_leaky_pool_len) adain_leaky_pool_len;
-  decltype(&st2_convt_interleave_stats_len) convt_interleave_stats_len;
-  decltype(&st2_har_source_len) har_source_len;
-  decltype(&st2_stft_mag_phase_len) stft_mag_phase_len;
-  decltype(&st2_istft_len) istft_len;
-  decltype(&st2_ragged_lengths) ragged_lengths;
-  decltype(&st2_expand_by_durations_len) expand_by_durations_len;
-  // length-aware entry points of the ragged style plan (slots after ST2_BACKEND_ENTRIES_RAGGED)
-  decltype(&st2_dwconv3x3s2_len) dwconv3x3s2_len;
-  decltype(&st2_avgpool2x2_len) avgpool2x2_len;
-  decltype(&st2_style_lengths) style_lengths;
-};
-
 void* hip_alloc(int64_t n) {
   void* p = nullptr;
   if (hipMalloc(&p, (size_t)n) != hipSuccess) {
@@ -95,6 +40,8 @@ int hip_upload(void* d, const void* s, int64_t n) {
   return hipMemcpy(d, s, (size_t)n, hipMemcpyHostToDevice) == hipSuccess ? 0 : 1;
 }
 
+// bidirectional LSTM recurrence with a scratch buffer: the HIP entry tries the cooperative kernel and falls back to
+// the single-CU one when the device cannot hold its workgroups co-resident (same policy as ops.lstm_bidir)
 int hip_lstm(const float* G, int64_t g_bs, int32_t g_cs, const float* whh_t, const int32_t* lengths, int32_t B, int32_t H,
              int32_t N, float* Y, int64_t y_bs, int32_t y_cs, void* scratch, int64_t scratch_bytes, void* stream) {
   // No sticky "refused" state: whether a cooperative launch fits depends on the device AND the batch (a refusal at B = 48
@@ -112,17 +59,78 @@ int hip_lstm(const float* G, int64_t g_bs, int32_t g_cs, const float* whh_t, con
   return st2_lstm_bidir(G, g_bs, g_cs, whh_t, lengths, B, H, N, Y, y_bs, y_cs, stream);
 }
 
-const Backend kHipBackend = {st2_conv1d_f16s, st2_conv1d_xs, st2_act_split, st2_stats_finalize, st2_conv1d_direct,
-                             st2_phase_split, st2_instnorm_stats, st2_colnorm_stats, st2_style_fc,
-                             st2_convt_interleave_stats, st2_adain_leaky_pool, st2_har_source, st2_stft_mag_phase,
-                             st2_istft, st2_attention_keylen, st2_add_chanvec, st2_mean_tokens_len, st2_axpbypcz,
-                             st2_time_features, st2_tokens_to_channels, st2_broadcast_cols, st2_copy_ncl,
-                             st2_expand_by_durations, hip_lstm, st2_colnorm_apply, st2_duration_head, st2_mask_tail,
-                             st2_embed_tokens, st2_dwconv3x3s2, st2_avgpool2x2, hip_alloc, hip_free, hip_upload,
-                             st2_act_split_len, st2_instnorm_stats_len, st2_stats_finalize_len, st2_conv1d_direct_len,
-                             st2_adain_leaky_pool_len, st2_convt_interleave_stats_len, st2_har_source_len,
-                             st2_stft_mag_phase_len, st2_istft_len, st2_ragged_lengths, st2_expand_by_durations_len,
-                             st2_dwconv3x3s2_len, st2_avgpool2x2_len, st2_style_lengths};
+// One line per slot, in the order of `enum st2_backend_slot` (st2.h): field, HIP entry point, slot constant.  The struct, the
+// HIP table and st2_debug_set_backend are generated from this list; a slot's type is that of its HIP entry (hip_lstm,
+// hip_alloc, hip_free and hip_upload above give the four slots that are no C-ABI entry point their types).
+#define ST2_BACKEND_SLOTS(X)                                                                   \
+  X(conv1d_f16s, st2_conv1d_f16s, ST2_BE_CONV1D_F16S)                                          \
+  X(conv1d_xs, st2_conv1d_xs, ST2_BE_CONV1D_XS)                                                \
+  X(act_split, st2_act_split, ST2_BE_ACT_SPLIT)                                                \
+  X(stats_finalize, st2_stats_finalize, ST2_BE_STATS_FINALIZE)                                 \
+  X(conv1d_direct, st2_conv1d_direct, ST2_BE_CONV1D_DIRECT)                                    \
+  X(phase_split, st2_phase_split, ST2_BE_PHASE_SPLIT)                                          \
+  X(instnorm_stats, st2_instnorm_stats, ST2_BE_INSTNORM_STATS)                                 \
+  X(colnorm_stats, st2_colnorm_stats, ST2_BE_COLNORM_STATS)                                    \
+  X(style_fc, st2_style_fc, ST2_BE_STYLE_FC)                                                   \
+  X(convt_interleave_stats, st2_convt_interleave_stats, ST2_BE_CONVT_INTERLEAVE_STATS)         \
+  X(adain_leaky_pool, st2_adain_leaky_pool, ST2_BE_ADAIN_LEAKY_POOL)                           \
+  X(har_source, st2_har_source, ST2_BE_HAR_SOURCE)                                             \
+  X(stft_mag_phase, st2_stft_mag_phase, ST2_BE_STFT_MAG_PHASE)                                 \
+  X(istft, st2_istft, ST2_BE_ISTFT)                                                            \
+  X(attention_keylen, st2_attention_keylen, ST2_BE_ATTENTION_KEYLEN)                           \
+  X(add_chanvec, st2_add_chanvec, ST2_BE_ADD_CHANVEC)                                          \
+  X(mean_tokens_len, st2_mean_tokens_len, ST2_BE_MEAN_TOKENS_LEN)                              \
+  X(axpbypcz, st2_axpbypcz, ST2_BE_AXPBYPCZ)                                                   \
+  X(time_features, st2_time_features, ST2_BE_TIME_FEATURES)                                    \
+  X(tokens_to_channels, st2_tokens_to_channels, ST2_BE_TOKENS_TO_CHANNELS)                     \
+  X(broadcast_cols, st2_broadcast_cols, ST2_BE_BROADCAST_COLS)                                 \
+  X(copy_ncl, st2_copy_ncl, ST2_BE_COPY_NCL)                                                   \
+  X(expand_by_durations, st2_expand_by_durations, ST2_BE_EXPAND_BY_DURATIONS)                  \
+  X(lstm_bidir, hip_lstm, ST2_BE_LSTM_BIDIR)                                                   \
+  X(colnorm_apply, st2_colnorm_apply, ST2_BE_COLNORM_APPLY)                                    \
+  X(duration_head, st2_duration_head, ST2_BE_DURATION_HEAD)                                    \
+  X(mask_tail, st2_mask_tail, ST2_BE_MASK_TAIL)                                                \
+  X(embed_tokens, st2_embed_tokens, ST2_BE_EMBED_TOKENS)                                       \
+  X(dwconv3x3s2, st2_dwconv3x3s2, ST2_BE_DWCONV3X3S2)                                          \
+  X(avgpool2x2, st2_avgpool2x2, ST2_BE_AVGPOOL2X2)                                             \
+  X(dev_alloc, hip_alloc, ST2_BE_DEV_ALLOC)                                                    \
+  X(dev_free, hip_free, ST2_BE_DEV_FREE)                                                       \
+  X(upload, hip_upload, ST2_BE_UPLOAD)                                                         \
+  /* ABI v23: length-aware entry points of the ragged plans (slots after ST2_BACKEND_ENTRIES_V22) */ \
+  X(act_split_len, st2_act_split_len, ST2_BE_ACT_SPLIT_LEN)                                    \
+  X(instnorm_stats_len, st2_instnorm_stats_len, ST2_BE_INSTNORM_STATS_LEN)                     \
+  X(stats_finalize_len, st2_stats_finalize_len, ST2_BE_STATS_FINALIZE_LEN)                     \
+  X(conv1d_direct_len, st2_conv1d_direct_len, ST2_BE_CONV1D_DIRECT_LEN)                        \
+  X(adain_leaky_pool_len, st2_adain_leaky_pool_len, ST2_BE_ADAIN_LEAKY_POOL_LEN)               \
+  X(convt_interleave_stats_len, st2_convt_interleave_stats_len, ST2_BE_CONVT_INTERLEAVE_STATS_LEN) \
+  X(har_source_len, st2_har_source_len, ST2_BE_HAR_SOURCE_LEN)                                 \
+  X(stft_mag_phase_len, st2_stft_mag_phase_len, ST2_BE_STFT_MAG_PHASE_LEN)                     \
+  X(istft_len, st2_istft_len, ST2_BE_ISTFT_LEN)                                                \
+  X(ragged_lengths, st2_ragged_lengths, ST2_BE_RAGGED_LENGTHS)                                 \
+  X(expand_by_durations_len, st2_expand_by_durations_len, ST2_BE_EXPAND_BY_DURATIONS_LEN)      \
+  /* length-aware entry points of the ragged style plan (slots after ST2_BACKEND_ENTRIES_RAGGED) */ \
+  X(dwconv3x3s2_len, st2_dwconv3x3s2_len, ST2_BE_DWCONV3X3S2_LEN)                              \
+  X(avgpool2x2_len, st2_avgpool2x2_len, ST2_BE_AVGPOOL2X2_LEN)                                 \
+  X(style_lengths, st2_style_lengths, ST2_BE_STYLE_LENGTHS)
+
+struct Backend {
+#define X(field, hip_fn, slot) decltype(&hip_fn) field;
+  ST2_BACKEND_SLOTS(X)
+#undef X
+};
+#define X(field, hip_fn, slot) hip_fn,
+const Backend kHipBackend = {ST2_BACKEND_SLOTS(X)};
+#undef X
+#define X(field, hip_fn, slot) slot,
+constexpr int kSlotOrder[] = {ST2_BACKEND_SLOTS(X)};
+#undef X
+constexpr bool slots_in_order() {
+  for (int i = 0; i < ST2_BACKEND_ENTRIES; ++i)
+    if (kSlotOrder[i] != i) return false;
+  return true;
+}
+static_assert(sizeof(kSlotOrder) / sizeof(kSlotOrder[0]) == ST2_BACKEND_ENTRIES && slots_in_order(),
+              "ST2_BACKEND_SLOTS must list every slot of enum st2_backend_slot, in its order");
 Backend g_be = kHipBackend;
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -177,6 +185,18 @@ struct Ctx {
   void* stream = nullptr;
   int rc = 0;
   bool dry = false;
+  static Ctx dry_run() {  // size query: the plan allocates and counts, nothing is launched
+    Ctx c;
+    c.dry = c.a.dry = true;
+    return c;
+  }
+  static Ctx live(void* workspace, int64_t bytes, void* stream) {
+    Ctx c;
+    c.stream = stream;
+    c.a.base = static_cast<char*>(workspace);
+    c.a.cap = bytes;
+    return c;
+  }
 };
 
 View new_ncl(Ctx& c, int B, int C, int L, bool padded = true) {
@@ -815,6 +835,81 @@ void instnorm_stats(Ctx& c, const View& x, float* stats) {
     RUN(c, g_be.instnorm_stats(x.p, x.bs, x.cs, x.B, x.C, x.L, 1e-5f, stats, c.stream));
 }
 
+// The other length-aware twins, the same way: the _len slot exactly when the view (or pointer) that carries the rows' lengths
+// has them, the plain slot -- all a 33-entry backend table provides -- otherwise.
+void act_split(Ctx& c, const View& x, const ConvOpt& o, float x_scale, void* xs, int cg, int Lp) {
+  if (x.len)
+    RUN(c, g_be.act_split_len(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
+                              o.gamma_plus_one, o.alpha, x_scale, xs, cg, Lp, XS_HALO, x.len, c.stream));
+  else
+    RUN(c, g_be.act_split(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
+                          o.gamma_plus_one, o.alpha, x_scale, xs, cg, Lp, XS_HALO, c.stream));
+}
+
+// x.len: the rows' ends are their zero padding; y.len (ragged rows only): exact zeros past it
+void conv1d_direct(Ctx& c, const View& x, const float* w, const float* bias, const View& y, int ks, int stride, int pad) {
+  if (x.len)
+    RUN(c, g_be.conv1d_direct_len(x.p, x.bs, x.cs, w, bias, y.p, y.bs, y.cs, x.B, x.C, y.C, x.L, y.L, ks, stride, pad, x.len,
+                                  y.len, c.stream));
+  else
+    RUN(c, g_be.conv1d_direct(x.p, x.bs, x.cs, w, bias, y.p, y.bs, y.cs, x.B, x.C, y.C, x.L, y.L, ks, stride, pad, c.stream));
+}
+
+// AdaIN + LeakyReLU + the depthwise x2 up-sampling pool: y [B][C][2 L]
+void adain_leaky_pool(Ctx& c, const View& x, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
+                      float slope, const float* w, const float* bias, const View& y) {
+  if (x.len)
+    RUN(c, g_be.adain_leaky_pool_len(x.p, x.bs, x.cs, stats, gamma, beta, gb_bs, slope, w, bias, y.p, y.bs, y.cs, x.B, x.C, x.L,
+                                     x.len, c.stream));
+  else
+    RUN(c, g_be.adain_leaky_pool(x.p, x.bs, x.cs, stats, gamma, beta, gb_bs, slope, w, bias, y.p, y.bs, y.cs, x.B, x.C, x.L,
+                                 c.stream));
+}
+
+// SineGen + the source's Linear at 24 kHz with the reference's constants; f_len: rows of U f_len[b] samples, exact zeros after
+void har_source(Ctx& c, const float* f0, int B, int Fr, int U, const float* noise, const float* lin_w, const float* lin_b,
+                float* scratch, float* out, const int32_t* f_len) {
+  if (f_len)
+    RUN(c, g_be.har_source_len(f0, B, Fr, U, 9, noise, lin_w, lin_b, 0.1f, 0.003f, 10.0f, 24000.0f, scratch, out, f_len, c.stream));
+  else
+    RUN(c, g_be.har_source(f0, B, Fr, U, 9, noise, lin_w, lin_b, 0.1f, 0.003f, 10.0f, 24000.0f, scratch, out, c.stream));
+}
+
+// length: reflect-padded at each row's end, exact zero frames after it
+void stft_mag_phase(Ctx& c, const float* x, int L, int n_fft, int hop, const View& har, const int32_t* length) {
+  if (length)
+    RUN(c, g_be.stft_mag_phase_len(x, har.B, L, n_fft, hop, har.p, har.bs, har.cs, length, c.stream));
+  else
+    RUN(c, g_be.stft_mag_phase(x, har.B, L, n_fft, hop, har.p, har.bs, har.cs, c.stream));
+}
+
+// ph.len / out.len: the ConvTranspose GEMM's columns and the stage's output length per row
+void convt_interleave_stats(Ctx& c, const View& ph, const float* bias, const View& add, const View& out, int stride, int pad,
+                            int L_raw, int reflect_left, float* part, int nt) {
+  if (ph.len)
+    RUN(c, g_be.convt_interleave_stats_len(ph.p, ph.bs, ph.cs, ph.L, bias, add.p, add.bs, add.cs, out.p, out.bs, out.cs, out.B,
+                                           out.C, stride, pad, L_raw, reflect_left, part, nt, ph.len, out.len, c.stream));
+  else
+    RUN(c, g_be.convt_interleave_stats(ph.p, ph.bs, ph.cs, ph.L, bias, add.p, add.bs, add.cs, out.p, out.bs, out.cs, out.B,
+                                       out.C, stride, pad, L_raw, reflect_left, part, nt, c.stream));
+}
+
+// sp.len: hop (M_b - 1) samples per row, exact zeros after them
+void istft(Ctx& c, const View& sp, int n_fft, int hop, float* wave, int64_t wave_bs) {
+  if (sp.len)
+    RUN(c, g_be.istft_len(sp.p, sp.bs, sp.cs, sp.B, sp.L, n_fft, hop, wave, wave_bs, sp.len, c.stream));
+  else
+    RUN(c, g_be.istft(sp.p, sp.bs, sp.cs, sp.B, sp.L, n_fft, hop, wave, wave_bs, c.stream));
+}
+
+// x [B][C][N] tokens -> y [B][C][T] frames; y.len: exact zeros past it
+void expand_by_durations(Ctx& c, const float* x, int N, const int64_t* dur, int shift, const View& y) {
+  if (y.len)
+    RUN(c, g_be.expand_by_durations_len(x, (int64_t)y.C * N, N, dur, y.B, y.C, N, y.L, shift, y.p, y.bs, y.cs, y.len, c.stream));
+  else
+    RUN(c, g_be.expand_by_durations(x, (int64_t)y.C * N, N, dur, y.B, y.C, N, y.L, shift, y.p, y.bs, y.cs, c.stream));
+}
+
 void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const View& y, const ConvOpt& o) {
   st2_conv_desc d;
   memset(&d, 0, sizeof(d));
@@ -844,12 +939,7 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
     const int cg = (x.C + 31) / 32 * 32 / 8;
     const int Lp = xs_row_slots(x.L);
     void* xs = c.a.alloc((int64_t)x.B * 2 * cg * Lp * 16);
-    if (x.len)
-      RUN(c, g_be.act_split_len(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
-                                o.gamma_plus_one, o.alpha, d.x_scale, xs, cg, Lp, XS_HALO, x.len, c.stream));
-    else
-      RUN(c, g_be.act_split(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
-                            o.gamma_plus_one, o.alpha, d.x_scale, xs, cg, Lp, XS_HALO, c.stream));
+    act_split(c, x, o, d.x_scale, xs, cg, Lp);
     d.xs = xs; d.xs_cg = cg; d.xs_lp = Lp; d.xs_halo = XS_HALO;
     float* part = nullptr;
     int nt = 0;
@@ -928,41 +1018,11 @@ extern "C" int st2_debug_set_backend(void* const* table, int32_t entries) {
               "st2_debug_set_backend: %d entries, expected %d (or %d: without the ragged style slots, or %d: the slots before "
               "ABI v23)", entries, (int)ST2_BACKEND_ENTRIES, (int)ST2_BACKEND_ENTRIES_RAGGED, (int)ST2_BACKEND_ENTRIES_V22);
   for (int i = 0; i < entries; ++i) ST2_REQUIRE(table[i] != nullptr, "st2_debug_set_backend: entry %d is null", i);
-#define SLOT(field, slot) g_be.field = reinterpret_cast<decltype(g_be.field)>(table[slot])
-  SLOT(conv1d_f16s, ST2_BE_CONV1D_F16S); SLOT(conv1d_xs, ST2_BE_CONV1D_XS); SLOT(act_split, ST2_BE_ACT_SPLIT);
-  SLOT(stats_finalize, ST2_BE_STATS_FINALIZE); SLOT(conv1d_direct, ST2_BE_CONV1D_DIRECT);
-  SLOT(phase_split, ST2_BE_PHASE_SPLIT); SLOT(instnorm_stats, ST2_BE_INSTNORM_STATS);
-  SLOT(colnorm_stats, ST2_BE_COLNORM_STATS); SLOT(style_fc, ST2_BE_STYLE_FC);
-  SLOT(convt_interleave_stats, ST2_BE_CONVT_INTERLEAVE_STATS); SLOT(adain_leaky_pool, ST2_BE_ADAIN_LEAKY_POOL);
-  SLOT(har_source, ST2_BE_HAR_SOURCE); SLOT(stft_mag_phase, ST2_BE_STFT_MAG_PHASE); SLOT(istft, ST2_BE_ISTFT);
-  SLOT(attention_keylen, ST2_BE_ATTENTION_KEYLEN); SLOT(add_chanvec, ST2_BE_ADD_CHANVEC);
-  SLOT(mean_tokens_len, ST2_BE_MEAN_TOKENS_LEN); SLOT(axpbypcz, ST2_BE_AXPBYPCZ);
-  SLOT(time_features, ST2_BE_TIME_FEATURES); SLOT(tokens_to_channels, ST2_BE_TOKENS_TO_CHANNELS);
-  SLOT(broadcast_cols, ST2_BE_BROADCAST_COLS); SLOT(copy_ncl, ST2_BE_COPY_NCL);
-  SLOT(expand_by_durations, ST2_BE_EXPAND_BY_DURATIONS); SLOT(lstm_bidir, ST2_BE_LSTM_BIDIR);
-  SLOT(colnorm_apply, ST2_BE_COLNORM_APPLY); SLOT(duration_head, ST2_BE_DURATION_HEAD); SLOT(mask_tail, ST2_BE_MASK_TAIL);
-  SLOT(embed_tokens, ST2_BE_EMBED_TOKENS); SLOT(dwconv3x3s2, ST2_BE_DWCONV3X3S2); SLOT(avgpool2x2, ST2_BE_AVGPOOL2X2);
-  SLOT(dev_alloc, ST2_BE_DEV_ALLOC); SLOT(dev_free, ST2_BE_DEV_FREE); SLOT(upload, ST2_BE_UPLOAD);
-  const Backend& h = kHipBackend;  // an ABI <= 22 table keeps the length-aware slots on their HIP kernels
-  g_be.act_split_len = h.act_split_len; g_be.instnorm_stats_len = h.instnorm_stats_len;
-  g_be.stats_finalize_len = h.stats_finalize_len; g_be.conv1d_direct_len = h.conv1d_direct_len;
-  g_be.adain_leaky_pool_len = h.adain_leaky_pool_len; g_be.convt_interleave_stats_len = h.convt_interleave_stats_len;
-  g_be.har_source_len = h.har_source_len; g_be.stft_mag_phase_len = h.stft_mag_phase_len; g_be.istft_len = h.istft_len;
-  g_be.ragged_lengths = h.ragged_lengths; g_be.expand_by_durations_len = h.expand_by_durations_len;
-  g_be.dwconv3x3s2_len = h.dwconv3x3s2_len; g_be.avgpool2x2_len = h.avgpool2x2_len; g_be.style_lengths = h.style_lengths;
-  if (entries >= ST2_BACKEND_ENTRIES_RAGGED) {
-    SLOT(act_split_len, ST2_BE_ACT_SPLIT_LEN); SLOT(instnorm_stats_len, ST2_BE_INSTNORM_STATS_LEN);
-    SLOT(stats_finalize_len, ST2_BE_STATS_FINALIZE_LEN); SLOT(conv1d_direct_len, ST2_BE_CONV1D_DIRECT_LEN);
-    SLOT(adain_leaky_pool_len, ST2_BE_ADAIN_LEAKY_POOL_LEN);
-    SLOT(convt_interleave_stats_len, ST2_BE_CONVT_INTERLEAVE_STATS_LEN); SLOT(har_source_len, ST2_BE_HAR_SOURCE_LEN);
-    SLOT(stft_mag_phase_len, ST2_BE_STFT_MAG_PHASE_LEN); SLOT(istft_len, ST2_BE_ISTFT_LEN);
-    SLOT(ragged_lengths, ST2_BE_RAGGED_LENGTHS); SLOT(expand_by_durations_len, ST2_BE_EXPAND_BY_DURATIONS_LEN);
-  }
-  if (entries == ST2_BACKEND_ENTRIES) {
-    SLOT(dwconv3x3s2_len, ST2_BE_DWCONV3X3S2_LEN); SLOT(avgpool2x2_len, ST2_BE_AVGPOOL2X2_LEN);
-    SLOT(style_lengths, ST2_BE_STYLE_LENGTHS);
-  }
-#undef SLOT
+  // entry `slot` < entries from the caller's table, the rest on (or back on) their HIP kernels
+#define X(field, hip_fn, slot) \
+  g_be.field = slot < entries ? reinterpret_cast<decltype(g_be.field)>(table[slot]) : kHipBackend.field;
+  ST2_BACKEND_SLOTS(X)
+#undef X
   return 0;
 }
 
@@ -1176,31 +1236,65 @@ extern "C" int st2_calibration_write(st2_engine* e, const float* scales, int32_t
   return 0;
 }
 
+namespace {
+// A workspace query: the plan on a dry Ctx; its peak, the alignment slack, and what the caller adds in front of it.
+template <class Plan>
+int64_t workspace_query(Plan plan, int64_t extra = 0) {
+  Ctx c = Ctx::dry_run();
+  plan(c);
+  return c.a.peak + 256 + extra;
+}
+
+// The common tail of a forward, after its argument checks: the plan on a live Ctx over the caller's workspace; `fn` and
+// `query` name the entry point and its workspace query in the messages.
+template <class Plan>
+int run_forward(const char* fn, const char* query, void* workspace, int64_t workspace_bytes, void* stream, Plan plan) {
+  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", fn);
+  Ctx c = Ctx::live(workspace, workspace_bytes, stream);
+  const int rc = plan(c);
+  ST2_REQUIRE(!c.a.overflow, "%s: workspace of %lld B is too small (need %lld B, see %s)", fn, (long long)workspace_bytes,
+              (long long)c.a.peak, query);
+  return rc;
+}
+
+// st2_decoder_forward (frames == NULL) and, after its own first two checks, st2_decoder_forward_ragged
+int decoder_forward(const char* fn, st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
+                    const float* sine_noise, const float* har_inject, const int32_t* frames, int32_t B, int32_t T, float* wave,
+                    void* workspace, int64_t workspace_bytes, const st2_decoder_taps* taps, void* stream) {
+  ST2_REQUIRE(e && e->dec.ready, "%s: decoder weights not finalized", fn);
+  ST2_REQUIRE(asr && f0 && n && s && wave && workspace && B > 0 && T > 0, "%s: bad arguments", fn);
+  ST2_REQUIRE(sine_noise || har_inject, "%s: sine_noise (or har_inject) is required", fn);
+  ST2_REQUIRE(!frames || !taps, "%s: taps are not supported (pass NULL)", fn);
+  return run_forward(fn, "st2_decoder_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return decoder_plan(c, *e, asr, f0, n, s, sine_noise, har_inject, B, T, wave, taps, frames);
+  });
+}
+
+// st2_prosody_forward (frames == NULL) and, after its own first two checks, st2_prosody_forward_ragged
+int prosody_forward(const char* fn, st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
+                    const float* s, const int32_t* frames, int32_t B, int32_t N, int32_t T, int32_t shift, float* asr,
+                    float* f0, float* n, void* workspace, int64_t workspace_bytes, void* stream) {
+  ST2_REQUIRE(e && e->pred.ready, "%s: predictor weights not finalized", fn);
+  ST2_REQUIRE(d_cm && t_en && durations && s && asr && f0 && n && workspace && B > 0 && N > 0 && T > 0, "%s: bad arguments", fn);
+  ST2_REQUIRE(N <= 512, "%s: N=%d tokens exceed the 512 of PL-BERT's position table", fn, N);
+  return run_forward(fn, "st2_prosody_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return prosody_plan(c, *e, d_cm, t_en, durations, s, B, N, T, shift, asr, f0, n, frames);
+  });
+}
+}  // namespace
+
 extern "C" int64_t st2_decoder_workspace_bytes(st2_engine* e, int32_t B, int32_t T) {
   if (!e || !e->dec.ready || B <= 0 || T <= 0) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  decoder_plan(c, *e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr);
   // + the per-row length table the ragged plan (st2_decoder_forward_ragged) puts in front of the same allocations
-  return c.a.peak + 256 + ragged_table_bytes(B, 16);
+  return workspace_query([&](Ctx& c) { decoder_plan(c, *e, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, nullptr, nullptr); },
+                         ragged_table_bytes(B, 16));
 }
 
 extern "C" int st2_decoder_forward(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
                                    const float* sine_noise, const float* har_inject, int32_t B, int32_t T, float* wave,
                                    void* workspace, int64_t workspace_bytes, const st2_decoder_taps* taps, void* stream) {
-  ST2_REQUIRE(e && e->dec.ready, "st2_decoder_forward: decoder weights not finalized");
-  ST2_REQUIRE(asr && f0 && n && s && wave && workspace && B > 0 && T > 0, "st2_decoder_forward: bad arguments");
-  ST2_REQUIRE(sine_noise || har_inject, "st2_decoder_forward: sine_noise (or har_inject) is required");
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_decoder_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = decoder_plan(c, *e, asr, f0, n, s, sine_noise, har_inject, B, T, wave, taps);
-  ST2_REQUIRE(!c.a.overflow, "st2_decoder_forward: workspace of %lld B is too small (need %lld B, see "
-              "st2_decoder_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return decoder_forward("st2_decoder_forward", e, asr, f0, n, s, sine_noise, har_inject, nullptr, B, T, wave, workspace,
+                         workspace_bytes, taps, stream);
 }
 
 extern "C" int st2_decoder_forward_ragged(st2_engine* e, const float* asr, const float* f0, const float* n, const float* s,
@@ -1209,53 +1303,26 @@ extern "C" int st2_decoder_forward_ragged(st2_engine* e, const float* asr, const
                                           const st2_decoder_taps* taps, void* stream) {
   ST2_REQUIRE(frames, "st2_decoder_forward_ragged: frames (int32 [B] on the device) is required");
   ST2_REQUIRE(B > 0 && T_max > 0, "st2_decoder_forward_ragged: bad geometry B=%d T_max=%d", B, T_max);
-  ST2_REQUIRE(e && e->dec.ready, "st2_decoder_forward_ragged: decoder weights not finalized");
-  ST2_REQUIRE(asr && f0 && n && s && wave && workspace, "st2_decoder_forward_ragged: bad arguments");
-  ST2_REQUIRE(sine_noise || har_inject, "st2_decoder_forward_ragged: sine_noise (or har_inject) is required");
-  ST2_REQUIRE(!taps, "st2_decoder_forward_ragged: taps are not supported (pass NULL)");
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-              "st2_decoder_forward_ragged: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = decoder_plan(c, *e, asr, f0, n, s, sine_noise, har_inject, B, T_max, wave, taps, frames);
-  ST2_REQUIRE(!c.a.overflow, "st2_decoder_forward_ragged: workspace of %lld B is too small (need %lld B, see "
-              "st2_decoder_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return decoder_forward("st2_decoder_forward_ragged", e, asr, f0, n, s, sine_noise, har_inject, frames, B, T_max, wave,
+                         workspace, workspace_bytes, taps, stream);
 }
 
 extern "C" int64_t st2_text_workspace_bytes(st2_engine* e, int32_t B, int32_t N) {
   if (!e || !e->text.ready || B <= 0 || N <= 0) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  text_plan(c, *e, nullptr, nullptr, B, N, nullptr);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) { text_plan(c, *e, nullptr, nullptr, B, N, nullptr); });
 }
 
 extern "C" int st2_text_forward(st2_engine* e, const int64_t* tokens, const int32_t* lengths, int32_t B, int32_t N,
                                 float* t_en, void* workspace, int64_t workspace_bytes, void* stream) {
   ST2_REQUIRE(e && e->text.ready, "st2_text_forward: text-encoder weights not finalized");
   ST2_REQUIRE(tokens && t_en && workspace && B > 0 && N > 0, "st2_text_forward: bad arguments");
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_text_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = text_plan(c, *e, tokens, lengths, B, N, t_en);
-  ST2_REQUIRE(!c.a.overflow, "st2_text_forward: workspace of %lld B is too small (need %lld B, see st2_text_workspace_bytes)",
-              (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return run_forward("st2_text_forward", "st2_text_workspace_bytes", workspace, workspace_bytes, stream,
+                     [&](Ctx& c) { return text_plan(c, *e, tokens, lengths, B, N, t_en); });
 }
 
 extern "C" int64_t st2_bert_workspace_bytes(st2_engine* e, int32_t B, int32_t N) {
   if (!e || !e->bert.ready || B <= 0 || N <= 0) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  bert_plan(c, *e, nullptr, nullptr, B, N);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) { bert_plan(c, *e, nullptr, nullptr, B, N); });
 }
 
 extern "C" int st2_bert_forward(st2_engine* e, const int64_t* tokens, const int32_t* lengths, int32_t B, int32_t N,
@@ -1263,26 +1330,17 @@ extern "C" int st2_bert_forward(st2_engine* e, const int64_t* tokens, const int3
   ST2_REQUIRE(e && e->bert.ready, "st2_bert_forward: PL-BERT weights not finalized");
   ST2_REQUIRE(tokens && hidden_cm && workspace && B > 0 && N > 0, "st2_bert_forward: bad arguments");
   ST2_REQUIRE(N <= e->bert.P, "st2_bert_forward: N=%d tokens exceed the %d rows of the position table", N, e->bert.P);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_bert_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  View X = bert_plan(c, *e, tokens, lengths, B, N);
-  View dst = wrap(hidden_cm, B, e->bert.H, N);
-  RUN(c, g_be.copy_ncl(X.p, X.bs, X.cs, dst.p, dst.bs, dst.cs, B, e->bert.H, N, c.stream));
-  ST2_REQUIRE(!c.a.overflow, "st2_bert_forward: workspace of %lld B is too small (need %lld B, see st2_bert_workspace_bytes)",
-              (long long)workspace_bytes, (long long)c.a.peak);
-  return c.rc;
+  return run_forward("st2_bert_forward", "st2_bert_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    View X = bert_plan(c, *e, tokens, lengths, B, N);
+    View dst = wrap(hidden_cm, B, e->bert.H, N);
+    RUN(c, g_be.copy_ncl(X.p, X.bs, X.cs, dst.p, dst.bs, dst.cs, B, e->bert.H, N, c.stream));
+    return c.rc;
+  });
 }
 
 extern "C" int64_t st2_style_workspace_bytes(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T) {
   if (!e || which < 0 || which > 1 || !e->style[which].ready || B <= 0 || n_mels != 80 || T < 80) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  style_plan(c, *e, e->style[which], nullptr, B, n_mels, T, nullptr);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) { style_plan(c, *e, e->style[which], nullptr, B, n_mels, T, nullptr); });
 }
 
 extern "C" int st2_style_forward(st2_engine* e, int32_t which, const float* mel, int32_t B, int32_t n_mels, int32_t T,
@@ -1291,25 +1349,17 @@ extern "C" int st2_style_forward(st2_engine* e, int32_t which, const float* mel,
   ST2_REQUIRE(mel && style && workspace && B > 0, "st2_style_forward: bad arguments");
   ST2_REQUIRE(n_mels == 80 && T >= 80, "st2_style_forward: needs an 80-bin mel of >= 80 frames (four halvings, then the 5x5 "
               "valid conv), got %d x %d", n_mels, T);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_style_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = style_plan(c, *e, e->style[which], mel, B, n_mels, T, style);
-  ST2_REQUIRE(!c.a.overflow, "st2_style_forward: workspace of %lld B is too small (need %lld B, see st2_style_workspace_bytes)",
-              (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return run_forward("st2_style_forward", "st2_style_workspace_bytes", workspace, workspace_bytes, stream,
+                     [&](Ctx& c) { return style_plan(c, *e, e->style[which], mel, B, n_mels, T, style); });
 }
 
 extern "C" int64_t st2_style_workspace_bytes_ragged(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T_cap) {
   if (!e || which < 0 || which > 1 || !e->style[which].ready || B <= 0 || n_mels != 80 || T_cap < 80) return -1;
   if ((int64_t)B * (n_mels + 2) - 2 > 65535) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  if (style_plan_ragged(c, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr) != 0) return -1;  // batch too large
-  return c.a.peak + 256;
+  int rc = 0;
+  const int64_t bytes = workspace_query(
+      [&](Ctx& c) { rc = style_plan_ragged(c, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr); });
+  return rc != 0 ? -1 : bytes;  // batch too large
 }
 
 extern "C" int st2_style_forward_ragged(st2_engine* e, int32_t which, const float* mel, const int32_t* mel_len, int32_t B,
@@ -1324,21 +1374,12 @@ extern "C" int st2_style_forward_ragged(st2_engine* e, int32_t which, const floa
   ST2_REQUIRE((int64_t)B * (n_mels + 2) - 2 <= 65535, "st2_style_forward_ragged: B=%d clips stack to more than 65535 conv rows", B);
   ST2_REQUIRE(e && which >= 0 && which <= 1 && e->style[which].ready, "st2_style_forward_ragged: style-encoder weights not finalized");
   ST2_REQUIRE(mel && style && workspace, "st2_style_forward_ragged: bad arguments");
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_style_forward_ragged: workspace must be 256-byte aligned");
-  {  // the plan once without launches: a batch one of its stacked launches cannot hold fails here, with nothing queued
-    Ctx dry;
-    dry.dry = true;
-    dry.a.dry = true;
+  return run_forward("st2_style_forward_ragged", "st2_style_workspace_bytes_ragged", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    // the plan once without launches: a batch one of its stacked launches cannot hold fails here, with nothing queued
+    Ctx dry = Ctx::dry_run();
     if (style_plan_ragged(dry, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr) != 0) return 1;
-  }
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = style_plan_ragged(c, *e, e->style[which], mel, mel_len, B, n_mels, T_cap, style);
-  ST2_REQUIRE(!c.a.overflow, "st2_style_forward_ragged: workspace of %lld B is too small (need %lld B, see "
-              "st2_style_workspace_bytes_ragged)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+    return style_plan_ragged(c, *e, e->style[which], mel, mel_len, B, n_mels, T_cap, style);
+  });
 }
 
 extern "C" int st2_sizeof_front_args(void) { return (int)sizeof(st2_front_args); }
@@ -1359,9 +1400,6 @@ const char* front_ready(const st2_engine* e) {
 
 extern "C" int64_t st2_front_workspace_bytes(st2_engine* e, const st2_front_args* a) {
   if (front_ready(e) || !a || a->B <= 0 || a->N <= 0 || a->steps < 2) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
   std::vector<double> table((size_t)(a->steps - 1) * ST2_SAMPLER_TABLE_COLS, 0.0);
   static const float dummy = 0.f;
   static int64_t dummy_dur;
@@ -1369,8 +1407,7 @@ extern "C" int64_t st2_front_workspace_bytes(st2_engine* e, const st2_front_args
   q.table = table.data();
   if (e->cfg.multispeaker) q.ref_s = &dummy;
   if (a->durations) q.durations = &dummy_dur;
-  front_plan(c, *e, q);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) { front_plan(c, *e, q); });
 }
 
 extern "C" int st2_front_forward(st2_engine* e, const st2_front_args* a, void* workspace, int64_t workspace_bytes,
@@ -1387,35 +1424,27 @@ extern "C" int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, con
   ST2_REQUIRE(!e->cfg.multispeaker || a->ref_s, "st2_front_forward: the multispeaker denoiser needs ref_s");
   ST2_REQUIRE(a->N <= e->bert.P && a->N <= e->cfg.dn_max_length && a->N <= 512,
               "st2_front_forward: N=%d tokens exceed the position / fixed-embedding tables", a->N);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_front_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  if (ctl && !(ctl->speed || ctl->alpha || ctl->beta || ctl->t)) ctl = nullptr;  // empty: st2_front_forward's launches
-  if (ctl) {
-    ST2_REQUIRE(!ctl->speed || a->durations, "st2_front_forward_ctl: speed with durations == NULL (forced durations): there is "
-                "nothing to scale");
-    const auto in01 = [](double w) { return w >= 0.0 && w <= 1.0; };
-    ST2_REQUIRE(in01(a->t) && in01(a->alpha) && in01(a->beta), "st2_front_forward_ctl: the scalar weights t=%g / alpha=%g / beta=%g "
-                "must lie in [0, 1]", a->t, a->alpha, a->beta);
-    ST2_REQUIRE(g_be.axpbypcz == kHipBackend.axpbypcz && g_be.duration_head == kHipBackend.duration_head,
-                "st2_front_forward_ctl: per-row controls have no slot in a debug backend (st2_debug_set_backend)");
-  }
-  const int rc = front_plan(c, *e, *a, ctl);
-  ST2_REQUIRE(!c.a.overflow, "st2_front_forward: workspace of %lld B is too small (need %lld B, see "
-              "st2_front_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return run_forward("st2_front_forward", "st2_front_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    if (ctl && !(ctl->speed || ctl->alpha || ctl->beta || ctl->t)) ctl = nullptr;  // empty: st2_front_forward's launches
+    if (ctl) {
+      ST2_REQUIRE(!ctl->speed || a->durations, "st2_front_forward_ctl: speed with durations == NULL (forced durations): there is "
+                  "nothing to scale");
+      const auto in01 = [](double w) { return w >= 0.0 && w <= 1.0; };
+      ST2_REQUIRE(in01(a->t) && in01(a->alpha) && in01(a->beta), "st2_front_forward_ctl: the scalar weights t=%g / alpha=%g / beta=%g "
+                  "must lie in [0, 1]", a->t, a->alpha, a->beta);
+      ST2_REQUIRE(g_be.axpbypcz == kHipBackend.axpbypcz && g_be.duration_head == kHipBackend.duration_head,
+                  "st2_front_forward_ctl: per-row controls have no slot in a debug backend (st2_debug_set_backend)");
+    }
+    return front_plan(c, *e, *a, ctl);
+  });
 }
 
 extern "C" int64_t st2_duration_workspace_bytes(st2_engine* e, int32_t B, int32_t N) {
   if (!e || !e->dur.ready || B <= 0 || N <= 0) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
   static int64_t dummy_dur;
-  duration_plan(c, *e, wrap(nullptr, B, e->cfg.pred_hidden, N), nullptr, nullptr, B, N, 0, nullptr, &dummy_dur);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) {
+    duration_plan(c, *e, wrap(nullptr, B, e->cfg.pred_hidden, N), nullptr, nullptr, B, N, 0, nullptr, &dummy_dur);
+  });
 }
 
 extern "C" int st2_duration_forward(st2_engine* e, const float* d_en, const float* s, const int32_t* lengths, int32_t B,
@@ -1424,43 +1453,23 @@ extern "C" int st2_duration_forward(st2_engine* e, const float* d_en, const floa
   ST2_REQUIRE(e && e->dur.ready, "st2_duration_forward: duration-encoder weights not finalized");
   ST2_REQUIRE(d_en && s && d_cm && workspace && B > 0 && N > 0 && tail >= 0, "st2_duration_forward: bad arguments");
   ST2_REQUIRE(N <= 512, "st2_duration_forward: N=%d tokens exceed the 512 of PL-BERT's position table", N);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_duration_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = duration_plan(c, *e, wrap(d_en, B, e->cfg.pred_hidden, N), s, lengths, B, N, tail, d_cm, durations);
-  ST2_REQUIRE(!c.a.overflow, "st2_duration_forward: workspace of %lld B is too small (need %lld B, see "
-              "st2_duration_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return run_forward("st2_duration_forward", "st2_duration_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return duration_plan(c, *e, wrap(d_en, B, e->cfg.pred_hidden, N), s, lengths, B, N, tail, d_cm, durations);
+  });
 }
 
 extern "C" int64_t st2_prosody_workspace_bytes(st2_engine* e, int32_t B, int32_t N, int32_t T) {
   if (!e || !e->pred.ready || B <= 0 || N <= 0 || T <= 0) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
-  prosody_plan(c, *e, nullptr, nullptr, nullptr, nullptr, B, N, T, 0, nullptr, nullptr, nullptr);
   // + the per-row length table of st2_prosody_forward_ragged, in front of the same allocations
-  return c.a.peak + 256 + ragged_table_bytes(B, 2);
+  return workspace_query([&](Ctx& c) { prosody_plan(c, *e, nullptr, nullptr, nullptr, nullptr, B, N, T, 0, nullptr, nullptr, nullptr); },
+                         ragged_table_bytes(B, 2));
 }
 
 extern "C" int st2_prosody_forward(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
                                    const float* s, int32_t B, int32_t N, int32_t T, int32_t shift, float* asr, float* f0,
                                    float* n, void* workspace, int64_t workspace_bytes, void* stream) {
-  ST2_REQUIRE(e && e->pred.ready, "st2_prosody_forward: predictor weights not finalized");
-  ST2_REQUIRE(d_cm && t_en && durations && s && asr && f0 && n && workspace && B > 0 && N > 0 && T > 0,
-              "st2_prosody_forward: bad arguments");
-  ST2_REQUIRE(N <= 512, "st2_prosody_forward: N=%d tokens exceed the 512 of PL-BERT's position table", N);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_prosody_forward: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = prosody_plan(c, *e, d_cm, t_en, durations, s, B, N, T, shift, asr, f0, n);
-  ST2_REQUIRE(!c.a.overflow, "st2_prosody_forward: workspace of %lld B is too small (need %lld B, see "
-              "st2_prosody_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return prosody_forward("st2_prosody_forward", e, d_cm, t_en, durations, s, nullptr, B, N, T, shift, asr, f0, n, workspace,
+                         workspace_bytes, stream);
 }
 
 extern "C" int st2_prosody_forward_ragged(st2_engine* e, const float* d_cm, const float* t_en, const int64_t* durations,
@@ -1469,19 +1478,8 @@ extern "C" int st2_prosody_forward_ragged(st2_engine* e, const float* d_cm, cons
                                           int64_t workspace_bytes, void* stream) {
   ST2_REQUIRE(frames, "st2_prosody_forward_ragged: frames (int32 [B] on the device) is required");
   ST2_REQUIRE(B > 0 && N > 0 && T_max > 0, "st2_prosody_forward_ragged: bad geometry B=%d N=%d T_max=%d", B, N, T_max);
-  ST2_REQUIRE(e && e->pred.ready, "st2_prosody_forward_ragged: predictor weights not finalized");
-  ST2_REQUIRE(d_cm && t_en && durations && s && asr && f0 && n && workspace, "st2_prosody_forward_ragged: bad arguments");
-  ST2_REQUIRE(N <= 512, "st2_prosody_forward_ragged: N=%d tokens exceed the 512 of PL-BERT's position table", N);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-              "st2_prosody_forward_ragged: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = prosody_plan(c, *e, d_cm, t_en, durations, s, B, N, T_max, shift, asr, f0, n, frames);
-  ST2_REQUIRE(!c.a.overflow, "st2_prosody_forward_ragged: workspace of %lld B is too small (need %lld B, see "
-              "st2_prosody_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return prosody_forward("st2_prosody_forward_ragged", e, d_cm, t_en, durations, s, frames, B, N, T_max, shift, asr, f0, n,
+                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int st2_sampler_table(int32_t steps, double sigma_min, double sigma_max, double rho, double sigma_data,
@@ -1519,14 +1517,12 @@ extern "C" int st2_sampler_table(int32_t steps, double sigma_min, double sigma_m
 
 extern "C" int64_t st2_sampler_workspace_bytes(st2_engine* e, int32_t B, int32_t N, int32_t steps, double embedding_scale) {
   if (!e || !e->dn.ready || B <= 0 || N <= 0 || steps < 2) return -1;
-  Ctx c;
-  c.dry = true;
-  c.a.dry = true;
   std::vector<double> table((size_t)(steps - 1) * ST2_SAMPLER_TABLE_COLS, 0.0);
   static const float dummy = 0.f;
-  sampler_plan(c, *e, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, B, N, steps, embedding_scale, table.data(), 1.0, nullptr,
-               nullptr);
-  return c.a.peak + 256;
+  return workspace_query([&](Ctx& c) {
+    sampler_plan(c, *e, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, B, N, steps, embedding_scale, table.data(), 1.0, nullptr,
+                 nullptr);
+  });
 }
 
 extern "C" int st2_sampler_run(st2_engine* e, const float* noise, const float* embedding, const float* features,
@@ -1538,14 +1534,8 @@ extern "C" int st2_sampler_run(st2_engine* e, const float* noise, const float* e
               "st2_sampler_run: bad arguments");
   ST2_REQUIRE(N <= e->cfg.dn_max_length, "st2_sampler_run: N=%d exceeds the fixed-embedding length %d", N,
               e->cfg.dn_max_length);
-  ST2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "st2_sampler_run: workspace must be 256-byte aligned");
-  Ctx c;
-  c.stream = stream;
-  c.a.base = static_cast<char*>(workspace);
-  c.a.cap = workspace_bytes;
-  const int rc = sampler_plan(c, *e, noise, embedding, nullptr, features, step_noise, lengths, B, N, steps, embedding_scale, table,
-                              sigma0, out, step_taps);
-  ST2_REQUIRE(!c.a.overflow, "st2_sampler_run: workspace of %lld B is too small (need %lld B, see "
-              "st2_sampler_workspace_bytes)", (long long)workspace_bytes, (long long)c.a.peak);
-  return rc;
+  return run_forward("st2_sampler_run", "st2_sampler_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
+    return sampler_plan(c, *e, noise, embedding, nullptr, features, step_noise, lengths, B, N, steps, embedding_scale, table,
+                        sigma0, out, step_taps);
+  });
 }

@@ -77,12 +77,8 @@ void run_adain_resblk(DecRun& r, const PAdainResBlk& p, const View& x, const Vie
   View t1 = new_ncl(c, B, p.dim_out, Lo).with_len(len_o);
   if (p.upsample) {
     View u = new_ncl(c, B, p.dim_in, 2 * L).with_len(len_o);
-    if (x.len)
-      RUN(c, g_be.adain_leaky_pool_len(x.p, x.bs, x.cs, st1, r.gamma(p.n1), r.beta(p.n1, p.dim_in), r.J, 0.2f,
-                                       r.e.F(p.pool_w), r.e.F(p.pool_b), u.p, u.bs, u.cs, B, p.dim_in, L, x.len, c.stream));
-    else
-      RUN(c, g_be.adain_leaky_pool(x.p, x.bs, x.cs, st1, r.gamma(p.n1), r.beta(p.n1, p.dim_in), r.J, 0.2f,
-                                   r.e.F(p.pool_w), r.e.F(p.pool_b), u.p, u.bs, u.cs, B, p.dim_in, L, c.stream));
+    adain_leaky_pool(c, x.rows(0, p.dim_in), st1, r.gamma(p.n1), r.beta(p.n1, p.dim_in), r.J, 0.2f, r.e.F(p.pool_w),
+                     r.e.F(p.pool_b), u);
     ConvOpt o;
     o.pad_left = 1; o.bias = r.e.F(p.conv1.bias); o.stats_out = st2;
     conv(c, r.e, u, p.conv1.w, t1, o);
@@ -184,16 +180,10 @@ int decoder_plan(Ctx& c, const st2_engine& e, const float* asr_p, const float* f
   View cat0 = new_ncl(c, B, Cin + 2, T, false).with_len(r.lenT);
   RUN(c, g_be.copy_ncl(asr.p, asr.bs, asr.cs, cat0.p, cat0.bs, cat0.cs, B, Cin, T, c.stream));
   {
-    View a = cat0.rows(Cin, Cin + 1), b = cat0.rows(Cin + 1, Cin + 2);
-    if (frames) {  // the F0 / N rows end at 2 T_b: the stride-2 convs see their zero padding there
-      RUN(c, g_be.conv1d_direct_len(f0.p, f0.bs, f0.cs, e.F(d.f0_w), e.F(d.f0_b), a.p, a.bs, a.cs, B, 1, 1, T2, T, 3, 2, 1,
-                                    f0.len, nullptr, c.stream));
-      RUN(c, g_be.conv1d_direct_len(nn.p, nn.bs, nn.cs, e.F(d.n_w), e.F(d.n_b), b.p, b.bs, b.cs, B, 1, 1, T2, T, 3, 2, 1,
-                                    nn.len, nullptr, c.stream));
-    } else {
-      RUN(c, g_be.conv1d_direct(f0.p, f0.bs, f0.cs, e.F(d.f0_w), e.F(d.f0_b), a.p, a.bs, a.cs, B, 1, 1, T2, T, 3, 2, 1, c.stream));
-      RUN(c, g_be.conv1d_direct(nn.p, nn.bs, nn.cs, e.F(d.n_w), e.F(d.n_b), b.p, b.bs, b.cs, B, 1, 1, T2, T, 3, 2, 1, c.stream));
-    }
+    // ragged rows: F0 / N end at 2 T_b, the stride-2 convs see their zero padding there; their outputs are not cut
+    View a = cat0.rows(Cin, Cin + 1).with_len(nullptr), b = cat0.rows(Cin + 1, Cin + 2).with_len(nullptr);
+    conv1d_direct(c, f0, e.F(d.f0_w), e.F(d.f0_b), a, 3, 2, 1);
+    conv1d_direct(c, nn, e.F(d.n_w), e.F(d.n_b), b, 3, 2, 1);
     View src = cat0.rows(Cin, Cin + 2), dst = cat.rows(1088, 1090);
     RUN(c, g_be.copy_ncl(src.p, src.bs, src.cs, dst.p, dst.bs, dst.cs, B, 2, T, c.stream));
   }
@@ -223,19 +213,11 @@ int decoder_plan(Ctx& c, const st2_engine& e, const float* asr_p, const float* f
   } else {
     float* scratch = c.a.f32((int64_t)B * 9 * T2);
     float* hs = c.a.f32((int64_t)B * L);
-    if (frames)  // rows of 600 T_b samples, exact zeros after them
-      RUN(c, g_be.har_source_len(f0_p, B, T2, up_scale, 9, sine_noise, e.F(g.lin_w), e.F(g.lin_b), 0.1f, 0.003f, 10.0f,
-                                 24000.0f, scratch, hs, r.len2T, c.stream));
-    else
-      RUN(c, g_be.har_source(f0_p, B, T2, up_scale, 9, sine_noise, e.F(g.lin_w), e.F(g.lin_b), 0.1f, 0.003f, 10.0f,
-                             24000.0f, scratch, hs, c.stream));
+    har_source(c, f0_p, B, T2, up_scale, sine_noise, e.F(g.lin_w), e.F(g.lin_b), scratch, hs, r.len2T);  // ragged: 600 T_b samples
     if (taps->har_source) RUN(c, g_be.copy_ncl(hs, L, L, taps->har_source, L, L, B, 1, L, c.stream));
     if (ist) {
       har = new_ncl(c, B, n_fft + 2, L / hop + 1, false);
-      if (frames)  // reflect-padded at each row's end, exact zero frames after it (phase_split then needs no lengths)
-        RUN(c, g_be.stft_mag_phase_len(hs, B, L, n_fft, hop, har.p, har.bs, har.cs, len_of(DecLens::SAMPLES), c.stream));
-      else
-        RUN(c, g_be.stft_mag_phase(hs, B, L, n_fft, hop, har.p, har.bs, har.cs, c.stream));
+      stft_mag_phase(c, hs, L, n_fft, hop, har, len_of(DecLens::SAMPLES));  // ragged: phase_split then needs no lengths
     } else {
       har = wrap(hs, B, 1, L);
     }
@@ -297,13 +279,7 @@ int decoder_plan(Ctx& c, const st2_engine& e, const float* asr_p, const float* f
       conv(c, e, x, g.ups_wt[i], Y, o);
       const int nt = (L_out + CVT_TILE - 1) / CVT_TILE;
       float* part = c.a.f32((int64_t)B * C * nt * 3);
-      if (frames)
-        RUN(c, g_be.convt_interleave_stats_len(Y.p, Y.bs, Y.cs, L_in + 1, e.F(g.ups_b[i]), xs_src.p, xs_src.bs, xs_src.cs,
-                                               xu.p, xu.bs, xu.cs, B, C, u, pad, L_raw, reflect ? 1 : 0, part, nt, Y.len,
-                                               len_o, c.stream));
-      else
-        RUN(c, g_be.convt_interleave_stats(Y.p, Y.bs, Y.cs, L_in + 1, e.F(g.ups_b[i]), xs_src.p, xs_src.bs, xs_src.cs,
-                                           xu.p, xu.bs, xu.cs, B, C, u, pad, L_raw, reflect ? 1 : 0, part, nt, c.stream));
+      convt_interleave_stats(c, Y, e.F(g.ups_b[i]), xs_src, xu, u, pad, L_raw, reflect ? 1 : 0, part, nt);
       finalize_stats(c, part, xu, nt, st, CVT_TILE);
       c.a.off = m;
     }
@@ -330,10 +306,7 @@ int decoder_plan(Ctx& c, const st2_engine& e, const float* asr_p, const float* f
     o.act_split = nb;
     conv(c, e, x, g.post.w, sp, o);
     tap(c, sp, taps->spec_phase);
-    if (frames)  // hop (M_b - 1) = 600 T_b samples per row, exact zeros after them
-      RUN(c, g_be.istft_len(sp.p, sp.bs, sp.cs, B, x.L, n_fft, hop, wave, (int64_t)hop * (x.L - 1), x.len, c.stream));
-    else
-      RUN(c, g_be.istft(sp.p, sp.bs, sp.cs, B, x.L, n_fft, hop, wave, (int64_t)hop * (x.L - 1), c.stream));
+    istft(c, sp, n_fft, hop, wave, (int64_t)hop * (x.L - 1));  // ragged: 600 T_b samples per row
   } else {
     View w = wrap(wave, B, 1, x.L).with_len(x.len);
     ConvOpt o;

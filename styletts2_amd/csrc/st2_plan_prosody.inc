@@ -93,14 +93,8 @@ int prosody_plan(Ctx& c, const st2_engine& e, const float* d_cm, const float* t_
     len2T = tab + B;
   }
   View en = new_ncl(c, B, Cd, T, false).with_len(lenT);
-  if (frames) {  // exact zeros past T_b
-    RUN(c, g_be.expand_by_durations_len(d_cm, (int64_t)Cd * N, N, dur, B, Cd, N, T, shift, en.p, en.bs, en.cs, lenT, c.stream));
-    RUN(c, g_be.expand_by_durations_len(t_en, (int64_t)Ct * N, N, dur, B, Ct, N, T, shift, asr, (int64_t)Ct * T, T, lenT,
-                                        c.stream));
-  } else {
-    RUN(c, g_be.expand_by_durations(d_cm, (int64_t)Cd * N, N, dur, B, Cd, N, T, shift, en.p, en.bs, en.cs, c.stream));
-    RUN(c, g_be.expand_by_durations(t_en, (int64_t)Ct * N, N, dur, B, Ct, N, T, shift, asr, (int64_t)Ct * T, T, c.stream));
-  }
+  expand_by_durations(c, d_cm, N, dur, shift, en);  // ragged: exact zeros past T_b
+  expand_by_durations(c, t_en, N, dur, shift, wrap(asr, B, Ct, T).with_len(lenT));
   // shared BiLSTM: input projection of every frame as one k = 1 conv, then the recurrence
   const int H = p.shared.H;
   View G = new_ncl(c, B, 8 * H, T, false).with_len(lenT);
@@ -128,12 +122,8 @@ int prosody_plan(Ctx& c, const st2_engine& e, const float* d_cm, const float* t_
       t = out.with_len(t.len && blks[i].upsample ? len2T : t.len);
     }
     float* dst = path ? nn : f0;
-    if (frames)  // F0 / N: exact zeros past 2 T_b
-      RUN(c, g_be.conv1d_direct_len(t.p, t.bs, t.cs, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), dst,
-                                    (int64_t)t.L, t.L, B, t.C, 1, t.L, t.L, 1, 1, 0, t.len, t.len, c.stream));
-    else
-      RUN(c, g_be.conv1d_direct(t.p, t.bs, t.cs, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), dst,
-                                (int64_t)t.L, t.L, B, t.C, 1, t.L, t.L, 1, 1, 0, c.stream));
+    // F0 / N; ragged: exact zeros past 2 T_b
+    conv1d_direct(c, t, e.F(path ? p.np_w : p.f0p_w), e.F(path ? p.np_b : p.f0p_b), wrap(dst, B, 1, t.L).with_len(t.len), 1, 1, 0);
   }
   return c.rc;
 }

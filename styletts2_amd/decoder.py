@@ -20,6 +20,7 @@ import torch.nn as nn
 from .layers import transient_state
 from . import ops
 from . import weights as W
+from .weights import _PackedCache
 from .layers import (AdaINParams, AdaINResBlock1Params, AdainResBlk1dParams, PlainConv1d, PlainLinear, WNConv1d,
                      WNConvTranspose1d)
 
@@ -268,7 +269,7 @@ class Generator(nn.Module):
 
 
 @transient_state
-class Decoder(nn.Module):
+class Decoder(_PackedCache, nn.Module):
     """Drop-in for the reference Decoder (both vocoder variants)."""
 
     def __init__(self, dim_in=512, F0_channel=512, style_dim=64, dim_out=80, resblock_kernel_sizes=(3, 7, 11),
@@ -301,26 +302,8 @@ class Decoder(nn.Module):
             object.__setattr__(self, "_eng", None)
         super().__setattr__(name, value)
 
-    # -- packed-weight cache ---------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._pk = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, state_dict, *a, **k):
-        self._pk = None
-        return super().load_state_dict(W.strip_module_prefix(state_dict), *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):  # also reached when a PARENT module's load_state_dict() recurses here
-        self._pk = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def refresh(self):
-        """Call after mutating parameters in place."""
-        self._pk = None
-
     def _prepare(self, device):
         pk = type("PackedDecoder", (), {})()
-        pk.device = device
         bank = StyleBank()
         for blk in [self.encode] + list(self.decode):
             bank.add(blk.norm1)
@@ -334,7 +317,6 @@ class Decoder(nn.Module):
         pk.n_w, pk.n_b = _dev(self.N_conv.folded(), device), _dev(self.N_conv.bias, device)
         pk.asr_res = _PackedConv(self.asr_res[0], device)
         pk.gen = self.generator.pack(device)
-        self._pk = pk
         return pk
 
     @torch.no_grad()
@@ -359,7 +341,7 @@ class Decoder(nn.Module):
         if frames is not None:
             raise RuntimeError("Decoder.forward(frames=...): the ragged decoder exists only in the C++ engine "
                                "(plan_mode 'engine', f16s convs on a HIP device)")
-        pk = self._pk if (self._pk is not None and self._pk.device == dev) else self._prepare(dev)
+        pk = self._packed(dev)
         bank = pk.bank
         asr = asr.float().contiguous()
         B, Cin, T = asr.shape

@@ -23,6 +23,7 @@ import torch.nn as nn
 from .layers import transient_state
 from . import ops
 from . import weights as W
+from .weights import _PackedCache
 from .layers import PlainConv1d, PlainLinear
 
 
@@ -327,7 +328,7 @@ class _Block(nn.Module):
 
 
 @transient_state
-class _Transformer(nn.Module):
+class _Transformer(_PackedCache, nn.Module):
     multispeaker = False
 
     def __init__(self, num_layers, channels, num_heads, head_features, multiplier, context_embedding_features,
@@ -349,22 +350,6 @@ class _Transformer(nn.Module):
         self.fixed_embedding = _FixedEmbedding(embedding_max_length, context_embedding_features)
         self._pk = None
 
-    # -- packed weights --------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        self._pk = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, state_dict, *a, **k):
-        self._pk = None
-        return super().load_state_dict(W.strip_module_prefix(state_dict), *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):  # also reached when a PARENT module's load_state_dict() recurses here
-        self._pk = None                        # (models.load_checkpoint loads `diffusion` at the shell level)
-        return super()._load_from_state_dict(*a, **k)
-
-    def refresh(self):
-        self._pk = None
-
     def __setattr__(self, name, value):
         if name == "_pk" and value is None:  # every invalidation of the Python-side pack (load_state_dict, .to(), refresh)
             object.__setattr__(self, "_engine_stale", True)   # ... makes the C++ plan's packed copy stale too
@@ -375,7 +360,6 @@ class _Transformer(nn.Module):
         d = lambda t: t.detach().float().contiguous().to(device)
         lin_t = lambda l: d(l.weight.detach().t())  # [in, out] for st2_style_fc
         pk = type("PackedDenoiser", (), {})()
-        pk.device = device
         pk.time_w = d(self.to_time[0][0].weights)
         pk.time_lin, pk.time_b = lin_t(self.to_time[0][1]), d(self.to_time[0][1].bias)
         pk.map0, pk.map0_b = lin_t(self.to_mapping[0]), d(self.to_mapping[0].bias)
@@ -403,7 +387,6 @@ class _Transformer(nn.Module):
         pk.out_t = d(self.to_out[1].weight.detach().reshape(self.channels, self.features).t())
         pk.out_b = d(self.to_out[1].bias)
         pk.fixed = d(self.fixed_embedding.embedding.weight)
-        self._pk = pk
         return pk
 
     # -- sessions: everything constant across the 2*(steps-1) net calls of one sampler run -------------
@@ -414,7 +397,7 @@ class _Transformer(nn.Module):
         equals that utterance's un-padded run (the reference runs one utterance at a time: no padding exists there)."""
         assert embedding is not None, "the denoiser is conditional: `embedding` is required (modules.py:410)"
         dev = x.device
-        pk = self._pk if (self._pk is not None and self._pk.device == dev) else self._prepare(dev)
+        pk = self._packed(dev)
         B, N, E = embedding.shape
         assert N <= self.fixed_embedding.max_length, "Input sequence length must be <= max_length"
         assert E == self.emb_features

@@ -41,6 +41,7 @@ import torch.nn.functional as F
 from .layers import transient_state
 from . import _hooks, _lib, ops
 from . import weights as W
+from .weights import _PackedCache
 
 MEL_MEAN, MEL_STD = -4.0, 4.0  # meldataset.py:60
 HOP = 300
@@ -99,7 +100,7 @@ class _ResBlk(nn.Module):
 
 
 @transient_state
-class StyleEncoder(nn.Module):
+class StyleEncoder(_PackedCache, nn.Module):
     """models.py:139-164: mel [B, 1, 80, T] -> style [B, style_dim].  T >= 80 frames (the 5x5 valid conv after four
     halvings needs a 5-wide map)."""
 
@@ -117,22 +118,6 @@ class StyleEncoder(nn.Module):
 
         self._pk = None
 
-    # -- packed-weight cache (invalidated by .to() / load_state_dict, also when a parent module recurses here) ----------
-    def _apply(self, fn, *a, **k):
-        self._pk = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, state_dict, *a, **k):
-        self._pk = None
-        return super().load_state_dict(W.strip_module_prefix(state_dict), *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._pk = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def refresh(self):
-        self._pk = None
-
     @staticmethod
     def _rows_as_channels(w2d):
         """Conv2d weight [Co][Ci][kh][kw] -> Conv1d weight [Co][kh*Ci][kw] acting on kh stacked image rows (channel
@@ -143,7 +128,6 @@ class StyleEncoder(nn.Module):
     def _prepare(self, device):
         d = lambda t: None if t is None else t.detach().float().contiguous().to(device)
         pk = type("PackedStyleEncoder", (), {})()
-        pk.device = device
         first = self.shared[0]
         pk.w0, pk.b0 = d(self._rows_as_channels(first.folded_host())), d(first.bias)            # [C0][3][3], direct conv
         pk.blocks = []
@@ -165,7 +149,6 @@ class StyleEncoder(nn.Module):
         pk.c_last = last.weight_orig.shape[0]
         pk.wl = W.pack_linear_auto(self.unshared.weight.detach().float().cpu()).to(device)
         pk.bl = d(self.unshared.bias)
-        self._pk = pk
         return pk
 
     @torch.no_grad()
@@ -189,7 +172,7 @@ class StyleEncoder(nn.Module):
         """The same plan kernel by kernel from Python (tests' tap path; module docstring)."""
         x = x.float()
         dev = x.device
-        pk = self._pk if (self._pk is not None and self._pk.device == dev) else self._prepare(dev)
+        pk = self._packed(dev)
         B, one, H, Wd = x.shape
         assert one == 1 and H % 16 == 0 and Wd >= 80, "StyleEncoder needs [B, 1, 16k, T >= 80], got %s" % (tuple(x.shape),)
         new_map = lambda h, c, w: torch.zeros((B, h + 2, c, w), device=dev, dtype=torch.float32)  # zero rows 0 and h+1

@@ -21,6 +21,7 @@ import torch.nn as nn
 from .layers import transient_state
 from . import _hooks, ops
 from . import weights as W
+from .weights import _PackedCache
 from .decoder import StyleBank, _PackedAdainResBlk, _PackedConv, run_adain_resblk
 from .layers import AdainResBlk1dParams, PlainConv1d, PlainLinear, WNConv1d
 
@@ -55,40 +56,26 @@ def _device_lengths(lengths, n, device):
 
 
 @transient_state
-class EngineLSTM(nn.LSTM):
+class EngineLSTM(_PackedCache, nn.LSTM):
     """nn.LSTM(1 layer, bidirectional, batch_first) parameter holder -- same state_dict keys as the reference's
     nn.LSTM -- whose arithmetic runs on the HIP kernels: the input projection of every time step is one k=1
     `st2_conv1d` (channel-major tokens), the recurrence is `st2_lstm_bidir`.  Pack/pad semantics of
     models.py:314-327 are reproduced through `lengths` (outputs past a sequence's end are zero)."""
+    strip_prefix = False
 
     def __init__(self, input_size, hidden_size):
         super().__init__(input_size, hidden_size, 1, batch_first=True, bidirectional=True)
         self._pk = None
 
-    def _apply(self, fn, *a, **k):
-        self._pk = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, state_dict, *a, **k):
-        self._pk = None
-        return super().load_state_dict(state_dict, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):  # also reached when a PARENT module's load_state_dict() recurses here
-        self._pk = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _packed(self, device):
-        if self._pk is None or self._pk.device != device:
-            d = lambda t: t.detach().float().contiguous().to(device)
-            pk = type("PackedLSTM", (), {})()
-            pk.device = device
-            w_ih = torch.cat([self.weight_ih_l0.detach(), self.weight_ih_l0_reverse.detach()], dim=0).float()
-            pk.w_ih = W.pack_linear_auto(w_ih).to(device)                             # [I, 8H] (split-f16 by default)
-            pk.bias = d(torch.cat([self.bias_ih_l0.detach() + self.bias_hh_l0.detach(),
-                                   self.bias_ih_l0_reverse.detach() + self.bias_hh_l0_reverse.detach()]))
-            pk.whh_t = d(torch.stack([self.weight_hh_l0.detach().t(), self.weight_hh_l0_reverse.detach().t()]))
-            self._pk = pk
-        return self._pk
+    def _prepare(self, device):
+        d = lambda t: t.detach().float().contiguous().to(device)
+        pk = type("PackedLSTM", (), {})()
+        w_ih = torch.cat([self.weight_ih_l0.detach(), self.weight_ih_l0_reverse.detach()], dim=0).float()
+        pk.w_ih = W.pack_linear_auto(w_ih).to(device)                             # [I, 8H] (split-f16 by default)
+        pk.bias = d(torch.cat([self.bias_ih_l0.detach() + self.bias_hh_l0.detach(),
+                               self.bias_ih_l0_reverse.detach() + self.bias_hh_l0_reverse.detach()]))
+        pk.whh_t = d(torch.stack([self.weight_hh_l0.detach().t(), self.weight_hh_l0_reverse.detach().t()]))
+        return pk
 
     def forward_cm(self, x_cm, lengths=None):
         """x_cm [B, I, N] channel-major -> [B, 2H, N]; lengths: int32 device tensor or None."""
@@ -113,33 +100,6 @@ class _ChannelLayerNorm(nn.Module):
         self.channels, self.eps = channels, eps
         self.gamma = nn.Parameter(torch.ones(channels))
         self.beta = nn.Parameter(torch.zeros(channels))
-
-
-class _PackedCache:
-    """Shared lazy packed-weight cache (invalidated by .to()/load_state_dict())."""
-
-    def _apply(self, fn, *a, **k):
-        self._pk = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, state_dict, *a, **k):
-        self._pk = None
-        return super().load_state_dict(W.strip_module_prefix(state_dict), *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):  # also reached when a PARENT module's load_state_dict() recurses here
-        self._pk = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def refresh(self):
-        self._pk = None
-
-    def _packed(self, device):
-        pk = getattr(self, "_pk", None)
-        if pk is None or pk.device != device:
-            pk = self._prepare(device)
-            pk.device = device
-            self._pk = pk
-        return pk
 
 
 @transient_state
@@ -348,26 +308,10 @@ def build_plbert(plbert_params):
     from transformers import AlbertConfig, AlbertModel
 
     @transient_state
-    class CustomAlbert(AlbertModel):
-        def _apply(self, fn, *a, **k):
-            self._pk = None
-            return super()._apply(fn, *a, **k)
+    class CustomAlbert(_PackedCache, AlbertModel):
+        strip_prefix = False
 
-        def load_state_dict(self, state_dict, *a, **k):
-            self._pk = None
-            return super().load_state_dict(state_dict, *a, **k)
-
-        def _load_from_state_dict(self, *a, **k):
-            self._pk = None
-            return super()._load_from_state_dict(*a, **k)
-
-        def refresh(self):
-            self._pk = None
-
-        def _packed(self, device):
-            pk = getattr(self, "_pk", None)
-            if pk is not None and pk.device == device:
-                return pk
+        def _prepare(self, device):
             cfg = self.config
             assert cfg.num_hidden_groups == 1 and cfg.inner_group_num == 1, "PL-BERT shares one ALBERT layer"
             assert cfg.hidden_act == "gelu_new" and cfg.hidden_size // cfg.num_attention_heads == 64
@@ -376,7 +320,6 @@ def build_plbert(plbert_params):
             lay = self.encoder.albert_layer_groups[0].albert_layers[0]
             att = lay.attention
             pk = type("PackedAlbert", (), {})()
-            pk.device = device
             emb = self.embeddings
             pk.word, pk.pos, pk.tok0 = d(emb.word_embeddings.weight), d(emb.position_embeddings.weight), d(
                 emb.token_type_embeddings.weight[0])
@@ -392,7 +335,6 @@ def build_plbert(plbert_params):
             pk.out, pk.out_b = W.pack_linear_auto(lay.ffn_output.weight.detach().float()).to(device), d(
                 lay.ffn_output.bias)
             pk.fln_w, pk.fln_b = row(lay.full_layer_layer_norm.weight), row(lay.full_layer_layer_norm.bias)
-            self._pk = pk
             return pk
 
         @torch.no_grad()

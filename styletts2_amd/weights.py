@@ -149,3 +149,35 @@ def strip_module_prefix(state_dict):
     for k, v in state_dict.items():
         out[k[7:] if k.startswith("module.") else k] = v
     return out
+
+
+class _PackedCache:
+    """Mixin, listed before the nn.Module base: the module's lazily packed weights (`_pk`) are dropped by everything that can
+    change a parameter or its device -- .to() / .float() (`_apply`), load_state_dict() of the module or of a PARENT recursing
+    here (`_load_from_state_dict`), and refresh() after an in-place mutation.  `_packed(device)` packs on demand through the
+    class's `_prepare(device)`."""
+    strip_prefix = True  # load_state_dict() also takes an nn.DataParallel checkpoint (`module.` keys)
+
+    def _apply(self, fn, *a, **k):
+        self._pk = None
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, state_dict, *a, **k):
+        self._pk = None
+        return super().load_state_dict(strip_module_prefix(state_dict) if self.strip_prefix else state_dict, *a, **k)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._pk = None
+        return super()._load_from_state_dict(*a, **k)
+
+    def refresh(self):
+        """Call after mutating parameters in place."""
+        self._pk = None
+
+    def _packed(self, device):
+        pk = getattr(self, "_pk", None)
+        if pk is None or pk.device != device:
+            pk = self._prepare(device)
+            pk.device = device
+            self._pk = pk
+        return pk
