@@ -537,6 +537,30 @@ int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_
                   int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets,
                   void* stream);
 
+/* ---- output sample rates and G.711 in the packed hand-over (added under ABI 23, additive: one kernel-level entry point, no
+ * new backend-table slot, no struct change; st2_wave_pack and its format codes are untouched) -------------------------- *
+ * st2_wave_resample_pack: st2_wave_pack with a rational polyphase resampler in it.  U = up, D = down, K = taps_per_phase,
+ * taps fp32 [U][K] on the device.  Row b has n_b = max(0, samples_per_frame * f_b - trim) input samples (f_b = frames[b]
+ * clamped to 0..T_cap: st2_wave_pack's rule) and m_b = (n_b U + D - 1) div D output samples; offsets (int64 [B + 1], device)
+ * receives the exclusive prefix sum of m_b.  For j < m_b, with c = (j D) div U and p = (j D) mod U,
+ *     y[j] = sum_{k = 0}^{K - 1} taps[p][k] * x_b[c - (K - 1) div 2 + k],      x_b[i] = 0 for i < 0 or i >= n_b,
+ * accumulated in fp32 with fmaf, k ascending -- the result does not depend on how the kernel tiles a row.  The zero is a
+ * SELECT: nothing of `wave` at or past n_b is read (the ragged decoder's tails may hold NaN bit patterns).
+ * out[offsets[b] + j] = cvt(y[j]):
+ *   ST2_PCM_F32   y (out is float);
+ *   ST2_PCM_S16   st2_wave_pack's 16-bit rule: (int16_t) rint(clamp(y, -1, 1) * 32767.0f), NaN -> 0 (out is int16_t);
+ *   ST2_PCM_ULAW / ST2_PCM_ALAW   ITU-T G.711 of that 16-bit sample, one byte each (out is uint8_t).
+ * `out_capacity` is in output SAMPLES: nothing at or past min(offsets[B], out_capacity) is written (offsets still describes
+ * the untruncated layout).  Two launches (scan, move), no allocation, no synchronisation; one workgroup per (tile of output
+ * samples, row) stages the phase table and the tile's input span in static LDS (63 KiB) and stores 16 bytes per lane on the
+ * aligned body of the destination, head and tail peeled.  Returns non-zero before any launch on: every condition of
+ * st2_wave_pack; NULL taps; up / down outside 1..1024; taps_per_phase outside 1..512; unknown fmt; out misaligned for its
+ * sample type; a table that leaves no room in LDS for a 16-sample tile. */
+enum st2_pcm_format { ST2_PCM_F32 = 0, ST2_PCM_S16 = 1, ST2_PCM_ULAW = 2, ST2_PCM_ALAW = 3 };
+int st2_wave_resample_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                           int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                           int32_t taps_per_phase, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets, void* stream);
+
 /* ---- reference-audio style path (compute_style, Demo/Inference_LibriTTS.ipynb:100-111) ------------------------- *
  * The mel front-end (meldataset.py:58-66: torchaudio MelSpectrogram(n_mels 80, n_fft 2048, win 1200, hop 300) ->
  * (log(1e-5 + mel) + 4) / 4) and StyleEncoder (models.py:139-164) run on the conv kernels above: the windowed DFT is a

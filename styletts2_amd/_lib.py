@@ -23,6 +23,7 @@ PRO_NONE, PRO_LEAKY, PRO_ADAIN_LEAKY, PRO_ADAIN_SNAKE, PRO_SNAKE, PRO_COLNORM = 
 STATUS_F16_RANGE, STATUS_LSTM_TIMEOUT, STATUS_DURATION_SUM, STATUS_LSTM_RECOVERED = 1, 2, 4, 8
 STATUS_FRAME_CAPACITY = 16  # added under ABI 23: a row was truncated to the caller's frame capacity
 PACK_F32, PACK_S16 = 0, 1  # enum st2_pack_format
+PCM_F32, PCM_S16, PCM_ULAW, PCM_ALAW = range(4)  # enum st2_pcm_format (st2_wave_resample_pack)
 ACT_NONE, ACT_GELU, ACT_EXP_SIN, ACT_TANH, ACT_LEAKY, ACT_GELU_TANH = range(6)
 
 
@@ -246,6 +247,8 @@ _SIGNATURES = {
     "st2_frames_from_durations": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "st2_wave_pack": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                 C.c_int64, C.c_void_p, C.c_void_p]),
+    "st2_wave_resample_pack": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "st2_sizeof_controls": (C.c_int, []),
     "st2_front_forward_ctl": (C.c_int, [C.c_void_p, C.POINTER(FrontArgs), C.POINTER(ControlRows), C.c_void_p, C.c_int64,
                                         C.c_void_p]),

@@ -3,6 +3,7 @@
 // never reads a predicted duration: it states a frame capacity, and frame counts travel as a device int32 [B] from the
 // duration head to the samples a server copies out.
 #include "st2_common.h"
+#include "st2_pcm.h"
 
 namespace {
 
@@ -24,40 +25,10 @@ __global__ __launch_bounds__(64) void frames_from_durations_kernel(const long lo
   }
 }
 
-__device__ __forceinline__ long long pack_row_samples(const int32_t* __restrict__ frames, int b, int T_cap, int spf, int trim) {
-  const long long f = min(max(frames[b], 0), T_cap);  // clamped to the capacity: never a read past the row
-  return max(0LL, f * spf - trim);
-}
-
-// offsets[b] = sum_{i < b} n_i, offsets[B] = the total: one wave scanning the rows in chunks of 64
+// offsets[b] = sum_{i < b} n_i, offsets[B] = the total
 __global__ __launch_bounds__(64) void pack_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf,
                                                           int trim, long long* __restrict__ offsets) {
-  long long carry = 0;
-  for (int base = 0; base < B; base += 64) {
-    const int b = base + threadIdx.x;
-    const long long n = b < B ? pack_row_samples(frames, b, T_cap, spf, trim) : 0;
-    long long v = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(v, off, 64);
-      if ((int)threadIdx.x >= off) v += u;
-    }
-    if (b < B) offsets[b] = carry + v - n;
-    carry += __shfl(v, 63, 64);
-  }
-  if (threadIdx.x == 0) offsets[B] = carry;
-}
-
-// The source of a row's aligned body starts wherever the destination's alignment puts it: 4-byte aligned only.
-struct __attribute__((packed, aligned(4))) f32x4_u {
-  float v[4];
-};
-
-__device__ __forceinline__ int16_t pcm16(float x) {
-  // (int16) rint(clamp(x, -1, 1) * 32767): v_rndne = round-to-nearest-even as np.rint; NaN -> 0 (fminf / fmaxf would turn
-  // it into a full-scale sample)
-  const float c = fminf(fmaxf(x, -1.0f), 1.0f);
-  return x != x ? (int16_t)0 : (int16_t)(int)rintf(c * 32767.0f);
+  pack_scan_rows(B, offsets, [&](int b) { return pack_row_samples(frames, b, T_cap, spf, trim); });
 }
 
 constexpr int PACK_THREADS = 256;

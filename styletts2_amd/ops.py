@@ -1145,6 +1145,50 @@ def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_p
     return out, offsets
 
 
+OUTPUT_FORMATS = {"f32": (_lib.PCM_F32, torch.float32), "s16": (_lib.PCM_S16, torch.int16),
+                  "ulaw": (_lib.PCM_ULAW, torch.uint8), "alaw": (_lib.PCM_ALAW, torch.uint8)}
+
+
+def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=None, samples_per_frame=600):
+    """`st2_wave_resample_pack`: `wave_pack` at an output rate and in an output format.  wave [B, 1, L] or [B, L] at 24 kHz,
+    frames int32 [B] on the device -> (packed, offsets): row b's n_b = max(0, samples_per_frame * frames[b] - trim) valid
+    samples resampled to `rate` (one of `resample.RATES`; m_b = ceil(n_b U / D) samples, U / D = rate / 24000 reduced) by the
+    polyphase table of `resample.design`, back to back as fp32 ("f32"), 16-bit PCM ("s16", `wave_pack`'s rule) or G.711
+    mu-law / A-law bytes of that 16-bit sample ("ulaw" / "alaw", uint8), and the int64 [B + 1] exclusive prefix sum of m_b.
+    `out` (1-D, of the format's dtype) bounds what is written: nothing at or past min(offsets[B], out.numel()); by default it
+    holds every row at capacity, ceil(L U / D) samples each.  No host read; the first call for a (rate, device) designs and
+    uploads the table, which therefore must not happen under stream capture."""
+    from . import resample
+    if fmt not in OUTPUT_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
+    code, dtype = OUTPUT_FORMATS[fmt]
+    if rate not in resample.RATES:
+        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf = int(samples_per_frame)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    lib = _lib.load()
+    U, D, K, taps = resample.table(rate, wave.device)
+    if out is None:
+        out = torch.empty((B * resample.output_samples(L, U, D),), device=wave.device, dtype=dtype)
+    _chk_dev(out, "out", dtype, 1)
+    if offsets is None:
+        offsets = torch.empty((B + 1,), device=wave.device, dtype=torch.int64)
+    _chk_dev(offsets, "offsets", torch.int64, 1)
+    if offsets.numel() != B + 1 or out.device != wave.device or offsets.device != wave.device:
+        raise _lib.St2Error("offsets must hold %d entries; out / offsets must live on the device of wave" % (B + 1))
+    _lib.check(lib.st2_wave_resample_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D,
+                                          taps.data_ptr(), K, code, out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()),
+               "st2_wave_resample_pack")
+    return out, offsets
+
+
 # ---- reference-audio style path (st2_style.hip) ----------------------------------------------------------------------
 def stft_frames(wave, n_win, hop, shift, lengths=None, min_length=None, want_frames=False):
     """`st2_stft_frames`: wave [B, L] -> frames [B, n_win, L // hop + 1] (reflect-padded frame columns of torch.stft).

@@ -12,7 +12,7 @@ Differences from the notebooks, all host-side:
 """
 import torch
 
-from . import _hooks, ops
+from . import _hooks, ops, resample
 
 
 def _engine_path(dev, taps=None):
@@ -679,19 +679,23 @@ class SynthesisResult:
     device and none of it waited for:
       wave     [B, 1, samples_per_frame * max_frames] fp32, exact zeros from row b's samples_per_frame * frames[b] on;
       frames   int32 [B]: every row's frame count, clamped to 1..max_frames;
-      packed   (with `pack`) the rows' valid samples minus `trim` each, back to back: int16 PCM ("s16") or fp32 ("f32");
-      offsets  (with `pack`) int64 [B + 1]: row b is packed[offsets[b]:offsets[b + 1]].
+      packed   (with `pack`) the rows' valid samples minus `trim` each, back to back: int16 PCM ("s16") or fp32 ("f32"), or --
+               with `sample_rate` / a G.711 `pack` -- those samples at `sample_rate` as fp32, int16 or mu-law / A-law bytes;
+      offsets  (with `pack`) int64 [B + 1]: row b is packed[offsets[b]:offsets[b + 1]];
+      sample_rate  the rate of `packed` (24000 unless the call asked for another); `wave` is always at 24 kHz.
     `to_host()` is the one place that waits."""
 
-    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None):
+    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
+        self.sample_rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
         self._buf = buf  # offsets and packed are views of this one allocation: one copy takes both
         self._host = None  # its pinned mirror, allocated by the first to_host()
 
     def to_host(self):
-        """The list of per-utterance 1-D numpy arrays (int16 for "s16", else float32; `trim` applied): ONE device -> host copy
+        """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
+        at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
         copy has waited for every kernel of the call, so a row truncated to `max_frames` (ST2_STATUS_FRAME_CAPACITY) is
         reported here, also on a graph replay, which runs no Python in between.  A result made without `pack` is packed as
@@ -701,7 +705,7 @@ class SynthesisResult:
         would need a second wait."""
         if self._buf is None:
             self._buf, self.packed, self.offsets = _pack_into_one(self.wave, self.frames, self.trim, self.pack or "f32",
-                                                                  self.samples_per_frame)
+                                                                  self.samples_per_frame, self.sample_rate)
         if self._host is None or self._host.shape != self._buf.shape:
             self._host = torch.empty(self._buf.shape, dtype=torch.uint8, pin_memory=True)
         host = self._host
@@ -717,19 +721,44 @@ class SynthesisResult:
         return [samples[offs[b]:offs[b + 1]] for b in range(B)]
 
 
-def _pack_into_one(wave, frames, trim, fmt, samples_per_frame):
-    """`ops.wave_pack` into ONE device allocation, [offsets int64 [B + 1] | pad to 16 bytes | samples at capacity], so that a
-    single copy brings both to the host.  Returns (the allocation as bytes, packed, offsets)."""
+def _check_output(pack, sample_rate):
+    """The output format and rate of the capacity-bound path: `pack` one of `ops.OUTPUT_FORMATS` or None, `sample_rate` one of
+    `resample.RATES` or None -- and only with `pack`."""
+    if pack is not None and pack not in ops.OUTPUT_FORMATS:
+        raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
+    if sample_rate is not None and pack is None:
+        raise ValueError("sample_rate is the rate of the packed samples: pass pack")
+    if sample_rate is not None and sample_rate not in resample.RATES:
+        raise ValueError("sample_rate must be None or one of %s, got %r" % (list(resample.RATES), sample_rate))
+
+
+def _resamples(fmt, sample_rate):
+    """True when the packing step is `ops.wave_resample_pack`: another rate than the model's, or a G.711 format.  24 kHz fp32 /
+    16-bit PCM stays `ops.wave_pack`."""
+    return sample_rate not in (None, resample.MODEL_RATE) or fmt not in ops.PACK_FORMATS
+
+
+def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None):
+    """`ops.wave_pack` -- or `ops.wave_resample_pack` -- into ONE device allocation, [offsets int64 [B + 1] | pad to 16 bytes |
+    samples at capacity: ceil(L U / D) per row], so that a single copy brings both to the host.  Returns (the allocation as
+    bytes, packed, offsets)."""
     B, L = wave.shape[0], wave.shape[-1]
-    dtype = ops.PACK_FORMATS[fmt][1]
+    dtype = ops.OUTPUT_FORMATS[fmt][1]
     hdr = (8 * (B + 1) + 15) // 16 * 16
-    buf = torch.empty((hdr + B * L * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
-    packed, offsets = ops.wave_pack(wave, frames, trim=trim, fmt=fmt, out=buf[hdr:].view(dtype),
-                                    offsets=buf[:8 * (B + 1)].view(torch.int64), samples_per_frame=samples_per_frame)
+    into = lambda buf: dict(trim=trim, fmt=fmt, out=buf[hdr:].view(dtype), offsets=buf[:8 * (B + 1)].view(torch.int64),
+                            samples_per_frame=samples_per_frame)
+    if not _resamples(fmt, sample_rate):
+        buf = torch.empty((hdr + B * L * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
+        packed, offsets = ops.wave_pack(wave, frames, **into(buf))
+        return buf, packed, offsets
+    rate = resample.MODEL_RATE if sample_rate is None else sample_rate
+    U, D = resample.table(rate, wave.device)[:2]
+    buf = torch.empty((hdr + B * resample.output_samples(L, U, D) * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
+    packed, offsets = ops.wave_resample_pack(wave, frames, rate, **into(buf))
     return buf, packed, offsets
 
 
-def _decode_capacity(model, p, sine_noise, pack, trim):
+def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
     back, nothing is sliced on the host."""
     T_cap = p["max_frames"]
@@ -738,8 +767,9 @@ def _decode_capacity(model, p, sine_noise, pack, trim):
         trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
     if pack is None:
         return SynthesisResult(w, p["frames"], T_cap, trim=trim)
-    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, w.shape[-1] // T_cap)
-    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf)
+    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, w.shape[-1] // T_cap, sample_rate)
+    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf,
+                           sample_rate=sample_rate)
 
 
 class GraphedSynthesis:
@@ -756,21 +786,25 @@ class GraphedSynthesis:
 
     Per-request controls are one more static buffer, `static["controls"]` (a `Controls` with all six rows):
     the graph is recorded over it holding the neutral values, `__call__(controls=)` copies the caller's rows in and a call
-    without them resets it to neutral.  Other controls never re-record."""
+    without them resets it to neutral.  Other controls never re-record.
+
+    `pack` / `sample_rate` as in `inference`: with an output rate or a G.711 format the packing step inside the graph is
+    `ops.wave_resample_pack`, whose filter table is designed and uploaded here, before any capture."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
-                 embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None):
+                 embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
         dev = torch.device(device) if device is not None else next(model.decoder.parameters()).device
         if not _engine_path(dev):
             raise ValueError("GraphedSynthesis needs the C++ engine path (HIP device, plan_mode 'engine')")
-        if pack is not None and pack not in ops.PACK_FORMATS:
-            raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.PACK_FORMATS), pack))
+        _check_output(pack, sample_rate)
+        if pack is not None and _resamples(pack, sample_rate):
+            resample.table(resample.MODEL_RATE if sample_rate is None else sample_rate, dev)
         self.device, self.max_frames, self.steps = dev, int(max_frames), int(diffusion_steps)
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
-                       max_frames=self.max_frames, pack=pack, trim=trim)
+                       max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate)
         z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
         self.static = dict(tokens=torch.zeros((B, N), device=dev, dtype=torch.int64),
                            lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=z(B, 1, 256),
@@ -863,7 +897,8 @@ def _decode_groups(model, groups, dec, main, noise_of, ready=None, first=0):
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
-              ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None):
+              ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
+              sample_rate=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -900,16 +935,18 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     row is read up to 600 frames[b] only); absent, it is drawn on the device at capacity.  `pack` ("s16" / "f32"): the result also
     carries `packed` (every row's valid samples back to back: 16-bit PCM or fp32, `ops.wave_pack`) and `offsets` (int64 [B + 1],
     device); `trim` samples are dropped from every row's end -- by default the notebooks' rule, 50 for a HiFi-GAN decoder and 0
-    for iSTFTNet.  `result.to_host()` is the one place that waits.  `lengths_dev` (int32 [B] on the device): the token counts of
+    for iSTFTNet.  `pack` also takes "ulaw" / "alaw" (ITU-T G.711 bytes) and `sample_rate` (with `pack` only) one of 8000, 16000,
+    22050, 24000, 32000, 44100 and 48000: the packing step then resamples on the device (`ops.wave_resample_pack`, DESIGN.md
+    section 15) and `packed` holds ceil(n_b U / D) samples per row at that rate; fp32 / 16-bit PCM at 24 kHz is the path above,
+    unchanged.  `result.to_host()` is the one place that waits.  `lengths_dev` (int32 [B] on the device): the token counts of
     a right-padded batch without any host copy (stream capture, `GraphedSynthesis`).  `decode_streams` and `total_frames` are
     refused with `max_frames`.
 
     `controls` (a `Controls`): per-row speaking rate, style mixing weights, pitch scale and energy shift, see `prepare`.
     """
+    _check_output(pack, sample_rate)
     if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
         raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
-    if pack is not None and pack not in ops.PACK_FORMATS:
-        raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.PACK_FORMATS), pack))
     if max_frames is not None and decode_streams:
         raise ValueError("max_frames: there is ONE decoder call, on the current stream; `decode_streams` has no meaning here")
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
@@ -931,7 +968,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
                   main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, pack, trim)
+        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:

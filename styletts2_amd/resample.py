@@ -1,0 +1,73 @@
+"""Filter tables of `st2_wave_resample_pack`: the polyphase taps that take the model's 24 kHz to an
+output rate, designed on the host in numpy fp64 -- once per rate -- and kept on the device, one copy per (rate, device).
+
+A table is never built under stream capture (the upload waits): whoever captures the packing step makes it first
+(`GraphedSynthesis.__init__` does), and `table()` refuses to build one while a capture is running."""
+import math
+
+import numpy as np
+import torch
+
+MODEL_RATE = 24000
+RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+ATTENUATION_DB = 96.0  # Kaiser's design attenuation; the acceptance condition on a table is 90 dB from f_N upward
+PASSBAND = 0.85  # the transition band runs from 0.85 f_N to f_N (f_N: the lower of the two Nyquist frequencies)
+CUTOFF = (1.0 + PASSBAND) / 2  # 0.925: the cutoff sits at the band's centre
+BETA = 0.1102 * (ATTENUATION_DB - 8.7)
+
+
+def taps_per_phase(up, down):
+    """K, even, from Kaiser's formula N = (A - 7.95) / (2.285 dw) for the prototype at `up` times the input rate: its
+    transition band is dw = 2 pi * 0.15 * (f_N / input rate) / up wide there and K = N / up.  The formula is empirical; every
+    supported rate meets both acceptance conditions with it (tests/test_resample_cpu.py computes them), so nothing is added."""
+    width = (1.0 - PASSBAND) * 0.5 * min(1.0, up / down)  # in cycles per input sample
+    K = int(math.ceil((ATTENUATION_DB - 7.95) / (2.285 * 2.0 * math.pi * width)))
+    return K + (K & 1)
+
+
+def design(rate, model_rate=MODEL_RATE):
+    """-> (U, D, taps float32 [U, K]): U / D is the reduced fraction rate / model_rate and
+    taps[p][k] = g(k - (K - 1) // 2 - p / U) with g(t) = r sinc(r t) kaiser(2 t / K; beta), r = 0.925 min(1, U / D)."""
+    if model_rate != MODEL_RATE or rate not in RATES:
+        raise ValueError("output rate %r is not supported: one of %s at a model rate of %d" % (rate, list(RATES), MODEL_RATE))
+    g = math.gcd(int(rate), int(model_rate))
+    U, D = int(rate) // g, int(model_rate) // g
+    if U == D:
+        return 1, 1, np.ones((1, 1), dtype=np.float32)
+    K = taps_per_phase(U, D)
+    r = CUTOFF * min(1.0, U / D)
+    t = np.arange(K, dtype=np.float64)[None, :] - (K - 1) // 2 - np.arange(U, dtype=np.float64)[:, None] / U
+    x = 2.0 * t / K
+    window = np.where(np.abs(x) <= 1.0, np.i0(BETA * np.sqrt(np.clip(1.0 - x * x, 0.0, None))) / np.i0(BETA), 0.0)
+    return U, D, (r * np.sinc(r * t) * window).astype(np.float32)
+
+
+def prototype(taps):
+    """The table flattened to the one low-pass it samples, at U times the input rate: taps[p][k] is its sample k U - p."""
+    U, K = taps.shape
+    proto = np.zeros(U * K, dtype=np.float64)
+    for p in range(U):
+        proto[U - 1 - p::U] = taps[p]
+    return proto
+
+
+def output_samples(n, up, down):
+    """m = ceil(n U / D): the output samples of a row of n input samples."""
+    return (int(n) * up + down - 1) // down
+
+
+_TABLES = {}
+
+
+def table(rate, device):
+    """-> (U, D, K, taps fp32 [U, K] on `device`), designed and uploaded on first use."""
+    dev = torch.device(device)
+    key = (int(rate), dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    hit = _TABLES.get(key)
+    if hit is None:
+        U, D, taps = design(rate)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the %d Hz filter table must exist before a stream capture: call resample.table(%d, device) "
+                               "first" % (rate, rate))
+        hit = _TABLES[key] = (U, D, taps.shape[1], torch.from_numpy(taps).to(dev))
+    return hit
