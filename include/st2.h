@@ -561,6 +561,39 @@ int st2_wave_resample_pack(const float* wave, int64_t w_bs, const int32_t* frame
                            int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
                            int32_t taps_per_phase, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets, void* stream);
 
+/* ---- reference clips at a client's rate and in G.711 (added under ABI 23, additive: one kernel-level entry point and its
+ * size helper, no new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
+ * st2_clip_ingest: the way in of a zero-shot request.  src holds B rows of N_cap samples (row b at
+ * src + b * src_bs samples) in format fmt; n (int32 [B], device) their sample counts.  U = up, D = down, K = taps_per_phase,
+ * taps fp32 [U][K] on the device, U / D = 24000 / rate reduced.
+ *  1. Decode.  Row b has n_b = clamp(n[b], 0, N_cap) samples; nothing of src at or past n_b is read.  ST2_PCM_F32 as it is;
+ *     ST2_PCM_S16 v / 32768; ST2_PCM_ULAW / ST2_PCM_ALAW the ITU-T G.711 16-bit value of the byte, / 32768 (all exact in fp32).
+ *  2. Resample: st2_wave_resample_pack's rule.  m_b = min(L_cap, (n_b U + D - 1) div D) and, with c = (j D) div U and
+ *     p = (j D) mod U,  r_b[j] = sum_{k < K} taps[p][k] * x_b[c - (K - 1) div 2 + k],  x_b = 0 outside [0, n_b) by select, in
+ *     fp32 with fmaf, k ascending: a sample depends neither on the tiling nor on the row's place in the batch.  U = D = K = 1
+ *     is the decode alone.
+ *  3. Trim: librosa.effects.trim(y, top_db, ref = max, frame_length 2048, hop_length 512) with centred, zero-padded frames.
+ *     Frame f = 0 .. m_b div 512 covers r_b[512 f - 1024, 512 f + 1024), zeros outside [0, m_b); e_f = max(sum r^2 / 2048,
+ *     1e-10); frame f is non-silent iff e_f > max_f e_f * 10^(-top_db / 10).  With f0 / f1 the first / last non-silent frame:
+ *     start = 512 f0, end = min(m_b, 512 (f1 + 1)).  A frame is the sum of four 512-sample block sums, each made once in a fixed
+ *     order (no atomics).  An all-zero row keeps its whole length.  top_db <= 0: start = 0, end = m_b.
+ *  4. Minimum length.  If end - start < L_min: end = min(m_b, start + L_min), then start = max(0, end - L_min).
+ *  5. Hand-over.  wave[b][i] = r_b[start + i] for i < end - start (row b at wave + b * w_bs, w_bs >= L_cap and a multiple of 4,
+ *     wave 16-byte aligned); nothing at or past wave[b][end - start] is written.  len[b] = end - start; start[b] (may be NULL)
+ *     the cut; flags[b] (may be NULL): bit 0 -- (n_b U + D - 1) div D > L_cap, the row was truncated to the capacity; bit 1 --
+ *     the minimum-length rule moved a bound, or the row is still shorter than L_min.
+ * `work` (16-byte aligned, st2_clip_ingest_work_bytes(B, L_cap) bytes; 0 for B or L_cap <= 0) holds the untrimmed 24 kHz rows
+ * and the block sums.  Three launches (resample + block sums, bounds, gather), no allocation, no synchronisation, no host
+ * read.  Returns non-zero before any launch on: NULL src / n / taps / wave / len / work; B outside 1..65535; N_cap or L_cap
+ * <= 0; w_bs < L_cap or not a multiple of 4; src_bs < N_cap with B > 1; up / down outside 1..1024; taps_per_phase outside
+ * 1..512; unknown fmt; L_min < 0 or > L_cap; a NaN top_db; work_bytes too small; src misaligned for its sample type (taps / n
+ * / len for theirs, wave / work for 16 bytes); a table that leaves no room in LDS (63 KiB) for a 512-sample tile. */
+int64_t st2_clip_ingest_work_bytes(int32_t B, int32_t L_cap);
+int st2_clip_ingest(const void* src, int64_t src_bs, const int32_t* n, int32_t B, int32_t N_cap, int32_t fmt, int32_t up,
+                    int32_t down, const float* taps, int32_t taps_per_phase, float top_db, int32_t L_min, float* wave,
+                    int64_t w_bs, int32_t L_cap, int32_t* len, int32_t* start, int32_t* flags, void* work, int64_t work_bytes,
+                    void* stream);
+
 /* ---- reference-audio style path (compute_style, Demo/Inference_LibriTTS.ipynb:100-111) ------------------------- *
  * The mel front-end (meldataset.py:58-66: torchaudio MelSpectrogram(n_mels 80, n_fft 2048, win 1200, hop 300) ->
  * (log(1e-5 + mel) + 4) / 4) and StyleEncoder (models.py:139-164) run on the conv kernels above: the windowed DFT is a

@@ -249,6 +249,10 @@ _SIGNATURES = {
                                 C.c_int64, C.c_void_p, C.c_void_p]),
     "st2_wave_resample_pack": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          C.c_int32, f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "st2_clip_ingest_work_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "st2_clip_ingest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                  C.c_int32, C.c_float, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_sizeof_controls": (C.c_int, []),
     "st2_front_forward_ctl": (C.c_int, [C.c_void_p, C.POINTER(FrontArgs), C.POINTER(ControlRows), C.c_void_p, C.c_int64,
                                         C.c_void_p]),

@@ -1,5 +1,6 @@
-// What the two packing entry points share (st2_pack.hip: st2_wave_pack; st2_resample.hip: st2_wave_resample_pack): a row's
-// valid sample count, the row-offset scan, the 4-byte-aligned 16-byte source vector and the sample conversions.
+// What the packing entry points and the clip ingest share (st2_pack.hip: st2_wave_pack; st2_resample.hip:
+// st2_wave_resample_pack; st2_ingest.hip: st2_clip_ingest): a row's valid sample count, the row-offset scan, the packed source
+// vectors and the sample conversions, both ways.
 #pragma once
 #include "st2_common.h"
 
@@ -32,6 +33,13 @@ __device__ __forceinline__ void pack_scan_rows(int B, long long* __restrict__ of
 struct __attribute__((packed, aligned(4))) f32x4_u {
   float v[4];
 };
+// Four 16-bit / 8-bit samples of a client's clip: a row starts wherever its sample type may.
+struct __attribute__((packed, aligned(2))) s16x4_u {
+  int16_t v[4];
+};
+struct __attribute__((packed, aligned(1))) u8x4_u {
+  uint8_t v[4];
+};
 
 __device__ __forceinline__ int16_t pcm16(float x) {
   // (int16) rint(clamp(x, -1, 1) * 32767): v_rndne = round-to-nearest-even as np.rint; NaN -> 0 (fminf / fmaxf would turn
@@ -56,4 +64,20 @@ __device__ __forceinline__ uint8_t g711_alaw(int s) {
     ix = (ix >> (e - 1)) - 16 + (e << 4);
   }
   return (uint8_t)((s < 0 ? ix : ix | 0x80) ^ 0x55);
+}
+
+// The way back, ITU-T G.711 expansion to the 16-bit value at the centre of the code's interval: mu-law takes the bias off again
+// (the two zero codes 0xFF / 0x7F both give 0), A-law's smallest magnitudes are +-8.
+__device__ __forceinline__ int g711_ulaw_decode(int code) {
+  const int inv = ~code & 0xFF;
+  const int lin = ((((inv & 15) << 3) + 0x84) << ((inv >> 4) & 7)) - 0x84;  // 0..32124
+  return code < 0x80 ? -lin : lin;
+}
+
+__device__ __forceinline__ int g711_alaw_decode(int code) {
+  const int ix = (code ^ 0x55) & 0x7F;
+  const int e = ix >> 4;
+  const int man = e > 0 ? (ix & 15) + 16 : (ix & 15);
+  const int lin = ((man << 4) + 8) << (e > 0 ? e - 1 : 0);  // 8..32256
+  return code > 127 ? lin : -lin;
 }

@@ -1189,6 +1189,51 @@ def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=
     return out, offsets
 
 
+def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):
+    """`st2_clip_ingest`: reference clips in a client's rate and sample format -> trimmed fp32 rows at 24 kHz.  src [B, N_cap]
+    on the device, of the dtype of `fmt` ("f32" float32, "s16" int16, "ulaw" / "alaw" uint8), n int32 [B] on the device (row
+    b's sample count, clamped to 0..N_cap; nothing of src at or past it is read), `rate` one of `resample.RATES` ->
+    (wave fp32 [B, >= L_cap], len int32 [B], start int32 [B], flags int32 [B]), all on the device: row b decoded, resampled by
+    the polyphase table of `resample.design_input`, cut to librosa's `effects.trim(top_db=)` bounds (top_db <= 0: not cut) and
+    widened to L_min samples where the clip has them; wave[b, :len[b]] holds it and nothing at or past len[b] is written.
+    flags bit 0: the row was truncated to L_cap (default: ceil(N_cap U / D), what any row can need); bit 1: the minimum-length
+    rule moved a bound or the row is still shorter than L_min.  `out`: fp32 [B, w] with w >= L_cap a multiple of 4, 16-byte
+    aligned.  No host read; the first call for a (rate, device) designs and uploads the table, which therefore must not happen
+    under stream capture."""
+    from . import resample
+    if fmt not in OUTPUT_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
+    code, dtype = OUTPUT_FORMATS[fmt]
+    if rate not in resample.RATES:
+        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
+    lp = _chk_len(n, "n", _nb(src, 2), src)
+    if not torch.is_tensor(src) or not src.is_cuda:
+        raise _lib.St2Error("src must live on a HIP device (got %s); the engine has no CPU path" % (
+            src.device if torch.is_tensor(src) else type(src).__name__))
+    if src.dtype != dtype or src.dim() != 2 or (src.shape[1] > 1 and src.stride(1) != 1):
+        raise _lib.St2Error("src must be a 2-D %s tensor with unit stride along its rows for fmt %r (got %s %s)"
+                            % (dtype, fmt, src.dtype, tuple(src.shape)))
+    B, N_cap = src.shape
+    lib = _lib.load()
+    U, D, K, taps = resample.input_table(rate, src.device)
+    if L_cap is None:
+        L_cap = resample.output_samples(N_cap, U, D)
+    L_cap = int(L_cap)
+    if out is None:
+        out = torch.empty((B, (L_cap + 3) // 4 * 4), device=src.device, dtype=torch.float32)
+    _chk_dev(out, "out", torch.float32, 2)
+    if out.shape[0] != B or out.device != src.device:
+        raise _lib.St2Error("out must hold %d rows on the device of src (got %s on %s)" % (B, tuple(out.shape), out.device))
+    i32 = lambda: torch.empty((B,), device=src.device, dtype=torch.int32)
+    length, start, flags = i32(), i32() if want_start else None, i32() if want_flags else None
+    nbytes = max(lib.st2_clip_ingest_work_bytes(B, L_cap), 16)
+    work = torch.empty((nbytes,), device=src.device, dtype=torch.uint8)
+    _lib.check(lib.st2_clip_ingest(src.data_ptr(), src.stride(0), lp, B, N_cap, code, U, D, taps.data_ptr(), K, float(top_db),
+                                   int(L_min), out.data_ptr(), out.stride(0), L_cap, length.data_ptr(), _ptr(start), _ptr(flags),
+                                   work.data_ptr(), nbytes, _stream()), "st2_clip_ingest")
+    return out, length, start, flags
+
+
 # ---- reference-audio style path (st2_style.hip) ----------------------------------------------------------------------
 def stft_frames(wave, n_win, hop, shift, lengths=None, min_length=None, want_frames=False):
     """`st2_stft_frames`: wave [B, L] -> frames [B, n_win, L // hop + 1] (reflect-padded frame columns of torch.stft).

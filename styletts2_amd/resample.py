@@ -1,8 +1,9 @@
-"""Filter tables of `st2_wave_resample_pack`: the polyphase taps that take the model's 24 kHz to an
-output rate, designed on the host in numpy fp64 -- once per rate -- and kept on the device, one copy per (rate, device).
+"""Filter tables of `st2_wave_resample_pack` and of `st2_clip_ingest` (section 16): the polyphase taps
+that take the model's 24 kHz to an output rate, and a client's rate to the model's 24 kHz, designed on the host in numpy fp64
+-- once per rate and direction -- and kept on the device, one copy per (direction, rate, device).
 
-A table is never built under stream capture (the upload waits): whoever captures the packing step makes it first
-(`GraphedSynthesis.__init__` does), and `table()` refuses to build one while a capture is running."""
+A table is never built under stream capture (the upload waits): whoever captures the step that reads it makes it first
+(`GraphedSynthesis.__init__` does), and `table()` / `input_table()` refuse to build one while a capture is running."""
 import math
 
 import numpy as np
@@ -31,7 +32,21 @@ def design(rate, model_rate=MODEL_RATE):
     if model_rate != MODEL_RATE or rate not in RATES:
         raise ValueError("output rate %r is not supported: one of %s at a model rate of %d" % (rate, list(RATES), MODEL_RATE))
     g = math.gcd(int(rate), int(model_rate))
-    U, D = int(rate) // g, int(model_rate) // g
+    return _kaiser_table(int(rate) // g, int(model_rate) // g)
+
+
+def design_input(rate, model_rate=MODEL_RATE):
+    """-> (U, D, taps float32 [U, K]) of the way in: U / D is the reduced fraction model_rate / rate, the taps are `design`'s
+    formula at that ratio.  K by `taps_per_phase`: 82 / 82 / 82 / 110 / 152 / 164 at 8 / 16 / 22.05 / 32 / 44.1 / 48 kHz; every
+    rate meets both acceptance conditions with it (tests/test_ingest_cpu.py computes them), so nothing is added."""
+    if model_rate != MODEL_RATE or rate not in RATES:
+        raise ValueError("input rate %r is not supported: one of %s at a model rate of %d" % (rate, list(RATES), MODEL_RATE))
+    g = math.gcd(int(rate), int(model_rate))
+    return _kaiser_table(int(model_rate) // g, int(rate) // g)
+
+
+def _kaiser_table(U, D):
+    """The table of the ratio U / D (reduced): what `design` and `design_input` share."""
     if U == D:
         return 1, 1, np.ones((1, 1), dtype=np.float32)
     K = taps_per_phase(U, D)
@@ -59,15 +74,24 @@ def output_samples(n, up, down):
 _TABLES = {}
 
 
-def table(rate, device):
-    """-> (U, D, K, taps fp32 [U, K] on `device`), designed and uploaded on first use."""
+def _device_table(key, rate, device, make, name):
     dev = torch.device(device)
-    key = (int(rate), dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = key + (int(rate), dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     hit = _TABLES.get(key)
     if hit is None:
-        U, D, taps = design(rate)
+        U, D, taps = make(rate)
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the %d Hz filter table must exist before a stream capture: call resample.table(%d, device) "
-                               "first" % (rate, rate))
+            raise RuntimeError("the %d Hz filter table must exist before a stream capture: call resample.%s(%d, device) "
+                               "first" % (rate, name, rate))
         hit = _TABLES[key] = (U, D, taps.shape[1], torch.from_numpy(taps).to(dev))
     return hit
+
+
+def table(rate, device):
+    """-> (U, D, K, taps fp32 [U, K] on `device`), designed and uploaded on first use."""
+    return _device_table((), rate, device, design, "table")
+
+
+def input_table(rate, device):
+    """`table` of the way in (`design_input`), under cache keys of its own."""
+    return _device_table(("in",), rate, device, design_input, "input_table")

@@ -326,15 +326,96 @@ def _style_engine(model, dev):
     return cached[1]
 
 
+ENCODINGS = {"f32": torch.float32, "s16": torch.int16, "ulaw": torch.uint8, "alaw": torch.uint8}
+TRIM_TOP_DB = 30.0  # the notebooks' librosa.effects.trim(wave, top_db=30)
+FLAG_CAPACITY, FLAG_MIN_LENGTH = 1, 2  # st2_clip_ingest's per-row flags
+
+
+def _ingest(clips, lengths, sample_rate, encoding, top_db):
+    """`ingest_clips` -> (wave, lengths_dev, flags, host): `host` says that the lengths came as a host list."""
+    from . import resample
+    if encoding not in ENCODINGS:
+        raise ValueError("encoding must be one of %s, got %r" % (sorted(ENCODINGS), encoding))
+    if sample_rate not in resample.RATES:
+        raise ValueError("sample_rate must be one of %s, got %r" % (list(resample.RATES), sample_rate))
+    dtype = ENCODINGS[encoding]
+    if isinstance(clips, (list, tuple)):
+        if lengths is not None:
+            raise _lib.St2Error("ingest_clips: a list of clips carries its own lengths")
+        if not clips:
+            raise _lib.St2Error("ingest_clips: empty list of clips")
+        rows = [w.reshape(-1) for w in clips]
+        bad = [w.dtype for w in rows if w.dtype != dtype]
+        if bad:
+            raise _lib.St2Error("encoding %r is %s samples, the clips are %s" % (encoding, dtype, bad[0]))
+        lengths = [int(w.numel()) for w in rows]
+        src = torch.zeros((len(rows), max(lengths)), device=rows[0].device, dtype=dtype)
+        for b, w in enumerate(rows):
+            src[b, :lengths[b]] = w
+    else:
+        src = clips.unsqueeze(0) if torch.is_tensor(clips) and clips.dim() == 1 else clips
+        if not torch.is_tensor(src) or src.dim() != 2:
+            raise _lib.St2Error("ingest_clips takes a list of 1-D clips or one buffer [B, N_cap]")
+        if src.dtype != dtype:
+            raise _lib.St2Error("encoding %r is %s samples, the buffer is %s" % (encoding, dtype, src.dtype))
+        if lengths is None:
+            lengths = [src.shape[1]] * src.shape[0]
+    B, N_cap = src.shape
+    g = math.gcd(int(sample_rate), resample.MODEL_RATE)
+    U, D = resample.MODEL_RATE // g, int(sample_rate) // g
+    host = not torch.is_tensor(lengths)
+    if host:  # validated up front; a device tensor is used as it is, without a host read
+        lengths = [int(v) for v in lengths]
+        if len(lengths) != B:
+            raise _lib.St2Error("lengths must hold %d entries, got %d" % (B, len(lengths)))
+        bad = [v for v in lengths if v > N_cap or resample.output_samples(v, U, D) < MIN_CLIP]
+        if bad:
+            raise _lib.St2Error("reference clips must give %d samples at 24 kHz at least (80 mel frames) and fit the buffer's "
+                                "row of %d, got %r at %d Hz" % (MIN_CLIP, N_cap, bad, sample_rate))
+        if src.device.type != "cuda":
+            raise _lib.St2Error("the clips must live on a HIP device (got %s); the engine has no CPU path" % (src.device,))
+        lengths = torch.tensor(lengths, dtype=torch.int32).to(src.device)
+    L_cap = max(resample.output_samples(N_cap, U, D), MIN_CLIP)
+    out = torch.zeros((B, (L_cap + 3) // 4 * 4), device=src.device, dtype=torch.float32)  # a short row's tail reads as silence
+    wave, n24, _, flags = ops.clip_ingest(src, lengths, sample_rate, encoding, top_db=top_db, L_cap=L_cap, L_min=MIN_CLIP,
+                                          out=out, want_start=False)
+    return wave, n24, flags, host
+
+
 @torch.no_grad()
-def compute_style(model, wave, lengths=None):
+def ingest_clips(clips_or_buffer, lengths=None, sample_rate=24000, encoding="f32", top_db=TRIM_TOP_DB):
+    """What the notebooks do on the host with librosa.load(path, sr=24000) and librosa.effects.trim(wave, top_db=30), on the
+    device (`st2_clip_ingest`): a list of 1-D clips, or one buffer [B, N_cap] with `lengths` (int32 [B] on
+    the device: used as it is, no host read, legal under graph capture; or a list of B ints, validated here: each clip gives
+    MIN_CLIP samples at 24 kHz at least), at `sample_rate` (one of `resample.RATES`) in `encoding` ("f32" float32, "s16" int16,
+    "ulaw" / "alaw" uint8 G.711) -> (wave fp32 [B, L_cap] at 24 kHz, lengths int32 [B] on the device, flags int32 [B] on the
+    device): what `compute_style(model, wave, lengths=)` takes.  A clip the trim leaves shorter than MIN_CLIP is widened to it
+    (flag FLAG_MIN_LENGTH); FLAG_CAPACITY cannot rise here, the buffer holds every row at capacity."""
+    return _ingest(clips_or_buffer, lengths, sample_rate, encoding, top_db)[:3]
+
+
+@torch.no_grad()
+def compute_style(model, wave, lengths=None, sample_rate=None, encoding=None, top_db=None):
     """`compute_style` of Demo/Inference_LibriTTS.ipynb:100-111 minus the file I/O: wave [L] or [B, L] at 24 kHz
     (already trimmed; the notebook trims with librosa.effects.trim(top_db=30) on the host) -> ref_s [B, 256].
 
     A ragged batch -- the clips of B zero-shot requests, no two of one length -- is one call too: `wave` [B, L_cap] with
     `lengths` (int32 [B] on the device: no host read, legal under graph capture; or a list of B ints, validated here), or
     simply a list of 1-D clips, which are copied into one buffer.  Row b equals the clip processed alone; whatever `wave`
-    holds at or past lengths[b] is never used.  Clips are MIN_CLIP (23 700) samples at least."""
+    holds at or past lengths[b] is never used.  Clips are MIN_CLIP (23 700) samples at least.
+
+    With any of `sample_rate` / `encoding` / `top_db` given, `wave` is what a client sent and `ingest_clips` runs first
+    (defaults 24 000 Hz, "f32", top_db 30): decode, resample, trim, all on the device.  Lengths from the host -- a list of
+    clips, a list of ints, none -- are checked: a row the ingest flagged raises here.  Device lengths are never read: what the
+    flags would have said is the caller's to ask `ingest_clips` for."""
+    if sample_rate is not None or encoding is not None or top_db is not None:
+        wave, lengths, flags, host = _ingest(wave, lengths, 24000 if sample_rate is None else sample_rate,
+                                             "f32" if encoding is None else encoding, TRIM_TOP_DB if top_db is None else top_db)
+        if host:
+            bad = flags.cpu().tolist()
+            if any(bad):
+                raise _lib.St2Error("reference clips came out of the trim shorter than %d samples (flag 2) or cut to capacity "
+                                    "(flag 1): flags %r" % (MIN_CLIP, bad))
     if isinstance(wave, (list, tuple)):
         if lengths is not None:
             raise _lib.St2Error("compute_style: a list of clips carries its own lengths")
