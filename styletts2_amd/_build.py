@@ -30,10 +30,9 @@ EXTRA_FLAGS = {s: ["-fno-slp-vectorize"] for s in SOURCES if s.startswith("st2_c
 # tools/simd_hazard_repro.hip).  No auto-packing there; the cooperative kernel packs along K by hand
 # (plain encoding).  tools/check_isa.py (run below after every link) keeps the encoding out of the WHOLE library.
 EXTRA_FLAGS.update({"st2_lstm.hip": ["-fno-slp-vectorize"], "st2_lstm_coop.hip": ["-fno-slp-vectorize"]})
-# The resampler's FMA chains (one per output sample, k ascending) gain nothing from packing two of them, and a pair that shares
-# a tap in an odd register would be that same encoding.
-EXTRA_FLAGS["st2_resample.hip"] = ["-fno-slp-vectorize"]
-EXTRA_FLAGS["st2_ingest.hip"] = ["-fno-slp-vectorize"]  # the same chains on the way in
+# The polyphase FMA chains of st2_polyphase.h (one per output sample, k ascending), on the way out and on the way in, gain
+# nothing from packing two of them, and a pair that shares a tap in an odd register would be that same encoding.
+EXTRA_FLAGS.update({"st2_resample.hip": ["-fno-slp-vectorize"], "st2_ingest.hip": ["-fno-slp-vectorize"]})
 
 
 def _hipcc():

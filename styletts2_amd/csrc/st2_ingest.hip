@@ -3,33 +3,16 @@
 // the model's 24 kHz by st2_wave_resample_pack's polyphase rule, trimmed of leading and trailing silence by librosa's
 // effects.trim rule and handed over as fp32 rows with their device lengths: three launches, no host read and no allocation, so
 // the call is legal under stream capture and runs straight into the style path.
-#include "st2_common.h"
-#include "st2_pcm.h"
+#include "st2_polyphase.h"
 
 namespace {
 
-constexpr int IN_THREADS = 256;
+constexpr int IN_THREADS = PP_THREADS;
 constexpr int IN_HOP = 512;         // the trim's hop: a frame of 2048 samples is four block sums
 constexpr int IN_TILE_MAX = 1024;   // output samples of a workgroup, a multiple of IN_HOP; rows of `work` are padded to it
 constexpr int IN_LDS_BYTES = 63 * 1024;
 
-__host__ __device__ constexpr int in_round4(int v) { return (v + 3) & ~3; }
-// Upper bound of the input span (in floats, from its 4-sample-aligned start) of a tile of `tile` output samples
-constexpr long long in_span_cap(long long tile, int U, int D, int K) { return tile * D / U + K + 8; }
 constexpr int64_t in_row_stride(int64_t L_cap) { return (L_cap + IN_TILE_MAX - 1) / IN_TILE_MAX * IN_TILE_MAX; }
-
-template <int FMT> struct in_src { using type = float; using vec = f32x4_u; };
-template <> struct in_src<ST2_PCM_S16> { using type = int16_t; using vec = s16x4_u; };
-template <> struct in_src<ST2_PCM_ULAW> { using type = uint8_t; using vec = u8x4_u; };
-template <> struct in_src<ST2_PCM_ALAW> { using type = uint8_t; using vec = u8x4_u; };
-
-template <int FMT>
-__device__ __forceinline__ float in_cvt(typename in_src<FMT>::type v) {
-  if constexpr (FMT == ST2_PCM_F32) return v;
-  else if constexpr (FMT == ST2_PCM_S16) return (float)v * (1.0f / 32768.0f);  // exact
-  else if constexpr (FMT == ST2_PCM_ULAW) return (float)g711_ulaw_decode(v) * (1.0f / 32768.0f);
-  else return (float)g711_alaw_decode(v) * (1.0f / 32768.0f);
-}
 
 // n_b = clamp(n[b], 0, N_cap) source samples; `full` = ceil(n_b U / D) samples at 24 kHz before the capacity cuts them
 __device__ __forceinline__ long long in_row_samples(const int32_t* __restrict__ n, int b, int N_cap, int U, int D) {
@@ -39,18 +22,16 @@ __device__ __forceinline__ long long in_row_samples(const int32_t* __restrict__ 
 
 // Launch one.  Workgroup (t, b) makes the 24 kHz samples [j0, j0 + tile) of row b, zeros from m_b on, into `work` and the sums
 // of squares of the tile's 512-sample blocks into `sums`:
-//   1. the phase table and the tile's decoded input span [c(j0) - h, c(j1 - 1) - h + K) go to LDS; a sample in front of the
-//      row or at / past n_b is a SELECTED zero -- nothing of `src` at or past n_b is read;
-//   2. lane l makes the samples j0 + l, j0 + l + 256, ...: y = sum_k taps[p][k] x[c - h + k] in fp32, fmaf, k ascending;
+//   1. the phase table and the tile's decoded input span [c(j0) - h, c(j1 - 1) - h + K) go to LDS (st2_polyphase.h);
+//   2. lane l makes the samples j0 + l, j0 + l + 256, ... by the chain of st2_polyphase.h;
 //   3. the tile leaves with one 16-byte store per lane and pass; wave w sums the squares of block w, lane l the samples
 //      l, l + 64, ... ascending, then the 64 partial sums by a butterfly: one fixed order, no atomics.
 // A workgroup whose tile lies behind the row's end leaves before any barrier: the grid is sized by the capacity.
 template <int FMT>
 __global__ __launch_bounds__(IN_THREADS) void ingest_resample_kernel(
-    const typename in_src<FMT>::type* __restrict__ src, int64_t src_bs, const int32_t* __restrict__ n_in, int N_cap, int U, int D,
+    const typename pcm_fmt<FMT>::type* __restrict__ src, int64_t src_bs, const int32_t* __restrict__ n_in, int N_cap, int U, int D,
     const float* __restrict__ taps, int K, int tile, int L_cap, float* __restrict__ work, int64_t wk_bs,
     float* __restrict__ sums, int nb_row) {
-  using VEC = typename in_src<FMT>::vec;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.y;
   const long long n = min(max(n_in[b], 0), N_cap);
@@ -58,55 +39,17 @@ __global__ __launch_bounds__(IN_THREADS) void ingest_resample_kernel(
   const long long j0 = (long long)blockIdx.x * tile;
   if (j0 >= m) return;
   const int len = (int)min((long long)tile, m - j0);
-  const int h = (K - 1) / 2;
-  const long long c0 = j0 * D / U;
-  const unsigned p0 = (unsigned)(j0 * D - c0 * U);
-  const long long i_lo = c0 - h;
-  const long long i_hi = c0 + ((long long)p0 + (long long)(len - 1) * D) / U - h + K - 1;  // the last input sample of the tile
-  const long long a0 = i_lo & ~3LL;  // floor to a multiple of 4, also for a negative start
-  const int n4 = (int)((i_hi - a0) / 4 + 1);
-  const int nt = U * K;
+  const pp_tile tg = pp_tile_of(j0, len, U, D, K);
 
   float* __restrict__ tab = lds;
-  float* __restrict__ xs = lds + in_round4(nt);
-  float* __restrict__ ys = xs + in_round4((int)in_span_cap(tile, U, D, K));
+  float* __restrict__ xs = lds + pp_round4(U * K);
+  float* __restrict__ ys = xs + pp_round4((int)pp_span_cap(tile, U, D, K));
   // -- 1. stage
-  for (int q = threadIdx.x; 4 * q + 4 <= nt; q += IN_THREADS) {
-    const f32x4_u a = *reinterpret_cast<const f32x4_u*>(taps + 4 * q);
-    *reinterpret_cast<float4*>(tab + 4 * q) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  }
-  if ((int)threadIdx.x < (nt & 3)) tab[(nt & ~3) + threadIdx.x] = taps[(nt & ~3) + threadIdx.x];
-  const typename in_src<FMT>::type* __restrict__ row = src + (int64_t)b * src_bs;
-  for (int q = threadIdx.x; q < n4; q += IN_THREADS) {
-    const long long i = a0 + 4LL * q;
-    float e[4];
-    if (i >= 0 && i + 4 <= n) {
-      const VEC a = *reinterpret_cast<const VEC*>(row + i);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) e[r] = in_cvt<FMT>(a.v[r]);
-    } else {  // an edge of the row: every sample on its own, loaded only where it is valid
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        e[r] = 0.0f;
-        if (i + r >= 0 && i + r < n) e[r] = in_cvt<FMT>(row[i + r]);
-      }
-    }
-    *reinterpret_cast<float4*>(xs + 4 * q) = make_float4(e[0], e[1], e[2], e[3]);
-  }
+  pp_stage_table(tab, taps, U * K);
+  pp_stage_span<FMT>(xs, src + (int64_t)b * src_bs, n, tg);
   __syncthreads();
   // -- 2. filter
-  const float* __restrict__ x0 = xs + (int)(i_lo - a0);
-  for (int jj = threadIdx.x; jj < tile; jj += IN_THREADS) {
-    float acc = 0.0f;
-    if (jj < len) {
-      const unsigned t = p0 + (unsigned)jj * (unsigned)D;  // < 2^21: jj < 1024, D <= 1024
-      const unsigned c = t / (unsigned)U;
-      const float* __restrict__ tp = tab + (t - c * (unsigned)U) * K;
-      const float* __restrict__ xp = x0 + c;
-      for (int k = 0; k < K; ++k) acc = fmaf(tp[k], xp[k], acc);
-    }
-    ys[jj] = acc;
-  }
+  for (int jj = threadIdx.x; jj < tile; jj += IN_THREADS) ys[jj] = jj < len ? pp_chain(tab, xs, tg, jj, U, D, K) : 0.0f;
   __syncthreads();
   // -- 3. store and block sums
   float* __restrict__ dst = work + (int64_t)b * wk_bs + j0;  // 16-byte aligned: wk_bs and j0 are multiples of 512
@@ -200,19 +143,10 @@ __global__ __launch_bounds__(IN_THREADS) void ingest_gather_kernel(const float* 
   const float* __restrict__ s = work + (int64_t)b * wk_bs + cut[b] + i;
   float* __restrict__ d = wave + (int64_t)b * w_bs + i;
   if (i + 4 <= L) {
-    const f32x4_u a = *reinterpret_cast<const f32x4_u*>(s);
-    *reinterpret_cast<float4*>(d) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
+    *reinterpret_cast<float4*>(d) = load_f32x4(s);
   } else {
     for (int r = 0; i + r < L; ++r) d[r] = s[r];
   }
-}
-
-template <int FMT>
-void launch_ingest(int gx, int B, size_t lds, hipStream_t s, const void* src, int64_t src_bs, const int32_t* n, int N_cap, int U,
-                   int D, const float* taps, int K, int tile, int L_cap, float* work, int64_t wk_bs, float* sums, int nb_row) {
-  hipLaunchKernelGGL((ingest_resample_kernel<FMT>), dim3(gx, B), dim3(IN_THREADS), lds, s,
-                     reinterpret_cast<const typename in_src<FMT>::type*>(src), src_bs, n, N_cap, U, D, taps, K, tile, L_cap, work,
-                     wk_bs, sums, nb_row);
 }
 
 }  // namespace
@@ -235,17 +169,13 @@ extern "C" int st2_clip_ingest(const void* src, int64_t src_bs, const int32_t* n
               (long long)w_bs, L_cap);
   ST2_REQUIRE(B == 1 || src_bs >= N_cap, "st2_clip_ingest: src_bs=%lld is less than the N_cap=%d samples of a row",
               (long long)src_bs, N_cap);
-  ST2_REQUIRE(up >= 1 && up <= 1024 && down >= 1 && down <= 1024, "st2_clip_ingest: bad ratio %d / %d (each 1..1024)", up, down);
-  ST2_REQUIRE(taps_per_phase >= 1 && taps_per_phase <= 512, "st2_clip_ingest: taps_per_phase=%d is outside 1..512",
-              taps_per_phase);
-  ST2_REQUIRE(fmt == ST2_PCM_F32 || fmt == ST2_PCM_S16 || fmt == ST2_PCM_ULAW || fmt == ST2_PCM_ALAW,
-              "st2_clip_ingest: unknown format %d", fmt);
+  if (pp_check("st2_clip_ingest", up, down, taps_per_phase, fmt)) return 1;
   ST2_REQUIRE(L_min >= 0 && L_min <= L_cap, "st2_clip_ingest: L_min=%d is outside 0..L_cap=%d", L_min, L_cap);
   ST2_REQUIRE(top_db == top_db, "st2_clip_ingest: top_db is NaN");
   const int64_t need = st2_clip_ingest_work_bytes(B, L_cap);
   ST2_REQUIRE(work_bytes >= need, "st2_clip_ingest: work_bytes=%lld is less than the %lld st2_clip_ingest_work_bytes asks for",
               (long long)work_bytes, (long long)need);
-  const int size = fmt == ST2_PCM_F32 ? 4 : (fmt == ST2_PCM_S16 ? 2 : 1);
+  const int size = pcm_sample_bytes(fmt);
   ST2_REQUIRE(reinterpret_cast<uintptr_t>(src) % size == 0 && reinterpret_cast<uintptr_t>(taps) % 4 == 0 &&
                   reinterpret_cast<uintptr_t>(wave) % 16 == 0 && reinterpret_cast<uintptr_t>(work) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(n) % 4 == 0 && reinterpret_cast<uintptr_t>(len) % 4 == 0,
@@ -253,7 +183,7 @@ extern "C" int st2_clip_ingest(const void* src, int64_t src_bs, const int32_t* n
   // the largest tile (a multiple of the trim's 512-sample hop) whose input span and output fit beside the table
   int tile = IN_TILE_MAX;
   auto lds_floats = [&](int t) {
-    return (long long)in_round4(up * taps_per_phase) + in_round4((int)in_span_cap(t, up, down, taps_per_phase)) + t;
+    return (long long)pp_round4(up * taps_per_phase) + pp_round4((int)pp_span_cap(t, up, down, taps_per_phase)) + t;
   };
   while (tile >= IN_HOP && lds_floats(tile) * 4 > IN_LDS_BYTES) tile /= 2;
   ST2_REQUIRE(tile >= IN_HOP, "st2_clip_ingest: a table of %d x %d taps at ratio %d / %d does not fit the %d bytes of LDS", up,
@@ -264,11 +194,11 @@ extern "C" int st2_clip_ingest(const void* src, int64_t src_bs, const int32_t* n
   float* rows = reinterpret_cast<float*>(work);
   float* sums = rows + (int64_t)B * wk_bs;
   int32_t* cut = reinterpret_cast<int32_t*>(sums + (int64_t)B * nb_row);
-  auto go = fmt == ST2_PCM_F32 ? launch_ingest<ST2_PCM_F32>
-            : fmt == ST2_PCM_S16 ? launch_ingest<ST2_PCM_S16>
-            : fmt == ST2_PCM_ULAW ? launch_ingest<ST2_PCM_ULAW> : launch_ingest<ST2_PCM_ALAW>;
-  go(st2_cdiv(L_cap, tile), B, (size_t)lds_floats(tile) * 4, s, src, src_bs, n, N_cap, up, down, taps, taps_per_phase, tile, L_cap,
-     rows, wk_bs, sums, nb_row);
+  pcm_dispatch(fmt, [&](auto f) {
+    hipLaunchKernelGGL((ingest_resample_kernel<f()>), dim3(st2_cdiv(L_cap, tile), B), dim3(IN_THREADS),
+                       (size_t)lds_floats(tile) * 4, s, reinterpret_cast<const typename pcm_fmt<f()>::type*>(src), src_bs, n, N_cap,
+                       up, down, taps, taps_per_phase, tile, L_cap, rows, wk_bs, sums, nb_row);
+  });
   ST2_CHECK_LAUNCH("st2_clip_ingest (resample)");
   const float threshold = top_db > 0.0f ? (float)pow(10.0, -(double)top_db / 10.0) : -1.0f;
   hipLaunchKernelGGL(ingest_bounds_kernel, dim3(B), dim3(IN_THREADS), 0, s, n, N_cap, up, down, L_cap, threshold, L_min, sums,

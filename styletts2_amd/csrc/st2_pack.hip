@@ -61,16 +61,15 @@ __global__ __launch_bounds__(PACK_THREADS) void wave_pack_kernel(const float* __
     if (v >= nvec) break;
     const long long i = head + v * V;
     if constexpr (V == 4) {
-      const f32x4_u a = *reinterpret_cast<const f32x4_u*>(src + i);
+      const float4 a = load_f32x4(src + i);
       uint4 o;
-      o.x = __float_as_uint(a.v[0]); o.y = __float_as_uint(a.v[1]); o.z = __float_as_uint(a.v[2]); o.w = __float_as_uint(a.v[3]);
+      o.x = __float_as_uint(a.x); o.y = __float_as_uint(a.y); o.z = __float_as_uint(a.z); o.w = __float_as_uint(a.w);
       *reinterpret_cast<uint4*>(dst + i) = o;
     } else {
-      const f32x4_u a = *reinterpret_cast<const f32x4_u*>(src + i);
-      const f32x4_u c = *reinterpret_cast<const f32x4_u*>(src + i + 4);
+      const float4 a = load_f32x4(src + i), c = load_f32x4(src + i + 4);
       auto two = [](float lo, float hi) { return (uint32_t)(uint16_t)pcm16(lo) | ((uint32_t)(uint16_t)pcm16(hi) << 16); };
       uint4 o;
-      o.x = two(a.v[0], a.v[1]); o.y = two(a.v[2], a.v[3]); o.z = two(c.v[0], c.v[1]); o.w = two(c.v[2], c.v[3]);
+      o.x = two(a.x, a.y); o.y = two(a.z, a.w); o.z = two(c.x, c.y); o.w = two(c.z, c.w);
       *reinterpret_cast<uint4*>(dst + i) = o;
     }
   }

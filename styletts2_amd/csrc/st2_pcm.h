@@ -1,7 +1,9 @@
 // What the packing entry points and the clip ingest share (st2_pack.hip: st2_wave_pack; st2_resample.hip:
 // st2_wave_resample_pack; st2_ingest.hip: st2_clip_ingest): a row's valid sample count, the row-offset scan, the packed source
-// vectors and the sample conversions, both ways.
+// vectors, the sample conversions, both ways, and the sample formats' types, size and dispatch.  The polyphase rule of the two
+// resamplers is st2_polyphase.h.
 #pragma once
+#include <type_traits>
 #include "st2_common.h"
 
 // n_b = max(0, spf * clamp(frames[b], 0, T_cap) - trim): the row's valid samples at the model rate
@@ -80,4 +82,47 @@ __device__ __forceinline__ int g711_alaw_decode(int code) {
   const int man = e > 0 ? (ix & 15) + 16 : (ix & 15);
   const int lin = ((man << 4) + 8) << (e > 0 ? e - 1 : 0);  // 8..32256
   return code > 127 ? lin : -lin;
+}
+
+// A sample format of st2.h as a type: what a sample is stored as, and four of them wherever a row of that type may start.
+template <int FMT> struct pcm_fmt { using type = float; using vec = f32x4_u; };
+template <> struct pcm_fmt<ST2_PCM_S16> { using type = int16_t; using vec = s16x4_u; };
+template <> struct pcm_fmt<ST2_PCM_ULAW> { using type = uint8_t; using vec = u8x4_u; };
+template <> struct pcm_fmt<ST2_PCM_ALAW> { using type = uint8_t; using vec = u8x4_u; };
+
+template <int FMT>
+__device__ __forceinline__ typename pcm_fmt<FMT>::type pcm_encode(float y) {
+  if constexpr (FMT == ST2_PCM_F32) return y;
+  else if constexpr (FMT == ST2_PCM_S16) return pcm16(y);
+  else if constexpr (FMT == ST2_PCM_ULAW) return g711_ulaw(pcm16(y));
+  else return g711_alaw(pcm16(y));
+}
+
+template <int FMT>
+__device__ __forceinline__ float pcm_decode(typename pcm_fmt<FMT>::type v) {
+  if constexpr (FMT == ST2_PCM_F32) return v;
+  else if constexpr (FMT == ST2_PCM_S16) return (float)v * (1.0f / 32768.0f);  // exact
+  else if constexpr (FMT == ST2_PCM_ULAW) return (float)g711_ulaw_decode(v) * (1.0f / 32768.0f);
+  else return (float)g711_alaw_decode(v) * (1.0f / 32768.0f);
+}
+
+// Four samples at an address aligned to their type only, with one load, decoded
+template <int FMT>
+__device__ __forceinline__ float4 pcm_decode4(const typename pcm_fmt<FMT>::type* __restrict__ p) {
+  const typename pcm_fmt<FMT>::vec a = *reinterpret_cast<const typename pcm_fmt<FMT>::vec*>(p);
+  return make_float4(pcm_decode<FMT>(a.v[0]), pcm_decode<FMT>(a.v[1]), pcm_decode<FMT>(a.v[2]), pcm_decode<FMT>(a.v[3]));
+}
+__device__ __forceinline__ float4 load_f32x4(const float* __restrict__ p) { return pcm_decode4<ST2_PCM_F32>(p); }
+
+inline int pcm_sample_bytes(int fmt) { return fmt == ST2_PCM_F32 ? 4 : (fmt == ST2_PCM_S16 ? 2 : 1); }
+
+// f(std::integral_constant<int, FMT>) for a format code of st2.h (checked by the caller)
+template <class F>
+inline void pcm_dispatch(int fmt, F&& f) {
+  switch (fmt) {
+    case ST2_PCM_F32: return f(std::integral_constant<int, ST2_PCM_F32>{});
+    case ST2_PCM_S16: return f(std::integral_constant<int, ST2_PCM_S16>{});
+    case ST2_PCM_ULAW: return f(std::integral_constant<int, ST2_PCM_ULAW>{});
+    default: return f(std::integral_constant<int, ST2_PCM_ALAW>{});
+  }
 }

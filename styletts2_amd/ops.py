@@ -1087,11 +1087,15 @@ def ragged_lengths(frames, T_max, coef):
     return out
 
 
-def _chk_dev(t, name, dtype, ndim):
-    """A non-fp32 device operand of the sync-free entry points: on a HIP device, of `dtype`, `ndim`-D and contiguous."""
+def _chk_on_dev(t, name):
     if not torch.is_tensor(t) or not t.is_cuda:
         raise _lib.St2Error("%s must live on a HIP device (got %s); the engine has no CPU path" % (
             name, t.device if torch.is_tensor(t) else type(t).__name__))
+
+
+def _chk_dev(t, name, dtype, ndim):
+    """A non-fp32 device operand of the sync-free entry points: on a HIP device, of `dtype`, `ndim`-D and contiguous."""
+    _chk_on_dev(t, name)
     if t.dtype != dtype or t.dim() != ndim or not t.is_contiguous():
         raise _lib.St2Error("%s must be a contiguous %d-D %s tensor (got %s %s)" % (name, ndim, dtype, t.dtype, tuple(t.shape)))
 
@@ -1113,15 +1117,10 @@ def frames_from_durations(dur, lengths_dev, T_cap):
 PACK_FORMATS = {"f32": (_lib.PACK_F32, torch.float32), "s16": (_lib.PACK_S16, torch.int16)}
 
 
-def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_per_frame=600):
-    """`st2_wave_pack`: wave [B, 1, L] or [B, L] (L a multiple of `samples_per_frame`: the batch's frame capacity), frames
-    int32 [B] on the device -> (packed, offsets): the first max(0, samples_per_frame * frames[b] - trim) samples of every row,
-    back to back, as int16 PCM ("s16": rint(clamp(x, -1, 1) * 32767), NaN -> 0) or fp32 ("f32": a copy), and their int64
-    [B + 1] exclusive prefix sum on the device (offsets[B] = the total).  `out` (1-D, of the format's dtype) bounds what is
-    written: nothing at or past min(offsets[B], out.numel()); by default it holds every row at capacity.  No host read."""
-    if fmt not in PACK_FORMATS:
-        raise ValueError("fmt must be one of %s, got %r" % (sorted(PACK_FORMATS), fmt))
-    code, dtype = PACK_FORMATS[fmt]
+def _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, out_samples):
+    """The operand work of the packing wrappers: wave [B, 1, L] or [B, L] flattened to [B, L], L a whole number of frames;
+    frames, `out` (default: B * out_samples(L) entries of `dtype`) and `offsets` checked.
+    -> (wave, frames pointer, B, L, samples per frame, out, offsets)"""
     lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
     _chk(wave, "wave")
     if wave.dim() == 3 and wave.shape[1] == 1:
@@ -1131,22 +1130,44 @@ def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_p
     spf = int(samples_per_frame)
     if spf <= 0 or L < spf or L % spf:
         raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
-    lib = _lib.load()
     if out is None:
-        out = torch.empty((B * L,), device=wave.device, dtype=dtype)
+        out = torch.empty((B * out_samples(L),), device=wave.device, dtype=dtype)
     _chk_dev(out, "out", dtype, 1)
     if offsets is None:
         offsets = torch.empty((B + 1,), device=wave.device, dtype=torch.int64)
     _chk_dev(offsets, "offsets", torch.int64, 1)
     if offsets.numel() != B + 1 or out.device != wave.device or offsets.device != wave.device:
         raise _lib.St2Error("offsets must hold %d entries; out / offsets must live on the device of wave" % (B + 1))
-    _lib.check(lib.st2_wave_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), code, out.data_ptr(),
-                                 out.numel(), offsets.data_ptr(), _stream()), "st2_wave_pack")
+    return wave, lp, B, L, spf, out, offsets
+
+
+def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_per_frame=600):
+    """`st2_wave_pack`: wave [B, 1, L] or [B, L] (L a multiple of `samples_per_frame`: the batch's frame capacity), frames
+    int32 [B] on the device -> (packed, offsets): the first max(0, samples_per_frame * frames[b] - trim) samples of every row,
+    back to back, as int16 PCM ("s16": rint(clamp(x, -1, 1) * 32767), NaN -> 0) or fp32 ("f32": a copy), and their int64
+    [B + 1] exclusive prefix sum on the device (offsets[B] = the total).  `out` (1-D, of the format's dtype) bounds what is
+    written: nothing at or past min(offsets[B], out.numel()); by default it holds every row at capacity.  No host read."""
+    if fmt not in PACK_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(PACK_FORMATS), fmt))
+    code, dtype = PACK_FORMATS[fmt]
+    wave, lp, B, L, spf, out, offsets = _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, lambda L: L)
+    _lib.check(_lib.load().st2_wave_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), code, out.data_ptr(),
+                                         out.numel(), offsets.data_ptr(), _stream()), "st2_wave_pack")
     return out, offsets
 
 
 OUTPUT_FORMATS = {"f32": (_lib.PCM_F32, torch.float32), "s16": (_lib.PCM_S16, torch.int16),
                   "ulaw": (_lib.PCM_ULAW, torch.uint8), "alaw": (_lib.PCM_ALAW, torch.uint8)}
+
+
+def _pcm_format(fmt, rate):
+    """(format code, dtype) of a sample format of OUTPUT_FORMATS at a rate of `resample.RATES`; ValueError for any other."""
+    from . import resample
+    if fmt not in OUTPUT_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
+    if rate not in resample.RATES:
+        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
+    return OUTPUT_FORMATS[fmt]
 
 
 def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=None, samples_per_frame=600):
@@ -1159,33 +1180,14 @@ def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=
     holds every row at capacity, ceil(L U / D) samples each.  No host read; the first call for a (rate, device) designs and
     uploads the table, which therefore must not happen under stream capture."""
     from . import resample
-    if fmt not in OUTPUT_FORMATS:
-        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
-    code, dtype = OUTPUT_FORMATS[fmt]
-    if rate not in resample.RATES:
-        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
-    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
-    _chk(wave, "wave")
-    if wave.dim() == 3 and wave.shape[1] == 1:
-        wave = wave[:, 0]
-    _chk(wave, "wave", 2)
-    B, L = wave.shape
-    spf = int(samples_per_frame)
-    if spf <= 0 or L < spf or L % spf:
-        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
-    lib = _lib.load()
-    U, D, K, taps = resample.table(rate, wave.device)
-    if out is None:
-        out = torch.empty((B * resample.output_samples(L, U, D),), device=wave.device, dtype=dtype)
-    _chk_dev(out, "out", dtype, 1)
-    if offsets is None:
-        offsets = torch.empty((B + 1,), device=wave.device, dtype=torch.int64)
-    _chk_dev(offsets, "offsets", torch.int64, 1)
-    if offsets.numel() != B + 1 or out.device != wave.device or offsets.device != wave.device:
-        raise _lib.St2Error("offsets must hold %d entries; out / offsets must live on the device of wave" % (B + 1))
-    _lib.check(lib.st2_wave_resample_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D,
-                                          taps.data_ptr(), K, code, out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()),
-               "st2_wave_resample_pack")
+    code, dtype = _pcm_format(fmt, rate)
+    table = lambda: resample.table(rate, wave.device)  # first asked for once `wave` is known to live on a device
+    wave, lp, B, L, spf, out, offsets = _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets,
+                                                       lambda L: resample.output_samples(L, *table()[:2]))
+    U, D, K, taps = table()
+    _lib.check(_lib.load().st2_wave_resample_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D,
+                                                  taps.data_ptr(), K, code, out.data_ptr(), out.numel(), offsets.data_ptr(),
+                                                  _stream()), "st2_wave_resample_pack")
     return out, offsets
 
 
@@ -1201,15 +1203,9 @@ def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, w
     aligned.  No host read; the first call for a (rate, device) designs and uploads the table, which therefore must not happen
     under stream capture."""
     from . import resample
-    if fmt not in OUTPUT_FORMATS:
-        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
-    code, dtype = OUTPUT_FORMATS[fmt]
-    if rate not in resample.RATES:
-        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
+    code, dtype = _pcm_format(fmt, rate)
     lp = _chk_len(n, "n", _nb(src, 2), src)
-    if not torch.is_tensor(src) or not src.is_cuda:
-        raise _lib.St2Error("src must live on a HIP device (got %s); the engine has no CPU path" % (
-            src.device if torch.is_tensor(src) else type(src).__name__))
+    _chk_on_dev(src, "src")
     if src.dtype != dtype or src.dim() != 2 or (src.shape[1] > 1 and src.stride(1) != 1):
         raise _lib.St2Error("src must be a 2-D %s tensor with unit stride along its rows for fmt %r (got %s %s)"
                             % (dtype, fmt, src.dtype, tuple(src.shape)))

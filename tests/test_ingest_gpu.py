@@ -136,6 +136,55 @@ def test_a_table_that_leaves_room_for_a_512_sample_tile_only():
     _check_rows(room.cpu().numpy(), ln.cpu().tolist(), st.cpu().tolist(), fl.cpu().tolist(), rows, "512-sample tiles")
 
 
+@pytest.mark.parametrize("U,D", [(3, 2), (147, 160)])
+def test_one_table_through_the_way_in_and_the_way_out_gives_the_same_bits(U, D):
+    """`st2_clip_ingest` (not cut: top_db = 0, L_min = 0) and `st2_wave_resample_pack` (F32, trim = 0) on the same fp32 rows,
+    ratio and table: both are section 15's chain -- fmaf from 0, k ascending, selected zeros outside the row -- so every valid
+    sample agrees bitwise, whatever the tiles: 1024 samples from the row's start on the way in, from the 16-byte grid of a
+    destination one float off it on the way out.  Straight through the C entry points."""
+    K, SPF, T_CAP, frames = 16, 600, 5, [5, 3, 1]
+    rng = np.random.default_rng(U)
+    taps = (rng.standard_normal((U, K)) / K).astype(np.float32)
+    n = [SPF * f for f in frames]
+    N_cap = SPF * T_CAP
+    x = (0.5 * rng.standard_normal((3, N_cap))).astype(np.float32)
+    for b, nb in enumerate(n):
+        x[b, nb:] = np.nan
+    m = [resample.output_samples(nb, U, D) for nb in n]
+    L_cap = m[0]
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    src, td = torch.from_numpy(x).to(DEV), torch.from_numpy(taps).to(DEV)
+    # the way in
+    w_bs = (L_cap + 3) // 4 * 4
+    room = torch.full((3, w_bs), SENTINEL, device=DEV)
+    nd = torch.tensor(n, dtype=torch.int32, device=DEV)
+    ln, st, fl = (torch.empty(3, dtype=torch.int32, device=DEV) for _ in range(3))
+    nbytes = lib.st2_clip_ingest_work_bytes(3, L_cap)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    _lib.check(lib.st2_clip_ingest(src.data_ptr(), N_cap, nd.data_ptr(), 3, N_cap, _lib.PCM_F32, U, D, td.data_ptr(), K, 0.0, 0,
+                                   room.data_ptr(), w_bs, L_cap, ln.data_ptr(), st.data_ptr(), fl.data_ptr(), work.data_ptr(),
+                                   nbytes, stream), "st2_clip_ingest")
+    # the way out
+    packed = torch.full((1 + sum(m) + 8,), SENTINEL, device=DEV)
+    out = packed[1:]
+    assert out.data_ptr() % 16 == 4, "row 0 starts off the 16-byte grid: its tiles are not those of the way in"
+    fd = torch.tensor(frames, dtype=torch.int32, device=DEV)
+    offs = torch.empty(4, dtype=torch.int64, device=DEV)
+    _lib.check(lib.st2_wave_resample_pack(src.data_ptr(), N_cap, fd.data_ptr(), 3, T_CAP, SPF, 0, U, D, td.data_ptr(), K,
+                                          _lib.PCM_F32, out.data_ptr(), out.numel(), offs.data_ptr(), stream),
+               "st2_wave_resample_pack")
+    torch.cuda.synchronize()
+    o = offs.cpu().tolist()
+    assert ln.cpu().tolist() == m and st.cpu().tolist() == [0, 0, 0] and fl.cpu().tolist() == [0, 0, 0]
+    assert o == [0, m[0], m[0] + m[1], sum(m)] and m[0] > 2 * 1024 and m[2] < 1024, "rows of several tiles and of one"
+    way_in, way_out = room.cpu().numpy(), out.cpu().numpy()
+    assert np.isfinite(way_out[:o[3]]).all() and (way_out[o[3]:] == np.float32(SENTINEL)).all()
+    for b in range(3):
+        assert np.array_equal(way_in[b, :m[b]].view(np.int32), way_out[o[b]:o[b + 1]].view(np.int32)), "row %d" % b
+        assert (way_in[b, m[b]:] == np.float32(SENTINEL)).all()
+
+
 # ---- trim, minimum length, capacity --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rate,fmt", I.TRIM_RATES)
 def test_trim_bounds_are_exact_and_the_samples_hold_the_bound(rate, fmt):
