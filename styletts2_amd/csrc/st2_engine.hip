@@ -855,6 +855,23 @@ void conv1d_direct(Ctx& c, const View& x, const float* w, const float* bias, con
     RUN(c, g_be.conv1d_direct(x.p, x.bs, x.cs, w, bias, y.p, y.bs, y.cs, x.B, x.C, y.C, x.L, y.L, ks, stride, pad, c.stream));
 }
 
+// The style encoder's map kernels on [B][H][C][W] maps (strides in elements); w_len: maps of w_len[b] <= W columns
+void avgpool2x2(Ctx& c, const float* x, int64_t x_bs, int64_t x_hs, int x_cs, int B, int C, int H, int W, float* y, int64_t y_bs,
+                int64_t y_hs, int y_cs, const int32_t* w_len) {
+  if (w_len)
+    RUN(c, g_be.avgpool2x2_len(x, x_bs, x_hs, x_cs, B, C, H, W, y, y_bs, y_hs, y_cs, w_len, c.stream));
+  else
+    RUN(c, g_be.avgpool2x2(x, x_bs, x_hs, x_cs, B, C, H, W, y, y_bs, y_hs, y_cs, c.stream));
+}
+
+void dwconv3x3s2(Ctx& c, const float* x, int64_t x_bs, int64_t x_hs, int x_cs, const float* w, const float* bias, int B, int C,
+                 int H, int W, float* y, int64_t y_bs, int64_t y_hs, int y_cs, const int32_t* w_len) {
+  if (w_len)
+    RUN(c, g_be.dwconv3x3s2_len(x, x_bs, x_hs, x_cs, w, bias, B, C, H, W, y, y_bs, y_hs, y_cs, w_len, c.stream));
+  else
+    RUN(c, g_be.dwconv3x3s2(x, x_bs, x_hs, x_cs, w, bias, B, C, H, W, y, y_bs, y_hs, y_cs, c.stream));
+}
+
 // AdaIN + LeakyReLU + the depthwise x2 up-sampling pool: y [B][C][2 L]
 void adain_leaky_pool(Ctx& c, const View& x, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
                       float slope, const float* w, const float* bias, const View& y) {
@@ -1338,9 +1355,38 @@ extern "C" int st2_bert_forward(st2_engine* e, const int64_t* tokens, const int3
   });
 }
 
-extern "C" int64_t st2_style_workspace_bytes(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T) {
+namespace {
+// st2_style_workspace_bytes and, after its own check of the stacked rows, st2_style_workspace_bytes_ragged
+int64_t style_workspace_bytes(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T, bool ragged) {
   if (!e || which < 0 || which > 1 || !e->style[which].ready || B <= 0 || n_mels != 80 || T < 80) return -1;
-  return workspace_query([&](Ctx& c) { style_plan(c, *e, e->style[which], nullptr, B, n_mels, T, nullptr); });
+  if (ragged && (int64_t)B * (n_mels + 2) - 2 > 65535) return -1;
+  const int32_t unread = 0;  // a dry walk launches nothing: the pointer only selects the ragged layout
+  int rc = 0;
+  const int64_t bytes = workspace_query(
+      [&](Ctx& c) { rc = style_plan(c, *e, e->style[which], nullptr, ragged ? &unread : nullptr, B, n_mels, T, nullptr); });
+  return ragged && rc != 0 ? -1 : bytes;  // ragged: a batch too large for one of its stacked launches
+}
+
+// st2_style_forward (mel_len == NULL) after its first three checks and st2_style_forward_ragged after its six
+int style_forward(const char* fn, const char* query, st2_engine* e, int32_t which, const float* mel, const int32_t* mel_len,
+                  int32_t B, int32_t n_mels, int32_t T, float* style, void* workspace, int64_t workspace_bytes, void* stream) {
+  return run_forward(fn, query, workspace, workspace_bytes, stream, [&](Ctx& c) {
+    // ragged: the plan once without launches, so that a batch one of its stacked launches cannot hold fails here, with nothing queued
+    if (mel_len) {
+      Ctx dry = Ctx::dry_run();
+      if (style_plan(dry, *e, e->style[which], nullptr, mel_len, B, n_mels, T, nullptr) != 0) return 1;
+    }
+    return style_plan(c, *e, e->style[which], mel, mel_len, B, n_mels, T, style);
+  });
+}
+}  // namespace
+
+extern "C" int64_t st2_style_workspace_bytes(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T) {
+  return style_workspace_bytes(e, which, B, n_mels, T, false);
+}
+
+extern "C" int64_t st2_style_workspace_bytes_ragged(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T_cap) {
+  return style_workspace_bytes(e, which, B, n_mels, T_cap, true);
 }
 
 extern "C" int st2_style_forward(st2_engine* e, int32_t which, const float* mel, int32_t B, int32_t n_mels, int32_t T,
@@ -1349,17 +1395,8 @@ extern "C" int st2_style_forward(st2_engine* e, int32_t which, const float* mel,
   ST2_REQUIRE(mel && style && workspace && B > 0, "st2_style_forward: bad arguments");
   ST2_REQUIRE(n_mels == 80 && T >= 80, "st2_style_forward: needs an 80-bin mel of >= 80 frames (four halvings, then the 5x5 "
               "valid conv), got %d x %d", n_mels, T);
-  return run_forward("st2_style_forward", "st2_style_workspace_bytes", workspace, workspace_bytes, stream,
-                     [&](Ctx& c) { return style_plan(c, *e, e->style[which], mel, B, n_mels, T, style); });
-}
-
-extern "C" int64_t st2_style_workspace_bytes_ragged(st2_engine* e, int32_t which, int32_t B, int32_t n_mels, int32_t T_cap) {
-  if (!e || which < 0 || which > 1 || !e->style[which].ready || B <= 0 || n_mels != 80 || T_cap < 80) return -1;
-  if ((int64_t)B * (n_mels + 2) - 2 > 65535) return -1;
-  int rc = 0;
-  const int64_t bytes = workspace_query(
-      [&](Ctx& c) { rc = style_plan_ragged(c, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr); });
-  return rc != 0 ? -1 : bytes;  // batch too large
+  return style_forward("st2_style_forward", "st2_style_workspace_bytes", e, which, mel, nullptr, B, n_mels, T, style, workspace,
+                       workspace_bytes, stream);
 }
 
 extern "C" int st2_style_forward_ragged(st2_engine* e, int32_t which, const float* mel, const int32_t* mel_len, int32_t B,
@@ -1374,12 +1411,8 @@ extern "C" int st2_style_forward_ragged(st2_engine* e, int32_t which, const floa
   ST2_REQUIRE((int64_t)B * (n_mels + 2) - 2 <= 65535, "st2_style_forward_ragged: B=%d clips stack to more than 65535 conv rows", B);
   ST2_REQUIRE(e && which >= 0 && which <= 1 && e->style[which].ready, "st2_style_forward_ragged: style-encoder weights not finalized");
   ST2_REQUIRE(mel && style && workspace, "st2_style_forward_ragged: bad arguments");
-  return run_forward("st2_style_forward_ragged", "st2_style_workspace_bytes_ragged", workspace, workspace_bytes, stream, [&](Ctx& c) {
-    // the plan once without launches: a batch one of its stacked launches cannot hold fails here, with nothing queued
-    Ctx dry = Ctx::dry_run();
-    if (style_plan_ragged(dry, *e, e->style[which], nullptr, nullptr, B, n_mels, T_cap, nullptr) != 0) return 1;
-    return style_plan_ragged(c, *e, e->style[which], mel, mel_len, B, n_mels, T_cap, style);
-  });
+  return style_forward("st2_style_forward_ragged", "st2_style_workspace_bytes_ragged", e, which, mel, mel_len, B, n_mels, T_cap,
+                       style, workspace, workspace_bytes, stream);
 }
 
 extern "C" int st2_sizeof_front_args(void) { return (int)sizeof(st2_front_args); }

@@ -82,194 +82,115 @@ int pack_style(st2_engine& e, Blob& blob, int which, std::string* err) {
   return 0;
 }
 
-int style_plan(Ctx& c, const st2_engine& e, const PStyleEnc& s, const float* mel, int B, int H, int W, float* out) {
-  // [B][h + 2][ch][w] map whose rows 0 and h + 1 are zero (the rows 1 .. h are written by the producing kernel)
-  auto new_map = [&](int h, int ch, int w) -> float* {
-    float* p = c.a.f32((int64_t)B * (h + 2) * ch * w);
-    for (int r : {0, h + 1})
-      RUN(c, g_be.broadcast_cols(e.F(e.zeros), 0, p + (int64_t)r * ch * w, (int64_t)(h + 2) * ch * w, w, B, ch, w, c.stream));
-    return p;
-  };
-  // rows r0 .. r0 + k - 1 of utterance b's padded map stacked along the channels: [h][k * ch][w] (overlapping view)
-  auto rows = [&](float* P, int b, int h, int ch, int w, int k, int r0) {
-    View v;
-    v.p = P + (int64_t)b * (h + 2) * ch * w + (int64_t)r0 * ch * w;
-    v.B = h; v.C = k * ch; v.L = w; v.bs = (int64_t)ch * w; v.cs = w;  // k = 3 from row 0 / k = 1 from row 1: h image rows
-    return v;
-  };
-  auto plain = [&](float* p, int b, int h, int ch, int w) {  // [h][ch][w] of utterance b in an unpadded [B][h][ch][w] buffer
-    View v;
-    v.p = p + (int64_t)b * h * ch * w;
-    v.B = h; v.C = ch; v.L = w; v.bs = (int64_t)ch * w; v.cs = w;
-    return v;
-  };
-  float* m0 = new_map(H, 1, W);
-  RUN(c, g_be.copy_ncl(mel, (int64_t)H * W, W, m0 + W, (int64_t)(H + 2) * W, W, B, H, W, c.stream));
-  int C = s.c0;
-  float* P = new_map(H, C, W);
-  for (int b = 0; b < B; ++b) {
-    const View x = rows(m0, b, H, 1, W, 3, 0);
-    RUN(c, g_be.conv1d_direct(x.p, x.bs, x.cs, e.F(s.w0), e.F(s.b0), P + (int64_t)b * (H + 2) * C * W + (int64_t)C * W,
-                              (int64_t)C * W, W, H, 3, C, W, W, 3, 1, 1, c.stream));
-  }
-  for (const PStyleBlk& blk : s.blocks) {
-    const int Co = blk.c_out, Ho = H / 2, Wo = (W + 1) / 2;
-    // shortcut: 1x1 conv at full resolution, then the 2x2 average (models.py:118-123)
-    float* SC = c.a.f32((int64_t)B * Ho * Co * Wo);
-    if (blk.has_sc) {
-      float* S = c.a.f32((int64_t)B * H * Co * W);
-      for (int b = 0; b < B; ++b) conv(c, e, rows(P, b, H, C, W, 1, 1), blk.wsc, plain(S, b, H, Co, W), ConvOpt());
-      RUN(c, g_be.avgpool2x2(S, (int64_t)H * Co * W, (int64_t)Co * W, W, B, Co, H, W, SC, (int64_t)Ho * Co * Wo, (int64_t)Co * Wo,
-                             Wo, c.stream));
-    } else {
-      RUN(c, g_be.avgpool2x2(P + (int64_t)C * W, (int64_t)(H + 2) * C * W, (int64_t)C * W, W, B, C, H, W, SC,
-                             (int64_t)Ho * Co * Wo, (int64_t)Co * Wo, Wo, c.stream));
-    }
-    // residual: leaky -> conv1 3x3 -> depthwise stride-2 3x3 -> leaky -> conv2 3x3 (models.py:125-135)
-    float* R1 = c.a.f32((int64_t)B * H * C * W);
-    for (int b = 0; b < B; ++b) {
-      ConvOpt o;
-      o.pad_left = 1; o.bias = e.F(blk.b1); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f;
-      conv(c, e, rows(P, b, H, C, W, 3, 0), blk.w1, plain(R1, b, H, C, W), o);
-    }
-    float* P2 = new_map(Ho, C, Wo);
-    RUN(c, g_be.dwconv3x3s2(R1, (int64_t)H * C * W, (int64_t)C * W, W, e.F(blk.wd), e.F(blk.bd), B, C, H, W, P2 + (int64_t)C * Wo,
-                            (int64_t)(Ho + 2) * C * Wo, (int64_t)C * Wo, Wo, c.stream));
-    float* Pn = new_map(Ho, Co, Wo);
-    for (int b = 0; b < B; ++b) {  // (shortcut + residual) / sqrt(2) in the epilogue
-      ConvOpt o;
-      o.pad_left = 1; o.bias = e.F(blk.b2); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f;
-      o.res = plain(SC, b, Ho, Co, Wo); o.div = (float)sqrt(2.0);
-      View y = rows(Pn, b, Ho, Co, Wo, 1, 1);
-      conv(c, e, rows(P2, b, Ho, C, Wo, 3, 0), blk.w2, y, o);
-    }
-    P = Pn; H = Ho; W = Wo; C = Co;
-  }
-  // LeakyReLU -> 5x5 valid conv -> global average -> LeakyReLU -> Linear (models.py:151-163)
-  const int Cl = s.c_last, Wf = W - 4;
-  float* Fm = c.a.f32((int64_t)B * Cl * Wf);
-  for (int b = 0; b < B; ++b) {
-    View x;
-    x.p = P + (int64_t)b * (H + 2) * C * W + (int64_t)C * W;
-    x.B = 1; x.C = 5 * C; x.L = W; x.bs = (int64_t)5 * C * W; x.cs = W;
-    View y;
-    y.p = Fm + (int64_t)b * Cl * Wf;
-    y.B = 1; y.C = Cl; y.L = Wf; y.bs = (int64_t)Cl * Wf; y.cs = Wf;
-    ConvOpt o;
-    o.bias = e.F(s.b5); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f;
-    conv(c, e, x, s.w5, y, o);
-  }
-  float* m = c.a.f32((int64_t)B * Cl);
-  RUN(c, g_be.mean_tokens_len(Fm, (int64_t)Cl * Wf, Wf, m, Cl, B, Cl, Wf, nullptr, c.stream));
-  {
-    View x, y;
-    x.p = m; x.B = B; x.C = Cl; x.L = 1; x.bs = Cl; x.cs = 1;
-    y.p = out; y.B = B; y.C = s.style_dim; y.L = 1; y.bs = s.style_dim; y.cs = 1;
-    ConvOpt o;
-    o.bias = e.F(s.bl); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f;
-    conv(c, e, x, s.wl, y, o);
-  }
-  return c.rc;
-}
+// One 2-D feature map of the plan, [B][h (+ 2)][ch][w]: p is row 1 of a padded map (image row 0 of clip 0) or the start of an
+// unpadded one, bs the stride between clips.
+struct StyleMap {
+  float* p = nullptr;
+  int64_t bs = 0;
+  int h = 0, ch = 0, w = 0;
+  int64_t row() const { return (int64_t)ch * w; }
+};
 
-// ------------------------------------------------------------------------------------------------------------------
-// ragged style plan == style_plan on B clips of unequal width in one [B][H][W] buffer (W = the capacity), row b as the clip
-// alone: every Conv2d ONE launch over the B (h + 2) - 2 stacked rows of the padded maps.  Three consecutive padded rows are a
-// conv's input channels whichever clip they belong to; a stacked row whose centre is an image row of clip b gets
-// x_len = y_len = that clip's width, one whose centre is a zero row between two clips (a seam) gets 0: its tiles exit before
-// any barrier and store nothing, so the zero rows stay zero.  Buffers the uniform plan keeps unpadded (S, R1, SC) take the
-// padded row stride here, so that one base pointer and one row stride describe the whole batch.
-// ------------------------------------------------------------------------------------------------------------------
-int style_plan_ragged(Ctx& c, const st2_engine& e, const PStyleEnc& s, const float* mel, const int32_t* mel_len, int B, int H,
-                      int W, float* out) {
+// Uniform batch (mel_len == NULL): every Conv2d once per clip, on the h image rows of that clip; the buffers that are no conv's
+// 3-row input (the shortcut before and after its pool, conv1's output) are unpadded [B][h][ch][w].  Plain backend slots only.
+//
+// Ragged batch (mel_len: int32 [B] frame counts on the device; W = the capacity), row b as the clip alone: every Conv2d ONE
+// launch over the B (h + 2) - 2 stacked rows of the padded maps.  Three consecutive padded rows are a conv's input channels
+// whichever clip they belong to; a stacked row whose centre is an image row of clip b gets x_len = y_len = that clip's width,
+// one whose centre is a zero row between two clips (a seam) gets 0: its tiles exit before any barrier and store nothing, so the
+// zero rows stay zero.  Every buffer takes the padded row stride, so that one base pointer and one row stride describe the whole
+// batch; the map kernels get the clips' widths.  A dry walk reads no lengths: any non-null mel_len selects this layout.
+int style_plan(Ctx& c, const st2_engine& e, const PStyleEnc& s, const float* mel, const int32_t* mel_len, int B, int H, int W,
+               float* out) {
   constexpr int S = 4;  // down-sampling stages (pack_style checks the block count)
-  // length tables (st2.h st2_style_lengths): per clip W_0 .. W_4 and W_4 - 4, then one per-stacked-row table per stage
-  const int64_t n_tab = st2_style_lengths_count(B, H, S);
-  int32_t* tab = static_cast<int32_t*>(c.a.alloc(n_tab * 4));
-  RUN(c, g_be.style_lengths(mel_len, B, 80, W, H, S, tab, c.stream));
-  const int32_t* wlen[S + 2];
-  const int32_t* rlen[S + 1];
-  for (int i = 0; i < S + 2; ++i) wlen[i] = tab + (int64_t)i * B;
-  {
+  const bool ragged = mel_len != nullptr;
+  // ragged only -- length tables (st2.h st2_style_lengths): per clip W_0 .. W_4 and W_4 - 4, then one per-stacked-row table per stage
+  const int32_t* wlen[S + 2] = {};
+  const int32_t* rlen[S + 1] = {};
+  if (ragged) {
+    int32_t* tab = static_cast<int32_t*>(c.a.alloc(st2_style_lengths_count(B, H, S) * 4));
+    RUN(c, g_be.style_lengths(mel_len, B, 80, W, H, S, tab, c.stream));
+    for (int i = 0; i < S + 2; ++i) wlen[i] = tab + (int64_t)i * B;
     int64_t off = (int64_t)(S + 2) * B;
     for (int i = 0; i <= S; ++i) {
       rlen[i] = tab + off;
       off += (int64_t)B * ((H >> i) + 2) - 2;
     }
   }
-  auto new_map = [&](int h, int ch, int w) -> float* {  // as in style_plan: rows 0 and h + 1 of every clip are zero
-    float* p = c.a.f32((int64_t)B * (h + 2) * ch * w);
-    for (int r : {0, h + 1})
-      RUN(c, g_be.broadcast_cols(e.F(e.zeros), 0, p + (int64_t)r * ch * w, (int64_t)(h + 2) * ch * w, w, B, ch, w, c.stream));
-    return p;
+  // a map whose rows 0 and h + 1 are zero in every clip (the rows 1 .. h are written by the producing kernel): a 3x3 conv's input
+  auto new_map = [&](int h, int ch, int w) {
+    StyleMap m{c.a.f32((int64_t)B * (h + 2) * ch * w), (int64_t)(h + 2) * ch * w, h, ch, w};
+    for (int r : {0, h + 1}) RUN(c, g_be.broadcast_cols(e.F(e.zeros), 0, m.p + r * m.row(), m.bs, w, B, ch, w, c.stream));
+    m.p += m.row();
+    return m;
   };
-  // padded rows r0 + r .. r0 + r + k - 1 of the whole [B (h + 2)][ch][w] stack as the channels of stacked row r:
-  // k = 3 from row 0 (a 3x3 conv's input) and k = 1 from row 1 (its output, a 1x1 conv's input) have the same centre row r + 1
-  auto stack = [&](float* P, int h, int ch, int w, int k, int r0, const int32_t* len) {
+  // a map that is never a 3x3 conv's input: unpadded, or (ragged) padded like the others with its outer rows left unwritten
+  auto scratch = [&](int h, int ch, int w) {
+    const int pad = ragged ? 2 : 0;
+    StyleMap m{c.a.f32((int64_t)B * (h + pad) * ch * w), (int64_t)(h + pad) * ch * w, h, ch, w};
+    m.p += (pad / 2) * m.row();
+    return m;
+  };
+  // k rows around each row of m stacked along the channels (k = 3: a 3x3 conv's input, from the row above; k = 1: the row
+  // itself): [h][k ch][w] of clip b (overlapping view), or (ragged, len = the stage's row table) of the whole stack
+  auto rows = [&](const StyleMap& m, int k, int b, const int32_t* len) {
     View v;
-    v.p = P + (int64_t)r0 * ch * w;
-    v.B = B * (h + 2) - 2; v.C = k * ch; v.L = w; v.bs = (int64_t)ch * w; v.cs = w; v.len = len;
+    v.p = m.p - (k / 2) * m.row() + (ragged ? 0 : b * m.bs);
+    v.B = ragged ? B * (m.h + 2) - 2 : m.h;
+    v.C = k * m.ch; v.L = m.w; v.bs = m.row(); v.cs = m.w; v.len = len;
     return v;
   };
-  float* m0 = new_map(H, 1, W);
-  RUN(c, g_be.copy_ncl(mel, (int64_t)H * W, W, m0 + W, (int64_t)(H + 2) * W, W, B, H, W, c.stream));
-  int C = s.c0;
-  float* P = new_map(H, C, W);
-  {
-    const View x = stack(m0, H, 1, W, 3, 0, rlen[0]);
-    RUN(c, g_be.conv1d_direct_len(x.p, x.bs, x.cs, e.F(s.w0), e.F(s.b0), P + (int64_t)C * W, (int64_t)C * W, W, x.B, 3, C, W, W, 3,
-                                  1, 1, rlen[0], rlen[0], c.stream));
-  }
+  const int launches = ragged ? 1 : B;  // per Conv2d
+  // the Conv2d wt over all clips: k stacked rows of x -> y, res (optional) added in the epilogue
+  auto conv2d = [&](const StyleMap& x, int k, const SplitW& wt, const StyleMap& y, ConvOpt o, const StyleMap* res,
+                    const int32_t* len) {
+    o.split_rows = ragged ? x.h : 0;
+    for (int b = 0; b < launches; ++b) {
+      if (res) o.res = rows(*res, 1, b, nullptr);
+      conv(c, e, rows(x, k, b, len), wt, rows(y, 1, b, len), o);
+    }
+  };
+  StyleMap m0 = new_map(H, 1, W);
+  RUN(c, g_be.copy_ncl(mel, (int64_t)H * W, W, m0.p, m0.bs, W, B, H, W, c.stream));
+  StyleMap P = new_map(H, s.c0, W);
+  for (int b = 0; b < launches; ++b)
+    conv1d_direct(c, rows(m0, 3, b, rlen[0]), e.F(s.w0), e.F(s.b0), rows(P, 1, b, rlen[0]), 3, 1, 1);
   int st = 0;
   for (const PStyleBlk& blk : s.blocks) {
-    const int Co = blk.c_out, Ho = H / 2, Wo = (W + 1) / 2;
-    const int32_t* rl = rlen[st];
-    const int32_t* rlo = rlen[st + 1];
+    const int C = P.ch, Co = blk.c_out, Ho = P.h / 2, Wo = (P.w + 1) / 2;
+    ConvOpt leaky;  // every 3x3 conv of the block: LeakyReLU on its input, zero column padding, bias
+    leaky.pad_left = 1; leaky.pro = ST2_PRO_LEAKY; leaky.slope = 0.2f;
     // shortcut: 1x1 conv at full resolution, then the 2x2 average (models.py:118-123)
-    float* SC = c.a.f32((int64_t)B * (Ho + 2) * Co * Wo);
+    StyleMap SC = scratch(Ho, Co, Wo);
+    StyleMap Sm = P;
     if (blk.has_sc) {
-      float* Sm = c.a.f32((int64_t)B * (H + 2) * Co * W);
-      ConvOpt o;
-      o.split_rows = H;
-      conv(c, e, stack(P, H, C, W, 1, 1, rl), blk.wsc, stack(Sm, H, Co, W, 1, 1, rl), o);
-      RUN(c, g_be.avgpool2x2_len(Sm + (int64_t)Co * W, (int64_t)(H + 2) * Co * W, (int64_t)Co * W, W, B, Co, H, W,
-                                 SC + (int64_t)Co * Wo, (int64_t)(Ho + 2) * Co * Wo, (int64_t)Co * Wo, Wo, wlen[st], c.stream));
-    } else {
-      RUN(c, g_be.avgpool2x2_len(P + (int64_t)C * W, (int64_t)(H + 2) * C * W, (int64_t)C * W, W, B, C, H, W,
-                                 SC + (int64_t)Co * Wo, (int64_t)(Ho + 2) * Co * Wo, (int64_t)Co * Wo, Wo, wlen[st], c.stream));
+      Sm = scratch(P.h, Co, P.w);
+      conv2d(P, 1, blk.wsc, Sm, ConvOpt(), nullptr, rlen[st]);
     }
+    avgpool2x2(c, Sm.p, Sm.bs, Sm.row(), Sm.w, B, Sm.ch, Sm.h, Sm.w, SC.p, SC.bs, SC.row(), Wo, wlen[st]);
     // residual: leaky -> conv1 3x3 -> depthwise stride-2 3x3 -> leaky -> conv2 3x3 (models.py:125-135)
-    float* R1 = c.a.f32((int64_t)B * (H + 2) * C * W);
-    {
-      ConvOpt o;
-      o.pad_left = 1; o.bias = e.F(blk.b1); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = H;
-      conv(c, e, stack(P, H, C, W, 3, 0, rl), blk.w1, stack(R1, H, C, W, 1, 1, rl), o);
-    }
-    float* P2 = new_map(Ho, C, Wo);
-    RUN(c, g_be.dwconv3x3s2_len(R1 + (int64_t)C * W, (int64_t)(H + 2) * C * W, (int64_t)C * W, W, e.F(blk.wd), e.F(blk.bd), B, C, H,
-                                W, P2 + (int64_t)C * Wo, (int64_t)(Ho + 2) * C * Wo, (int64_t)C * Wo, Wo, wlen[st], c.stream));
-    float* Pn = new_map(Ho, Co, Wo);
-    {  // (shortcut + residual) / sqrt(2) in the epilogue
-      ConvOpt o;
-      o.pad_left = 1; o.bias = e.F(blk.b2); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = Ho;
-      o.res = stack(SC, Ho, Co, Wo, 1, 1, nullptr); o.div = (float)sqrt(2.0);
-      conv(c, e, stack(P2, Ho, C, Wo, 3, 0, rlo), blk.w2, stack(Pn, Ho, Co, Wo, 1, 1, rlo), o);
-    }
-    P = Pn; H = Ho; W = Wo; C = Co;
+    StyleMap R1 = scratch(P.h, C, P.w);
+    leaky.bias = e.F(blk.b1);
+    conv2d(P, 3, blk.w1, R1, leaky, nullptr, rlen[st]);
+    StyleMap P2 = new_map(Ho, C, Wo);
+    dwconv3x3s2(c, R1.p, R1.bs, R1.row(), R1.w, e.F(blk.wd), e.F(blk.bd), B, C, R1.h, R1.w, P2.p, P2.bs, P2.row(), Wo, wlen[st]);
+    StyleMap Pn = new_map(Ho, Co, Wo);
+    leaky.bias = e.F(blk.b2); leaky.div = (float)sqrt(2.0);  // (shortcut + residual) / sqrt(2) in the epilogue
+    conv2d(P2, 3, blk.w2, Pn, leaky, &SC, rlen[st + 1]);
+    P = Pn;
     ++st;
   }
-  // LeakyReLU -> 5x5 valid conv -> global average over the clip's own W_4 - 4 columns -> LeakyReLU -> Linear (models.py:151-163)
-  const int Cl = s.c_last, Wf = W - 4;
+  // LeakyReLU -> 5x5 valid conv (the 5 image rows as its channels) -> global average (ragged: over the clip's own W_4 - 4
+  // columns) -> LeakyReLU -> Linear (models.py:151-163)
+  const int Cl = s.c_last, Wf = P.w - 4;
   float* Fm = c.a.f32((int64_t)B * Cl * Wf);
-  {
-    View x;
-    x.p = P + (int64_t)C * W;
-    x.B = B; x.C = 5 * C; x.L = W; x.bs = (int64_t)(H + 2) * C * W; x.cs = W; x.len = wlen[S];
-    View y;
-    y.p = Fm;
-    y.B = B; y.C = Cl; y.L = Wf; y.bs = (int64_t)Cl * Wf; y.cs = Wf; y.len = wlen[S + 1];
+  for (int b = 0; b < launches; ++b) {
+    const int nb = ragged ? B : 1;  // clips of this launch
+    View x, y;
+    x.p = P.p + b * P.bs; x.B = nb; x.C = 5 * P.ch; x.L = P.w; x.bs = ragged ? P.bs : 5 * P.row(); x.cs = P.w; x.len = wlen[S];
+    y.p = Fm + (int64_t)b * Cl * Wf; y.B = nb; y.C = Cl; y.L = Wf; y.bs = (int64_t)Cl * Wf; y.cs = Wf; y.len = wlen[S + 1];
     ConvOpt o;
-    o.bias = e.F(s.b5); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = 1;
+    o.bias = e.F(s.b5); o.pro = ST2_PRO_LEAKY; o.slope = 0.2f; o.split_rows = ragged ? 1 : 0;
     conv(c, e, x, s.w5, y, o);
   }
   float* m = c.a.f32((int64_t)B * Cl);

@@ -1,5 +1,6 @@
 """Length-aware reference-style path on the GPU: the four `_len` kernels and st2_style_lengths against
-per-row references computed on the row sliced to its own length (NaN in every tail), st2_style_forward_ragged against the
+per-row references computed on the row sliced to its own length (NaN in every tail), the plain entry of each of the four
+against its `_len` entry at full lengths (one kernel behind both: the same bits), st2_style_forward_ragged against the
 oracle and against the engine's own solo runs, `compute_style` on a ragged batch end to end, device against host lengths, the
 clamp of an over-long device length, and one graph recorded with device lengths and replayed with others."""
 import pytest
@@ -73,6 +74,43 @@ def test_dwconv_and_avgpool_len_rows_are_the_maps_alone(shape, widths):
         refp = R.avgpool2x2(xm, torch.empty(1, H // 2, C, wo))
         assert (outp[b:b + 1, :, :, :wo] - refp).abs().max().item() < 1e-6
         assert bool((outp[b, :, :, wo:] == SENT).all())
+
+
+# ---- the plain entry and the `_len` entry at full lengths: one kernel each, the same bits --------------------------------------
+def test_stft_frames_plain_and_full_lengths_agree_bitwise():
+    wave = torch.randn(2, 1030, generator=torch.Generator().manual_seed(31)).to(DEV)   # M = 258: a second 256-wide chunk
+    plain = ops.stft_frames(wave, 8, 4, 4)
+    fr, m_len = ops.stft_frames(wave, 8, 4, 4, lengths=lens([1030, 1030]), want_frames=True)
+    assert plain.shape == (2, 8, 258) and m_len.tolist() == [258, 258]
+    assert torch.equal(plain, fr)
+
+
+def test_log_norm_plain_and_full_lengths_agree_bitwise():
+    x = (torch.rand(2, 3, 259, generator=torch.Generator().manual_seed(32)) * 10).to(DEV)   # 1 554 elements, 259 columns
+    plain = ops.log_norm_(x.clone(), 1e-5, -4.0, 4.0)
+    assert torch.equal(plain, ops.log_norm_(x.clone(), 1e-5, -4.0, 4.0, lengths=lens([259, 259])))
+    flat = ops.log_norm_(x.reshape(1554).clone(), 1e-5, -4.0, 4.0)                # the flat path covers every element
+    assert flat.shape == (1554,) and torch.equal(flat, plain.reshape(1554))
+    ref = R.log_norm_(x.cpu().reshape(1554).clone(), 1e-5, -4.0, 4.0)
+    assert (flat.cpu() - ref).abs().max().item() < 1e-6
+
+
+@pytest.mark.parametrize("H,C,W", [(4, 3, 515), (6, 5, 33)])                      # Wo = 258 from an odd W; one chunk, odd W
+def test_dwconv_and_avgpool_plain_and_full_lengths_agree_bitwise(H, C, W):
+    g = torch.Generator().manual_seed(33)
+    x = torch.randn(2, H + 2, C, W, generator=g).to(DEV)[:, 1:H + 1]              # interior view of a padded map
+    wt, bias = torch.randn(C, 3, 3, generator=g).to(DEV), torch.randn(C, generator=g).to(DEV)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    SENT = -12345.0
+
+    def fresh(h):
+        return torch.full((2, h, C, Wo), SENT, device=DEV)
+    plain = ops.dwconv3x3s2(x, wt, bias, fresh(Ho))
+    assert torch.equal(plain, ops.dwconv3x3s2(x, wt, bias, fresh(Ho), lengths=lens([W, W])))
+    assert bool((plain != SENT).all())
+    plain = ops.avgpool2x2(x, fresh(H // 2))
+    assert torch.equal(plain, ops.avgpool2x2(x, fresh(H // 2), lengths=lens([W, W])))
+    assert bool((plain != SENT).all())
 
 
 def test_style_lengths_table_and_clamp():
