@@ -871,6 +871,67 @@ int st2_sizeof_controls(void);
 int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ---- timing marks and per-token prosody controls (added under ABI 23, additive: kernel-level entry points, one plan-level
+ * entry and one new struct; no new backend-table slot, no change to an existing struct or signature) -- *
+ * Both rest on ONE rule: where a token lies in the decoder frames of its row.
+ *
+ * The boundary rule.  Row b has durations dur[b][0..N) (int64, non-negative, N <= 512), n_b tokens (len[b] clamped to 0..N,
+ * NULL = N) and T_b frames (frames[b] clamped to 0..T_cap, NULL = T_cap).  With
+ *     c[n] = min(T_cap, sum_{m < min(n, n_b)} dur[b][m])                       (a 64-bit sum that saturates)
+ * -- st2_expand_by_durations_len's cum[n - 1] for every n <= n_b; tokens at or past n_b hold 0 wherever len is given, the
+ * duration head writes that -- bound[b][n], n = 0..N, is the first frame t in [0, T_b] whose token index idx(b, t) of the
+ * expansion is >= n:
+ *     bound[0] = 0;   bound[n] = min(T_b, c[n] == 0 ? 0 : c[n] + shift)  for 1 <= n <= N - 1;   bound[N] = T_b
+ * (shift = 1: the HiFi-GAN one-frame right shift; the last token owns whatever the durations leave over, as the expansion's
+ * idx = min(lo, N - 1) does).  Monotone by construction; a row truncated to T_cap (ST2_STATUS_FRAME_CAPACITY) gets T_b for
+ * every token that fell off, and so do pad tokens.
+ *
+ * st2_token_marks: marks (int32 [B][N + 1]) = row-relative sample positions in the PACKED stream of st2_wave_pack (up = down =
+ * 1) / st2_wave_resample_pack (U = up, D = down).  With n_smp = max(0, samples_per_frame * T_b - trim) and
+ * s = min(samples_per_frame * bound[b][n], n_smp):   marks[b][n] = (s U + D - 1) div D,   the first output sample at or after
+ * the boundary's time under the resampler's c = (j D) div U.  Hence marks[b][N] = offsets[b + 1] - offsets[b] exactly, and
+ * token n of row b is packed[offsets[b] + marks[b][n] : offsets[b] + marks[b][n + 1]].  bound_out (int32 [B][N + 1], optional)
+ * receives bound, in frames.  All intermediates are 64-bit.  One launch, one wave per row, no allocation, no synchronisation,
+ * legal under stream capture.  Returns non-zero before any launch on: NULL dur / marks; B, N, T_cap or samples_per_frame
+ * <= 0; N > 512; up or down outside 1..1024; trim < 0; a row at capacity whose ceil(samples_per_frame T_cap U / D) samples do
+ * not fit int32. */
+int st2_token_marks(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* frames, int32_t T_cap,
+                    int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, int32_t* marks,
+                    int32_t* bound_out, void* stream);
+
+/* Per-token controls: fp32 [B][N] device rows, clamped where they are read like the per-row controls above.
+ *   tok_speed     dur[b][n] = max(1, rint(total[b][n] / r)), r = clamp(clamp(speed[b]) * clamp(tok_speed[b][n])): ONE fp32
+ *                 product in front of st2_duration_head_rate's one division; every clamp is to [0.25, 4], NaN -> 1, a NULL speed
+ *                 row is 1.  1 * 1 and x / 1 are exact: neutral keeps st2_duration_head's bits.
+ *   tok_f0_scale  F0[b][l] *= tok_f0_scale[b][idx(b, l div 2)] for l < 2 T_b.  Clamped to [0.5, 2]; NaN -> 1.
+ *   tok_n_shift   N[b][l] += tok_n_shift[b][idx(b, l div 2)] for l < 2 T_b.  Clamped to [-2, 2]; NaN -> 0; a shift of 0 keeps x
+ *                 itself.
+ * idx(b, t) is st2_expand_by_durations_len's for the same dur / shift: the values are stepwise at the token boundaries
+ * (nothing is smoothed across them).
+ * st2_duration_head_rate_tok: st2_duration_head_rate with tok_speed (not NULL) and an optional speed.
+ * st2_prosody_controls_tok: st2_prosody_controls with token rows; L = 2 T must be even, dur int64 [B][N], N <= 512.  Workgroup
+ * (1024 columns, row) rebuilds the prefix sum in LDS as the expansion does, searches once per frame, applies one operation
+ * per element (never fused) and leaves at once at or past 2 T_b, where nothing is read or written.  A NULL row leaves that curve
+ * alone; both NULL launches nothing.
+ * Both: one launch, no allocation, no synchronisation, legal under stream capture; bad arguments return non-zero before any
+ * launch. */
+int st2_duration_head_rate_tok(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias, int32_t B,
+                               int32_t K, int32_t J, int32_t N, const int32_t* len, int32_t tail, const float* speed,
+                               const float* tok_speed, int64_t* dur, float* dsum, void* stream);
+int st2_prosody_controls_tok(float* f0, float* n, int64_t bs, int32_t B, int32_t L, const int64_t* dur, int32_t N,
+                             int32_t shift, const float* tok_f0_scale, const float* tok_n_shift, const int32_t* frames,
+                             void* stream);
+
+/* st2_front_forward_ctl with a per-token rate: tok->speed (fp32 [B][N], device) makes the duration head
+ * st2_duration_head_rate_tok (`durations` must then be non-NULL).  A NULL `tok`, or one whose member is NULL, is
+ * st2_front_forward_ctl, which is this call with NULL.  Refused while a debug backend is installed, as `ctl` is. */
+typedef struct st2_token_controls {
+  const float* speed;  /* fp32 [B][N] on the device, or NULL */
+} st2_token_controls;
+int st2_sizeof_token_controls(void);
+int st2_front_forward_tok(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, const st2_token_controls* tok,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* StyleEncoder.forward (models.py:139-164; `compute_style`, Demo/Inference_LibriTTS.ipynb:100-111): mel [B][80][T] (the
  * normalised log-mel of the reference recording, T >= 80 frames) -> style [B][style_dim].  which = 0: `style_encoder`
  * (acoustic half of ref_s), 1: `predictor_encoder` (prosodic half); ref_s = cat(which 0, which 1).  Conv2d layers run as

@@ -90,6 +90,11 @@ class ControlRows(C.Structure):
     _fields_ = [("speed", C.c_void_p), ("alpha", C.c_void_p), ("beta", C.c_void_p), ("t", C.c_void_p)]
 
 
+class TokenControlRows(C.Structure):
+    """Mirror of `st2_token_controls`: the per-token rate of st2_front_forward_tok, fp32 [B][N] on the device or NULL."""
+    _fields_ = [("speed", C.c_void_p)]
+
+
 class DecoderTaps(C.Structure):
     """Mirror of `st2_decoder_taps`."""
     _fields_ = [("encode", f32p), ("front", f32p), ("har_source", f32p), ("har", f32p), ("stage", f32p * 4),
@@ -261,6 +266,15 @@ _SIGNATURES = {
     "st2_style_mix_rows": (C.c_int, [f32p, f32p, f32p, f32p, f32p, f32p, C.c_double, C.c_double, C.c_double, C.c_int32,
                                      C.c_int32, C.c_int32, f32p, f32p, f32p, C.c_void_p]),
     "st2_prosody_controls": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_void_p, C.c_void_p]),
+    "st2_token_marks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "st2_duration_head_rate_tok": (C.c_int, [f32p, C.c_int64, C.c_int32, f32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "st2_prosody_controls_tok": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, f32p,
+                                           f32p, C.c_void_p, C.c_void_p]),
+    "st2_sizeof_token_controls": (C.c_int, []),
+    "st2_front_forward_tok": (C.c_int, [C.c_void_p, C.POINTER(FrontArgs), C.POINTER(ControlRows), C.POINTER(TokenControlRows),
+                                        C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_prosody_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "st2_prosody_forward": (C.c_int, [C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -354,6 +368,9 @@ def load():
     if lib.st2_sizeof_controls() != C.sizeof(ControlRows):
         raise St2Error("st2_controls layout mismatch: library %d B, binding %d B"
                        % (lib.st2_sizeof_controls(), C.sizeof(ControlRows)))
+    if lib.st2_sizeof_token_controls() != C.sizeof(TokenControlRows):
+        raise St2Error("st2_token_controls layout mismatch: library %d B, binding %d B"
+                       % (lib.st2_sizeof_token_controls(), C.sizeof(TokenControlRows)))
     _lib = lib
     return lib
 

@@ -1450,6 +1450,11 @@ extern "C" int st2_front_forward(st2_engine* e, const st2_front_args* a, void* w
 
 extern "C" int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, void* workspace,
                                      int64_t workspace_bytes, void* stream) {
+  return st2_front_forward_tok(e, a, ctl, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int st2_front_forward_tok(st2_engine* e, const st2_front_args* a, const st2_controls* ctl, const st2_token_controls* tok,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
   const char* why = front_ready(e);
   ST2_REQUIRE(!why, "st2_front_forward: %s", why);
   ST2_REQUIRE(a && a->tokens && a->noise && a->step_noise && a->table && a->t_en && a->d_cm && a->s && a->ref && workspace &&
@@ -1459,16 +1464,24 @@ extern "C" int st2_front_forward_ctl(st2_engine* e, const st2_front_args* a, con
               "st2_front_forward: N=%d tokens exceed the position / fixed-embedding tables", a->N);
   return run_forward("st2_front_forward", "st2_front_workspace_bytes", workspace, workspace_bytes, stream, [&](Ctx& c) {
     if (ctl && !(ctl->speed || ctl->alpha || ctl->beta || ctl->t)) ctl = nullptr;  // empty: st2_front_forward's launches
+    const float* tok_speed = tok ? tok->speed : nullptr;
     if (ctl) {
       ST2_REQUIRE(!ctl->speed || a->durations, "st2_front_forward_ctl: speed with durations == NULL (forced durations): there is "
                   "nothing to scale");
       const auto in01 = [](double w) { return w >= 0.0 && w <= 1.0; };
       ST2_REQUIRE(in01(a->t) && in01(a->alpha) && in01(a->beta), "st2_front_forward_ctl: the scalar weights t=%g / alpha=%g / beta=%g "
                   "must lie in [0, 1]", a->t, a->alpha, a->beta);
+    }
+    if (tok_speed)
+      ST2_REQUIRE(a->durations, "st2_front_forward_tok: a token rate with durations == NULL (forced durations): there is nothing "
+                  "to scale");
+    if (ctl)
       ST2_REQUIRE(g_be.axpbypcz == kHipBackend.axpbypcz && g_be.duration_head == kHipBackend.duration_head,
                   "st2_front_forward_ctl: per-row controls have no slot in a debug backend (st2_debug_set_backend)");
-    }
-    return front_plan(c, *e, *a, ctl);
+    if (tok_speed)
+      ST2_REQUIRE(g_be.axpbypcz == kHipBackend.axpbypcz && g_be.duration_head == kHipBackend.duration_head,
+                  "st2_front_forward_tok: per-token controls have no slot in a debug backend (st2_debug_set_backend)");
+    return front_plan(c, *e, *a, ctl, tok_speed);
   });
 }
 

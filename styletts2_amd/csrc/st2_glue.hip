@@ -75,17 +75,20 @@ __global__ __launch_bounds__(256) void copy_ncl_kernel(const float* __restrict__
 //   + tail on the utterance's own last token.  x is channel-major [B][K][N] (the duration LSTM's output layout).
 // RATE (st2_duration_head_rate): the sum is divided by the row's speaking rate before it is rounded -- one correctly rounded
 // fp32 division behind the unchanged reduction, so dsum and the RATE = false instantiation are what they were.
+// TOK (st2_duration_head_rate_tok): the rate is the row's (1 without a row) times the token's own, both clamped where they are
+// read and the fp32 product clamped again: one multiplication in front of that same division.
 __device__ __forceinline__ float rate_clamped(const float* __restrict__ speed, int b) {
   const float s = speed[b];
   return s != s ? 1.0f : fminf(fmaxf(s, 0.25f), 4.0f);  // a bad device value gives a clamped row, never a fault
 }
 
-template <bool RATE>
+template <bool RATE, bool TOK = false>
 __global__ __launch_bounds__(64) void duration_head_kernel(const float* __restrict__ x, int64_t x_bs, int x_cs,
                                                            const float* __restrict__ w, const float* __restrict__ bias,
                                                            int K, int J, int N, const int* __restrict__ len, int tail,
                                                            long long* __restrict__ dur, float* __restrict__ dsum,
-                                                           const float* __restrict__ speed) {
+                                                           const float* __restrict__ speed,
+                                                           const float* __restrict__ tok_speed = nullptr) {
   const int n = blockIdx.x;
   const int b = blockIdx.y;
   const int lane = threadIdx.x;
@@ -102,7 +105,10 @@ __global__ __launch_bounds__(64) void duration_head_kernel(const float* __restri
   }
   if (lane == 0) {
     float scaled = total;
-    if constexpr (RATE) scaled = total / rate_clamped(speed, b);  // x / 1 is exact: a neutral rate keeps the bits
+    if constexpr (TOK) {
+      const float r = (speed ? rate_clamped(speed, b) : 1.0f) * rate_clamped(tok_speed + (int64_t)b * N, n);  // 1 * 1 is exact
+      scaled = total / fminf(fmaxf(r, 0.25f), 4.0f);
+    } else if constexpr (RATE) scaled = total / rate_clamped(speed, b);  // x / 1 is exact: a neutral rate keeps the bits
     long long d = (long long)fmaxf(rintf(scaled), 1.0f);  // torch.round = round-half-even = rintf
     if (n >= n_b) d = 0;
     if (n == n_b - 1) d += tail;
@@ -308,6 +314,20 @@ extern "C" int st2_duration_head_rate(const float* x, int64_t x_bs, int32_t x_cs
   hipLaunchKernelGGL(duration_head_kernel<true>, dim3(N, B), dim3(64), 0, s, x, x_bs, x_cs, w, bias, K, J, N,
                      reinterpret_cast<const int*>(len), tail, reinterpret_cast<long long*>(dur), dsum, speed);
   ST2_CHECK_LAUNCH("st2_duration_head_rate");
+  return 0;
+}
+
+extern "C" int st2_duration_head_rate_tok(const float* x, int64_t x_bs, int32_t x_cs, const float* w, const float* bias,
+                                          int32_t B, int32_t K, int32_t J, int32_t N, const int32_t* len, int32_t tail,
+                                          const float* speed, const float* tok_speed, int64_t* dur, float* dsum, void* stream) {
+  ST2_REQUIRE(x && w && bias && dur && tok_speed, "st2_duration_head_rate_tok: x / w / bias / tok_speed / dur is NULL");
+  ST2_REQUIRE(B > 0 && K > 0 && J > 0 && N > 0 && tail >= 0,
+              "st2_duration_head_rate_tok: bad geometry (B=%d, K=%d, J=%d, N=%d, tail=%d)", B, K, J, N, tail);
+  ST2_REQUIRE(B <= 65535, "st2_duration_head_rate_tok: grid too large");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL((duration_head_kernel<true, true>), dim3(N, B), dim3(64), 0, s, x, x_bs, x_cs, w, bias, K, J, N,
+                     reinterpret_cast<const int*>(len), tail, reinterpret_cast<long long*>(dur), dsum, speed, tok_speed);
+  ST2_CHECK_LAUNCH("st2_duration_head_rate_tok");
   return 0;
 }
 

@@ -39,7 +39,7 @@ View lstm_run(Ctx& c, const st2_engine& e, const PLstm& l, const View& x, const 
 }
 
 int duration_plan(Ctx& c, const st2_engine& e, const View& d_en, const float* s_p, const int32_t* lens, int B, int N,
-                  int tail, float* d_cm, int64_t* durations, const float* speed = nullptr) {
+                  int tail, float* d_cm, int64_t* durations, const float* speed = nullptr, const float* tok_speed = nullptr) {
   const st2_model_config& cfg = e.cfg;
   const PDuration& d = e.dur;
   const int dh = cfg.pred_hidden, sty = cfg.style_dim, Cd = dh + sty;
@@ -69,7 +69,10 @@ int duration_plan(Ctx& c, const st2_engine& e, const View& d_en, const float* s_
   }
   if (durations) {
     View x = lstm_run(c, e, d.dur_lstm, h, lens);
-    if (speed)  // per-row speaking rate (st2_front_forward_ctl): the twin kernel, no backend slot
+    if (tok_speed)  // per-token rate on top of the row's (st2_front_forward_tok): the third instantiation, no backend slot
+      RUN(c, st2_duration_head_rate_tok(x.p, x.bs, x.cs, e.F(d.proj_w), e.F(d.proj_b), B, dh, d.max_dur, N, lens, tail, speed,
+                                        tok_speed, durations, nullptr, c.stream));
+    else if (speed)  // per-row speaking rate (st2_front_forward_ctl): the twin kernel, no backend slot
       RUN(c, st2_duration_head_rate(x.p, x.bs, x.cs, e.F(d.proj_w), e.F(d.proj_b), B, dh, d.max_dur, N, lens, tail, speed,
                                     durations, nullptr, c.stream));
     else

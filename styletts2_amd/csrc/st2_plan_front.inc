@@ -127,7 +127,8 @@ View bert_plan(Ctx& c, const st2_engine& e, const int64_t* tokens, const int32_t
   return X;
 }
 
-int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_controls* ctl = nullptr) {
+int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_controls* ctl = nullptr,
+               const float* tok_speed = nullptr) {
   const st2_model_config& cfg = e.cfg;
   const int B = a.B, N = a.N, sty = cfg.style_dim, C2 = cfg.dn_channels, dh = cfg.pred_hidden;
   text_plan(c, e, a.tokens, a.lengths, B, N, a.t_en);
@@ -154,7 +155,7 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_c
     // the launches below in their order
     RUN(c, st2_style_mix_rows(sp, a.s_prev, a.ref_s, ctl->t, ctl->alpha, ctl->beta, a.t, a.alpha, a.beta, B, sty,
                               a.carry && B > 1, a.ref, a.s, a.s_pred_out, c.stream));
-    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
+    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed, tok_speed);
     return c.rc;
   }
   if (a.carry && B > 1) {
@@ -186,7 +187,7 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_c
     }
     RUN(c, g_be.copy_ncl(mixed, C2, sty, a.ref, sty, sty, B, 1, sty, c.stream));
     RUN(c, g_be.copy_ncl(mixed + sty, C2, sty, a.s, sty, sty, B, 1, sty, c.stream));
-    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
+    duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed, tok_speed);
     return c.rc;
   }
   const float* cur = sp;
@@ -211,6 +212,6 @@ int front_plan(Ctx& c, const st2_engine& e, const st2_front_args& a, const st2_c
     RUN(c, g_be.copy_ncl(ref_src, C2, sty, a.s_pred_out, C2, sty, B, 1, sty, c.stream));
     RUN(c, g_be.copy_ncl(s_src, C2, sty, a.s_pred_out + sty, C2, sty, B, 1, sty, c.stream));
   }
-  duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed);
+  duration_plan(c, e, D, a.s, a.lengths, B, N, a.tail, a.d_cm, a.durations, speed, tok_speed);
   return c.rc;
 }

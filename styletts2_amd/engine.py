@@ -335,7 +335,8 @@ class Engine:
         (None unless `predict`).  `carry`: the rows are consecutive sentences of one passage, row k's style is mixed with row
         k-1's mixed style (`s_prev` [1, 2 sty] or None feeds row 0): st2.h st2_front_args.carry.  `controls` (a dict of fp32
         [B] device rows under "speed" / "alpha" / "beta" / "t", any subset): `st2_front_forward_ctl` -- row b's own speaking rate
-        and mixing weights; the mixing is then one launch."""
+        and mixing weights; the mixing is then one launch.  "tok_speed" (fp32 [B, N]): the per-token rate on top of the row's,
+        `st2_front_forward_tok`."""
         cfg = self.cfg
         B, N = tokens.shape
         dev = tokens.device
@@ -363,19 +364,29 @@ class Engine:
         if not controls:
             _lib.check(self.lib.st2_front_forward(self.h, C.byref(a), ws_ptr, nbytes, _stream(dev)), "st2_front_forward")
             return out
-        rows = {}
+        rows, tok = {}, None
         for name, row in controls.items():
+            if name == "tok_speed":  # the per-token rate: fp32 [B, N] (`st2_front_forward_tok`)
+                if not torch.is_tensor(row) or row.dtype != torch.float32 or tuple(row.shape) != (B, N) \
+                        or not row.is_contiguous() or row.device != dev:
+                    raise _lib.St2Error("control tok_speed must be a contiguous float32 [%d, %d] tensor on %s" % (B, N, dev))
+                tok = _lib.TokenControlRows(speed=row.data_ptr())
+                continue
             if name not in ("speed", "alpha", "beta", "t"):
                 raise ValueError("unknown front control %r" % (name,))
             if not torch.is_tensor(row) or row.dtype != torch.float32 or row.dim() != 1 or row.numel() != B \
                     or not row.is_contiguous() or row.device != dev:
                 raise _lib.St2Error("control %s must be a contiguous float32 [%d] tensor on %s" % (name, B, dev))
             rows[name] = row.data_ptr()
-        if "speed" in rows and not predict:
+        if ("speed" in rows or tok is not None) and not predict:
             raise ValueError("speed with forced durations: there is nothing to scale")
         ctl = _lib.ControlRows(**rows)
-        _lib.check(self.lib.st2_front_forward_ctl(self.h, C.byref(a), C.byref(ctl), ws_ptr, nbytes, _stream(dev)),
-                   "st2_front_forward_ctl")
+        if tok is not None:
+            _lib.check(self.lib.st2_front_forward_tok(self.h, C.byref(a), C.byref(ctl), C.byref(tok), ws_ptr, nbytes, _stream(dev)),
+                       "st2_front_forward_tok")
+        else:
+            _lib.check(self.lib.st2_front_forward_ctl(self.h, C.byref(a), C.byref(ctl), ws_ptr, nbytes, _stream(dev)),
+                       "st2_front_forward_ctl")
         if rows.keys() & {"alpha", "beta", "t"}:
             from . import ops
             ops.style_mix_launches += 1

@@ -984,11 +984,29 @@ def _chk_row(t, name, n, like):
     return t.data_ptr()
 
 
-def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False, speed=None):
+def _chk_tok_row(t, name, B, N, like):
+    """A per-token control (include/st2.h "per-token controls"): fp32 [B, N], contiguous, on the device of `like`.  Checked
+    before anything else of the call, as `_chk_row` checks the per-row ones.  Returns the device pointer (0 for None)."""
+    if t is None:
+        return 0
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _lib.St2Error("%s must be a float32 tensor (got %s)" % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if tuple(t.shape) != (B, N) or not t.is_contiguous():
+        raise _lib.St2Error("%s must be a contiguous [%d, %d] tensor (got shape %s)" % (name, B, N, tuple(t.shape)))
+    if not t.is_cuda or not torch.is_tensor(like) or t.device != like.device:
+        raise _lib.St2Error("%s must live on the device of the tensor it describes (%s, got %s)" % (
+            name, like.device if torch.is_tensor(like) else None, t.device))
+    return t.data_ptr()
+
+
+def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False, speed=None, tok_speed=None):
     """`st2_duration_head`: x [B, K, N] channel-major, w [J, K], bias [J] -> int64 durations [B, N] (and the un-rounded
     sigmoid sums when want_sums).  `speed` (fp32 [B] on the device, `st2_duration_head_rate`): row b's sums are divided by
-    speed[b] (clamped to [0.25, 4], NaN -> 1) before they are rounded; the sums handed back stay un-scaled."""
+    speed[b] (clamped to [0.25, 4], NaN -> 1) before they are rounded; the sums handed back stay un-scaled.  `tok_speed` (fp32
+    [B, N] on the device, `st2_duration_head_rate_tok`): token n of row b is divided by the clamped fp32 product of speed[b] (1
+    without `speed`) and tok_speed[b, n] instead."""
     sp = _chk_row(speed, "speed", _nb(x), x)
+    tsp = _chk_tok_row(tok_speed, "tok_speed", _nb(x), x.shape[2] if _nb(x) >= 0 else -1, x)
     lib = _lib.load()
     _chk(x, "x", 3)
     _chk(w, "w", 2)
@@ -1000,6 +1018,8 @@ def duration_head(x, w, bias, lengths=None, tail=0, want_sums=False, speed=None)
     dur = torch.empty((B, N), device=x.device, dtype=torch.int64)
     sums = torch.empty((B, N), device=x.device, dtype=torch.float32) if want_sums else None
     entry, rate = ("st2_duration_head", ()) if speed is None else ("st2_duration_head_rate", (sp,))
+    if tok_speed is not None:
+        entry, rate = "st2_duration_head_rate_tok", (sp, tsp)
     _lib.check(getattr(lib, entry)(x.data_ptr(), x.stride(0), x.stride(1), w.data_ptr(), bias.data_ptr(), B, K, J, N,
                                    lp, int(tail), *rate, dur.data_ptr(), _ptr(sums), _stream()), entry)
     return (dur, sums) if want_sums else dur
@@ -1054,6 +1074,30 @@ def prosody_controls(f0, n, f0_scale=None, n_shift=None, frames=None):
             tuple(f0.shape), tuple(n.shape)))
     _lib.check(lib.st2_prosody_controls(f0.data_ptr(), n.data_ptr(), f0.stride(0), B, f0.shape[1], sc, sh, fp, _stream()),
                "st2_prosody_controls")
+    return f0, n
+
+
+def prosody_controls_tok(f0, n, dur, tok_f0_scale=None, tok_n_shift=None, frames=None, shift=False):
+    """`st2_prosody_controls_tok`, in place: f0[b, l] *= tok_f0_scale[b, idx(b, l // 2)] and n[b, l] += tok_n_shift[b, idx(b,
+    l // 2)] for l < 2 * frames[b] (every l without `frames`), idx(b, t) the token `expand_by_durations(.., dur, shift=)` gathers
+    frame t from.  f0, n [B, L] fp32 of equal strides, L even; dur int64 [B, N] on the device; the token rows fp32 [B, N] on the
+    device (clamped to [0.5, 2] / [-2, 2] where they are read; None leaves that curve alone); frames int32 [B] on the device.
+    Nothing at or past a row's end is read or written.  Returns (f0, n)."""
+    B = _nb(f0, 2)
+    fp = _chk_len(frames, "frames", B, f0)
+    N = dur.shape[1] if torch.is_tensor(dur) and dur.dim() == 2 else -1
+    sc, sh = _chk_tok_row(tok_f0_scale, "tok_f0_scale", B, N, f0), _chk_tok_row(tok_n_shift, "tok_n_shift", B, N, f0)
+    lib = _lib.load()
+    _chk(f0, "f0", 2)
+    _chk(n, "n", 2)
+    if n.shape != f0.shape or n.stride() != f0.stride() or n.device != f0.device:
+        raise _lib.St2Error("f0 and n must have one shape, one layout and one device (got %s / %s)" % (
+            tuple(f0.shape), tuple(n.shape)))
+    _chk_dev(dur, "dur", torch.int64, 2)
+    if dur.shape[0] != B or dur.device != f0.device:
+        raise _lib.St2Error("dur must hold %d rows on the device of f0 (got %s on %s)" % (B, tuple(dur.shape), dur.device))
+    _lib.check(lib.st2_prosody_controls_tok(f0.data_ptr(), n.data_ptr(), f0.stride(0), B, f0.shape[1], dur.data_ptr(), N,
+                                            1 if shift else 0, sc, sh, fp, _stream()), "st2_prosody_controls_tok")
     return f0, n
 
 
@@ -1112,6 +1156,31 @@ def frames_from_durations(dur, lengths_dev, T_cap):
     _lib.check(lib.st2_frames_from_durations(dur.data_ptr(), B, N, lp, int(T_cap), frames.data_ptr(), _stream()),
                "st2_frames_from_durations")
     return frames
+
+
+def token_marks(dur, frames, T_cap, lengths=None, shift=False, trim=0, rate=None, samples_per_frame=600, out=None,
+                want_bound=False):
+    """`st2_token_marks`: where every token starts in its row's packed samples, without a host read.  dur int64 [B, N] on the
+    device, frames int32 [B] on the device (None: every row has T_cap frames), lengths int32 [B] on the device or None ->
+    int32 [B, N + 1]: marks[b, n] is the first sample of token n among the row's samples as `wave_pack` (rate None or 24000) /
+    `wave_resample_pack` (`rate` one of `resample.RATES`) hand them over with the same `trim` and `samples_per_frame`;
+    marks[b, N] is the row's sample count.  `shift`: the HiFi-GAN one-frame right shift of the expansion.  `out`: a contiguous
+    int32 [B, N + 1] device tensor to write into.  `want_bound`: also return the boundaries in decoder frames (int32 [B, N + 1])."""
+    from . import resample
+    _chk_dev(dur, "dur", torch.int64, 2)
+    B, N = dur.shape
+    lp = _chk_len(lengths, "lengths", B, dur)
+    fp = _chk_len(frames, "frames", B, dur)
+    U, D = resample.ratio(resample.MODEL_RATE if rate is None else rate)
+    if out is None:
+        out = torch.empty((B, N + 1), device=dur.device, dtype=torch.int32)
+    _chk_dev(out, "out", torch.int32, 2)
+    if tuple(out.shape) != (B, N + 1) or out.device != dur.device:
+        raise _lib.St2Error("out must be [%d, %d] on the device of dur (got %s on %s)" % (B, N + 1, tuple(out.shape), out.device))
+    bound = torch.empty((B, N + 1), device=dur.device, dtype=torch.int32) if want_bound else None
+    _lib.check(_lib.load().st2_token_marks(dur.data_ptr(), B, N, lp, fp, int(T_cap), 1 if shift else 0, int(samples_per_frame),
+                                           int(trim), U, D, out.data_ptr(), _ptr(bound), _stream()), "st2_token_marks")
+    return (out, bound) if want_bound else out
 
 
 PACK_FORMATS = {"f32": (_lib.PACK_F32, torch.float32), "s16": (_lib.PACK_S16, torch.int16)}

@@ -152,19 +152,33 @@ class Controls:
 
     Every control is a float (the whole batch), a sequence or a tensor of B values, or left out: an absent control keeps the
     behaviour without it.  Host values are validated here (ValueError when out of range or not finite).  A tensor already on
-    the device is not read: it is clamped to the same range by the kernel that reads it (NaN = absent)."""
+    the device is not read: it is clamped to the same range by the kernel that reads it (NaN = absent).
+
+    Per-token controls are a second fp32 device tensor of three rows of [B][N] -- tok_speed, tok_f0_scale,
+    tok_n_shift -- made only when one of them or `N` is given:
+
+        tok_speed     token n's rate on top of the row's: max(1, rint(sum / clamp(speed[b] * tok_speed[b][n])))   [0.25, 4]  absent = 1
+        tok_f0_scale  F0 *= tok_f0_scale[b][n] over token n's frames                                              [0.5, 2]   absent = 1
+        tok_n_shift   N += tok_n_shift[b][n] over token n's frames                                                [-2, 2]    absent = 0
+
+    each a float (every token), a [B, N] array or tensor, or left out; the same validation, ABSENT and `slice` rules."""
     NAMES = ("speed", "alpha", "beta", "t", "f0_scale", "n_shift")
+    TOK_NAMES = ("tok_speed", "tok_f0_scale", "tok_n_shift")
+    TOK_RANGES = {"tok_speed": (0.25, 4.0), "tok_f0_scale": (0.5, 2.0), "tok_n_shift": (-2.0, 2.0)}
+    TOK_ABSENT = {"tok_speed": 1.0, "tok_f0_scale": 1.0, "tok_n_shift": 0.0}
     RANGES = {"speed": (0.25, 4.0), "alpha": (0.0, 1.0), "beta": (0.0, 1.0), "t": (0.0, 1.0), "f0_scale": (0.5, 2.0),
               "n_shift": (-2.0, 2.0)}
     # what an absent row holds: the device clamp's neutral value (NaN = "the call's scalar" for the mixing weights)
     ABSENT = {"speed": 1.0, "alpha": float("nan"), "beta": float("nan"), "t": float("nan"), "f0_scale": 1.0, "n_shift": 0.0}
 
-    def __init__(self, B, speed=None, alpha=None, beta=None, t=None, f0_scale=None, n_shift=None, device=None):
+    def __init__(self, B, speed=None, alpha=None, beta=None, t=None, f0_scale=None, n_shift=None, device=None,
+                 tok_speed=None, tok_f0_scale=None, tok_n_shift=None, N=None):
         B = int(B)
         if B <= 0:
             raise ValueError("Controls: B must be positive, got %r" % (B,))
         given = dict(speed=speed, alpha=alpha, beta=beta, t=t, f0_scale=f0_scale, n_shift=n_shift)
-        on_dev = [v for v in given.values() if torch.is_tensor(v) and v.is_cuda]
+        tok = dict(tok_speed=tok_speed, tok_f0_scale=tok_f0_scale, tok_n_shift=tok_n_shift)
+        on_dev = [v for v in list(given.values()) + list(tok.values()) if torch.is_tensor(v) and v.is_cuda]
         if device is None:
             device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
         host = torch.empty((len(self.NAMES), B), dtype=torch.float32)
@@ -193,13 +207,60 @@ class Controls:
         self.buf = host.to(device)  # ONE host -> device copy
         for i, v in late:
             self.buf[i].copy_(v.detach().reshape(B).to(torch.float32))
+        self.N, self.tok_present, self.tok_buf = None, (), None
+        self._init_tokens(tok, N, device)
+
+    def _init_tokens(self, tok, N, device):
+        """The [3][B][N] tensor of the per-token rows, by the rules of the six rows above; nothing when neither a row nor N is given."""
+        B = self.B
+        if N is None:
+            dims = [v.shape if torch.is_tensor(v) else torch.as_tensor(v).shape for v in tok.values() if v is not None]
+            shapes = {d[-1] for d in dims if len(d) == 2}
+            if len(shapes) == 1:
+                N = shapes.pop()
+            elif any(v is not None for v in tok.values()):
+                raise ValueError("Controls: the per-token controls %s need N (the batch's token width) or one [B, N] array"
+                                 % ([n for n in self.TOK_NAMES if tok[n] is not None],))
+            else:
+                return
+        N = int(N)
+        if N <= 0 or N > 512:
+            raise ValueError("Controls: N must lie in 1..512, got %r" % (N,))
+        host = torch.empty((len(self.TOK_NAMES), B, N), dtype=torch.float32)
+        late = []
+        for i, name in enumerate(self.TOK_NAMES):
+            v = tok[name]
+            host[i] = self.TOK_ABSENT[name]
+            if v is None:
+                continue
+            if torch.is_tensor(v) and v.is_cuda:  # never read: clamped where the kernels read it
+                if tuple(v.shape) != (B, N):
+                    raise ValueError("Controls: %s must be [%d, %d], got shape %s" % (name, B, N, tuple(v.shape)))
+                late.append((i, v))
+                continue
+            rows = torch.as_tensor(v, dtype=torch.float64)
+            if rows.numel() == 1:
+                rows = rows.reshape(1, 1).expand(B, N)
+            if tuple(rows.shape) != (B, N):
+                raise ValueError("Controls: %s must be one value or [%d, %d] values, got shape %s" % (name, B, N, tuple(rows.shape)))
+            lo, hi = self.TOK_RANGES[name]
+            if not bool((torch.isfinite(rows) & (rows >= lo) & (rows <= hi)).all()):
+                raise ValueError("Controls: %s must lie in [%g, %g]" % (name, lo, hi))
+            host[i] = rows.to(torch.float32)
+        self.N = N
+        self.tok_present = tuple(n for n in self.TOK_NAMES if tok[n] is not None)
+        self.tok_buf = host.to(device)  # ONE host -> device copy
+        for i, v in late:
+            self.tok_buf[i].copy_(v.detach().to(torch.float32))
 
     @classmethod
-    def neutral(cls, B, alpha=None, beta=None, t=None, device=None):
+    def neutral(cls, B, alpha=None, beta=None, t=None, device=None, N=None):
         """All six rows present and neutral: speed 1, f0_scale 1, n_shift 0 and the given mixing weights (None = the call's
-        scalars).  Equals the call without controls bit for bit."""
-        c = cls(B, speed=1.0, alpha=alpha, beta=beta, t=t, f0_scale=1.0, n_shift=0.0, device=device)
+        scalars).  Equals the call without controls bit for bit.  With `N` the three per-token rows too: 1, 1 and 0."""
+        c = cls(B, speed=1.0, alpha=alpha, beta=beta, t=t, f0_scale=1.0, n_shift=0.0, device=device, N=N)
         c.present = cls.NAMES
+        if N is not None:
+            c.tok_present = cls.TOK_NAMES
         return c
 
     @property
@@ -210,18 +271,27 @@ class Controls:
         """The fp32 [B] device row of a control, None when it is absent."""
         return self.buf[self.NAMES.index(name)] if name in self.present else None
 
+    def tok_row(self, name):
+        """The fp32 [B, N] device rows of a per-token control, None when it is absent."""
+        return self.tok_buf[self.TOK_NAMES.index(name)] if name in self.tok_present else None
+
     def front_rows(self):
-        """The present rows `st2_front_forward_ctl` reads (speed and the mixing weights)."""
-        return {n: self.row(n) for n in ("speed", "alpha", "beta", "t") if n in self.present}
+        """The present rows `st2_front_forward_ctl` reads (speed and the mixing weights), and under "tok_speed" the per-token
+        rate of `st2_front_forward_tok`."""
+        rows = {n: self.row(n) for n in ("speed", "alpha", "beta", "t") if n in self.present}
+        if "tok_speed" in self.tok_present:
+            rows["tok_speed"] = self.tok_row("tok_speed")
+        return rows
 
     def slice(self, i, j):
         """Rows i .. j-1 of the batch as a Controls over the same memory (long-form: a front group's sentences)."""
         c = object.__new__(Controls)
         c.B, c.present, c.buf = j - i, self.present, self.buf[:, i:j]
+        c.N, c.tok_present, c.tok_buf = self.N, self.tok_present, None if self.tok_buf is None else self.tok_buf[:, i:j]
         return c
 
 
-def _check_controls(controls, dev, B, taps, front, durations):
+def _check_controls(controls, dev, B, taps, front, durations, N=None):
     """What `controls=` cannot be combined with: refused before anything is launched."""
     if not isinstance(controls, Controls):
         raise ValueError("controls must be a pipeline.Controls, got %s" % type(controls).__name__)
@@ -237,6 +307,10 @@ def _check_controls(controls, dev, B, taps, front, durations):
         raise ValueError("controls describe %d rows on %s, the batch has %d on %s" % (controls.B, controls.device, B, dev))
     if durations is not None and "speed" in controls.present:
         raise ValueError("controls.speed with forced durations: there is nothing to scale")
+    if durations is not None and "tok_speed" in controls.tok_present:
+        raise ValueError("controls.tok_speed with forced durations: there is nothing to scale")
+    if controls.tok_present and N is not None and controls.N != N:
+        raise ValueError("controls hold per-token rows of %d tokens, the batch is %d wide" % (controls.N, N))
 
 
 def _prosody_controls(controls, F0, N, frames=None, sel=None):
@@ -249,6 +323,19 @@ def _prosody_controls(controls, F0, N, frames=None, sel=None):
     if sel is not None:
         rows = [None if v is None else sel(v).contiguous() for v in rows]
     ops.prosody_controls(F0, N, rows[0], rows[1], frames=frames)
+
+
+def _prosody_controls_tok(controls, F0, N, dur, frames=None, sel=None, shift=False):
+    """Token n's pitch scale / energy shift applied in place over its frames of the prosody call's curves, behind the per-row
+    controls (one launch; none when both are absent)."""
+    if controls is None or not controls.tok_present:
+        return
+    rows = [controls.tok_row("tok_f0_scale"), controls.tok_row("tok_n_shift")]
+    if rows[0] is None and rows[1] is None:
+        return
+    if sel is not None:
+        rows = [None if v is None else sel(v).contiguous() for v in rows]
+    ops.prosody_controls_tok(F0, N, dur.contiguous(), rows[0], rows[1], frames=frames, shift=shift)
 
 
 @torch.no_grad()
@@ -510,18 +597,22 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     `frames` (device) and no `frames_host`.  The whole call is then legal under stream capture when every input is a device
     tensor; a caller that passes `lengths_dev` gets the padded-batch semantics from it alone (`input_lengths` is not looked
     at: a captured call serves other lengths at replay).  A row whose durations sum to more than `max_frames` is synthesised
-    truncated to it and raises ST2_STATUS_FRAME_CAPACITY (a warning at the next `ops.check_status()`).  Forced `durations`
+    truncated to it and raises ST2_STATUS_FRAME_CAPACITY (a warning at the next `ops.check_status()`).  The result also carries
+    `token_lengths`: the device token counts the durations were predicted under (None for forced durations, whose rows count
+    whole), which `ops.token_marks` takes as its `lengths`.  Forced `durations`
     take the same route (their rows are summed whole, pad tokens included, as on the other paths).  `allow_ragged` and
     `ragged_decode` are implied whatever the caller passed; `total_frames` and `group_events` are refused.
 
     `controls` (a `Controls`; C++ engine path, no taps, no `front=`): per-row speaking rate, style mixing weights, pitch scale
     and energy shift.  Rate and weights are read by the front (`st2_front_forward_ctl`: the mixing is
     then one launch), pitch and energy are applied to F0 / N right behind every prosody call (`ops.prosody_controls`).  Nothing
-    of it is read on the host; None takes the code paths without it."""
+    of it is read on the host; None takes the code paths without it.  Its per-token rows go the same two
+    ways: the rate through `st2_front_forward_tok`, pitch and energy through `ops.prosody_controls_tok` right behind
+    `ops.prosody_controls`."""
     dev = tokens.device
     B, N = tokens.shape
     if controls is not None:
-        _check_controls(controls, dev, B, taps, front, durations)
+        _check_controls(controls, dev, B, taps, front, durations, N)
     if max_frames is not None:
         if int(max_frames) <= 0:
             raise ValueError("max_frames must be a positive frame count, got %r" % (max_frames,))
@@ -566,6 +657,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T, shift=hifigan,
                                                                          frames=frames)
         _prosody_controls(controls, F0_pred, N_pred, frames=frames, sel=sel)
+        _prosody_controls_tok(controls, F0_pred, N_pred, dur, frames=frames, sel=sel, shift=hifigan)
         return dict(asr=asr, F0=F0_pred, N=N_pred)
 
     if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
@@ -578,7 +670,8 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         durations = durations.contiguous()
         frames = ops.frames_from_durations(durations, len_arg, T_cap)
         d_cm = d.transpose(-1, -2).contiguous()
-        return dict(out, durations=durations, **prosody(whole, durations, T_cap, frames), frames=frames, max_frames=T_cap)
+        return dict(out, durations=durations, **prosody(whole, durations, T_cap, frames), frames=frames, max_frames=T_cap,
+                    token_lengths=len_arg)
     if durations is None:
         durations = f["durations"]
         tot = durations.sum(dim=1).tolist()  # the path's one data-dependent host sync: the frame counts
@@ -682,18 +775,24 @@ class SynthesisResult:
       packed   (with `pack`) the rows' valid samples minus `trim` each, back to back: int16 PCM ("s16") or fp32 ("f32"), or --
                with `sample_rate` / a G.711 `pack` -- those samples at `sample_rate` as fp32, int16 or mu-law / A-law bytes;
       offsets  (with `pack`) int64 [B + 1]: row b is packed[offsets[b]:offsets[b + 1]];
-      sample_rate  the rate of `packed` (24000 unless the call asked for another); `wave` is always at 24 kHz.
+      sample_rate  the rate of `packed` (24000 unless the call asked for another); `wave` is always at 24 kHz;
+      marks    (with `marks=True`) int32 [B, N + 1]: token n of row b is
+               packed[offsets[b] + marks[b, n] : offsets[b] + marks[b, n + 1]], marks[b, N] = the row's sample count.  The
+               positions are at `sample_rate`, after `trim`; pad tokens and tokens a truncated row lost sit at the row's end.
+               Kept in the same allocation, between `offsets` and the samples: `to_host(marks=True)` is still one copy.
     `to_host()` is the one place that waits."""
 
-    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None):
+    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None,
+                 marks=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
         self.sample_rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
-        self._buf = buf  # offsets and packed are views of this one allocation: one copy takes both
+        self.marks = marks
+        self._buf = buf  # offsets, marks and packed are views of this one allocation: one copy takes all
         self._host = None  # its pinned mirror, allocated by the first to_host()
 
-    def to_host(self):
+    def to_host(self, marks=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -702,7 +801,10 @@ class SynthesisResult:
         fp32 first.  The pinned buffer is allocated once per result object (a pinned allocation costs milliseconds) and the
         arrays are views of it: a `GraphedSynthesis` hands out the same result at every replay, so consume or copy them
         before the next `to_host()`.  The copy takes the buffer at capacity, not at offsets[B]: sizing it by the total
-        would need a second wait."""
+        would need a second wait.  `marks=True` (a result made with `marks=True`): returns (arrays, marks) with the timing marks as
+        an int32 [B, N + 1] numpy array out of the same copy."""
+        if marks and self.marks is None:
+            raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
         if self._buf is None:
             self._buf, self.packed, self.offsets = _pack_into_one(self.wave, self.frames, self.trim, self.pack or "f32",
                                                                   self.samples_per_frame, self.sample_rate)
@@ -718,7 +820,11 @@ class SynthesisResult:
         hdr = self._buf.numel() - self.packed.numel() * self.packed.element_size()
         offs = host[:8 * (B + 1)].view(torch.int64).tolist()
         samples = host[hdr:].view(self.packed.dtype).numpy()
-        return [samples[offs[b]:offs[b + 1]] for b in range(B)]
+        rows = [samples[offs[b]:offs[b + 1]] for b in range(B)]
+        if not marks:
+            return rows
+        m0 = 8 * (B + 1)
+        return rows, host[m0:m0 + 4 * self.marks.numel()].view(torch.int32).numpy().reshape(tuple(self.marks.shape))
 
 
 def _check_output(pack, sample_rate):
@@ -738,13 +844,13 @@ def _resamples(fmt, sample_rate):
     return sample_rate not in (None, resample.MODEL_RATE) or fmt not in ops.PACK_FORMATS
 
 
-def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None):
-    """`ops.wave_pack` -- or `ops.wave_resample_pack` -- into ONE device allocation, [offsets int64 [B + 1] | pad to 16 bytes |
-    samples at capacity: ceil(L U / D) per row], so that a single copy brings both to the host.  Returns (the allocation as
-    bytes, packed, offsets)."""
+def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0):
+    """`ops.wave_pack` -- or `ops.wave_resample_pack` -- into ONE device allocation, [offsets int64 [B + 1] | `n_marks` int32 |
+    pad to 16 bytes | samples at capacity: ceil(L U / D) per row], so that a single copy brings all of it to the host.  Returns
+    (the allocation as bytes, packed, offsets); with n_marks = 0 the layout is the one without marks, byte for byte."""
     B, L = wave.shape[0], wave.shape[-1]
     dtype = ops.OUTPUT_FORMATS[fmt][1]
-    hdr = (8 * (B + 1) + 15) // 16 * 16
+    hdr = (8 * (B + 1) + 4 * n_marks + 15) // 16 * 16
     into = lambda buf: dict(trim=trim, fmt=fmt, out=buf[hdr:].view(dtype), offsets=buf[:8 * (B + 1)].view(torch.int64),
                             samples_per_frame=samples_per_frame)
     if not _resamples(fmt, sample_rate):
@@ -758,18 +864,27 @@ def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None)
     return buf, packed, offsets
 
 
-def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None):
+def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
-    back, nothing is sliced on the host."""
+    back, nothing is sliced on the host.  `marks`: one `ops.token_marks` launch behind the packing writes the timing marks
+    into the hand-over allocation."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     if trim is None:
         trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
     if pack is None:
         return SynthesisResult(w, p["frames"], T_cap, trim=trim)
-    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, w.shape[-1] // T_cap, sample_rate)
+    dur = p["durations"]
+    B, N = dur.shape
+    spf = w.shape[-1] // T_cap
+    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0)
+    m = None
+    if marks:
+        m = buf[8 * (B + 1):8 * (B + 1) + 4 * B * (N + 1)].view(torch.int32).view(B, N + 1)
+        ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=model.decoder.kind == "hifigan", trim=trim,
+                        rate=sample_rate, samples_per_frame=spf, out=m)
     return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf,
-                           sample_rate=sample_rate)
+                           sample_rate=sample_rate, marks=m)
 
 
 class GraphedSynthesis:
@@ -788,11 +903,17 @@ class GraphedSynthesis:
     the graph is recorded over it holding the neutral values, `__call__(controls=)` copies the caller's rows in and a call
     without them resets it to neutral.  Other controls never re-record.
 
+    `marks=True`: the marks launch is recorded in the graph and the result carries `marks`.
+    `token_controls` (default: `marks`): the static `Controls` also holds the three per-token rows, neutral, and the graph is
+    recorded with the kernels that read them, so that one graph serves any token controls too; without it the graph issues
+    the launches it always did and refuses a `Controls` with token rows.
+
     `pack` / `sample_rate` as in `inference`: with an output rate or a G.711 format the packing step inside the graph is
     `ops.wave_resample_pack`, whose filter table is designed and uploaded here, before any capture."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
-                 embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None):
+                 embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
+                 token_controls=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -800,19 +921,25 @@ class GraphedSynthesis:
         if not _engine_path(dev):
             raise ValueError("GraphedSynthesis needs the C++ engine path (HIP device, plan_mode 'engine')")
         _check_output(pack, sample_rate)
+        if marks and pack is None:
+            raise ValueError("marks are positions in the packed samples: pass pack")
         if pack is not None and _resamples(pack, sample_rate):
             resample.table(resample.MODEL_RATE if sample_rate is None else sample_rate, dev)
         self.device, self.max_frames, self.steps = dev, int(max_frames), int(diffusion_steps)
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate)
+        if marks:
+            self.kw["marks"] = True
         z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
         self.static = dict(tokens=torch.zeros((B, N), device=dev, dtype=torch.int64),
                            lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=z(B, 1, 256),
                            step_noise=z(max(self.steps - 1, 0), B, 1, 256), sine_noise=z(B, 600 * self.max_frames, 9),
                            ref_s=None if ref_s is None else ref_s.detach().to(dev, torch.float32).reshape(-1, 256)
                            .expand(B, -1).contiguous())
-        self.static["controls"] = Controls.neutral(B, device=dev)  # NaN weights: the call's own scalars
+        tok = bool(marks) if token_controls is None else bool(token_controls)
+        self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
+        self._neutral_tok = self.static["controls"].tok_buf.clone() if tok else None
         self._g = None
 
     def _run(self):
@@ -836,9 +963,17 @@ class GraphedSynthesis:
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
+            if controls.tok_present and self._neutral_tok is None:
+                raise ValueError("per-token controls need a graph built with token_controls=True (or marks=True)")
+            if controls.tok_buf is not None and self._neutral_tok is not None and controls.N != st["controls"].N:
+                raise ValueError("controls hold per-token rows of %d tokens, this graph's token_controls are %d wide"
+                                 % (controls.N, st["controls"].N))
             st["controls"].buf.copy_(controls.buf, non_blocking=True)  # an absent row holds its neutral value
         else:
             st["controls"].buf.copy_(self._neutral, non_blocking=True)
+        if self._neutral_tok is not None:
+            has_tok = controls is not None and controls.tok_buf is not None
+            st["controls"].tok_buf.copy_(controls.tok_buf if has_tok else self._neutral_tok, non_blocking=True)
         for name, val in (("tokens", tokens), ("lengths_dev", lengths), ("noise", noise), ("step_noise", step_noise),
                           ("sine_noise", sine_noise), ("ref_s", ref_s)):
             if val is not None:
@@ -898,7 +1033,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
-              sample_rate=None):
+              sample_rate=None, marks=False):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -942,9 +1077,16 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     a right-padded batch without any host copy (stream capture, `GraphedSynthesis`).  `decode_streams` and `total_frames` are
     refused with `max_frames`.
 
-    `controls` (a `Controls`): per-row speaking rate, style mixing weights, pitch scale and energy shift, see `prepare`.
+    `controls` (a `Controls`): per-row speaking rate, style mixing weights, pitch scale and energy shift, and their per-token
+    forms, see `prepare`.
+
+    `marks=True` (with `max_frames` and `pack`): the result also carries `marks`, int32 [B, N + 1] on the
+    device -- where every token starts among its row's packed samples -- from one more launch (`ops.token_marks`);
+    `result.to_host(marks=True)` brings them over in its one copy.
     """
     _check_output(pack, sample_rate)
+    if marks and (max_frames is None or pack is None):
+        raise ValueError("marks are positions in the packed samples of the capacity-bound path: pass max_frames and pack")
     if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
         raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
     if max_frames is not None and decode_streams:
@@ -968,7 +1110,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
                   main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate)
+        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate, marks=bool(marks))
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1063,6 +1205,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
         raise ValueError("controls must be a pipeline.Controls of one row per sentence (%d)" % len(sentences))
+    if controls is not None and controls.tok_present:
+        raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
     if trim is None:
         trim = 100 if multispeaker else 0

@@ -26,6 +26,14 @@ def taps_per_phase(up, down):
     return K + (K & 1)
 
 
+def ratio(rate):
+    """-> (U, D): the reduced fraction rate / MODEL_RATE of an output rate of RATES, without designing its table."""
+    if rate not in RATES:
+        raise ValueError("output rate %r is not supported: one of %s at a model rate of %d" % (rate, list(RATES), MODEL_RATE))
+    g = math.gcd(int(rate), MODEL_RATE)
+    return int(rate) // g, MODEL_RATE // g
+
+
 def design(rate, model_rate=MODEL_RATE):
     """-> (U, D, taps float32 [U, K]): U / D is the reduced fraction rate / model_rate and
     taps[p][k] = g(k - (K - 1) // 2 - p / U) with g(t) = r sinc(r t) kaiser(2 t / K; beta), r = 0.925 min(1, U / D)."""
