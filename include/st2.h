@@ -561,6 +561,30 @@ int st2_wave_resample_pack(const float* wave, int64_t w_bs, const int32_t* frame
                            int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
                            int32_t taps_per_phase, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets, void* stream);
 
+/* ---- passages: breaks behind the rows of the packed hand-over (added under ABI 23, additive: one kernel-level entry point, no
+ * new backend-table slot, no struct change) ------------------------------------------------------ *
+ * st2_wave_pack_gaps: st2_wave_pack / st2_wave_resample_pack with g_b samples of silence behind row b -- the rows of a batch
+ * as the sentences of one passage, with SSML's <break> / <s> / <p> between them, in the hand-over's own rate and format.
+ *   m_b   the row's sample count by the wrapped entry's rule.  taps != NULL: st2_wave_resample_pack's m_b = (n_b U + D - 1)
+ *         div D.  taps == NULL: the caller passes up == down == 1 and fmt ST2_PCM_F32 or ST2_PCM_S16 (the codes of
+ *         ST2_PACK_F32 / ST2_PACK_S16), m_b = st2_wave_pack's n_b and its move kernel does the work.
+ *   g_b = clamp(gaps[b], 0, gap_cap), in OUTPUT samples; gaps int32 [B] on the device (a negative value gives 0).  gaps ==
+ *         NULL or gap_cap == 0: no gaps, and the call IS the wrapped entry (its two launches, its bytes).
+ *   offsets[b] = sum_{i < b} (m_i + g_i) (int64 [B + 1], device; 64-bit sums); offsets[B] the total, the last row's gap included.
+ *   out[offsets[b] + j], j < m_b: byte for byte what the wrapped entry writes for that row (its move kernel, unchanged).
+ *   out[offsets[b] + m_b + j] = cvt(0.0f), j < g_b: what the format's encoder gives for a zero sample -- 0.0f, 0, or the G.711
+ *         mu-law / A-law code of 0 (0xFF / 0xD5: silence is not byte 0 there).
+ * Nothing at or past min(offsets[B], out_capacity) is written (the bound may fall inside a gap), every element below it is
+ * written exactly once, and nothing of `wave` at or past a row's valid samples is read.  Three launches (gap-aware scan, move,
+ * fill), no allocation, no synchronisation: legal under stream capture.  The fill is one workgroup per (chunk, row), its grid
+ * sized by gap_cap and its work by g_b (a workgroup whose chunk lies past its gap's end leaves at once); it stores 16 bytes
+ * per lane on the aligned body of the gap and peels head and tail.  Returns non-zero before any launch on: every refusal of the
+ * entry it wraps; gap_cap < 0; taps == NULL together with up / down != 1 or a G.711 format; gaps misaligned for int32. */
+int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                       int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                       int32_t taps_per_phase, int32_t fmt /* st2_pcm_format */, const int32_t* gaps, int32_t gap_cap,
+                       void* out, int64_t out_capacity, int64_t* offsets, void* stream);
+
 /* ---- reference clips at a client's rate and in G.711 (added under ABI 23, additive: one kernel-level entry point and its
  * size helper, no new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
  * st2_clip_ingest: the way in of a zero-shot request.  src holds B rows of N_cap samples (row b at

@@ -97,24 +97,29 @@ extern "C" int st2_frames_from_durations(const int64_t* dur, int32_t B, int32_t 
   return 0;
 }
 
-extern "C" int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                             int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
-                             int64_t* offsets, void* stream) {
-  ST2_REQUIRE(wave && frames && out && offsets, "st2_wave_pack: wave / frames / out / offsets is NULL");
+int st2_wave_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                        int32_t samples_per_frame, int32_t trim, int32_t fmt, const void* out, int64_t out_capacity,
+                        const int64_t* offsets) {
+  ST2_REQUIRE(wave && frames && out && offsets, "%s: wave / frames / out / offsets is NULL", who);
   ST2_REQUIRE(B > 0 && B <= 65535 && T_cap > 0 && samples_per_frame > 0,
-              "st2_wave_pack: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)", B, T_cap, samples_per_frame);
-  ST2_REQUIRE(trim >= 0 && out_capacity >= 0, "st2_wave_pack: trim=%d / out_capacity=%lld must not be negative", trim,
+              "%s: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)", who, B, T_cap, samples_per_frame);
+  ST2_REQUIRE(trim >= 0 && out_capacity >= 0, "%s: trim=%d / out_capacity=%lld must not be negative", who, trim,
               (long long)out_capacity);
-  ST2_REQUIRE(fmt == ST2_PACK_F32 || fmt == ST2_PACK_S16, "st2_wave_pack: unknown format %d", fmt);
+  ST2_REQUIRE(fmt == ST2_PACK_F32 || fmt == ST2_PACK_S16, "%s: unknown format %d", who, fmt);
   ST2_REQUIRE(reinterpret_cast<uintptr_t>(out) % (fmt == ST2_PACK_S16 ? 2 : 4) == 0 && reinterpret_cast<uintptr_t>(wave) % 4 == 0,
-              "st2_wave_pack: wave / out is not aligned to its sample type");
+              "%s: wave / out is not aligned to its sample type", who);
   const int64_t row = (int64_t)samples_per_frame * T_cap;
-  ST2_REQUIRE(B == 1 || w_bs >= row, "st2_wave_pack: w_bs=%lld is less than the %lld samples of a row at capacity",
-              (long long)w_bs, (long long)row);
+  ST2_REQUIRE(B == 1 || w_bs >= row, "%s: w_bs=%lld is less than the %lld samples of a row at capacity", who, (long long)w_bs,
+              (long long)row);
+  return 0;
+}
+
+int st2_wave_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                       int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
+                       const int64_t* offsets, void* stream) {
+  const int64_t row = (int64_t)samples_per_frame * T_cap;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  long long* offs = reinterpret_cast<long long*>(offsets);
-  hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(64), 0, s, frames, B, T_cap, samples_per_frame, trim, offs);
-  ST2_CHECK_LAUNCH("st2_wave_pack (offsets)");
+  const long long* offs = reinterpret_cast<const long long*>(offsets);
   if (fmt == ST2_PACK_S16) {
     const int gx = st2_cdiv(st2_cdiv(row, 8), PACK_THREADS * PACK_ITERS);
     hipLaunchKernelGGL((wave_pack_kernel<int16_t, 8>), dim3(gx, B), dim3(PACK_THREADS), 0, s, wave, w_bs, frames, B, T_cap,
@@ -124,6 +129,18 @@ extern "C" int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* fra
     hipLaunchKernelGGL((wave_pack_kernel<float, 4>), dim3(gx, B), dim3(PACK_THREADS), 0, s, wave, w_bs, frames, B, T_cap,
                        samples_per_frame, trim, reinterpret_cast<float*>(out), (long long)out_capacity, offs);
   }
-  ST2_CHECK_LAUNCH("st2_wave_pack");
+  ST2_CHECK_LAUNCH(who);
   return 0;
+}
+
+extern "C" int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                             int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
+                             int64_t* offsets, void* stream) {
+  if (st2_wave_pack_check("st2_wave_pack", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets))
+    return 1;
+  hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), frames, B, T_cap,
+                     samples_per_frame, trim, reinterpret_cast<long long*>(offsets));
+  ST2_CHECK_LAUNCH("st2_wave_pack (offsets)");
+  return st2_wave_pack_move("st2_wave_pack", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets,
+                            stream);
 }

@@ -1,0 +1,111 @@
+// st2_wave_pack_gaps (st2.h, added under ABI 23): the packing step of the sync-free path with a BREAK
+// behind every row -- silence of a per-row length read from device memory, in the hand-over's own rate and sample format.  The
+// rows of one batch are then the sentences of a passage, laid out as a client plays them.  Three launches: a scan that counts
+// every row's samples and its gap, the move kernel of st2_wave_pack / st2_wave_resample_pack as it is (it takes a row's start
+// from offsets[b] and its length from the frames), and a fill of the gaps.
+#include "st2_common.h"
+#include "st2_pcm.h"
+
+namespace {
+
+// g_b = clamp(gaps[b], 0, gap_cap) output samples
+__device__ __forceinline__ long long gap_samples(const int32_t* __restrict__ gaps, int b, int gap_cap) {
+  return min(max(gaps[b], 0), gap_cap);
+}
+
+// offsets[b] = sum_{i < b} (m_i + g_i), m_i = (n_i U + D - 1) div D  (U = D = 1: n_i, st2_wave_pack's count)
+__global__ __launch_bounds__(64) void gap_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf, int trim,
+                                                         int U, int D, const int32_t* __restrict__ gaps, int gap_cap,
+                                                         long long* __restrict__ offsets) {
+  pack_scan_rows(B, offsets, [&](int b) {
+    return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D + gap_samples(gaps, b, gap_cap);
+  });
+}
+
+constexpr int FILL_THREADS = 256;
+constexpr int FILL_ITERS = 4;  // 16-byte stores per lane and workgroup
+
+// Workgroup (chunk, b) writes FILL_THREADS * FILL_ITERS 16-byte vectors of the ALIGNED body of row b's gap -- the g_b samples
+// in front of offsets[b + 1] -- with the format's code of a zero sample; chunk 0 also writes the gap's head (the samples in front
+// of the first 16-byte boundary of the destination) and its tail, both shorter than one vector.  A workgroup whose chunk lies
+// behind the gap's end -- or behind the write bound -- leaves at once: the grid is sized by gap_cap, the work by g_b.
+template <int FMT>
+__global__ __launch_bounds__(FILL_THREADS) void gap_fill_kernel(const int32_t* __restrict__ gaps, int gap_cap, int B,
+                                                                typename pcm_fmt<FMT>::type* __restrict__ out,
+                                                                long long out_capacity, const long long* __restrict__ offsets) {
+  using OUT = typename pcm_fmt<FMT>::type;
+  constexpr int V = 16 / (int)sizeof(OUT);
+  const int b = blockIdx.y;
+  const long long limit = min(offsets[B], out_capacity);  // nothing at or past it is written
+  const long long g = gap_samples(gaps, b, gap_cap);
+  const long long start = offsets[b + 1] - g;  // = offsets[b] + m_b: the scan counted the same g
+  const long long n = min(g, max(limit - start, 0LL));
+  if (n <= 0) return;
+  OUT* __restrict__ dst = out + start;
+  const long long head = min(n, (long long)((16 - (int)(reinterpret_cast<uintptr_t>(dst) & 15)) & 15) / (long long)sizeof(OUT));
+  const long long nvec = (n - head) / V;
+  const long long v0 = (long long)blockIdx.x * (FILL_THREADS * FILL_ITERS);
+  if (v0 >= nvec && blockIdx.x != 0) return;
+  const OUT z = pcm_encode<FMT>(0.0f);  // silence as the format's own encoder states it: 0.0f, 0, mu-law 0xFF, A-law 0xD5
+  union {
+    OUT s[V];
+    uint4 q;
+  } zv;
+#pragma unroll
+  for (int r = 0; r < V; ++r) zv.s[r] = z;
+#pragma unroll
+  for (int it = 0; it < FILL_ITERS; ++it) {
+    const long long v = v0 + it * FILL_THREADS + threadIdx.x;
+    if (v >= nvec) break;
+    *reinterpret_cast<uint4*>(dst + head + v * V) = zv.q;
+  }
+  if (blockIdx.x == 0) {
+    const long long t0 = head + nvec * V;  // head < V and n - t0 < V, V <= 16: one lane per sample
+    long long i = -1;
+    if ((long long)threadIdx.x < head) i = threadIdx.x;
+    else if (threadIdx.x >= 64 && t0 + (threadIdx.x - 64) < n) i = t0 + (threadIdx.x - 64);
+    if (i >= 0) dst[i] = z;
+  }
+}
+
+}  // namespace
+
+extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                                  int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                                  int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
+                                  int64_t out_capacity, int64_t* offsets, void* stream) {
+  const char* who = "st2_wave_pack_gaps";
+  ST2_REQUIRE(gap_cap >= 0, "%s: gap_cap=%d must not be negative", who, gap_cap);
+  ST2_REQUIRE(reinterpret_cast<uintptr_t>(gaps) % 4 == 0, "%s: gaps is not aligned to int32", who);
+  int tile = 0;
+  if (!taps) {
+    ST2_REQUIRE(up == 1 && down == 1, "%s: without taps the rows are moved as they are: up=%d / down=%d must be 1", who, up, down);
+    ST2_REQUIRE(fmt == ST2_PCM_F32 || fmt == ST2_PCM_S16,
+                "%s: format %d needs the resampling move (taps); without taps fp32 and 16-bit PCM only", who, fmt);
+    if (st2_wave_pack_check(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets)) return 1;
+  } else if (st2_wave_resample_pack_check(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps,
+                                          taps_per_phase, fmt, out, out_capacity, offsets, &tile)) {
+    return 1;
+  }
+  if (!gaps || gap_cap == 0)  // no gaps: the wrapped entry itself, scan and move
+    return taps ? st2_wave_resample_pack(wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt,
+                                         out, out_capacity, offsets, stream)
+                : st2_wave_pack(wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets, stream);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  long long* offs = reinterpret_cast<long long*>(offsets);
+  hipLaunchKernelGGL(gap_offsets_kernel, dim3(1), dim3(64), 0, s, frames, B, T_cap, samples_per_frame, trim, up, down, gaps,
+                     gap_cap, offs);
+  ST2_CHECK_LAUNCH("st2_wave_pack_gaps (offsets)");
+  const int rc = taps ? st2_wave_resample_pack_move(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps,
+                                                    taps_per_phase, fmt, tile, out, out_capacity, offsets, stream)
+                      : st2_wave_pack_move(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity,
+                                           offsets, stream);
+  if (rc) return rc;
+  const int gx = st2_cdiv(st2_cdiv(gap_cap, 16 / pcm_sample_bytes(fmt)), FILL_THREADS * FILL_ITERS);  // >= 1: gap_cap > 0
+  pcm_dispatch(fmt, [&](auto f) {
+    hipLaunchKernelGGL((gap_fill_kernel<f()>), dim3(gx, B), dim3(FILL_THREADS), 0, s, gaps, gap_cap, B,
+                       reinterpret_cast<typename pcm_fmt<f()>::type*>(out), (long long)out_capacity, offs);
+  });
+  ST2_CHECK_LAUNCH("st2_wave_pack_gaps (fill)");
+  return 0;
+}

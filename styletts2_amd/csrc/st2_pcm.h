@@ -114,6 +114,24 @@ __device__ __forceinline__ float4 pcm_decode4(const typename pcm_fmt<FMT>::type*
 }
 __device__ __forceinline__ float4 load_f32x4(const float* __restrict__ p) { return pcm_decode4<ST2_PCM_F32>(p); }
 
+// The two packing entries in two steps each, so that st2_wave_pack_gaps (st2_passage.hip) wraps them with the move kernels as
+// they are: `check` is every refusal of the entry (`who` names the caller in the message; the resampling one also returns the
+// output tile its LDS budget allows), `move` the move launch over offsets that some scan has written on the same stream.
+int st2_wave_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                        int32_t samples_per_frame, int32_t trim, int32_t fmt, const void* out, int64_t out_capacity,
+                        const int64_t* offsets);
+int st2_wave_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                       int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
+                       const int64_t* offsets, void* stream);
+int st2_wave_resample_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B,
+                                 int32_t T_cap, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down,
+                                 const float* taps, int32_t taps_per_phase, int32_t fmt, const void* out, int64_t out_capacity,
+                                 const int64_t* offsets, int* tile);
+int st2_wave_resample_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                                int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                                int32_t taps_per_phase, int32_t fmt, int tile, void* out, int64_t out_capacity,
+                                const int64_t* offsets, void* stream);
+
 inline int pcm_sample_bytes(int fmt) { return fmt == ST2_PCM_F32 ? 4 : (fmt == ST2_PCM_S16 ? 2 : 1); }
 
 // f(std::integral_constant<int, FMT>) for a format code of st2.h (checked by the caller)

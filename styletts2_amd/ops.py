@@ -1260,6 +1260,36 @@ def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=
     return out, offsets
 
 
+def wave_pack_gaps(wave, frames, gaps, max_gap, rate=None, fmt="s16", trim=0, out=None, offsets=None, samples_per_frame=600):
+    """`st2_wave_pack_gaps`: `wave_pack` (rate None: "f32" / "s16" at the model rate) or `wave_resample_pack` (`rate` one of
+    `resample.RATES`, any format of OUTPUT_FORMATS) with a break behind every row.  gaps int32 [B] on the device: row b is
+    followed by clamp(gaps[b], 0, max_gap) samples of silence at the output rate, in the output format's own code for a zero
+    sample (0.0, 0, mu-law 0xFF, A-law 0xD5); None = no gaps, the wrapped entry itself.  -> (packed, offsets): offsets[b] =
+    sum_{i < b} (m_i + g_i), the speech of row b at packed[offsets[b] : offsets[b + 1] - g_b], byte for byte what the wrapped entry
+    writes.  `out` (1-D, of the format's dtype) bounds what is written: nothing at or past min(offsets[B], out.numel()); by
+    default it holds every row at capacity and `max_gap` samples behind each.  No host read; with a rate the first call for a
+    (rate, device) designs and uploads the table, which therefore must not happen under stream capture."""
+    from . import resample
+    max_gap = int(max_gap)
+    if rate is None:
+        if fmt not in PACK_FORMATS:
+            raise ValueError("fmt must be one of %s without a rate, got %r" % (sorted(PACK_FORMATS), fmt))
+        code, dtype = OUTPUT_FORMATS[fmt]
+        table = lambda: (1, 1, 0, None)
+    else:
+        code, dtype = _pcm_format(fmt, rate)
+        table = lambda: resample.table(rate, wave.device)  # first asked for once `wave` is known to live on a device
+    wave, lp, B, L, spf, out, offsets = _pack_operands(
+        wave, frames, samples_per_frame, dtype, out, offsets,
+        lambda L: resample.output_samples(L, *table()[:2]) + max(max_gap, 0))
+    gp = _chk_len(gaps, "gaps", B, wave)
+    U, D, K, taps = table()
+    _lib.check(_lib.load().st2_wave_pack_gaps(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D, _ptr(taps), K,
+                                              code, gp, max_gap, out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()),
+               "st2_wave_pack_gaps")
+    return out, offsets
+
+
 def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):
     """`st2_clip_ingest`: reference clips in a client's rate and sample format -> trimmed fp32 rows at 24 kHz.  src [B, N_cap]
     on the device, of the dtype of `fmt` ("f32" float32, "s16" int16, "ulaw" / "alaw" uint8), n int32 [B] on the device (row

@@ -780,19 +780,27 @@ class SynthesisResult:
                packed[offsets[b] + marks[b, n] : offsets[b] + marks[b, n + 1]], marks[b, N] = the row's sample count.  The
                positions are at `sample_rate`, after `trim`; pad tokens and tokens a truncated row lost sit at the row's end.
                Kept in the same allocation, between `offsets` and the samples: `to_host(marks=True)` is still one copy.
+      style    [B, 256]: the mixed style rows (`prepare`'s `s_pred`); a passage continues in the next call with
+               `s_prev=result.style[-1:]` (DESIGN.md section 19);
+      gaps     (with `gaps=`) int32 [B]: the samples of silence asked for behind every row, as the packing step read them (it
+               clamps them to 0..`max_gap`), kept in the same allocation behind the marks.  Row b's speech is then
+               packed[offsets[b] : offsets[b + 1] - g_b], its break the g_b samples behind it, and offsets[B] the length of the
+               whole passage.  `marks` stay relative to their row: a position in the passage is offsets[b] + marks[b, n], and
+               offsets[b + 1] - offsets[b] = marks[b, N] + g_b.
     `to_host()` is the one place that waits."""
 
     def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None,
-                 marks=None):
+                 marks=None, style=None, gaps=None, max_gap=0):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
         self.sample_rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
         self.marks = marks
+        self.style, self.gaps, self.max_gap = style, gaps, int(max_gap)
         self._buf = buf  # offsets, marks and packed are views of this one allocation: one copy takes all
         self._host = None  # its pinned mirror, allocated by the first to_host()
 
-    def to_host(self, marks=False):
+    def to_host(self, marks=False, passage=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -802,7 +810,9 @@ class SynthesisResult:
         arrays are views of it: a `GraphedSynthesis` hands out the same result at every replay, so consume or copy them
         before the next `to_host()`.  The copy takes the buffer at capacity, not at offsets[B]: sizing it by the total
         would need a second wait.  `marks=True` (a result made with `marks=True`): returns (arrays, marks) with the timing marks as
-        an int32 [B, N + 1] numpy array out of the same copy."""
+        an int32 [B, N + 1] numpy array out of the same copy.  A result with `gaps` gives every row's speech WITHOUT its break,
+        as a result without gaps does; `passage=True` gives instead the ONE contiguous array packed[:offsets[B]], speech and
+        breaks as a client plays them."""
         if marks and self.marks is None:
             raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
         if self._buf is None:
@@ -820,10 +830,17 @@ class SynthesisResult:
         hdr = self._buf.numel() - self.packed.numel() * self.packed.element_size()
         offs = host[:8 * (B + 1)].view(torch.int64).tolist()
         samples = host[hdr:].view(self.packed.dtype).numpy()
-        rows = [samples[offs[b]:offs[b + 1]] for b in range(B)]
+        m0 = 8 * (B + 1)
+        if passage:
+            rows = samples[:offs[B]]
+        elif self.gaps is None:
+            rows = [samples[offs[b]:offs[b + 1]] for b in range(B)]
+        else:  # the breaks as the packing step counted them: clamped to 0..max_gap
+            g0 = m0 + (4 * self.marks.numel() if self.marks is not None else 0)
+            g = host[g0:g0 + 4 * B].view(torch.int32).clamp(0, self.max_gap).tolist()
+            rows = [samples[offs[b]:offs[b + 1] - g[b]] for b in range(B)]
         if not marks:
             return rows
-        m0 = 8 * (B + 1)
         return rows, host[m0:m0 + 4 * self.marks.numel()].view(torch.int32).numpy().reshape(tuple(self.marks.shape))
 
 
@@ -838,21 +855,84 @@ def _check_output(pack, sample_rate):
         raise ValueError("sample_rate must be None or one of %s, got %r" % (list(resample.RATES), sample_rate))
 
 
+def gap_samples(ms, sample_rate=None):
+    """A break of `ms` milliseconds as samples of the hand-over at `sample_rate` (None: the model's 24 kHz): rint(ms * rate /
+    1000), ties to even -- the one conversion between SSML's break times and `gaps=`.  A scalar gives an int, a sequence a list."""
+    rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
+    one = lambda v: int(round(float(v) * rate / 1000.0))  # Python's round: half to even, as rint
+    return [one(v) for v in ms] if isinstance(ms, (list, tuple)) else one(ms)
+
+
+def _check_gaps(gaps, max_gap, B):
+    """`gaps=` -> (int32 [B] tensor, host or device as given; max_gap): a host sequence defaults `max_gap` to its own maximum, a
+    device tensor is never read and needs it."""
+    if torch.is_tensor(gaps) and gaps.is_cuda:
+        if max_gap is None:
+            raise ValueError("gaps on the device are never read on the host: pass max_gap, the longest break in samples")
+        if gaps.dtype != torch.int32 or gaps.numel() != B:
+            raise ValueError("gaps must be an int32 tensor of %d entries, got %s %s" % (B, gaps.dtype, tuple(gaps.shape)))
+    else:
+        gaps = torch.as_tensor(gaps).reshape(-1)
+        if gaps.numel() != B or gaps.dtype.is_floating_point or int(gaps.abs().max()) >= 2 ** 31:
+            raise ValueError("gaps must be %d whole sample counts (pipeline.gap_samples converts milliseconds)" % B)
+        if max_gap is None:
+            max_gap = max(int(gaps.max()), 0)
+        gaps = gaps.to(torch.int32)
+    if int(max_gap) < 0:
+        raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
+    return gaps, int(max_gap)
+
+
+def _passage_controls(controls, starts, B, dev):
+    """The start flags of `inference(passage=[...])` as mixing weight t = 0 on the flagged rows: a `Controls` over a copy of the
+    caller's rows (all absent when there are none) whose `t` row -- what `st2_style_mix_rows` weighs the previous style with -- is
+    0 where a passage begins and the caller's value (NaN = the call's scalar) elsewhere.  mix2(0, prev, 1, cur) is cur for a finite
+    prev.  A device tensor of flags is never read on the host."""
+    if torch.is_tensor(starts) and starts.is_cuda:
+        flag = starts.reshape(-1) != 0
+    else:
+        flag = torch.as_tensor(starts).reshape(-1) != 0
+    if flag.numel() != B:
+        raise ValueError("passage must be True or %d start flags, got %d" % (B, flag.numel()))
+    flag = flag.to(dev)
+    if controls is None:
+        controls = Controls(B, device=dev)
+    c = controls.slice(0, B)
+    c.buf = controls.buf.clone()
+    i = Controls.NAMES.index("t")
+    c.buf[i] = torch.where(flag, torch.zeros((), device=dev), controls.buf[i])
+    c.present = tuple(n for n in Controls.NAMES if n in controls.present or n == "t")
+    return c
+
+
 def _resamples(fmt, sample_rate):
     """True when the packing step is `ops.wave_resample_pack`: another rate than the model's, or a G.711 format.  24 kHz fp32 /
     16-bit PCM stays `ops.wave_pack`."""
     return sample_rate not in (None, resample.MODEL_RATE) or fmt not in ops.PACK_FORMATS
 
 
-def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0):
+def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0):
     """`ops.wave_pack` -- or `ops.wave_resample_pack` -- into ONE device allocation, [offsets int64 [B + 1] | `n_marks` int32 |
     pad to 16 bytes | samples at capacity: ceil(L U / D) per row], so that a single copy brings all of it to the host.  Returns
-    (the allocation as bytes, packed, offsets); with n_marks = 0 the layout is the one without marks, byte for byte."""
+    (the allocation as bytes, packed, offsets); with n_marks = 0 the layout is the one without marks, byte for byte.
+    `gaps` (int32 [B], host or device): the layout gains B int32 behind the marks, into which the gaps are
+    copied and from which `ops.wave_pack_gaps` reads them, and `max_gap` more samples per row; returns the gaps' view as a fourth
+    value.  Without `gaps` nothing changes: the same two wrappers, the same bytes."""
     B, L = wave.shape[0], wave.shape[-1]
     dtype = ops.OUTPUT_FORMATS[fmt][1]
-    hdr = (8 * (B + 1) + 4 * n_marks + 15) // 16 * 16
+    hdr = (8 * (B + 1) + 4 * n_marks + (0 if gaps is None else 4 * B) + 15) // 16 * 16
     into = lambda buf: dict(trim=trim, fmt=fmt, out=buf[hdr:].view(dtype), offsets=buf[:8 * (B + 1)].view(torch.int64),
                             samples_per_frame=samples_per_frame)
+    if gaps is not None:
+        rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
+        U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
+        room = B * (resample.output_samples(L, U, D) + max_gap)
+        buf = torch.empty((hdr + room * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
+        g0 = 8 * (B + 1) + 4 * n_marks
+        g = buf[g0:g0 + 4 * B].view(torch.int32)
+        g.copy_(gaps.reshape(B), non_blocking=True)
+        packed, offsets = ops.wave_pack_gaps(wave, frames, g, max_gap, rate=rate, **into(buf))
+        return buf, packed, offsets, g
     if not _resamples(fmt, sample_rate):
         buf = torch.empty((hdr + B * L * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
         packed, offsets = ops.wave_pack(wave, frames, **into(buf))
@@ -864,27 +944,32 @@ def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None,
     return buf, packed, offsets
 
 
-def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False):
+def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False, gaps=None, max_gap=0):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `marks`: one `ops.token_marks` launch behind the packing writes the timing marks
-    into the hand-over allocation."""
+    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows (`_pack_into_one`)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     if trim is None:
         trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
     if pack is None:
-        return SynthesisResult(w, p["frames"], T_cap, trim=trim)
+        return SynthesisResult(w, p["frames"], T_cap, trim=trim, style=p["s_pred"])
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0)
+    n_marks = B * (N + 1) if marks else 0
+    if gaps is None:
+        buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=n_marks)
+    else:
+        buf, packed, offsets, gaps = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=n_marks, gaps=gaps,
+                                                    max_gap=max_gap)
     m = None
     if marks:
         m = buf[8 * (B + 1):8 * (B + 1) + 4 * B * (N + 1)].view(torch.int32).view(B, N + 1)
         ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=model.decoder.kind == "hifigan", trim=trim,
                         rate=sample_rate, samples_per_frame=spf, out=m)
     return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf,
-                           sample_rate=sample_rate, marks=m)
+                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=gaps, max_gap=max_gap)
 
 
 class GraphedSynthesis:
@@ -909,11 +994,18 @@ class GraphedSynthesis:
     the launches it always did and refuses a `Controls` with token rows.
 
     `pack` / `sample_rate` as in `inference`: with an output rate or a G.711 format the packing step inside the graph is
-    `ops.wave_resample_pack`, whose filter table is designed and uploaded here, before any capture."""
+    `ops.wave_resample_pack`, whose filter table is designed and uploaded here, before any capture.
+
+    `passage=True` / `max_gap`: the graph records the style carry-over and, with `max_gap` (which needs
+    `pack`), the gap-aware pack, over three more static buffers -- `starts` (int32 [B]: 1 where a row begins a passage; at first
+    row 0 alone), `s_prev` ([1, 256]: the style row 0 continues from unless its start flag is set) and `gaps` (int32 [B], zeros:
+    samples of silence behind every row, clamped to 0..max_gap by the kernel).  `__call__(starts=, s_prev=, gaps=)` fills them
+    (what is left out keeps its contents): one recorded graph serves any breaks up to `max_gap`, any start flags and any
+    `s_prev`.  `t` is the carry-over's weight.  Built without them, the graph records exactly what it recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None):
+                 token_controls=None, passage=False, max_gap=None, t=0.7):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -940,13 +1032,30 @@ class GraphedSynthesis:
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
         self._neutral_tok = self.static["controls"].tok_buf.clone() if tok else None
+        if max_gap is not None and pack is None:
+            raise ValueError("gaps are silence in the packed samples: pass pack")
+        if max_gap is not None and int(max_gap) < 0:
+            raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
+        self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
+        if self.passage:
+            starts = torch.zeros((B,), device=dev, dtype=torch.int32)
+            starts[:1] = 1
+            self.static.update(starts=starts, s_prev=z(1, 256))
+            self.kw["t"] = t
+        if self.max_gap is not None:
+            self.static["gaps"] = torch.zeros((B,), device=dev, dtype=torch.int32)
         self._g = None
 
     def _run(self):
         st = self.static
+        more = {}
+        if self.passage:
+            more.update(passage=st["starts"], s_prev=st["s_prev"])
+        if self.max_gap is not None:
+            more.update(gaps=st["gaps"], max_gap=self.max_gap)
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
-                         controls=st["controls"], **self.kw)
+                         controls=st["controls"], **more, **self.kw)
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -958,8 +1067,18 @@ class GraphedSynthesis:
         return dict(graph=graph, out=out, gen=_sampler_generation(self.sampler), engines=[(e, e.calib_gen) for e in engs])
 
     @torch.no_grad()
-    def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None):
+    def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
+                 starts=None, s_prev=None, gaps=None):
         st = self.static
+        for name, val in (("starts", starts), ("s_prev", s_prev), ("gaps", gaps)):
+            if val is None:
+                continue
+            if name not in st:
+                raise ValueError("this graph was built without %s: pass %s" % (name, "max_gap" if name == "gaps" else "passage=True"))
+            val = val if torch.is_tensor(val) else torch.as_tensor(val)
+            if val.numel() != st[name].numel():
+                raise ValueError("%s must hold %d values, got %d" % (name, st[name].numel(), val.numel()))
+            st[name].copy_(val.reshape(st[name].shape), non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
@@ -1033,7 +1152,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
-              sample_rate=None, marks=False):
+              sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1083,8 +1202,33 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     `marks=True` (with `max_frames` and `pack`): the result also carries `marks`, int32 [B, N + 1] on the
     device -- where every token starts among its row's packed samples -- from one more launch (`ops.token_marks`);
     `result.to_host(marks=True)` brings them over in its one copy.
+
+    `passage` (with `max_frames`): True -- the B rows are consecutive sentences of ONE passage: row k's
+    sampled style is mixed with row k-1's mixed style with weight `t` (`prepare(carry=True)`), and `s_prev` ([1, 256] or None)
+    feeds row 0.  A [B] host sequence or device tensor of start flags -- one batch, several passages: every flagged row begins a
+    new one (its mixing weight is 0, through the `Controls` `t` row); row 0 begins one unless `s_prev` is given.  A device
+    tensor is never read on the host.  `result.style[-1:]` is the `s_prev` of the call that continues the passage.
+    `gaps` (with `max_frames` and `pack`): per-row samples of silence behind every row, at the hand-over's rate and in its format
+    (`ops.wave_pack_gaps`; `gap_samples(ms, sample_rate)` converts milliseconds) -- an int32 [B] device tensor, which needs
+    `max_gap` (the packing step clamps to 0..max_gap and sizes its allocation by it), or a host list, whose maximum is the
+    default.  `marks` stay relative to their row (`SynthesisResult`).
     """
     _check_output(pack, sample_rate)
+    if max_frames is None and (passage is not None or gaps is not None or max_gap is not None or s_prev is not None):
+        raise ValueError("passage / gaps / max_gap / s_prev belong to the capacity-bound path: pass max_frames")
+    if pack is None and (gaps is not None or max_gap is not None):
+        raise ValueError("gaps are silence in the packed samples: pass pack")
+    if gaps is None and max_gap is not None:
+        raise ValueError("max_gap bounds `gaps`: pass gaps")
+    carry = passage is not None and passage is not False
+    if s_prev is not None and not carry:
+        raise ValueError("s_prev is the style a passage continues from: pass passage")
+    if gaps is not None:
+        gaps, max_gap = _check_gaps(gaps, max_gap, tokens.shape[0])
+    if carry and passage is not True:
+        if controls is not None:
+            _check_controls(controls, tokens.device, tokens.shape[0], taps, front, durations, tokens.shape[1])
+        controls = _passage_controls(controls, passage, tokens.shape[0], tokens.device)
     if marks and (max_frames is None or pack is None):
         raise ValueError("marks are positions in the packed samples of the capacity-bound path: pass max_frames and pack")
     if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
@@ -1097,6 +1241,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               front=front, ragged_decode=ragged_decode, controls=controls)
     if max_frames is not None:
         kw.update(max_frames=max_frames, lengths_dev=lengths_dev)
+    if carry:
+        kw.update(carry=True, s_prev=s_prev, t=t)
     if front_stream is None:
         p = prepare(model, sampler, tokens, **kw)
     else:
@@ -1110,7 +1256,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
                   main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate, marks=bool(marks))
+        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate, marks=bool(marks), gaps=gaps,
+                                max_gap=0 if gaps is None else max_gap)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1157,7 +1304,8 @@ def _decode_stream_list(decode_streams, use_streams, make):
 def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, t=0.7, diffusion_steps=5,
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
-                    ragged_decode=False, controls=None):
+                    ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
+                    max_gap=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1201,10 +1349,28 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `controls` (a `Controls` of one row per SENTENCE): per-sentence speaking rate, mixing weights (`t` of row k weighs sentence
     k-1's style into sentence k), pitch scale and energy shift.  A front group's carry-over is then ONE launch
     (`st2_style_mix_rows`) instead of five per sentence.
+
+    `max_frames` (int): the passage on the sync-free path.  Every front group is ONE
+    `inference(max_frames=, passage=True, s_prev=<the previous group's style[-1:]>)` on the caller's stream: the token counts
+    come from the sentences' shapes, nothing is read back, and the return value is (list of `SynthesisResult`, one per front
+    group, final style [1, 256]); `on_chunk(k, result)` is called per GROUP.  `pack`, `sample_rate`, `marks` and `gaps` (one
+    break per sentence: a host list, or an int32 device tensor with `max_gap`) are `inference`'s and need `max_frames`.
+    `sine_noises` rows are stacked, zero-padded, to the capacity.  Per-token controls are served here: the rows are
+    right-padded to the controls' width N, which must be the longest sentence's.  `decode_streams` > 1 is refused (there is one
+    decoder call per group, on the caller's stream); `overlap`, `front`, `side_stream` and `ragged_decode` have no meaning.
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
         raise ValueError("controls must be a pipeline.Controls of one row per sentence (%d)" % len(sentences))
+    if max_frames is not None:
+        return _synthesize_long_capacity(model, sampler, sentences, ref_s=ref_s, alpha=alpha, beta=beta, t=t,
+                                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, noises=noises,
+                                         step_noises=step_noises, sine_noises=sine_noises, durations=durations, trim=trim,
+                                         on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch,
+                                         decode_streams=decode_streams, controls=controls, max_frames=max_frames, pack=pack,
+                                         sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap)
+    if pack is not None or sample_rate is not None or marks or gaps is not None or max_gap is not None:
+        raise ValueError("pack / sample_rate / marks / gaps / max_gap belong to the capacity-bound path: pass max_frames")
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
@@ -1293,6 +1459,70 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     if use_streams:
         _hand_off((s_prev,), main)  # allocated on the side stream, handed to the caller's
     return waves, s_prev
+
+
+def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
+                              step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap):
+    """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
+    dev = sentences[0].device
+    K = len(sentences)
+    T_cap = int(max_frames)
+    if isinstance(decode_streams, (list, tuple)) and len(decode_streams) > 1 or \
+            not isinstance(decode_streams, (list, tuple)) and decode_streams and int(decode_streams) > 1:
+        raise ValueError("max_frames: there is ONE decoder call per front group, on the current stream; `decode_streams` has no "
+                         "meaning here")
+    if front is not None:
+        raise ValueError("max_frames: the front runs inside inference(max_frames=); a GraphedFront has no place here")
+    if trim is None:
+        trim = 100 if ref_s is not None else 0
+    ns_all = [s.numel() for s in sentences]
+    tok_ctl = controls is not None and controls.tok_buf is not None
+    if tok_ctl and controls.N != max(ns_all):
+        raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
+    if gaps is not None:
+        gaps, max_gap = _check_gaps(gaps, max_gap, K)
+    prepped = []
+    for i, i_end in _front_chunks(front_batch, K):
+        ids = list(range(i, i_end))
+        ns = ns_all[i:i_end]
+        npad = max(ns_all) if tok_ctl else max(ns)
+        if bucket and npad % bucket and not tok_ctl:
+            npad = (npad + bucket - 1) // bucket * bucket
+        tokens = torch.zeros((len(ids), npad), dtype=sentences[i].dtype, device=dev)  # token id 0 = pad
+        for j, k in enumerate(ids):
+            tokens[j, :ns[j]] = sentences[k].reshape(-1)
+        ragged = any(n != npad for n in ns)
+        dur = None
+        if durations is not None:
+            dur = torch.zeros((len(ids), npad), dtype=torch.long, device=dev)  # pad tokens get no frames
+            for j, k in enumerate(ids):
+                dur[j, :ns[j]] = durations[k].reshape(-1).long().to(dev)
+        sine = None
+        if sine_noises is not None:  # every sentence's own draws (>= 600 x its frames), zero-padded to the capacity
+            rows = [sine_noises[k].reshape(-1, sine_noises[k].shape[-1])[:600 * T_cap] for k in ids]
+            sine = torch.zeros((len(ids), 600 * T_cap, rows[0].shape[-1]), device=dev, dtype=torch.float32)
+            for j, r in enumerate(rows):
+                sine[j, :r.shape[0]] = r
+        cat = lambda seq, dim: None if seq is None else torch.cat([seq[k] for k in ids], dim=dim)
+        prepped.append(dict(ids=ids, tokens=tokens, dur=dur, sine=sine, noise=cat(noises, 0), step_noise=cat(step_noises, 1),
+                            lengths=torch.LongTensor(ns) if ragged else None,
+                            lens_dev=torch.tensor(ns, dtype=torch.int32).to(dev) if ragged else None,
+                            ref_s=None if ref_s is None else ref_s.reshape(1, -1).expand(len(ids), -1).contiguous()))
+    s_prev, results = None, []
+    for k, q in enumerate(prepped):
+        i, j = q["ids"][0], q["ids"][-1] + 1
+        more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=max_gap)
+        res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
+                        diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
+                        lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
+                        pack=pack, trim=trim, sample_rate=sample_rate, marks=marks, passage=True, s_prev=s_prev, t=t,
+                        controls=None if controls is None else controls.slice(i, j), **more)
+        s_prev = res.style[-1:]
+        results.append(res)
+        if on_chunk is not None:
+            on_chunk(k, res)
+    return results, s_prev
 
 
 # ---------------------------------------------------------------------------------------------------------------------
