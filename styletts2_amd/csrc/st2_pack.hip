@@ -25,12 +25,6 @@ __global__ __launch_bounds__(64) void frames_from_durations_kernel(const long lo
   }
 }
 
-// offsets[b] = sum_{i < b} n_i, offsets[B] = the total
-__global__ __launch_bounds__(64) void pack_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf,
-                                                          int trim, long long* __restrict__ offsets) {
-  pack_scan_rows(B, offsets, [&](int b) { return pack_row_samples(frames, b, T_cap, spf, trim); });
-}
-
 constexpr int PACK_THREADS = 256;
 constexpr int PACK_ITERS = 4;  // 16-byte stores per lane and workgroup
 
@@ -97,37 +91,18 @@ extern "C" int st2_frames_from_durations(const int64_t* dur, int32_t B, int32_t 
   return 0;
 }
 
-int st2_wave_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                        int32_t samples_per_frame, int32_t trim, int32_t fmt, const void* out, int64_t out_capacity,
-                        const int64_t* offsets) {
-  ST2_REQUIRE(wave && frames && out && offsets, "%s: wave / frames / out / offsets is NULL", who);
-  ST2_REQUIRE(B > 0 && B <= 65535 && T_cap > 0 && samples_per_frame > 0,
-              "%s: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)", who, B, T_cap, samples_per_frame);
-  ST2_REQUIRE(trim >= 0 && out_capacity >= 0, "%s: trim=%d / out_capacity=%lld must not be negative", who, trim,
-              (long long)out_capacity);
-  ST2_REQUIRE(fmt == ST2_PACK_F32 || fmt == ST2_PACK_S16, "%s: unknown format %d", who, fmt);
-  ST2_REQUIRE(reinterpret_cast<uintptr_t>(out) % (fmt == ST2_PACK_S16 ? 2 : 4) == 0 && reinterpret_cast<uintptr_t>(wave) % 4 == 0,
-              "%s: wave / out is not aligned to its sample type", who);
-  const int64_t row = (int64_t)samples_per_frame * T_cap;
-  ST2_REQUIRE(B == 1 || w_bs >= row, "%s: w_bs=%lld is less than the %lld samples of a row at capacity", who, (long long)w_bs,
-              (long long)row);
-  return 0;
-}
-
-int st2_wave_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                       int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
-                       const int64_t* offsets, void* stream) {
-  const int64_t row = (int64_t)samples_per_frame * T_cap;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const long long* offs = reinterpret_cast<const long long*>(offsets);
-  if (fmt == ST2_PACK_S16) {
+int pack_move(const char* who, const pack_args& a) {
+  const int64_t row = (int64_t)a.samples_per_frame * a.T_cap;
+  hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
+  const long long* offs = reinterpret_cast<const long long*>(a.offsets);
+  if (a.fmt == ST2_PCM_S16) {
     const int gx = st2_cdiv(st2_cdiv(row, 8), PACK_THREADS * PACK_ITERS);
-    hipLaunchKernelGGL((wave_pack_kernel<int16_t, 8>), dim3(gx, B), dim3(PACK_THREADS), 0, s, wave, w_bs, frames, B, T_cap,
-                       samples_per_frame, trim, reinterpret_cast<int16_t*>(out), (long long)out_capacity, offs);
+    hipLaunchKernelGGL((wave_pack_kernel<int16_t, 8>), dim3(gx, a.B), dim3(PACK_THREADS), 0, s, a.wave, a.w_bs, a.frames, a.B,
+                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<int16_t*>(a.out), (long long)a.out_capacity, offs);
   } else {
     const int gx = st2_cdiv(st2_cdiv(row, 4), PACK_THREADS * PACK_ITERS);
-    hipLaunchKernelGGL((wave_pack_kernel<float, 4>), dim3(gx, B), dim3(PACK_THREADS), 0, s, wave, w_bs, frames, B, T_cap,
-                       samples_per_frame, trim, reinterpret_cast<float*>(out), (long long)out_capacity, offs);
+    hipLaunchKernelGGL((wave_pack_kernel<float, 4>), dim3(gx, a.B), dim3(PACK_THREADS), 0, s, a.wave, a.w_bs, a.frames, a.B,
+                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<float*>(a.out), (long long)a.out_capacity, offs);
   }
   ST2_CHECK_LAUNCH(who);
   return 0;
@@ -136,11 +111,6 @@ int st2_wave_pack_move(const char* who, const float* wave, int64_t w_bs, const i
 extern "C" int st2_wave_pack(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
                              int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
                              int64_t* offsets, void* stream) {
-  if (st2_wave_pack_check("st2_wave_pack", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets))
-    return 1;
-  hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), frames, B, T_cap,
-                     samples_per_frame, trim, reinterpret_cast<long long*>(offsets));
-  ST2_CHECK_LAUNCH("st2_wave_pack (offsets)");
-  return st2_wave_pack_move("st2_wave_pack", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets,
-                            stream);
+  return pack_plan("st2_wave_pack", pack_args{wave, w_bs, frames, B, T_cap, samples_per_frame, trim, 1, 1, nullptr, 0, fmt, nullptr,
+                                              0, out, out_capacity, offsets, stream});
 }

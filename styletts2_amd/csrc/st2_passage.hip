@@ -1,10 +1,9 @@
 // st2_wave_pack_gaps (st2.h, added under ABI 23): the packing step of the sync-free path with a BREAK
 // behind every row -- silence of a per-row length read from device memory, in the hand-over's own rate and sample format.  The
-// rows of one batch are then the sentences of a passage, laid out as a client plays them.  Three launches: a scan that counts
-// every row's samples and its gap, the move kernel of st2_wave_pack / st2_wave_resample_pack as it is (it takes a row's start
-// from offsets[b] and its length from the frames), and a fill of the gaps.
-#include "st2_common.h"
-#include "st2_pcm.h"
+// rows of one batch are then the sentences of a passage, laid out as a client plays them.  Here too is the pack plan that serves
+// all three packing entries (st2_pcm.h): a scan that counts every row's samples and its gap, the move kernel of st2_wave_pack
+// or st2_wave_resample_pack (it takes a row's start from offsets[b] and its length from the frames), and a fill of the gaps.
+#include "st2_polyphase.h"
 
 namespace {
 
@@ -13,13 +12,26 @@ __device__ __forceinline__ long long gap_samples(const int32_t* __restrict__ gap
   return min(max(gaps[b], 0), gap_cap);
 }
 
-// offsets[b] = sum_{i < b} (m_i + g_i), m_i = (n_i U + D - 1) div D  (U = D = 1: n_i, st2_wave_pack's count)
-__global__ __launch_bounds__(64) void gap_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf, int trim,
-                                                         int U, int D, const int32_t* __restrict__ gaps, int gap_cap,
-                                                         long long* __restrict__ offsets) {
-  pack_scan_rows(B, offsets, [&](int b) {
-    return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D + gap_samples(gaps, b, gap_cap);
-  });
+// offsets[b] = sum_{i < b} (m_i + g_i), offsets[B] = the total: one wave scanning the rows in chunks of 64.  gaps == NULL: no
+// g_i; U = D = 1: m_i = n_i, st2_wave_pack's count.
+__global__ __launch_bounds__(64) void pack_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf, int trim,
+                                                          int U, int D, const int32_t* __restrict__ gaps, int gap_cap,
+                                                          long long* __restrict__ offsets) {
+  long long carry = 0;
+  for (int base = 0; base < B; base += 64) {
+    const int b = base + threadIdx.x;
+    long long n = 0;
+    if (b < B) n = pack_row_out_samples(frames, b, T_cap, spf, trim, U, D) + (gaps ? gap_samples(gaps, b, gap_cap) : 0LL);
+    long long v = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const long long u = __shfl_up(v, off, 64);
+      if ((int)threadIdx.x >= off) v += u;
+    }
+    if (b < B) offsets[b] = carry + v - n;
+    carry += __shfl(v, 63, 64);
+  }
+  if (threadIdx.x == 0) offsets[B] = carry;
 }
 
 constexpr int FILL_THREADS = 256;
@@ -70,6 +82,45 @@ __global__ __launch_bounds__(FILL_THREADS) void gap_fill_kernel(const int32_t* _
 
 }  // namespace
 
+int pack_plan(const char* who, const pack_args& a) {
+  const bool rs = a.taps != nullptr;  // the resampling move; else the plain one
+  ST2_REQUIRE(a.wave && a.frames && a.out && a.offsets,
+              rs ? "%s: wave / frames / taps / out / offsets is NULL" : "%s: wave / frames / out / offsets is NULL", who);
+  ST2_REQUIRE(a.B > 0 && a.B <= 65535 && a.T_cap > 0 && a.samples_per_frame > 0,
+              "%s: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)", who, a.B, a.T_cap, a.samples_per_frame);
+  ST2_REQUIRE(a.trim >= 0 && a.out_capacity >= 0, "%s: trim=%d / out_capacity=%lld must not be negative", who, a.trim,
+              (long long)a.out_capacity);
+  if (rs) {
+    if (pp_check(who, a.up, a.down, a.taps_per_phase, a.fmt)) return 1;
+  } else {
+    ST2_REQUIRE(a.fmt == ST2_PCM_F32 || a.fmt == ST2_PCM_S16, "%s: unknown format %d", who, a.fmt);
+  }
+  ST2_REQUIRE(reinterpret_cast<uintptr_t>(a.out) % pcm_sample_bytes(a.fmt) == 0 && reinterpret_cast<uintptr_t>(a.wave) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(a.taps) % 4 == 0,
+              rs ? "%s: wave / taps / out is not aligned to its sample type" : "%s: wave / out is not aligned to its sample type", who);
+  const int64_t row = (int64_t)a.samples_per_frame * a.T_cap;
+  ST2_REQUIRE(a.B == 1 || a.w_bs >= row, "%s: w_bs=%lld is less than the %lld samples of a row at capacity", who,
+              (long long)a.w_bs, (long long)row);
+  int tile = 0;
+  if (rs && pack_resample_tile(who, a, &tile)) return 1;
+
+  const bool fill = a.gaps && a.gap_cap > 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(a.stream);
+  long long* offs = reinterpret_cast<long long*>(a.offsets);
+  hipLaunchKernelGGL(pack_offsets_kernel, dim3(1), dim3(64), 0, s, a.frames, a.B, a.T_cap, a.samples_per_frame, a.trim, a.up,
+                     a.down, fill ? a.gaps : nullptr, a.gap_cap, offs);
+  ST2_CHECK_LAUNCH(who);
+  if (rs ? pack_resample_move(who, a, tile) : pack_move(who, a)) return 1;
+  if (!fill) return 0;
+  const int gx = st2_cdiv(st2_cdiv(a.gap_cap, 16 / pcm_sample_bytes(a.fmt)), FILL_THREADS * FILL_ITERS);  // >= 1: gap_cap > 0
+  pcm_dispatch(a.fmt, [&](auto f) {
+    hipLaunchKernelGGL((gap_fill_kernel<f()>), dim3(gx, a.B), dim3(FILL_THREADS), 0, s, a.gaps, a.gap_cap, a.B,
+                       reinterpret_cast<typename pcm_fmt<f()>::type*>(a.out), (long long)a.out_capacity, offs);
+  });
+  ST2_CHECK_LAUNCH(who);
+  return 0;
+}
+
 extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
                                   int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
                                   int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
@@ -77,35 +128,11 @@ extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t
   const char* who = "st2_wave_pack_gaps";
   ST2_REQUIRE(gap_cap >= 0, "%s: gap_cap=%d must not be negative", who, gap_cap);
   ST2_REQUIRE(reinterpret_cast<uintptr_t>(gaps) % 4 == 0, "%s: gaps is not aligned to int32", who);
-  int tile = 0;
-  if (!taps) {
+  if (!taps) {  // this entry's own words for what the plain move cannot do
     ST2_REQUIRE(up == 1 && down == 1, "%s: without taps the rows are moved as they are: up=%d / down=%d must be 1", who, up, down);
     ST2_REQUIRE(fmt == ST2_PCM_F32 || fmt == ST2_PCM_S16,
                 "%s: format %d needs the resampling move (taps); without taps fp32 and 16-bit PCM only", who, fmt);
-    if (st2_wave_pack_check(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets)) return 1;
-  } else if (st2_wave_resample_pack_check(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps,
-                                          taps_per_phase, fmt, out, out_capacity, offsets, &tile)) {
-    return 1;
   }
-  if (!gaps || gap_cap == 0)  // no gaps: the wrapped entry itself, scan and move
-    return taps ? st2_wave_resample_pack(wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt,
-                                         out, out_capacity, offsets, stream)
-                : st2_wave_pack(wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity, offsets, stream);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  long long* offs = reinterpret_cast<long long*>(offsets);
-  hipLaunchKernelGGL(gap_offsets_kernel, dim3(1), dim3(64), 0, s, frames, B, T_cap, samples_per_frame, trim, up, down, gaps,
-                     gap_cap, offs);
-  ST2_CHECK_LAUNCH("st2_wave_pack_gaps (offsets)");
-  const int rc = taps ? st2_wave_resample_pack_move(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps,
-                                                    taps_per_phase, fmt, tile, out, out_capacity, offsets, stream)
-                      : st2_wave_pack_move(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, fmt, out, out_capacity,
-                                           offsets, stream);
-  if (rc) return rc;
-  const int gx = st2_cdiv(st2_cdiv(gap_cap, 16 / pcm_sample_bytes(fmt)), FILL_THREADS * FILL_ITERS);  // >= 1: gap_cap > 0
-  pcm_dispatch(fmt, [&](auto f) {
-    hipLaunchKernelGGL((gap_fill_kernel<f()>), dim3(gx, B), dim3(FILL_THREADS), 0, s, gaps, gap_cap, B,
-                       reinterpret_cast<typename pcm_fmt<f()>::type*>(out), (long long)out_capacity, offs);
-  });
-  ST2_CHECK_LAUNCH("st2_wave_pack_gaps (fill)");
-  return 0;
+  return pack_plan(who, pack_args{wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt, gaps,
+                                  gap_cap, out, out_capacity, offsets, stream});
 }

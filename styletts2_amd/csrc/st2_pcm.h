@@ -1,6 +1,7 @@
 // What the packing entry points and the clip ingest share (st2_pack.hip: st2_wave_pack; st2_resample.hip:
-// st2_wave_resample_pack; st2_ingest.hip: st2_clip_ingest): a row's valid sample count, the row-offset scan, the packed source
-// vectors, the sample conversions, both ways, and the sample formats' types, size and dispatch.  The polyphase rule of the two
+// st2_wave_resample_pack; st2_passage.hip: st2_wave_pack_gaps and the pack plan; st2_ingest.hip: st2_clip_ingest): a row's
+// sample counts, the pack plan's arguments, the packed source vectors, the sample conversions, both ways, and the sample
+// formats' types, size and dispatch.  The polyphase rule of the two
 // resamplers is st2_polyphase.h.
 #pragma once
 #include <type_traits>
@@ -12,23 +13,10 @@ __device__ __forceinline__ long long pack_row_samples(const int32_t* __restrict_
   return max(0LL, f * spf - trim);
 }
 
-// offsets[b] = sum_{i < b} count(i), offsets[B] = the total: one wave scanning the rows in chunks of 64
-template <class F>
-__device__ __forceinline__ void pack_scan_rows(int B, long long* __restrict__ offsets, F count) {
-  long long carry = 0;
-  for (int base = 0; base < B; base += 64) {
-    const int b = base + threadIdx.x;
-    const long long n = b < B ? count(b) : 0;
-    long long v = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(v, off, 64);
-      if ((int)threadIdx.x >= off) v += u;
-    }
-    if (b < B) offsets[b] = carry + v - n;
-    carry += __shfl(v, 63, 64);
-  }
-  if (threadIdx.x == 0) offsets[B] = carry;
+// m_b = (n_b U + D - 1) div D: the row's samples at the output rate U / D of the model's, in 64 bits (U = D = 1: n_b itself)
+__device__ __forceinline__ long long pack_row_out_samples(const int32_t* __restrict__ frames, int b, int T_cap, int spf, int trim,
+                                                          int U, int D) {
+  return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D;
 }
 
 // The source of a row's aligned body starts wherever the destination's alignment puts it: 4-byte aligned only.
@@ -114,23 +102,32 @@ __device__ __forceinline__ float4 pcm_decode4(const typename pcm_fmt<FMT>::type*
 }
 __device__ __forceinline__ float4 load_f32x4(const float* __restrict__ p) { return pcm_decode4<ST2_PCM_F32>(p); }
 
-// The two packing entries in two steps each, so that st2_wave_pack_gaps (st2_passage.hip) wraps them with the move kernels as
-// they are: `check` is every refusal of the entry (`who` names the caller in the message; the resampling one also returns the
-// output tile its LDS budget allows), `move` the move launch over offsets that some scan has written on the same stream.
-int st2_wave_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                        int32_t samples_per_frame, int32_t trim, int32_t fmt, const void* out, int64_t out_capacity,
-                        const int64_t* offsets);
-int st2_wave_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                       int32_t samples_per_frame, int32_t trim, int32_t fmt, void* out, int64_t out_capacity,
-                       const int64_t* offsets, void* stream);
-int st2_wave_resample_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B,
-                                 int32_t T_cap, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down,
-                                 const float* taps, int32_t taps_per_phase, int32_t fmt, const void* out, int64_t out_capacity,
-                                 const int64_t* offsets, int* tile);
-int st2_wave_resample_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                                int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
-                                int32_t taps_per_phase, int32_t fmt, int tile, void* out, int64_t out_capacity,
-                                const int64_t* offsets, void* stream);
+// The pack plan (st2_passage.hip): what the three packing entries st2_wave_pack, st2_wave_resample_pack
+// and st2_wave_pack_gaps receive, and the one function that serves them -- every refusal once (`who` names the entry in the
+// message), then the row scan, the move, and the fill where there are gaps.  taps == NULL: the plain move (up = down = 1,
+// fp32 / 16-bit PCM); gaps == NULL or gap_cap == 0: no fill.
+static_assert((int)ST2_PACK_F32 == (int)ST2_PCM_F32 && (int)ST2_PACK_S16 == (int)ST2_PCM_S16,
+              "st2_wave_pack's format codes are the first two of st2_pcm_format: the code below tests ST2_PCM_* only");
+struct pack_args {
+  const float* wave;
+  int64_t w_bs;
+  const int32_t* frames;
+  int32_t B, T_cap, samples_per_frame, trim, up, down;
+  const float* taps;
+  int32_t taps_per_phase, fmt;
+  const int32_t* gaps;
+  int32_t gap_cap;
+  void* out;
+  int64_t out_capacity;
+  int64_t* offsets;
+  void* stream;
+};
+int pack_plan(const char* who, const pack_args& a);
+// The move launch over offsets that the scan has written on the same stream, each beside its kernel (st2_pack.hip,
+// st2_resample.hip), and the output tile the resampling move's LDS budget allows (a refusal when there is none).
+int pack_move(const char* who, const pack_args& a);
+int pack_resample_tile(const char* who, const pack_args& a, int* tile);
+int pack_resample_move(const char* who, const pack_args& a, int tile);
 
 inline int pcm_sample_bytes(int fmt) { return fmt == ST2_PCM_F32 ? 4 : (fmt == ST2_PCM_S16 ? 2 : 1); }
 

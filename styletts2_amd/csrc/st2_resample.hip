@@ -12,17 +12,6 @@ constexpr int RS_TILE_BYTES = RS_THREADS * 16;  // a tile of output: one 16-byte
 constexpr int RS_LDS_FLOATS = 16128;
 constexpr int RS_OUT_FLOATS = (RS_TILE_BYTES + 16) / 4;
 
-// m_b = ceil(n_b U / D) output samples
-__device__ __forceinline__ long long rs_row_samples(const int32_t* __restrict__ frames, int b, int T_cap, int spf, int trim,
-                                                    int U, int D) {
-  return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D;
-}
-
-__global__ __launch_bounds__(64) void resample_offsets_kernel(const int32_t* __restrict__ frames, int B, int T_cap, int spf,
-                                                              int trim, int U, int D, long long* __restrict__ offsets) {
-  pack_scan_rows(B, offsets, [&](int b) { return rs_row_samples(frames, b, T_cap, spf, trim, U, D); });
-}
-
 // Workgroup (t, b) makes the output samples [j0, j1) of row b: tile 0 starts at the row's first sample and ends `tile` samples
 // behind the first 16-byte boundary of the destination, every later tile starts and ends on such a boundary (`tile` samples
 // are a whole number of 16-byte vectors).  Three phases with a barrier between them:
@@ -85,49 +74,28 @@ __global__ __launch_bounds__(RS_THREADS) void wave_resample_pack_kernel(
 
 }  // namespace
 
-int st2_wave_resample_pack_check(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B,
-                                 int32_t T_cap, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down,
-                                 const float* taps, int32_t taps_per_phase, int32_t fmt, const void* out, int64_t out_capacity,
-                                 const int64_t* offsets, int* tile_out) {
-  ST2_REQUIRE(wave && frames && out && offsets && taps, "%s: wave / frames / taps / out / offsets is NULL", who);
-  ST2_REQUIRE(B > 0 && B <= 65535 && T_cap > 0 && samples_per_frame > 0,
-              "%s: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)", who, B, T_cap, samples_per_frame);
-  ST2_REQUIRE(trim >= 0 && out_capacity >= 0, "%s: trim=%d / out_capacity=%lld must not be negative", who, trim,
-              (long long)out_capacity);
-  if (pp_check(who, up, down, taps_per_phase, fmt)) return 1;
-  const int size = pcm_sample_bytes(fmt);
-  ST2_REQUIRE(reinterpret_cast<uintptr_t>(out) % size == 0 && reinterpret_cast<uintptr_t>(wave) % 4 == 0 &&
-                  reinterpret_cast<uintptr_t>(taps) % 4 == 0,
-              "%s: wave / taps / out is not aligned to its sample type", who);
-  const int64_t row = (int64_t)samples_per_frame * T_cap;
-  ST2_REQUIRE(B == 1 || w_bs >= row, "%s: w_bs=%lld is less than the %lld samples of a row at capacity", who, (long long)w_bs,
-              (long long)row);
+int pack_resample_tile(const char* who, const pack_args& a, int* tile_out) {
   // the largest tile (a whole number of 16-byte vectors, at most one per lane) whose input span -- with a head of less than 16
   // samples in front of tile 0 -- fits beside the table
-  const int room = RS_LDS_FLOATS - RS_OUT_FLOATS - pp_round4(up * taps_per_phase);
-  int tile = RS_TILE_BYTES / size;
-  while (tile >= 16 && pp_round4((int)pp_span_cap(tile + 16, up, down, taps_per_phase)) > room) tile /= 2;
-  ST2_REQUIRE(tile >= 16, "%s: a table of %d x %d taps at ratio %d / %d does not fit the %d bytes of LDS", who, up, taps_per_phase,
-              up, down, RS_LDS_FLOATS * 4);
-  const int64_t m_cap = (row * up + down - 1) / down;
+  const int room = RS_LDS_FLOATS - RS_OUT_FLOATS - pp_round4(a.up * a.taps_per_phase);
+  int tile = RS_TILE_BYTES / pcm_sample_bytes(a.fmt);
+  while (tile >= 16 && pp_round4((int)pp_span_cap(tile + 16, a.up, a.down, a.taps_per_phase)) > room) tile /= 2;
+  ST2_REQUIRE(tile >= 16, "%s: a table of %d x %d taps at ratio %d / %d does not fit the %d bytes of LDS", who, a.up,
+              a.taps_per_phase, a.up, a.down, RS_LDS_FLOATS * 4);
+  const int64_t m_cap = ((int64_t)a.samples_per_frame * a.T_cap * a.up + a.down - 1) / a.down;
   ST2_REQUIRE(st2_cdiv(m_cap, tile) <= 0x7fffffff / 2, "%s: a row of %lld output samples is too long", who, (long long)m_cap);
   *tile_out = tile;
   return 0;
 }
 
-int st2_wave_resample_pack_move(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                                int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
-                                int32_t taps_per_phase, int32_t fmt, int tile, void* out, int64_t out_capacity,
-                                const int64_t* offsets, void* stream) {
-  const int64_t row = (int64_t)samples_per_frame * T_cap;
-  const int64_t m_cap = (row * up + down - 1) / down;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const long long* offs = reinterpret_cast<const long long*>(offsets);
+int pack_resample_move(const char* who, const pack_args& a, int tile) {
+  const int64_t m_cap = ((int64_t)a.samples_per_frame * a.T_cap * a.up + a.down - 1) / a.down;
   const int gx = st2_cdiv(m_cap, tile);
-  pcm_dispatch(fmt, [&](auto f) {
-    hipLaunchKernelGGL((wave_resample_pack_kernel<f()>), dim3(gx, B), dim3(RS_THREADS), 0, s, wave, w_bs, frames, B, T_cap,
-                       samples_per_frame, trim, up, down, taps, taps_per_phase, tile,
-                       reinterpret_cast<typename pcm_fmt<f()>::type*>(out), (long long)out_capacity, offs);
+  pcm_dispatch(a.fmt, [&](auto f) {
+    hipLaunchKernelGGL((wave_resample_pack_kernel<f()>), dim3(gx, a.B), dim3(RS_THREADS), 0, reinterpret_cast<hipStream_t>(a.stream),
+                       a.wave, a.w_bs, a.frames, a.B, a.T_cap, a.samples_per_frame, a.trim, a.up, a.down, a.taps, a.taps_per_phase,
+                       tile, reinterpret_cast<typename pcm_fmt<f()>::type*>(a.out), (long long)a.out_capacity,
+                       reinterpret_cast<const long long*>(a.offsets));
   });
   ST2_CHECK_LAUNCH(who);
   return 0;
@@ -138,13 +106,7 @@ extern "C" int st2_wave_resample_pack(const float* wave, int64_t w_bs, const int
                                       int32_t taps_per_phase, int32_t fmt, void* out, int64_t out_capacity, int64_t* offsets,
                                       void* stream) {
   const char* who = "st2_wave_resample_pack";
-  int tile = 0;
-  if (st2_wave_resample_pack_check(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt,
-                                   out, out_capacity, offsets, &tile))
-    return 1;
-  hipLaunchKernelGGL(resample_offsets_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), frames, B, T_cap,
-                     samples_per_frame, trim, up, down, reinterpret_cast<long long*>(offsets));
-  ST2_CHECK_LAUNCH("st2_wave_resample_pack (offsets)");
-  return st2_wave_resample_pack_move(who, wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt,
-                                     tile, out, out_capacity, offsets, stream);
+  ST2_REQUIRE(taps, "%s: wave / frames / taps / out / offsets is NULL", who);  // to the plan, no taps would mean the plain move
+  return pack_plan(who, pack_args{wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt, nullptr,
+                                  0, out, out_capacity, offsets, stream});
 }

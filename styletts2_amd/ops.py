@@ -1183,7 +1183,19 @@ def token_marks(dur, frames, T_cap, lengths=None, shift=False, trim=0, rate=None
     return (out, bound) if want_bound else out
 
 
-PACK_FORMATS = {"f32": (_lib.PACK_F32, torch.float32), "s16": (_lib.PACK_S16, torch.int16)}
+OUTPUT_FORMATS = {"f32": (_lib.PCM_F32, torch.float32), "s16": (_lib.PCM_S16, torch.int16),
+                  "ulaw": (_lib.PCM_ULAW, torch.uint8), "alaw": (_lib.PCM_ALAW, torch.uint8)}
+PACK_FORMATS = {k: OUTPUT_FORMATS[k] for k in ("f32", "s16")}  # what the plain move (no rate) writes; _lib.PACK_* are these codes
+
+
+def _pcm_format(fmt, rate):
+    """(format code, dtype) of a sample format of OUTPUT_FORMATS at a rate of `resample.RATES`; ValueError for any other."""
+    from . import resample
+    if fmt not in OUTPUT_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
+    if rate not in resample.RATES:
+        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
+    return OUTPUT_FORMATS[fmt]
 
 
 def _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, out_samples):
@@ -1210,33 +1222,38 @@ def _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, out_sam
     return wave, lp, B, L, spf, out, offsets
 
 
+def _wave_pack(entry, wave, frames, rate, fmt, trim, out, offsets, samples_per_frame, plain=None, gaps=None, max_gap=None):
+    """The body of the three packing wrappers; `entry` is the C entry the caller chose.  `plain`: the entry's refusal of a
+    format outside PACK_FORMATS when there is no rate (the plain move, no table); None: the entry needs a rate.  `max_gap`
+    (the gaps entry only): `gaps` and `max_gap` are passed on, and `out` defaults to `max_gap` more samples per row."""
+    from . import resample
+    if rate is None and plain is not None:
+        if fmt not in PACK_FORMATS:
+            raise ValueError(plain % (sorted(PACK_FORMATS), fmt))
+        code, dtype = PACK_FORMATS[fmt]
+        table = lambda: (1, 1, 0, None)
+    else:
+        code, dtype = _pcm_format(fmt, rate)
+        table = lambda: resample.table(rate, wave.device)  # first asked for once `wave` is known to live on a device
+    room = 0 if max_gap is None else max(max_gap, 0)
+    wave, lp, B, L, spf, out, offsets = _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets,
+                                                       lambda L: resample.output_samples(L, *table()[:2]) + room)
+    breaks = () if max_gap is None else (_chk_len(gaps, "gaps", B, wave), max_gap)
+    U, D, K, taps = table()
+    how = (code,) if entry == "st2_wave_pack" else (U, D, _ptr(taps), K, code)
+    _lib.check(getattr(_lib.load(), entry)(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), *how, *breaks,
+                                           out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()), entry)
+    return out, offsets
+
+
 def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_per_frame=600):
     """`st2_wave_pack`: wave [B, 1, L] or [B, L] (L a multiple of `samples_per_frame`: the batch's frame capacity), frames
     int32 [B] on the device -> (packed, offsets): the first max(0, samples_per_frame * frames[b] - trim) samples of every row,
     back to back, as int16 PCM ("s16": rint(clamp(x, -1, 1) * 32767), NaN -> 0) or fp32 ("f32": a copy), and their int64
     [B + 1] exclusive prefix sum on the device (offsets[B] = the total).  `out` (1-D, of the format's dtype) bounds what is
     written: nothing at or past min(offsets[B], out.numel()); by default it holds every row at capacity.  No host read."""
-    if fmt not in PACK_FORMATS:
-        raise ValueError("fmt must be one of %s, got %r" % (sorted(PACK_FORMATS), fmt))
-    code, dtype = PACK_FORMATS[fmt]
-    wave, lp, B, L, spf, out, offsets = _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, lambda L: L)
-    _lib.check(_lib.load().st2_wave_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), code, out.data_ptr(),
-                                         out.numel(), offsets.data_ptr(), _stream()), "st2_wave_pack")
-    return out, offsets
-
-
-OUTPUT_FORMATS = {"f32": (_lib.PCM_F32, torch.float32), "s16": (_lib.PCM_S16, torch.int16),
-                  "ulaw": (_lib.PCM_ULAW, torch.uint8), "alaw": (_lib.PCM_ALAW, torch.uint8)}
-
-
-def _pcm_format(fmt, rate):
-    """(format code, dtype) of a sample format of OUTPUT_FORMATS at a rate of `resample.RATES`; ValueError for any other."""
-    from . import resample
-    if fmt not in OUTPUT_FORMATS:
-        raise ValueError("fmt must be one of %s, got %r" % (sorted(OUTPUT_FORMATS), fmt))
-    if rate not in resample.RATES:
-        raise ValueError("rate must be one of %s, got %r" % (list(resample.RATES), rate))
-    return OUTPUT_FORMATS[fmt]
+    return _wave_pack("st2_wave_pack", wave, frames, None, fmt, trim, out, offsets, samples_per_frame,
+                      plain="fmt must be one of %s, got %r")
 
 
 def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=None, samples_per_frame=600):
@@ -1248,16 +1265,7 @@ def wave_resample_pack(wave, frames, rate, fmt="s16", trim=0, out=None, offsets=
     `out` (1-D, of the format's dtype) bounds what is written: nothing at or past min(offsets[B], out.numel()); by default it
     holds every row at capacity, ceil(L U / D) samples each.  No host read; the first call for a (rate, device) designs and
     uploads the table, which therefore must not happen under stream capture."""
-    from . import resample
-    code, dtype = _pcm_format(fmt, rate)
-    table = lambda: resample.table(rate, wave.device)  # first asked for once `wave` is known to live on a device
-    wave, lp, B, L, spf, out, offsets = _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets,
-                                                       lambda L: resample.output_samples(L, *table()[:2]))
-    U, D, K, taps = table()
-    _lib.check(_lib.load().st2_wave_resample_pack(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D,
-                                                  taps.data_ptr(), K, code, out.data_ptr(), out.numel(), offsets.data_ptr(),
-                                                  _stream()), "st2_wave_resample_pack")
-    return out, offsets
+    return _wave_pack("st2_wave_resample_pack", wave, frames, rate, fmt, trim, out, offsets, samples_per_frame)
 
 
 def wave_pack_gaps(wave, frames, gaps, max_gap, rate=None, fmt="s16", trim=0, out=None, offsets=None, samples_per_frame=600):
@@ -1269,25 +1277,8 @@ def wave_pack_gaps(wave, frames, gaps, max_gap, rate=None, fmt="s16", trim=0, ou
     writes.  `out` (1-D, of the format's dtype) bounds what is written: nothing at or past min(offsets[B], out.numel()); by
     default it holds every row at capacity and `max_gap` samples behind each.  No host read; with a rate the first call for a
     (rate, device) designs and uploads the table, which therefore must not happen under stream capture."""
-    from . import resample
-    max_gap = int(max_gap)
-    if rate is None:
-        if fmt not in PACK_FORMATS:
-            raise ValueError("fmt must be one of %s without a rate, got %r" % (sorted(PACK_FORMATS), fmt))
-        code, dtype = OUTPUT_FORMATS[fmt]
-        table = lambda: (1, 1, 0, None)
-    else:
-        code, dtype = _pcm_format(fmt, rate)
-        table = lambda: resample.table(rate, wave.device)  # first asked for once `wave` is known to live on a device
-    wave, lp, B, L, spf, out, offsets = _pack_operands(
-        wave, frames, samples_per_frame, dtype, out, offsets,
-        lambda L: resample.output_samples(L, *table()[:2]) + max(max_gap, 0))
-    gp = _chk_len(gaps, "gaps", B, wave)
-    U, D, K, taps = table()
-    _lib.check(_lib.load().st2_wave_pack_gaps(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), U, D, _ptr(taps), K,
-                                              code, gp, max_gap, out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()),
-               "st2_wave_pack_gaps")
-    return out, offsets
+    return _wave_pack("st2_wave_pack_gaps", wave, frames, rate, fmt, trim, out, offsets, samples_per_frame,
+                      plain="fmt must be one of %s without a rate, got %r", gaps=gaps, max_gap=int(max_gap))
 
 
 def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):

@@ -181,39 +181,11 @@ class Controls:
         on_dev = [v for v in list(given.values()) + list(tok.values()) if torch.is_tensor(v) and v.is_cuda]
         if device is None:
             device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
-        host = torch.empty((len(self.NAMES), B), dtype=torch.float32)
-        late = []
-        for i, name in enumerate(self.NAMES):
-            v = given[name]
-            host[i] = self.ABSENT[name]
-            if v is None:
-                continue
-            if torch.is_tensor(v) and v.is_cuda:  # never read: clamped where the kernels read it
-                if v.numel() != B:
-                    raise ValueError("Controls: %s must hold %d values, got shape %s" % (name, B, tuple(v.shape)))
-                late.append((i, v))
-                continue
-            row = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
-            if row.numel() == 1:
-                row = row.expand(B)
-            if row.numel() != B:
-                raise ValueError("Controls: %s must be one value or %d values, got %d" % (name, B, row.numel()))
-            lo, hi = self.RANGES[name]
-            if not bool((torch.isfinite(row) & (row >= lo) & (row <= hi)).all()):
-                raise ValueError("Controls: %s must lie in [%g, %g], got %s" % (name, lo, hi, row.tolist()))
-            host[i] = row.to(torch.float32)
         self.B = B
         self.present = tuple(n for n in self.NAMES if given[n] is not None)
-        self.buf = host.to(device)  # ONE host -> device copy
-        for i, v in late:
-            self.buf[i].copy_(v.detach().reshape(B).to(torch.float32))
+        self.buf = self._table(self.NAMES, self.RANGES, self.ABSENT, given, (B,), device)
         self.N, self.tok_present, self.tok_buf = None, (), None
-        self._init_tokens(tok, N, device)
-
-    def _init_tokens(self, tok, N, device):
-        """The [3][B][N] tensor of the per-token rows, by the rules of the six rows above; nothing when neither a row nor N is given."""
-        B = self.B
-        if N is None:
+        if N is None:  # the token width from the one [B, N] array given; nothing when neither a row nor N is given
             dims = [v.shape if torch.is_tensor(v) else torch.as_tensor(v).shape for v in tok.values() if v is not None]
             shapes = {d[-1] for d in dims if len(d) == 2}
             if len(shapes) == 1:
@@ -226,32 +198,47 @@ class Controls:
         N = int(N)
         if N <= 0 or N > 512:
             raise ValueError("Controls: N must lie in 1..512, got %r" % (N,))
-        host = torch.empty((len(self.TOK_NAMES), B, N), dtype=torch.float32)
+        self.tok_buf = self._table(self.TOK_NAMES, self.TOK_RANGES, self.TOK_ABSENT, tok, (B, N), device)
+        self.N, self.tok_present = N, tuple(n for n in self.TOK_NAMES if tok[n] is not None)
+
+    @staticmethod
+    def _table(names, ranges, absent, given, shape, device):
+        """The fp32 [len(names), *shape] device tensor of a set of controls, one row per name: the absent value where `given`
+        has None, a host value validated (one value for every entry, or `shape` values) and all of them sent in ONE host ->
+        device copy, a device tensor copied in behind it, unread.  The [B] rows take B values of any shape and name the
+        offending ones; the [B, N] rows must have that shape."""
+        flat = len(shape) == 1
+        dims = "%d" % shape if flat else "[%d, %d]" % shape
+        host = torch.empty((len(names),) + shape, dtype=torch.float32)
         late = []
-        for i, name in enumerate(self.TOK_NAMES):
-            v = tok[name]
-            host[i] = self.TOK_ABSENT[name]
+        for i, name in enumerate(names):
+            v = given[name]
+            host[i] = absent[name]
             if v is None:
                 continue
-            if torch.is_tensor(v) and v.is_cuda:  # never read: clamped where the kernels read it
-                if tuple(v.shape) != (B, N):
-                    raise ValueError("Controls: %s must be [%d, %d], got shape %s" % (name, B, N, tuple(v.shape)))
-                late.append((i, v))
+            on_dev = torch.is_tensor(v) and v.is_cuda  # never read: clamped where the kernels read it
+            rows = v.detach() if on_dev else torch.as_tensor(v, dtype=torch.float64)
+            if flat:
+                rows = rows.reshape(-1)
+            if not on_dev and rows.numel() == 1:
+                rows = rows.reshape((1,) * len(shape)).expand(shape)
+            if tuple(rows.shape) != shape and on_dev:
+                raise ValueError("Controls: %s must %s, got shape %s" % (name, ("hold %s values" if flat else "be %s") % dims,
+                                                                        tuple(v.shape)))
+            if tuple(rows.shape) != shape:
+                raise ValueError("Controls: %s must be one value or %s values, got %s"
+                                 % (name, dims, rows.numel() if flat else "shape %s" % (tuple(rows.shape),)))
+            if on_dev:
+                late.append((i, rows))
                 continue
-            rows = torch.as_tensor(v, dtype=torch.float64)
-            if rows.numel() == 1:
-                rows = rows.reshape(1, 1).expand(B, N)
-            if tuple(rows.shape) != (B, N):
-                raise ValueError("Controls: %s must be one value or [%d, %d] values, got shape %s" % (name, B, N, tuple(rows.shape)))
-            lo, hi = self.TOK_RANGES[name]
+            lo, hi = ranges[name]
             if not bool((torch.isfinite(rows) & (rows >= lo) & (rows <= hi)).all()):
-                raise ValueError("Controls: %s must lie in [%g, %g]" % (name, lo, hi))
+                raise ValueError("Controls: %s must lie in [%g, %g]%s" % (name, lo, hi, ", got %s" % rows.tolist() if flat else ""))
             host[i] = rows.to(torch.float32)
-        self.N = N
-        self.tok_present = tuple(n for n in self.TOK_NAMES if tok[n] is not None)
-        self.tok_buf = host.to(device)  # ONE host -> device copy
-        for i, v in late:
-            self.tok_buf[i].copy_(v.detach().to(torch.float32))
+        buf = host.to(device)  # ONE host -> device copy
+        for i, rows in late:
+            buf[i].copy_(rows.to(torch.float32))
+        return buf
 
     @classmethod
     def neutral(cls, B, alpha=None, beta=None, t=None, device=None, N=None):
@@ -313,29 +300,20 @@ def _check_controls(controls, dev, B, taps, front, durations, N=None):
         raise ValueError("controls hold per-token rows of %d tokens, the batch is %d wide" % (controls.N, N))
 
 
-def _prosody_controls(controls, F0, N, frames=None, sel=None):
-    """Row b's pitch scale / energy shift applied in place to the prosody call's curves (one launch; none when both are absent)."""
+def _prosody_controls(controls, F0, N, dur, frames=None, sel=None, shift=False):
+    """Row b's pitch scale / energy shift, then token n's over its frames, applied in place to the prosody call's curves: one
+    launch each, none for a pair of which both are absent."""
     if controls is None:
         return
-    rows = [controls.row("f0_scale"), controls.row("n_shift")]
-    if rows[0] is None and rows[1] is None:
-        return
-    if sel is not None:
-        rows = [None if v is None else sel(v).contiguous() for v in rows]
-    ops.prosody_controls(F0, N, rows[0], rows[1], frames=frames)
-
-
-def _prosody_controls_tok(controls, F0, N, dur, frames=None, sel=None, shift=False):
-    """Token n's pitch scale / energy shift applied in place over its frames of the prosody call's curves, behind the per-row
-    controls (one launch; none when both are absent)."""
-    if controls is None or not controls.tok_present:
-        return
-    rows = [controls.tok_row("tok_f0_scale"), controls.tok_row("tok_n_shift")]
-    if rows[0] is None and rows[1] is None:
-        return
-    if sel is not None:
-        rows = [None if v is None else sel(v).contiguous() for v in rows]
-    ops.prosody_controls_tok(F0, N, dur.contiguous(), rows[0], rows[1], frames=frames, shift=shift)
+    per_row = lambda sc, sh: ops.prosody_controls(F0, N, sc, sh, frames=frames)
+    per_token = lambda sc, sh: ops.prosody_controls_tok(F0, N, dur.contiguous(), sc, sh, frames=frames, shift=shift)
+    for rows, apply in (([controls.row("f0_scale"), controls.row("n_shift")], per_row),
+                        ([controls.tok_row("tok_f0_scale"), controls.tok_row("tok_n_shift")], per_token)):
+        if rows[0] is None and rows[1] is None:
+            continue
+        if sel is not None:
+            rows = [None if v is None else sel(v).contiguous() for v in rows]
+        apply(*rows)
 
 
 @torch.no_grad()
@@ -656,8 +634,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         channel-major copy where it always did.  hifigan: one-frame right shift, Demo/Inference_LibriTTS.ipynb:306-319."""
         asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T, shift=hifigan,
                                                                          frames=frames)
-        _prosody_controls(controls, F0_pred, N_pred, frames=frames, sel=sel)
-        _prosody_controls_tok(controls, F0_pred, N_pred, dur, frames=frames, sel=sel, shift=hifigan)
+        _prosody_controls(controls, F0_pred, N_pred, dur, frames=frames, sel=sel, shift=hifigan)
         return dict(asr=asr, F0=F0_pred, N=N_pred)
 
     if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
@@ -816,8 +793,8 @@ class SynthesisResult:
         if marks and self.marks is None:
             raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
         if self._buf is None:
-            self._buf, self.packed, self.offsets = _pack_into_one(self.wave, self.frames, self.trim, self.pack or "f32",
-                                                                  self.samples_per_frame, self.sample_rate)
+            ho = _hand_over(self.wave, self.frames, self.trim, self.pack or "f32", self.samples_per_frame, self.sample_rate)
+            self._buf, self.packed, self.offsets = ho.buf, ho.packed, ho.offsets
         if self._host is None or self._host.shape != self._buf.shape:
             self._host = torch.empty(self._buf.shape, dtype=torch.uint8, pin_memory=True)
         host = self._host
@@ -827,21 +804,19 @@ class SynthesisResult:
         done.synchronize()
         ops.check_status()
         B = self.frames.numel()
-        hdr = self._buf.numel() - self.packed.numel() * self.packed.element_size()
-        offs = host[:8 * (B + 1)].view(torch.int64).tolist()
-        samples = host[hdr:].view(self.packed.dtype).numpy()
-        m0 = 8 * (B + 1)
+        layout = _HandOver(B, self.pack or "f32", 0 if self.marks is None else self.marks.numel(), self.gaps is not None)
+        offs, m, g, samples = layout.views(host)
+        offs, samples = offs.tolist(), samples.numpy()
         if passage:
             rows = samples[:offs[B]]
-        elif self.gaps is None:
+        elif g is None:
             rows = [samples[offs[b]:offs[b + 1]] for b in range(B)]
         else:  # the breaks as the packing step counted them: clamped to 0..max_gap
-            g0 = m0 + (4 * self.marks.numel() if self.marks is not None else 0)
-            g = host[g0:g0 + 4 * B].view(torch.int32).clamp(0, self.max_gap).tolist()
+            g = g.clamp(0, self.max_gap).tolist()
             rows = [samples[offs[b]:offs[b + 1] - g[b]] for b in range(B)]
         if not marks:
             return rows
-        return rows, host[m0:m0 + 4 * self.marks.numel()].view(torch.int32).numpy().reshape(tuple(self.marks.shape))
+        return rows, m.numpy().reshape(tuple(self.marks.shape))
 
 
 def _check_output(pack, sample_rate):
@@ -863,9 +838,18 @@ def gap_samples(ms, sample_rate=None):
     return [one(v) for v in ms] if isinstance(ms, (list, tuple)) else one(ms)
 
 
+def _check_gap_args(pack, gaps, max_gap):
+    """What `gaps` / `max_gap` need wherever they are given (`inference`, `synthesize_long`, `GraphedSynthesis`): a packed
+    hand-over to be silence in, and a bound that is not negative."""
+    if pack is None and (gaps is not None or max_gap is not None):
+        raise ValueError("gaps are silence in the packed samples: pass pack")
+    if max_gap is not None and int(max_gap) < 0:
+        raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
+
+
 def _check_gaps(gaps, max_gap, B):
     """`gaps=` -> (int32 [B] tensor, host or device as given; max_gap): a host sequence defaults `max_gap` to its own maximum, a
-    device tensor is never read and needs it."""
+    device tensor is never read and needs it.  (`max_gap` itself: `_check_gap_args`.)"""
     if torch.is_tensor(gaps) and gaps.is_cuda:
         if max_gap is None:
             raise ValueError("gaps on the device are never read on the host: pass max_gap, the longest break in samples")
@@ -878,8 +862,6 @@ def _check_gaps(gaps, max_gap, B):
         if max_gap is None:
             max_gap = max(int(gaps.max()), 0)
         gaps = gaps.to(torch.int32)
-    if int(max_gap) < 0:
-        raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
     return gaps, int(max_gap)
 
 
@@ -911,43 +893,61 @@ def _resamples(fmt, sample_rate):
     return sample_rate not in (None, resample.MODEL_RATE) or fmt not in ops.PACK_FORMATS
 
 
-def _pack_into_one(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0):
-    """`ops.wave_pack` -- or `ops.wave_resample_pack` -- into ONE device allocation, [offsets int64 [B + 1] | `n_marks` int32 |
-    pad to 16 bytes | samples at capacity: ceil(L U / D) per row], so that a single copy brings all of it to the host.  Returns
-    (the allocation as bytes, packed, offsets); with n_marks = 0 the layout is the one without marks, byte for byte.
-    `gaps` (int32 [B], host or device): the layout gains B int32 behind the marks, into which the gaps are
-    copied and from which `ops.wave_pack_gaps` reads them, and `max_gap` more samples per row; returns the gaps' view as a fourth
-    value.  Without `gaps` nothing changes: the same two wrappers, the same bytes."""
+class _HandOver:
+    """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
+
+        [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | pad to 16 bytes | samples of `fmt`]
+
+    with `n_marks` = 0 / no gaps the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the four
+    parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
+    its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps` and `packed` are the
+    buffer and its views (None for a part the layout does not have)."""
+
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False):
+        self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
+        self.offsets_at = 0
+        self.marks_at = 8 * (self.B + 1)
+        self.gaps_at = self.marks_at + 4 * self.n_marks
+        self.samples_at = (self.gaps_at + (4 * self.B if self.with_gaps else 0) + 15) // 16 * 16
+        self.buf = self.offsets = self.marks = self.gaps = self.packed = None
+
+    def views(self, buf):
+        """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples) of a uint8 buffer."""
+        i32 = lambda at, n: buf[at:at + 4 * n].view(torch.int32)
+        return (buf[self.offsets_at:self.marks_at].view(torch.int64), i32(self.marks_at, self.n_marks) if self.n_marks else None,
+                i32(self.gaps_at, self.B) if self.with_gaps else None, buf[self.samples_at:].view(self.dtype))
+
+    def allocate(self, samples, device):
+        self.buf = torch.empty((self.samples_at + samples * self.dtype.itemsize,), device=device, dtype=torch.uint8)
+        self.offsets, self.marks, self.gaps, self.packed = self.views(self.buf)
+        return self
+
+
+def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0):
+    """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
+    D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
+    with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
+    are copied into here; else, where `_resamples`, `ops.wave_resample_pack`; else `ops.wave_pack`."""
     B, L = wave.shape[0], wave.shape[-1]
-    dtype = ops.OUTPUT_FORMATS[fmt][1]
-    hdr = (8 * (B + 1) + 4 * n_marks + (0 if gaps is None else 4 * B) + 15) // 16 * 16
-    into = lambda buf: dict(trim=trim, fmt=fmt, out=buf[hdr:].view(dtype), offsets=buf[:8 * (B + 1)].view(torch.int64),
-                            samples_per_frame=samples_per_frame)
+    rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
+    U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
+    room = resample.output_samples(L, U, D) + (0 if gaps is None else max_gap)
+    ho = _HandOver(B, fmt, n_marks, gaps is not None).allocate(B * room, wave.device)
+    into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
-        rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
-        U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
-        room = B * (resample.output_samples(L, U, D) + max_gap)
-        buf = torch.empty((hdr + room * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
-        g0 = 8 * (B + 1) + 4 * n_marks
-        g = buf[g0:g0 + 4 * B].view(torch.int32)
-        g.copy_(gaps.reshape(B), non_blocking=True)
-        packed, offsets = ops.wave_pack_gaps(wave, frames, g, max_gap, rate=rate, **into(buf))
-        return buf, packed, offsets, g
-    if not _resamples(fmt, sample_rate):
-        buf = torch.empty((hdr + B * L * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
-        packed, offsets = ops.wave_pack(wave, frames, **into(buf))
-        return buf, packed, offsets
-    rate = resample.MODEL_RATE if sample_rate is None else sample_rate
-    U, D = resample.table(rate, wave.device)[:2]
-    buf = torch.empty((hdr + B * resample.output_samples(L, U, D) * dtype.itemsize,), device=wave.device, dtype=torch.uint8)
-    packed, offsets = ops.wave_resample_pack(wave, frames, rate, **into(buf))
-    return buf, packed, offsets
+        ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
+        ops.wave_pack_gaps(wave, frames, ho.gaps, max_gap, rate=rate, **into)
+    elif rate is not None:
+        ops.wave_resample_pack(wave, frames, rate, **into)
+    else:
+        ops.wave_pack(wave, frames, **into)
+    return ho
 
 
 def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False, gaps=None, max_gap=0):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `marks`: one `ops.token_marks` launch behind the packing writes the timing marks
-    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows (`_pack_into_one`)."""
+    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows (`_hand_over`)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     if trim is None:
@@ -957,19 +957,14 @@ def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=F
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    n_marks = B * (N + 1) if marks else 0
-    if gaps is None:
-        buf, packed, offsets = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=n_marks)
-    else:
-        buf, packed, offsets, gaps = _pack_into_one(w, p["frames"], trim, pack, spf, sample_rate, n_marks=n_marks, gaps=gaps,
-                                                    max_gap=max_gap)
+    ho = _hand_over(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0, gaps=gaps, max_gap=max_gap)
     m = None
     if marks:
-        m = buf[8 * (B + 1):8 * (B + 1) + 4 * B * (N + 1)].view(torch.int32).view(B, N + 1)
+        m = ho.marks.view(B, N + 1)
         ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=model.decoder.kind == "hifigan", trim=trim,
                         rate=sample_rate, samples_per_frame=spf, out=m)
-    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=packed, offsets=offsets, buf=buf,
-                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=gaps, max_gap=max_gap)
+    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=ho.packed, offsets=ho.offsets, buf=ho.buf,
+                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=ho.gaps, max_gap=max_gap)
 
 
 class GraphedSynthesis:
@@ -1032,10 +1027,7 @@ class GraphedSynthesis:
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
         self._neutral_tok = self.static["controls"].tok_buf.clone() if tok else None
-        if max_gap is not None and pack is None:
-            raise ValueError("gaps are silence in the packed samples: pass pack")
-        if max_gap is not None and int(max_gap) < 0:
-            raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
+        _check_gap_args(pack, None, max_gap)
         self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
         if self.passage:
             starts = torch.zeros((B,), device=dev, dtype=torch.int32)
@@ -1070,14 +1062,19 @@ class GraphedSynthesis:
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
                  starts=None, s_prev=None, gaps=None):
         st = self.static
-        for name, val in (("starts", starts), ("s_prev", s_prev), ("gaps", gaps)):
+        built_by = dict(starts="passage=True", s_prev="passage=True", gaps="max_gap")  # the buffers a plain graph lacks
+        for name, val in (("starts", starts), ("s_prev", s_prev), ("gaps", gaps), ("tokens", tokens), ("lengths_dev", lengths),
+                          ("noise", noise), ("step_noise", step_noise), ("sine_noise", sine_noise), ("ref_s", ref_s)):
             if val is None:
                 continue
-            if name not in st:
-                raise ValueError("this graph was built without %s: pass %s" % (name, "max_gap" if name == "gaps" else "passage=True"))
-            val = val if torch.is_tensor(val) else torch.as_tensor(val)
-            if val.numel() != st[name].numel():
-                raise ValueError("%s must hold %d values, got %d" % (name, st[name].numel(), val.numel()))
+            if st.get(name) is None:
+                raise ValueError("this graph was built without %s" % name + (": pass %s" % built_by[name] if name in built_by else ""))
+            if name in built_by:  # host lists too
+                val = torch.as_tensor(val)
+                if val.numel() != st[name].numel():
+                    raise ValueError("%s must hold %d values, got %d" % (name, st[name].numel(), val.numel()))
+            elif name == "sine_noise":
+                val = val[:, :st[name].shape[1]]
             st[name].copy_(val.reshape(st[name].shape), non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
@@ -1093,14 +1090,6 @@ class GraphedSynthesis:
         if self._neutral_tok is not None:
             has_tok = controls is not None and controls.tok_buf is not None
             st["controls"].tok_buf.copy_(controls.tok_buf if has_tok else self._neutral_tok, non_blocking=True)
-        for name, val in (("tokens", tokens), ("lengths_dev", lengths), ("noise", noise), ("step_noise", step_noise),
-                          ("sine_noise", sine_noise), ("ref_s", ref_s)):
-            if val is not None:
-                if st[name] is None:
-                    raise ValueError("this graph was built without %s" % name)
-                if name == "sine_noise":
-                    val = val[:, :st[name].shape[1]]
-                st[name].copy_(val.reshape(st[name].shape), non_blocking=True)
         g = self._g
         if g is not None and (g["gen"] != _sampler_generation(self.sampler)
                               or any(_engine_changed(e, rec, gen) for e, (rec, gen) in zip(self._engines(), g["engines"]))):
@@ -1145,6 +1134,35 @@ def _decode_groups(model, groups, dec, main, noise_of, ready=None, first=0):
         w.record_stream(main)
         queued.append((idx, w, ev))
     yield from queued
+
+
+def _check_capacity_args(tokens, *, max_frames, pack, trim, sample_rate, lengths_dev, marks, passage, gaps, max_gap, s_prev,
+                         controls, taps, front, durations, decode_streams):
+    """What `inference` refuses about the arguments of the capacity-bound path, before anything is launched, and what it
+    settles on the way -> (carry, gaps, max_gap, controls): whether the rows are a passage, the breaks as `_check_gaps` hands
+    them on, and the controls with the start flags of `passage=[...]` in their `t` row."""
+    _check_output(pack, sample_rate)
+    if max_frames is None and (passage is not None or gaps is not None or max_gap is not None or s_prev is not None):
+        raise ValueError("passage / gaps / max_gap / s_prev belong to the capacity-bound path: pass max_frames")
+    _check_gap_args(pack, gaps, max_gap)
+    if gaps is None and max_gap is not None:
+        raise ValueError("max_gap bounds `gaps`: pass gaps")
+    carry = passage is not None and passage is not False
+    if s_prev is not None and not carry:
+        raise ValueError("s_prev is the style a passage continues from: pass passage")
+    if gaps is not None:
+        gaps, max_gap = _check_gaps(gaps, max_gap, tokens.shape[0])
+    if carry and passage is not True:
+        if controls is not None:
+            _check_controls(controls, tokens.device, tokens.shape[0], taps, front, durations, tokens.shape[1])
+        controls = _passage_controls(controls, passage, tokens.shape[0], tokens.device)
+    if marks and (max_frames is None or pack is None):
+        raise ValueError("marks are positions in the packed samples of the capacity-bound path: pass max_frames and pack")
+    if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
+        raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
+    if max_frames is not None and decode_streams:
+        raise ValueError("max_frames: there is ONE decoder call, on the current stream; `decode_streams` has no meaning here")
+    return carry, gaps, max_gap, controls
 
 
 @torch.no_grad()
@@ -1213,28 +1231,10 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     `max_gap` (the packing step clamps to 0..max_gap and sizes its allocation by it), or a host list, whose maximum is the
     default.  `marks` stay relative to their row (`SynthesisResult`).
     """
-    _check_output(pack, sample_rate)
-    if max_frames is None and (passage is not None or gaps is not None or max_gap is not None or s_prev is not None):
-        raise ValueError("passage / gaps / max_gap / s_prev belong to the capacity-bound path: pass max_frames")
-    if pack is None and (gaps is not None or max_gap is not None):
-        raise ValueError("gaps are silence in the packed samples: pass pack")
-    if gaps is None and max_gap is not None:
-        raise ValueError("max_gap bounds `gaps`: pass gaps")
-    carry = passage is not None and passage is not False
-    if s_prev is not None and not carry:
-        raise ValueError("s_prev is the style a passage continues from: pass passage")
-    if gaps is not None:
-        gaps, max_gap = _check_gaps(gaps, max_gap, tokens.shape[0])
-    if carry and passage is not True:
-        if controls is not None:
-            _check_controls(controls, tokens.device, tokens.shape[0], taps, front, durations, tokens.shape[1])
-        controls = _passage_controls(controls, passage, tokens.shape[0], tokens.device)
-    if marks and (max_frames is None or pack is None):
-        raise ValueError("marks are positions in the packed samples of the capacity-bound path: pass max_frames and pack")
-    if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
-        raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
-    if max_frames is not None and decode_streams:
-        raise ValueError("max_frames: there is ONE decoder call, on the current stream; `decode_streams` has no meaning here")
+    carry, gaps, max_gap, controls = _check_capacity_args(
+        tokens, max_frames=max_frames, pack=pack, trim=trim, sample_rate=sample_rate, lengths_dev=lengths_dev, marks=marks,
+        passage=passage, gaps=gaps, max_gap=max_gap, s_prev=s_prev, controls=controls, taps=taps, front=front, durations=durations,
+        decode_streams=decode_streams)
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
@@ -1298,6 +1298,27 @@ def _decode_stream_list(decode_streams, use_streams, make):
     if use_streams and decode_streams and int(decode_streams) > 1:
         return [make(i) for i in range(int(decode_streams))]
     return []
+
+
+def _stack_group(sentences, ids, npad, durations, noises, step_noises, ref_s, dev):
+    """The inputs of ONE front call over the sentences `ids` of a passage, stacked at the token width `npad`: `tokens`
+    right-padded with id 0 (the pad: text_utils / ipynb:277), `dur` (forced durations) zero-padded -- pad tokens get no frames --,
+    `noise` / `step_noise` concatenated along their batch axis, `ref_s` repeated per row, and the sentences' token counts as
+    `lengths` (host int64) and `lens_dev` (device int32), both None for a group no row of which is padded."""
+    ns = [sentences[k].numel() for k in ids]
+    tokens = torch.zeros((len(ids), npad), dtype=sentences[ids[0]].dtype, device=dev)
+    for j, k in enumerate(ids):
+        tokens[j, :ns[j]] = sentences[k].reshape(-1)
+    dur = None
+    if durations is not None:
+        dur = torch.zeros((len(ids), npad), dtype=torch.long, device=dev)
+        for j, k in enumerate(ids):
+            dur[j, :ns[j]] = durations[k].reshape(-1).long().to(dev)
+    lengths = torch.LongTensor(ns) if any(n != npad for n in ns) else None
+    cat = lambda seq, dim: None if seq is None else torch.cat([seq[k] for k in ids], dim=dim)
+    return dict(tokens=tokens, dur=dur, lengths=lengths, lens_dev=None if lengths is None else lengths.to(torch.int32).to(dev),
+                noise=cat(noises, 0), step_noise=cat(step_noises, 1),
+                ref_s=None if ref_s is None else ref_s.reshape(1, -1).expand(len(ids), -1).contiguous())
 
 
 @torch.no_grad()
@@ -1390,24 +1411,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
         npad = max(ns)
         if bucket and npad % bucket:
             npad = (npad + bucket - 1) // bucket * bucket
-        tokens = torch.zeros((len(ids), npad), dtype=sentences[i].dtype, device=dev)  # token id 0 = pad (text_utils / ipynb:277)
-        for j, k in enumerate(ids):
-            tokens[j, :ns[j]] = sentences[k].reshape(-1)
-        ragged = any(n != npad for n in ns)
-        lengths = torch.LongTensor(ns) if ragged else None
-        dur, frames = None, None
-        if durations is not None:
-            rows = [durations[k].reshape(-1).long() for k in ids]
-            if not rows[0].is_cuda:
-                frames = [int(r.sum()) for r in rows]
-            dur = torch.zeros((len(ids), npad), dtype=torch.long, device=dev)  # pad tokens get no frames
-            for j, r in enumerate(rows):
-                dur[j, :ns[j]] = r.to(dev)
-        cat = lambda seq, dim: None if seq is None else torch.cat([seq[k] for k in ids], dim=dim)
-        prepped.append(dict(ids=ids, tokens=tokens, lengths=lengths, dur=dur, frames=frames,
-                            lens_dev=None if lengths is None else lengths.to(torch.int32).to(dev),
-                            noise=cat(noises, 0), step_noise=cat(step_noises, 1),
-                            ref_s=None if ref_s is None else ref_s.reshape(1, -1).expand(len(ids), -1).contiguous()))
+        frames = None  # the host's frame sums of forced durations it can read: no sync for them later
+        if durations is not None and not durations[i].is_cuda:
+            frames = [int(durations[k].long().sum()) for k in ids]
+        prepped.append(dict(_stack_group(sentences, ids, npad, durations, noises, step_noises, ref_s, dev), ids=ids, frames=frames))
     dec = _decode_stream_list(decode_streams, use_streams, lambda i: ops.aux_stream(dev, 0, index=i + 1))
     if use_streams:
         # weights and inputs produced on the caller's stream -- including the rows stacked just above -- are visible to the other streams
@@ -1481,6 +1488,7 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     if tok_ctl and controls.N != max(ns_all):
         raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
     if gaps is not None:
+        _check_gap_args(pack, gaps, max_gap)
         gaps, max_gap = _check_gaps(gaps, max_gap, K)
     prepped = []
     for i, i_end in _front_chunks(front_batch, K):
@@ -1489,26 +1497,13 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
         npad = max(ns_all) if tok_ctl else max(ns)
         if bucket and npad % bucket and not tok_ctl:
             npad = (npad + bucket - 1) // bucket * bucket
-        tokens = torch.zeros((len(ids), npad), dtype=sentences[i].dtype, device=dev)  # token id 0 = pad
-        for j, k in enumerate(ids):
-            tokens[j, :ns[j]] = sentences[k].reshape(-1)
-        ragged = any(n != npad for n in ns)
-        dur = None
-        if durations is not None:
-            dur = torch.zeros((len(ids), npad), dtype=torch.long, device=dev)  # pad tokens get no frames
-            for j, k in enumerate(ids):
-                dur[j, :ns[j]] = durations[k].reshape(-1).long().to(dev)
         sine = None
         if sine_noises is not None:  # every sentence's own draws (>= 600 x its frames), zero-padded to the capacity
             rows = [sine_noises[k].reshape(-1, sine_noises[k].shape[-1])[:600 * T_cap] for k in ids]
             sine = torch.zeros((len(ids), 600 * T_cap, rows[0].shape[-1]), device=dev, dtype=torch.float32)
             for j, r in enumerate(rows):
                 sine[j, :r.shape[0]] = r
-        cat = lambda seq, dim: None if seq is None else torch.cat([seq[k] for k in ids], dim=dim)
-        prepped.append(dict(ids=ids, tokens=tokens, dur=dur, sine=sine, noise=cat(noises, 0), step_noise=cat(step_noises, 1),
-                            lengths=torch.LongTensor(ns) if ragged else None,
-                            lens_dev=torch.tensor(ns, dtype=torch.int32).to(dev) if ragged else None,
-                            ref_s=None if ref_s is None else ref_s.reshape(1, -1).expand(len(ids), -1).contiguous()))
+        prepped.append(dict(_stack_group(sentences, ids, npad, durations, noises, step_noises, ref_s, dev), ids=ids, sine=sine))
     s_prev, results = None, []
     for k, q in enumerate(prepped):
         i, j = q["ids"][0], q["ids"][-1] + 1

@@ -206,8 +206,8 @@ def test_synthesize_long_max_frames_accepts_token_controls_and_chains_the_style(
 
 
 def test_calls_without_the_new_arguments_stay_on_the_old_wrappers(monkeypatch):
-    """`_pack_into_one` without gaps goes through ops.wave_pack / ops.wave_resample_pack with the layout it always had; with
-    gaps through ops.wave_pack_gaps, B * max_gap samples and B int32 larger."""
+    """`_hand_over` without gaps goes through ops.wave_pack / ops.wave_resample_pack with the layout it always had; with gaps
+    through ops.wave_pack_gaps, B * max_gap samples and B int32 larger."""
     seen = []
 
     def spy(name):
@@ -220,20 +220,23 @@ def test_calls_without_the_new_arguments_stay_on_the_old_wrappers(monkeypatch):
     monkeypatch.setattr(pipeline.resample, "table", lambda rate, dev: pipeline.resample.ratio(rate) + (0, None))
     B, L = 3, 1200
     wave, frames = torch.zeros(B, 1, L), torch.ones(B, dtype=torch.int32)
-    buf, packed, offsets = pipeline._pack_into_one(wave, frames, 0, "s16", 600)
-    assert seen[-1][0] == "wave_pack" and buf.numel() == 32 + 2 * B * L and packed.numel() == B * L
-    buf, packed, offsets = pipeline._pack_into_one(wave, frames, 0, "ulaw", 600, 8000, n_marks=B * 6)
-    assert seen[-1][0] == "wave_resample_pack" and seen[-1][1] == (8000,) and buf.numel() == (32 + 4 * B * 6 + 15) // 16 * 16 + B * 400
+    ho = pipeline._hand_over(wave, frames, 0, "s16", 600)
+    assert seen[-1][0] == "wave_pack" and ho.buf.numel() == 32 + 2 * B * L and ho.packed.numel() == B * L and ho.gaps is None
+    ho = pipeline._hand_over(wave, frames, 0, "ulaw", 600, 8000, n_marks=B * 6)
+    assert seen[-1][0] == "wave_resample_pack" and seen[-1][1] == (8000,)
+    assert ho.buf.numel() == (32 + 4 * B * 6 + 15) // 16 * 16 + B * 400 and ho.gaps is None
     assert not any(n == "wave_pack_gaps" for n, *_ in seen)
     gaps = torch.tensor([5, 0, 70], dtype=torch.int32)
-    buf, packed, offsets, g = pipeline._pack_into_one(wave, frames, 0, "s16", 600, gaps=gaps, max_gap=64)
+    ho = pipeline._hand_over(wave, frames, 0, "s16", 600, gaps=gaps, max_gap=64)
     assert seen[-1][0] == "wave_pack_gaps" and seen[-1][2]["rate"] is None and seen[-1][1][1] == 64
-    assert packed.numel() == B * (L + 64) and buf.numel() == (32 + 4 * B + 15) // 16 * 16 + 2 * B * (L + 64)
-    assert g.tolist() == [5, 0, 70] and g.data_ptr() == buf.data_ptr() + 32  # the kernel reads them from the hand-over's header
-    buf, packed, offsets, g = pipeline._pack_into_one(wave, frames, 0, "alaw", 600, 8000, n_marks=B * 6, gaps=gaps, max_gap=8)
-    assert seen[-1][0] == "wave_pack_gaps" and seen[-1][2]["rate"] == 8000 and packed.numel() == B * (400 + 8)
-    assert g.data_ptr() == buf.data_ptr() + 32 + 4 * B * 6
-    buf, packed, offsets, g = pipeline._pack_into_one(wave, frames, 0, "ulaw", 600, None, gaps=gaps, max_gap=8)
+    assert ho.packed.numel() == B * (L + 64) and ho.buf.numel() == (32 + 4 * B + 15) // 16 * 16 + 2 * B * (L + 64)
+    g = ho.gaps
+    assert g.tolist() == [5, 0, 70] and g.data_ptr() == ho.buf.data_ptr() + 32  # the kernel reads them from the hand-over's header
+    assert seen[-1][1][0].data_ptr() == g.data_ptr()
+    ho = pipeline._hand_over(wave, frames, 0, "alaw", 600, 8000, n_marks=B * 6, gaps=gaps, max_gap=8)
+    assert seen[-1][0] == "wave_pack_gaps" and seen[-1][2]["rate"] == 8000 and ho.packed.numel() == B * (400 + 8)
+    assert ho.gaps.data_ptr() == ho.buf.data_ptr() + 32 + 4 * B * 6
+    ho = pipeline._hand_over(wave, frames, 0, "ulaw", 600, None, gaps=gaps, max_gap=8)
     assert seen[-1][2]["rate"] == 24000  # G.711 at the model rate: the resampling move with U = D = 1
 
 
