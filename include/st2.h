@@ -232,6 +232,41 @@ int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int
  * bit.  k = 3 / 7 / 11 launches of up to three utterances: 32 below ~100 tiles of 128 x 128, 64 up to ~900 (k = 3) / 340 (k = 7,
  * 11); 128 otherwise (y is bitwise the same either way: st2_conv1d_xs_impl.h). */
 int st2_conv1d_xs_part_cols(const st2_conv_desc* d);
+/* ---- the conv launch rule (added under ABI 23, additive; host-only: launches nothing, never touches the GPU) ------- *
+ * How ONE split-f16 convolution is issued.  Both host routines that issue them -- conv() of the C++ plans and ops.conv1d of
+ * the per-kernel Python plans -- ask here and do what the answer says, so a layer is routed, scaled and sized the same way by
+ * both (the plans are held bitwise equal).  Reads B, C_in, C_out, L_in, L_out, ks, pad_left and pro of *d.
+ *   route         ST2_CONV_ROUTE_XS (st2_act_split + st2_conv1d_xs) when pad_left <= xs_halo, L_in >= xs_min_l, the conv has a
+ *                 prologue or C_in >= 64 (the split pass is then cheap next to the conv), and not prefer_fused; else
+ *                 ST2_CONV_ROUTE_FUSED (st2_conv1d_f16s).  force_fused != 0 (the contract tests' selector) = fused always.
+ *   prefer_fused  1: a prologue and C_in <= 64, or ks <= 3 and C_in <= 128 -- the xs pair of such a layer is HBM-bound (20
+ *                 against 12 bytes per element), the fused kernel wins whatever the length (measured per layer at B = 32).
+ *   x_scale       the operand scale by rule: 8 after a normalising prologue (ADAIN_LEAKY, ADAIN_SNAKE, COLNORM), else 1; a
+ *                 calibrated per-layer value (st2_calibrate) overrides it.
+ *   xs_min_l      256: shorter rows stay on the fused kernel (an xs row is >= 640 slots).
+ *   xs_*          the split planes of THIS input, filled on either route (st2_act_split can be driven on any layer):
+ *                 xs_cg = C_in rounded up to 32, in groups of 8; xs_lp = slots per row = xs_halo + (L_in + 1 rounded up to the
+ *                 widest conv tile, 512) + 96 for the last tile's taps; xs_halo = 32 zero columns in front of every row (>= the
+ *                 largest pad_left on the path); xs_bytes = B * 2 * xs_cg * xs_lp * 16.
+ *   part_*        want_stats != 0: the partial-sum layout of the output's InstanceNorm statistics -- part_cols columns per slot
+ *                 (st2_conv1d_xs_part_cols(d) on the xs route, to be passed as d.part_cols; 128 on the fused route, whose
+ *                 d.part_cols stays 0), part_nt = ceil(L_out / part_cols) slots, part_floats = B * C_out * part_nt * 3.  All 0
+ *                 without want_stats.
+ *   splitk_bytes  fused route without statistics: st2_conv1d_f16s_splitk_bytes(d); else 0.
+ * Returns non-zero (with the error text set) for gb_seg > 0 on the fused route: the per-segment affine exists in
+ * st2_act_split only. */
+enum st2_conv_route { ST2_CONV_ROUTE_XS = 0, ST2_CONV_ROUTE_FUSED = 1 };
+typedef struct st2_conv_plan {
+  int32_t route;         /* enum st2_conv_route */
+  int32_t prefer_fused;
+  float x_scale;
+  int32_t xs_cg, xs_lp, xs_halo, xs_min_l;
+  int64_t xs_bytes;
+  int32_t part_cols, part_nt;
+  int64_t part_floats;
+  int64_t splitk_bytes;
+} st2_conv_plan;
+int st2_conv_launch_plan(const st2_conv_desc* d, int32_t want_stats, int32_t gb_seg, int32_t force_fused, st2_conv_plan* plan);
 int st2_stats_finalize(const float* part, int32_t rows, int32_t nt, int32_t L, float eps, float* stats, int32_t cols, void* stream);
 /* Ragged rows (ABI v23): row r covers len[r / len_div] <= L columns (len int32 on the device, NULL = L; len_div = channels per
  * batch item).  Slots wholly past that end are not read; the last one counts only its valid columns. */
@@ -320,6 +355,9 @@ int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs, int32_t p_
                                    int32_t B, int32_t C, int32_t stride, int32_t pad, int32_t L_raw,
                                    int32_t reflect_left, float* part, int32_t part_nt, const int32_t* q_len,
                                    const int32_t* out_len, void* stream);
+/* Positions per partial-sum slot of the two entries above (1024; added under ABI 23, host-only): part_nt >= ceil(L_out / this), and the `cols`
+ * their sums go to st2_stats_finalize with. */
+int st2_convt_interleave_part_cols(void);
 
 /* ---- AdaIN + LeakyReLU + depthwise ConvTranspose1d(k3,s2,p1,op1) ("pool") ------------ *
  * Replaces Modules/istftnet.py:441-444 with upsample=True (weights w[c][3], bias[c]). */

@@ -56,6 +56,17 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvPlan(C.Structure):
+    """Mirror of `st2_conv_plan` (include/st2.h): the launch rule's answer for one split-f16 conv."""
+    _fields_ = [("route", C.c_int32), ("prefer_fused", C.c_int32), ("x_scale", C.c_float),
+                ("xs_cg", C.c_int32), ("xs_lp", C.c_int32), ("xs_halo", C.c_int32), ("xs_min_l", C.c_int32),
+                ("xs_bytes", C.c_int64), ("part_cols", C.c_int32), ("part_nt", C.c_int32), ("part_floats", C.c_int64),
+                ("splitk_bytes", C.c_int64)]
+
+
+CONV_ROUTE_XS, CONV_ROUTE_FUSED = 0, 1  # enum st2_conv_route
+
+
 class ModelConfig(C.Structure):
     """Mirror of `st2_model_config` (include/st2.h)."""
     _fields_ = [
@@ -331,6 +342,8 @@ _SIGNATURES = {
     "st2_style_workspace_bytes_ragged": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "st2_style_forward_ragged": (C.c_int, [C.c_void_p, C.c_int32, f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, f32p,
                                            C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_conv_launch_plan": (C.c_int, [C.POINTER(ConvDesc), C.c_int32, C.c_int32, C.c_int32, C.POINTER(ConvPlan)]),
+    "st2_convt_interleave_part_cols": (C.c_int, []),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -3,6 +3,7 @@
 // autotuner that picks, per shape class and device, the fastest of the bitwise-equivalent builds of a launch.
 #include "st2_conv1d_xs_impl.h"
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -288,6 +289,47 @@ extern "C" int st2_conv_tune_read(double* rows, int32_t cap_rows) {
 
 extern "C" int st2_conv1d_xs_part_cols(const st2_conv_desc* dp) {
   return dp ? st2xs::small_grid_cols(*dp) : 128;
+}
+
+// The conv launch rule (st2.h st2_conv_launch_plan): the ONE statement of how a split-f16 conv is routed,
+// scaled and sized.  conv() of the C++ plans and ops.conv1d of the Python plans both ask here.
+constexpr int XS_HALO = 32;         // zero columns in front of every xs row (>= the largest pad_left on the path: 25)
+constexpr int XS_MIN_L = 256;       // shorter rows stay on the fused kernel: an xs row is >= 640 slots
+constexpr int XS_MIN_C_PLAIN = 64;  // prologue-free convs take the xs pair from this many input channels on (the split pass is
+                                    // then cheap next to the conv; measured 39 us vs 80 us per denoiser Linear at B*N = 3200)
+// Layers whose xs pair is HBM-bound take the fused kernel (prologue arithmetic on the VALU beside the MFMAs, no activation pass:
+// 12 instead of 20 bytes per element): the narrow HiFi-GAN stages (C <= 64) and the k = 3 resblock convs at C = 128.  Measured
+// per layer at B = 32 (tools/probe_conv.py, profiles/archive/r02/r02y_probe_conv_b32.log): fused / pair = 0.80-0.96 at C = 64,
+// 0.86-0.91 at C = 32, 0.89-0.92 at C = 128 k = 3; 1.04-1.19 everywhere else.
+constexpr int FUSED_MAX_C = 64, FUSED_K3_MAX_C = 128;
+
+extern "C" int st2_conv_launch_plan(const st2_conv_desc* dp, int32_t want_stats, int32_t gb_seg, int32_t force_fused,
+                                    st2_conv_plan* p) {
+  ST2_REQUIRE(dp && p, "st2_conv_launch_plan: null descriptor or plan");
+  const st2_conv_desc& d = *dp;
+  const bool norm = d.pro == ST2_PRO_ADAIN_LEAKY || d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_COLNORM;
+  const bool prefer_fused = d.pro != ST2_PRO_NONE && (d.C_in <= FUSED_MAX_C || (d.ks <= 3 && d.C_in <= FUSED_K3_MAX_C));
+  const bool xs = !force_fused && d.pad_left <= XS_HALO && d.L_in >= XS_MIN_L &&
+                  (d.pro != ST2_PRO_NONE || d.C_in >= XS_MIN_C_PLAIN) && !prefer_fused;
+  *p = st2_conv_plan{};
+  p->route = xs ? ST2_CONV_ROUTE_XS : ST2_CONV_ROUTE_FUSED;
+  p->prefer_fused = prefer_fused;
+  p->x_scale = norm ? 8.0f : 1.0f;
+  p->xs_cg = (d.C_in + 31) / 32 * 32 / 8;
+  p->xs_lp = XS_HALO + (std::max(d.L_in, 1) + 1 + 511) / 512 * 512 + 96;
+  p->xs_halo = XS_HALO;
+  p->xs_min_l = XS_MIN_L;
+  p->xs_bytes = (int64_t)d.B * 2 * p->xs_cg * p->xs_lp * 16;
+  ST2_REQUIRE(xs || gb_seg <= 0, "st2_conv_launch_plan: a per-segment affine (gb_seg) exists on the st2_act_split + st2_conv1d_xs "
+              "route only; this layer takes the fused kernel");
+  if (want_stats) {  // one slot per 128 columns, or per 64 / 32-column tile of a small xs grid (one utterance)
+    p->part_cols = xs ? st2_conv1d_xs_part_cols(dp) : 128;
+    p->part_nt = st2_cdiv(d.L_out, p->part_cols);
+    p->part_floats = (int64_t)d.B * d.C_out * p->part_nt * 3;  // (sum, sum of squares) per slot, then the slots' shifts
+  } else if (!xs) {
+    p->splitk_bytes = st2_conv1d_f16s_splitk_bytes(dp);  // skinny layers run split-K (this thread's st2_conv1d_f16s_split_as holds)
+  }
+  return 0;
 }
 
 extern "C" int st2_conv1d_xs(const st2_conv_desc* dp, void* stream) {

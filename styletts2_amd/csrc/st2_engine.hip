@@ -136,12 +136,6 @@ Backend g_be = kHipBackend;
 // ------------------------------------------------------------------------------------------------------------------
 // workspace arena, views
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int XS_HALO = 32;        // == styletts2_amd.ops.XS_HALO
-constexpr int FUSED_MAX_C = 64, FUSED_K3_MAX_C = 128;  // ops.prefer_fused
-constexpr int XS_MIN_L = 256;      // shorter rows stay on the fused kernel
-constexpr int XS_MIN_C_PLAIN = 64;  // prologue-free convs take the xs pair from this many input channels on
-constexpr int CVT_TILE = 1024;     // positions per st2_convt_interleave_stats partial sum
-
 struct Arena {
   char* base = nullptr;
   int64_t off = 0, cap = 0, peak = 0;
@@ -792,7 +786,7 @@ int pack_denoiser(st2_engine& e, Blob& blob, std::string* err) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// conv dispatch == styletts2_amd.ops.conv1d for split-f16 weights
+// conv dispatch: what st2_conv_launch_plan says for the layer, as styletts2_amd.ops.conv1d does for split-f16 weights
 // ------------------------------------------------------------------------------------------------------------------
 struct ConvOpt {
   int dil = 1, pad_left = 0;
@@ -815,10 +809,15 @@ struct ConvOpt {
   int split_rows = 0;  // > 0: split-K as a launch of this many batch rows decides it (stacked launches of the ragged style plan)
 };
 
-float x_scale_for(int pro) {
-  return (pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_COLNORM) ? 8.0f : 1.0f;
+// The launch rule's answer for a conv of B x C_in x L columns -> C_out channels (nothing here is refused without gb_seg)
+st2_conv_plan conv_rule(int pro, int ks = 1, int B = 0, int C_in = 0, int C_out = 0, int L = 0) {
+  st2_conv_desc d;
+  memset(&d, 0, sizeof(d));
+  d.B = B; d.C_in = C_in; d.C_out = C_out; d.L_in = d.L_out = L; d.ks = ks; d.dil = 1; d.pro = pro;
+  st2_conv_plan p;
+  (void)st2_conv_launch_plan(&d, 0, 0, 0, &p);
+  return p;
 }
-int xs_row_slots(int L) { return XS_HALO + (std::max(L, 1) + 1 + 511) / 512 * 512 + 96; }
 
 // InstanceNorm statistics of y from per-slot partial sums; ragged rows reduce over their own columns only
 void finalize_stats(Ctx& c, float* part, const View& y, int nt, float* stats, int cols) {
@@ -837,13 +836,13 @@ void instnorm_stats(Ctx& c, const View& x, float* stats) {
 
 // The other length-aware twins, the same way: the _len slot exactly when the view (or pointer) that carries the rows' lengths
 // has them, the plain slot -- all a 33-entry backend table provides -- otherwise.
-void act_split(Ctx& c, const View& x, const ConvOpt& o, float x_scale, void* xs, int cg, int Lp) {
+void act_split(Ctx& c, const View& x, const ConvOpt& o, float x_scale, void* xs, const st2_conv_plan& p) {
   if (x.len)
     RUN(c, g_be.act_split_len(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
-                              o.gamma_plus_one, o.alpha, x_scale, xs, cg, Lp, XS_HALO, x.len, c.stream));
+                              o.gamma_plus_one, o.alpha, x_scale, xs, p.xs_cg, p.xs_lp, p.xs_halo, x.len, c.stream));
   else
     RUN(c, g_be.act_split(x.p, x.bs, x.cs, x.B, x.C, x.L, o.pro, o.slope, o.stats, o.gamma, o.beta, o.gb_bs, o.gb_seg,
-                          o.gamma_plus_one, o.alpha, x_scale, xs, cg, Lp, XS_HALO, c.stream));
+                          o.gamma_plus_one, o.alpha, x_scale, xs, p.xs_cg, p.xs_lp, p.xs_halo, c.stream));
 }
 
 // x.len: the rows' ends are their zero padding; y.len (ragged rows only): exact zeros past it
@@ -931,8 +930,24 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
   st2_conv_desc d;
   memset(&d, 0, sizeof(d));
   d.B = x.B; d.C_in = x.C; d.C_out = y.C; d.L_in = x.L; d.L_out = y.L; d.ks = w.ks; d.dil = o.dil; d.pad_left = o.pad_left;
+  d.pro = o.pro;
+  if (w.C_in != x.C || w.C_out != y.C) {
+    if (c.rc == 0) { st2_set_error("engine: conv weight is %d->%d, call has %d->%d", w.C_in, w.C_out, x.C, y.C); c.rc = 1; }
+    return;
+  }
+  // route, operand scale by rule and every size below: the library's launch rule.  A stacked launch (split_rows) splits K as its
+  // per-clip launch would; the setting holds from the plan's workspace query to the fused launch.
+  if (!o.stats_out) st2_conv1d_f16s_split_as(o.split_rows);
+  st2_conv_plan p;
+  // refuses gb_seg on the fused route; asked about it only while no error is pending, so that the first error keeps its text
+  if (st2_conv_launch_plan(&d, o.stats_out != nullptr, c.rc == 0 ? o.gb_seg : 0, 0, &p) != 0) {
+    c.rc = 1;
+    st2_conv1d_f16s_split_as(0);
+    return;
+  }
+  const bool use_xs = p.route == ST2_CONV_ROUTE_XS;
   d.wq = e.P<const void>(w.wq); d.wq_co_pad = w.co_pad; d.wq_cin_pad = w.cin_pad;
-  d.x_scale = e.x_scale(w.site, x_scale_for(o.pro));  // calibrated per layer, else the rule (both powers of two)
+  d.x_scale = e.x_scale(w.site, p.x_scale);  // calibrated per layer, else the rule (both powers of two)
   d.out_scale = 1.0f / d.x_scale;
   if (!c.dry) st2_headroom_set_site(&e, w.site);  // telemetry / calibration: which conv the next launches belong to
   d.w_row_scale = e.F(w.row_scale);
@@ -943,67 +958,38 @@ void conv(Ctx& c, const st2_engine& e, const View& x, const SplitW& w, const Vie
   d.div = o.div;
   d.act = o.act; d.act_split = o.act_split; d.act_slope = o.act_slope;
   d.x_len = x.len; d.y_len = y.len;  // ragged rows (NULL: today's launches)
-  if (w.C_in != x.C || w.C_out != y.C) {
-    if (c.rc == 0) { st2_set_error("engine: conv weight is %d->%d, call has %d->%d", w.C_in, w.C_out, x.C, y.C); c.rc = 1; }
+  const int64_t mark = c.a.off;
+  // a stacked launch's grid (rows x K slices) is checked here, dry runs included, so that a batch too large for it is refused
+  // by the workspace query and before the first launch of the forward
+  if (!use_xs && !o.stats_out && (int64_t)d.B * st2_conv1d_f16s_slices(&d) > 65535) {
+    if (c.rc == 0) { st2_set_error("engine: %d conv rows x %d K slices exceed the 65535 grid rows of one launch", d.B, st2_conv1d_f16s_slices(&d)); c.rc = 1; }
+    st2_conv1d_f16s_split_as(0);
     return;
   }
-  // == styletts2_amd.ops.prefer_fused: HBM-bound layers (C <= 64; k = 3 at C <= 128) skip the activation pass
-  const bool prefer_fused = o.pro != ST2_PRO_NONE && (x.C <= FUSED_MAX_C || (w.ks <= 3 && x.C <= FUSED_K3_MAX_C));
-  const bool use_xs = o.pad_left <= XS_HALO && x.L >= XS_MIN_L && (o.pro != ST2_PRO_NONE || x.C >= XS_MIN_C_PLAIN) &&
-                      !prefer_fused;
-  const int64_t mark = c.a.off;
   if (use_xs) {
-    const int cg = (x.C + 31) / 32 * 32 / 8;
-    const int Lp = xs_row_slots(x.L);
-    void* xs = c.a.alloc((int64_t)x.B * 2 * cg * Lp * 16);
-    act_split(c, x, o, d.x_scale, xs, cg, Lp);
-    d.xs = xs; d.xs_cg = cg; d.xs_lp = Lp; d.xs_halo = XS_HALO;
-    float* part = nullptr;
-    int nt = 0;
-    if (o.stats_out) {
-      // small grids (one utterance) run 64 / 32-column tiles, one partial-sum slot per tile: the library says which
-      const int pc = st2_conv1d_xs_part_cols(&d);
-      nt = (y.L + pc - 1) / pc;
-      part = c.a.f32((int64_t)y.B * y.C * nt * 3);  // (sum, sum of squares) per slot, then the slots' shifts
-      d.part = part; d.part_nt = nt; d.part_cols = pc;
-    }
-    RUN(c, g_be.conv1d_xs(&d, c.stream));
-    if (o.stats_out) finalize_stats(c, part, y, nt, o.stats_out, d.part_cols);
+    d.pro = ST2_PRO_NONE;  // the prologue runs in the activation pass
+    void* xs = c.a.alloc(p.xs_bytes);
+    act_split(c, x, o, d.x_scale, xs, p);
+    d.xs = xs; d.xs_cg = p.xs_cg; d.xs_lp = p.xs_lp; d.xs_halo = p.xs_halo;
+    d.part_cols = p.part_cols;  // 0 without statistics; the fused kernel's slots are always 128 columns and its field stays 0
   } else {
-    if (o.gb_seg > 0) {
-      if (c.rc == 0) { st2_set_error("engine: a per-segment affine (gb_seg) needs the act_split + xs path"); c.rc = 1; }
-      return;
-    }
     d.x = x.p; d.x_bs = x.bs; d.x_cs = x.cs;
-    d.pro = o.pro; d.slope = o.slope;
+    d.slope = o.slope;
     d.stats = o.stats; d.gamma = o.gamma; d.beta = o.beta; d.gb_bs = o.gb_bs; d.gamma_plus_one = o.gamma_plus_one;
     d.alpha = o.alpha;
-    float* part = nullptr;
-    int nt = 0;
-    if (o.stats_out) {  // statistics of the output from the epilogue's per-tile partial sums
-      nt = (y.L + 127) / 128;
-      part = c.a.f32((int64_t)y.B * y.C * nt * 3);
-      d.part = part; d.part_nt = nt;
-    } else {
-      st2_conv1d_f16s_split_as(o.split_rows);
-      // a stacked launch splits as its per-clip launch would: the grid (rows x slices) is checked here, dry runs included, so
-      // that a batch too large for it is refused by the workspace query and before the first launch of the forward
-      if ((int64_t)d.B * st2_conv1d_f16s_slices(&d) > 65535) {
-        if (c.rc == 0) { st2_set_error("engine: %d conv rows x %d K slices exceed the 65535 grid rows of one launch", d.B, st2_conv1d_f16s_slices(&d)); c.rc = 1; }
-        st2_conv1d_f16s_split_as(0);
-        c.a.off = mark;
-        return;
-      }
-      const int64_t skb = st2_conv1d_f16s_splitk_bytes(&d);  // skinny layers run split-K inside the workspace
-      if (skb > 0) {
-        d.splitk_ws = c.a.alloc(skb);
-        d.splitk_ws_bytes = skb;
-      }
+    if (p.splitk_bytes > 0) {  // skinny layers run split-K inside the workspace
+      d.splitk_ws = c.a.alloc(p.splitk_bytes);
+      d.splitk_ws_bytes = p.splitk_bytes;
     }
-    RUN(c, g_be.conv1d_f16s(&d, c.stream));
-    st2_conv1d_f16s_split_as(0);
-    if (o.stats_out) finalize_stats(c, part, y, nt, o.stats_out, 128);
   }
+  float* part = o.stats_out ? c.a.f32(p.part_floats) : nullptr;  // statistics of the output from the epilogue's per-slot sums
+  d.part = part; d.part_nt = p.part_nt;
+  if (use_xs)
+    RUN(c, g_be.conv1d_xs(&d, c.stream));
+  else
+    RUN(c, g_be.conv1d_f16s(&d, c.stream));
+  st2_conv1d_f16s_split_as(0);
+  if (o.stats_out) finalize_stats(c, part, y, p.part_nt, o.stats_out, p.part_cols);
   c.a.off = mark;  // planes / partial sums are dead once the launches are queued (stream order protects reuse)
   if (!c.dry) st2_headroom_set_site(nullptr, -1);
 }
@@ -1195,7 +1181,7 @@ extern "C" int st2_calibrate(st2_engine* e, int32_t margin_bits, int32_t* n_clam
     if (r[11] != me || site < 0 || site >= (int)seen.size() || !(r[5] > 0.0)) continue;
     if (r[6] >= 65504.0) ++clamped;  // the operand hit the clamp at the scale it ran with: this pass only bounds it from below
     seen[(size_t)site] = std::max(seen[(size_t)site], (float)(r[6] / r[5]));  // max |pro(x)| over every launch of the site
-    if (x_scale_for((int)r[1]) == 1.0f) free_range[(size_t)site] = 1;
+    if (conv_rule((int)r[1]).x_scale == 1.0f) free_range[(size_t)site] = 1;
   }
   e->site_scale.resize(e->sites.size(), 0.f);
   e->site_seen.resize(e->sites.size(), 0.f);

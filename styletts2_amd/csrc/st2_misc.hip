@@ -345,6 +345,8 @@ extern "C" int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs,
   return 0;
 }
 
+extern "C" int st2_convt_interleave_part_cols(void) { return CVT_TILE; }
+
 extern "C" int st2_adain_leaky_pool(const float* x, int64_t x_bs, int32_t x_cs, const float* stats,
                                     const float* gamma, const float* beta, int64_t gb_bs, float slope, const float* w,
                                     const float* bias, float* y, int64_t y_bs, int32_t y_cs, int32_t B, int32_t C,

@@ -277,10 +277,10 @@ int decoder_plan(Ctx& c, const st2_engine& e, const float* asr_p, const float* f
       o.pad_left = 1;
       if (ist) { o.pro = ST2_PRO_LEAKY; o.slope = 0.1f; } else { o.pro = ST2_PRO_SNAKE; o.alpha = e.F(g.alphas[i]); }
       conv(c, e, x, g.ups_wt[i], Y, o);
-      const int nt = (L_out + CVT_TILE - 1) / CVT_TILE;
+      const int tile = st2_convt_interleave_part_cols(), nt = (L_out + tile - 1) / tile;
       float* part = c.a.f32((int64_t)B * C * nt * 3);
       convt_interleave_stats(c, Y, e.F(g.ups_b[i]), xs_src, xu, u, pad, L_raw, reflect ? 1 : 0, part, nt);
-      finalize_stats(c, part, xu, nt, st, CVT_TILE);
+      finalize_stats(c, part, xu, nt, st, tile);
       c.a.off = m;
     }
     // multi-receptive-field fusion (istftnet.py:369-375): ((r0 + r1) + r2) / n in the last convs' epilogues

@@ -478,10 +478,9 @@ class _Transformer(_PackedCache, nn.Module):
             st = ops.colnorm_stats(X)
             # The multispeaker net's AdaLayerNorm affine is per utterance.  With the token-merged storage its q / kv convs
             # still run as ONE GEMM over the B*N columns: st2_act_split takes the affine row of a column from its
-            # utterance (gb_seg = N).  Needs the xs pair (>= XS_MIN_L columns); smaller calls keep the [B, F, N] view.
-            # ... and a net wide enough that ops.conv1d does not route its k = 1 convs to the fused kernel (no gb_seg there)
-            seg = (self.multispeaker and s.merged and B > 1 and B * N >= ops.XS_MIN_L
-                   and not ops.prefer_fused(ops.PRO_COLNORM, Fz, 1))
+            # utterance (gb_seg = N).  Needs the xs pair: short calls and narrow nets, whose k = 1 convs the launch rule sends
+            # to the fused kernel (no gb_seg there), keep the [B, F, N] view.
+            seg = self.multispeaker and s.merged and B > 1 and ops.token_merge_takes_xs(Fz, mid, B * N)
             stv = st if (self.multispeaker and not seg) else st.view(1, B * N, 2)
             qkv = A(3 * mid)
             if self.multispeaker:

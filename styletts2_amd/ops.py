@@ -174,7 +174,7 @@ def x_scale_for(pro):
     range; un-normalised inputs (plain / LeakyReLU / Snake prologues: the decoder's `cat` buffer carries the F0 curve
     in Hz, generator stage outputs, FFN intermediates) take 1, i.e. the full +-65504 of f16 (the lo half is then exact
     to 2^-25 absolute through f16 subnormals).  Beyond the range the kernels clamp and raise STATUS_F16_RANGE."""
-    return F16S_X_SCALE if pro in _PRO_NORM else 1.0
+    return conv_plan(pro=pro).x_scale
 
 
 def calibrated_x_scale(max_abs, margin_bits=3):
@@ -342,26 +342,46 @@ def probe_box(level=0):
     return json.loads(buf.value.decode())
 
 
-XS_HALO = 32  # zero columns in front of every xs row (>= the largest pad_left on the path: 25)
-FUSED_MAX_C, FUSED_K3_MAX_C = 64, 128  # see prefer_fused()
-XS_MIN_L = 256  # shorter rows stay on the fused kernel: an xs row is >= 640 slots
-XS_MIN_C_PLAIN = 64  # prologue-free convs take the xs pair too from this many input channels on (the split pass is
-#                      then cheap next to the conv; measured 39 us vs 80 us per denoiser Linear at B*N = 3200)
+def conv_plan(B=0, C_in=0, C_out=0, L_in=0, L_out=0, ks=1, pad_left=0, pro=PRO_NONE, want_stats=False, gb_seg=0,
+              force_fused=None):
+    """`st2_conv_launch_plan` (include/st2.h): how the library issues a split-f16 conv of this geometry
+    -- route, operand scale by rule, split-plane geometry, partial-sum layout, split-K workspace -- as a `_lib.ConvPlan`.  The
+    C++ plans ask the same entry, so nothing of the rule is restated here.  `force_fused` defaults to the tests' selector
+    (`conv_path() == "fused"`).  Host-only: needs no GPU."""
+    d = ConvDesc()
+    d.B, d.C_in, d.C_out, d.L_in, d.L_out, d.ks, d.dil, d.pad_left, d.pro = B, C_in, C_out, L_in, L_out, ks, 1, pad_left, pro
+    p = _lib.ConvPlan()
+    force = conv_path() != "xs" if force_fused is None else force_fused
+    _lib.check(_lib.load().st2_conv_launch_plan(C.byref(d), int(want_stats), int(gb_seg), int(force), C.byref(p)),
+               "st2_conv_launch_plan")
+    return p
+
+
+def __getattr__(name):
+    """XS_HALO, XS_MIN_L, CVT_TILE: constants of the library, read from it (importing this module needs no built library)."""
+    if name in ("XS_HALO", "XS_MIN_L"):
+        return getattr(conv_plan(), {"XS_HALO": "xs_halo", "XS_MIN_L": "xs_min_l"}[name])
+    if name == "CVT_TILE":
+        return _lib.load().st2_convt_interleave_part_cols()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def prefer_fused(pro, C_in, ks):
-    """Layers whose xs pair is HBM-bound take the fused kernel instead (prologue arithmetic on the VALU beside the MFMAs,
-    no activation pass: 12 instead of 20 bytes per element): the narrow HiFi-GAN stages (C <= 64) and the k = 3 resblock
-    convs at C = 128.  Measured per layer at B = 32 (tools/probe_conv.py, profiles/archive/r02/r02y_probe_conv_b32.log): fused / pair =
-    0.80-0.96 at C = 64, 0.86-0.91 at C = 32, 0.89-0.92 at C = 128 k = 3; 1.04-1.19 everywhere else.  The same rule lives in
-    csrc/st2_engine.hip (conv())."""
-    return pro != PRO_NONE and (C_in <= FUSED_MAX_C or (ks <= 3 and C_in <= FUSED_K3_MAX_C))
+    """Layers whose xs pair is HBM-bound take the fused kernel instead, whatever their length: the narrow HiFi-GAN stages
+    (C <= 64) and the k = 3 resblock convs at C = 128 (the rule and its measurements: csrc/st2_conv1d_xs.hip)."""
+    return bool(conv_plan(C_in=C_in, ks=ks, pro=pro).prefer_fused)
+
+
+def token_merge_takes_xs(C_in, C_out, cols):
+    """Does a k = 1 PRO_COLNORM conv over the token-merged view [1, C_in, cols] take the xs pair (the only route with a
+    per-segment affine, `gb_seg`)?  What the C++ sampler plan asks for its q / kv convs, test selector aside."""
+    return conv_plan(1, C_in, C_out, cols, cols, pro=PRO_COLNORM, force_fused=False).route == _lib.CONV_ROUTE_XS
 
 
 def conv_path():
-    """How convs with a prologue over split-f16 weights are issued: "xs" = st2_act_split + st2_conv1d_xs (activation in an
-    HBM-bound pass of its own, pure MFMA conv, InstanceNorm partial sums from the conv epilogue) unless `prefer_fused`
-    routes the layer to st2_conv1d_f16s; "fused" (contract tests only, _hooks.py) = st2_conv1d_f16s everywhere."""
+    """How convs over split-f16 weights are issued: "xs" = by the library's launch rule (`conv_plan`): st2_act_split +
+    st2_conv1d_xs (activation in an HBM-bound pass of its own, pure MFMA conv, InstanceNorm partial sums from the conv
+    epilogue) or st2_conv1d_f16s; "fused" (contract tests only, _hooks.py) = st2_conv1d_f16s everywhere."""
     return _hooks.conv_path
 
 
@@ -384,11 +404,11 @@ class XsTensor:
 def xs_row_slots(L):
     """Slots per xs row for a tensor of length L: halo + L rounded up to the widest conv tile (512) + room for the
     last tile's taps (checked again inside st2_conv1d_xs)."""
-    return XS_HALO + (max(L, 1) + 1 + 511) // 512 * 512 + 96
+    return conv_plan(L_in=L).xs_lp
 
 
 def activate(x, *, pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, gamma_plus_one=False, alpha=None,
-              c_pad=32, gb_seg=0, x_scale=None, lengths=None):
+              c_pad=32, gb_seg=0, x_scale=None, lengths=None, _plan=None):
     """`st2_act_split`: x [B, C, L] fp32 -> XsTensor holding split_f16(x_scale * pro(x)) with the conv's zero padding
     (x_scale = x_scale_for(pro) unless the caller passes a calibrated power of two, `calibrated_x_scale`).  `gb_seg` > 0 (PRO_COLNORM on a token-merged view [1, C, G * gb_seg]): gamma / beta
     are [G, C] and row l // gb_seg applies at position l (per-utterance AdaLayerNorm affine, include/st2.h).  `lengths` (int32 [B]
@@ -399,15 +419,15 @@ def activate(x, *, pro=PRO_NONE, slope=0.0, stats=None, gamma=None, beta=None, g
     lib = _lib.load()
     _chk(x, "x", 3)
     B, Cc, L = x.shape
-    cg = (Cc + c_pad - 1) // c_pad * c_pad // 8
-    Lp = xs_row_slots(L)
-    data = torch.empty((B, 2, cg, Lp, 8), device=x.device, dtype=torch.float16)
+    p = _plan or conv_plan(B, Cc, L_in=L, pro=pro)  # the planes' geometry and the scale by rule (`_plan`: conv1d has asked)
+    cg = p.xs_cg if c_pad == 32 else (Cc + c_pad - 1) // c_pad * c_pad // 8
+    data = torch.empty((B, 2, cg, p.xs_lp, 8), device=x.device, dtype=torch.float16)
     gbs = _chk_prologue(pro, B, Cc, L, stats, gamma, beta, alpha, gb_seg)
-    xsc = float(x_scale) if x_scale else x_scale_for(pro)
+    xsc = float(x_scale) if x_scale else p.x_scale
     _lib.check(lib.st2_act_split_len(x.data_ptr(), x.stride(0), x.stride(1), B, Cc, L, pro, slope, _ptr(stats),
                                      _ptr(gamma), _ptr(beta), gbs, int(gb_seg), 1 if gamma_plus_one else 0, _ptr(alpha),
-                                     xsc, data.data_ptr(), cg, Lp, XS_HALO, lp, _stream()), "st2_act_split_len")
-    return XsTensor(data, Cc, L, XS_HALO, xsc)
+                                     xsc, data.data_ptr(), cg, p.xs_lp, p.xs_halo, lp, _stream()), "st2_act_split_len")
+    return XsTensor(data, Cc, L, p.xs_halo, xsc)
 
 
 def new_part(B, C, nt, device):
@@ -464,7 +484,7 @@ def conv1d_xs(xs, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, ou
     _fill_epilogue(d, B, C_out, L_out, res, res_shift, res2, div, act, act_split, act_slope)
     part = None
     if want_stats:
-        # 128, or 64 / 32 on a small grid (same rule as the C++ plans: bitwise); `part_cols=128` (tests) keeps the 128-column tiles
+        # 128, or 64 / 32 on a small grid: the library says which; `part_cols=128` (tests) keeps the 128-column tiles
         pc = part_cols or lib.st2_conv1d_xs_part_cols(C.byref(d))
         nt = (L_out + pc - 1) // pc
         part = new_part(B, C_out, nt, out.device)
@@ -509,14 +529,18 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     _chk(x, "x", 3)
     B, C_in, L_in = x.shape
     split = isinstance(wt, SplitConvWeight)
-    if (split and pad_left <= XS_HALO and L_in >= XS_MIN_L and (pro != PRO_NONE or C_in >= XS_MIN_C_PLAIN)
-            and conv_path() == "xs" and not prefer_fused(pro, C_in, ks)):
+    if L_out is None:
+        L_out = L_in
+    p = None  # the exact-fp32 kernel has one route and no workspace
+    if split:  # refuses gb_seg (per-segment affine of a token-merged view) on the fused route
+        p = conv_plan(B, C_in, C_out, L_in, L_out, ks, pad_left, pro, want_stats, gb_seg)
+    if p is not None and p.route == _lib.CONV_ROUTE_XS:
         xs = activate(x, pro=pro, slope=slope, stats=stats, gamma=gamma, beta=beta,
-                      gamma_plus_one=gamma_plus_one, alpha=alpha, gb_seg=gb_seg, x_scale=x_scale, lengths=x_len)
+                      gamma_plus_one=gamma_plus_one, alpha=alpha, gb_seg=gb_seg, x_scale=x_scale, lengths=x_len, _plan=p)
         return conv1d_xs(xs, wt, C_out, ks, dil=dil, pad_left=pad_left, L_out=L_out, bias=bias, out=out, res=res,
                          res_shift=res_shift, res2=res2, div=div, act=act, act_split=act_split, act_slope=act_slope,
-                         want_stats=want_stats, y_len=y_len)
-    if gb_seg:
+                         want_stats=want_stats, part_cols=p.part_cols, y_len=y_len)
+    if gb_seg:  # exact-fp32 weights (the plan has refused it for split ones)
         raise _lib.St2Error("gb_seg (per-segment affine of a token-merged view) exists on the st2_act_split + "
                             "st2_conv1d_xs path only; this call routes to the fused kernel")
     if split:
@@ -526,8 +550,6 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
         if wt.shape[0] != C_in * ks or not wt.is_contiguous():
             raise _lib.St2Error("packed weight has shape %s, expected [%d, >=%d]" % (tuple(wt.shape), C_in * ks,
                                                                                       C_out))
-    if L_out is None:
-        L_out = L_in
     if out is None:
         out = torch.empty((B, C_out, L_out), device=x.device, dtype=torch.float32)
     _chk(out, "out", 3)
@@ -537,7 +559,7 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     d.x, d.x_bs, d.x_cs = x.data_ptr(), x.stride(0), x.stride(1)
     if split:
         d.wq, d.wq_co_pad, d.wq_cin_pad = wt.wq.data_ptr(), wt.co_pad, wt.cin_pad
-        d.x_scale = float(x_scale) if x_scale else x_scale_for(pro)
+        d.x_scale = float(x_scale) if x_scale else p.x_scale
         d.out_scale, d.w_row_scale = 1.0 / d.x_scale, wt.row_scale.data_ptr()
         fn, fname = lib.st2_conv1d_f16s, "st2_conv1d_f16s"
     else:
@@ -557,18 +579,15 @@ def conv1d(x, wt, C_out, ks, *, dil=1, pad_left=0, L_out=None, bias=None, out=No
     _fill_epilogue(d, B, C_out, L_out, res, res_shift, res2, div, act, act_split, act_slope)
     ws = part = None
     if split and want_stats:  # InstanceNorm statistics of the output from the epilogue's per-tile partial sums
-        nt = (L_out + 127) // 128
-        part = new_part(B, C_out, nt, out.device)
-        d.part, d.part_nt = part.data_ptr(), nt
-    elif split:  # skinny layers (few workgroups, long k loop) run split-K: the library says how much workspace it wants
-        nb = lib.st2_conv1d_f16s_splitk_bytes(C.byref(d))
-        if nb > 0:
-            ws = torch.empty((nb,), device=x.device, dtype=torch.uint8)  # caching allocator: stream- and capture-safe
-            d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), nb
+        part = torch.empty((p.part_floats,), device=out.device, dtype=torch.float32)
+        d.part, d.part_nt = part.data_ptr(), p.part_nt
+    elif split and p.splitk_bytes > 0:  # skinny layers (few workgroups, long k loop) run split-K inside this workspace
+        ws = torch.empty((p.splitk_bytes,), device=x.device, dtype=torch.uint8)  # caching allocator: stream- and capture-safe
+        d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), p.splitk_bytes
     _launch_conv(fn, fname, d)
     if want_stats:
         if part is not None:
-            return out, stats_finalize(part, B, C_out, nt, L_out, lengths=y_len, len_div=C_out)
+            return out, stats_finalize(part, B, C_out, p.part_nt, L_out, cols=p.part_cols, lengths=y_len, len_div=C_out)
         return out, instnorm_stats(out, lengths=y_len)
     return out
 
@@ -651,9 +670,6 @@ def style_fc(s, wt, bias, act=ACT_NONE, out=None):
     return out
 
 
-CVT_TILE = 1024  # positions per st2_convt_interleave tile (= per entry of its partial-sum output)
-
-
 def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, reflect_left=False, out=None,
                      want_stats=False, q_len=None, out_len=None):
     """`st2_convt_interleave[_stats]`; with want_stats returns (out, InstanceNorm statistics of out [B, C_out, 2]) from
@@ -676,15 +692,16 @@ def convt_interleave(phases, C_out, stride, pad, L_raw, bias=None, add=None, ref
         assert add.shape == (B, C_out, L_out), (add.shape, (B, C_out, L_out))
     a_bs, a_cs = (add.stride(0), add.stride(1)) if add is not None else (0, 0)
     part, nt = None, 0
+    tile = lib.st2_convt_interleave_part_cols()  # positions per tile = per entry of the partial-sum output
     if want_stats:
-        nt = (L_out + CVT_TILE - 1) // CVT_TILE
+        nt = (L_out + tile - 1) // tile
         part = new_part(B, C_out, nt, phases.device)
     _lib.check(lib.st2_convt_interleave_stats_len(phases.data_ptr(), phases.stride(0), phases.stride(1), Lq, _ptr(bias),
                                                   _ptr(add), a_bs, a_cs, out.data_ptr(), out.stride(0), out.stride(1), B,
                                                   C_out, stride, pad, L_raw, 1 if reflect_left else 0, _ptr(part), nt,
                                                   qlp, olp, _stream()), "st2_convt_interleave_stats_len")
     if want_stats:
-        return out, stats_finalize(part, B, C_out, nt, L_out, cols=CVT_TILE, lengths=out_len, len_div=C_out)
+        return out, stats_finalize(part, B, C_out, nt, L_out, cols=tile, lengths=out_len, len_div=C_out)
     return out
 
 

@@ -179,15 +179,42 @@ def test_splitk_workspace_query_is_a_function_of_the_geometry():
 
 
 def test_conv_routing_rule_is_the_same_in_both_plans():
-    """ops.prefer_fused (Python plans) and conv() in csrc/st2_engine.hip (C++ plans) must route a layer to the same
-    kernel, or the plans stop being bitwise equal: the constants are compared at the source level."""
+    """ops.conv1d (Python plans) and conv() in csrc/st2_engine.hip (C++ plans) must route, scale and size a layer the same way,
+    or the plans stop being bitwise equal.  Both ask st2_conv_launch_plan, the one statement of the rule: over a grid that
+    brackets every threshold, every field of its answer equals tests/golden/conv_launch_plan.json, recorded from the two
+    statements it replaces (the ops.py rule and the st2_conv1d_xs_part_cols / st2_conv1d_f16s_splitk_bytes queries of the
+    commit before), and a per-segment affine is refused exactly on the fused route."""
+    import itertools
+    import json
     from styletts2_amd import ops
-    src = open(os.path.join(ROOT, "styletts2_amd", "csrc", "st2_engine.hip")).read()
-    m = re.search(r"FUSED_MAX_C = (\d+), FUSED_K3_MAX_C = (\d+)", src)
-    assert m and (int(m.group(1)), int(m.group(2))) == (ops.FUSED_MAX_C, ops.FUSED_K3_MAX_C)
-    m = re.search(r"XS_MIN_L = (\d+)", src)
-    assert m and int(m.group(1)) == ops.XS_MIN_L
-    m = re.search(r"XS_MIN_C_PLAIN = (\d+)", src)
-    assert m and int(m.group(1)) == ops.XS_MIN_C_PLAIN
+    with open(os.path.join(ROOT, "tests", "golden", "conv_launch_plan.json")) as f:
+        gold = json.load(f)
+    grid = gold["grid"]
+    assert grid == {"L_in": [255, 256], "C_in": [32, 63, 64, 65, 128, 129], "ks": [1, 3, 7],
+                    "pro": [ops.PRO_NONE, ops.PRO_LEAKY, ops.PRO_ADAIN_SNAKE, ops.PRO_COLNORM], "pad_left": [0, 32, 33],
+                    "want_stats": [0, 1], "B": [1, 32], "force_fused": [0, 1]}
+    cases = list(itertools.product(*grid.values()))
+    assert len(cases) == len(gold["rows"]) == 3456
+    assert sorted(gold["fields"]) == sorted(n for n, _ in _lib.ConvPlan._fields_), "the table must cover every field of the plan"
+    routes = set()
+    for (L_in, C_in, ks, pro, pad_left, want_stats, B, force), want in zip(cases, gold["rows"]):
+        kw = dict(B=B, C_in=C_in, C_out=gold["C_out"], L_in=L_in, L_out=L_in, ks=ks, pad_left=pad_left, pro=pro,
+                  want_stats=want_stats, force_fused=force)
+        p = ops.conv_plan(**kw)
+        assert [getattr(p, n) for n in gold["fields"]] == want, (kw, dict(zip(gold["fields"], want)))
+        if p.route == _lib.CONV_ROUTE_XS:
+            assert ops.conv_plan(gb_seg=7, **kw).part_nt == p.part_nt
+        else:
+            with pytest.raises(_lib.St2Error, match="gb_seg"):
+                ops.conv_plan(gb_seg=7, **kw)
+        routes.add((p.route, p.part_cols, p.splitk_bytes > 0))
+    # both routes, with and without statistics, a narrow-tile slot and a split-K workspace all occur on the grid
+    assert routes >= {(0, 0, False), (0, 128, False), (0, 32, False), (1, 0, False), (1, 128, False), (1, 0, True)}, routes
     assert ops.prefer_fused(ops.PRO_ADAIN_SNAKE, 64, 11) and ops.prefer_fused(ops.PRO_ADAIN_SNAKE, 128, 3)
     assert not ops.prefer_fused(ops.PRO_ADAIN_SNAKE, 128, 7) and not ops.prefer_fused(ops.PRO_NONE, 32, 3)
+    # the sampler's token-merge decision (csrc/st2_plan_sampler.inc and diffusion.py ask the same question)
+    seg = [int(ops.token_merge_takes_xs(Fz, 192, cols)) for Fz, cols in itertools.product(*gold["seg_grid"].values())]
+    assert gold["seg_grid"] == {"Fz": [128, 129, 512], "cols": [255, 256]} and seg == gold["seg"]
+    # the names tests and tools read are reads of the library
+    assert (ops.XS_HALO, ops.XS_MIN_L, ops.CVT_TILE) == (32, 256, 1024) and ops.xs_row_slots(300) == 32 + 512 + 96
+    assert ops.x_scale_for(ops.PRO_COLNORM) == 8.0 and ops.x_scale_for(ops.PRO_SNAKE) == 1.0

@@ -8,7 +8,7 @@ import torch
 
 from _util import make_conv_case, rel_err
 from oracle import ops_ref as R
-from styletts2_amd import _hooks, ops, weights
+from styletts2_amd import _hooks, _lib, ops, weights
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -91,6 +91,43 @@ def test_conv1d_matches_contract(case, kernel, monkeypatch):
     e64 = rel_err(out, exact)
     assert e64 < 3e-6, "rel err vs fp64 %g" % e64
     assert ops.status() == 0, "benign inputs must not raise a device-side status bit"
+
+
+ROUTE_PAIRS = {  # two layers either side of each threshold of the launch rule (include/st2.h st2_conv_launch_plan): (C_in, L, ks, pro, pad_left)
+    "L_in_255_256": [(128, 255, 7, R.PRO_ADAIN_SNAKE, 3), (128, 256, 7, R.PRO_ADAIN_SNAKE, 3)],
+    "C_in_64_65_k7_prologue": [(64, 256, 7, R.PRO_ADAIN_SNAKE, 3), (65, 256, 7, R.PRO_ADAIN_SNAKE, 3)],
+    "C_in_128_129_k3": [(128, 256, 3, R.PRO_ADAIN_LEAKY, 1), (129, 256, 3, R.PRO_ADAIN_LEAKY, 1)],
+    "C_in_63_64_no_prologue": [(63, 256, 3, R.PRO_NONE, 1), (64, 256, 3, R.PRO_NONE, 1)],
+    "pad_left_32_33": [(128, 256, 7, R.PRO_LEAKY, 32), (128, 256, 7, R.PRO_LEAKY, 33)],
+}
+
+
+@pytest.mark.parametrize("pair", sorted(ROUTE_PAIRS))
+def test_conv1d_issues_what_the_launch_plan_names(pair):
+    """Either side of every threshold of the launch rule, ops.conv1d(want_stats=True) is bitwise -- output and statistics -- the
+    call routed by hand to what `ops.conv_plan` names: activate + conv1d_xs, or the same call under conv_path="fused".  The two
+    layers of a pair take different routes."""
+    B, C_out = 2, 32
+    routes = []
+    for C_in, L, ks, pro, pad_left in ROUTE_PAIRS[pair]:
+        x, w, kw = make_conv_case(seed=77, B=B, C_in=C_in, C_out=C_out, L=L, ks=ks, dil=1, pro=pro, pad_left=pad_left, res=True)
+        wt = weights.pack_conv_f16s(w).to(DEV)
+        kwg = {k: (g(v) if torch.is_tensor(v) else v) for k, v in kw.items()}
+        out, st = ops.conv1d(g(x), wt, C_out, ks, want_stats=True, **kwg)
+        p = ops.conv_plan(B, C_in, C_out, L, L, ks, pad_left, pro, want_stats=True)
+        routes.append(p.route)
+        if p.route == _lib.CONV_ROUTE_XS:
+            PRO_KEYS = ("pro", "slope", "stats", "gamma", "beta", "alpha")
+            xs = ops.activate(g(x), **{k: v for k, v in kwg.items() if k in PRO_KEYS})
+            assert (xs.cg, xs.Lp, xs.halo, xs.x_scale) == (p.xs_cg, p.xs_lp, p.xs_halo, p.x_scale)
+            hand, st_hand = ops.conv1d_xs(xs, wt, C_out, ks, want_stats=True, **{k: v for k, v in kwg.items() if k not in PRO_KEYS})
+        else:
+            with _hooks.override(conv_path="fused"):
+                hand, st_hand = ops.conv1d(g(x), wt, C_out, ks, want_stats=True, **kwg)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all()) and torch.equal(out, hand) and torch.equal(st, st_hand), (pair, C_in, L, pad_left)
+    assert sorted(routes) == [_lib.CONV_ROUTE_XS, _lib.CONV_ROUTE_FUSED], (pair, routes)
+    assert ops.status() == 0
 
 
 WS_CASES = [
