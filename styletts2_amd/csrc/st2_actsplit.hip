@@ -8,7 +8,7 @@
 // The per-channel parameters (mean, rstd, gamma, beta, alpha) are wave-uniform and come through the scalar cache.
 // Zero padding of the conv (halo columns, the tail up to Lp, channel padding) is materialised here, AFTER the
 // activation as F.conv1d pads the activated tensor, so the MFMA kernel never tests a boundary.
-// Arithmetic is op for op that of the fused prologue in st2_conv1d_f16s.hip (same helpers, st2_act.h).
+// The arithmetic is st2_prologue + st2_split_f16 (st2_act.h), the functions the fused convs' prologues call.
 #include "st2_common.h"
 #include "st2_act.h"
 #include <algorithm>
@@ -71,42 +71,29 @@ __global__ __launch_bounds__(256) void act_split_kernel(const ActArgs a) {
   for (int e = 0; e < 8; ++e) {
     const int ci = cg * 8 + e;
     const int cc = min(ci, a.C - 1);  // wave-uniform -> scalar loads
-    float u = v[e];
-    if constexpr (PRO == ST2_PRO_LEAKY) {
-      u = leaky(u, a.slope);
-    } else if constexpr (PRO == ST2_PRO_ADAIN_LEAKY || PRO == ST2_PRO_ADAIN_SNAKE) {
+    st2_chan_par<float> p = ST2_CHAN_PAR_FILL;  // this channel's parameters, in registers (no table: one position per thread)
+    if constexpr (st2_pro_is_adain(PRO)) {
       const float* st = a.stats + ((int64_t)b * a.C + cc) * 2;
-      const float g = 1.0f + a.gamma[(int64_t)b * a.gb_bs + cc];
-      const float bt = a.beta[(int64_t)b * a.gb_bs + cc];
-      float w = (u - st[0]) * st[1];
-      w = g * w + bt;
-      if constexpr (PRO == ST2_PRO_ADAIN_LEAKY) {
-        u = leaky(w, a.slope);
-      } else {
-        const float al = a.alpha[cc];
-        u = snake(w, al, 1.0f / al);
-      }
-    } else if constexpr (PRO == ST2_PRO_SNAKE) {
-      const float al = a.alpha[cc];
-      u = snake(u, al, 1.0f / al);
+      p.g = 1.0f + a.gamma[(int64_t)b * a.gb_bs + cc];
+      p.beta = a.beta[(int64_t)b * a.gb_bs + cc];
+      p.mean = st[0];
+      p.rstd = st[1];
     } else if constexpr (PRO == ST2_PRO_COLNORM) {
       // affine row: the batch item (wave-uniform, scalar loads) or -- token-merged view of several utterances -- the
       // utterance this position belongs to (per lane; the rows are a few KB and L2 / L1 resident)
       const int64_t row = a.gb_seg > 0 ? (int64_t)(lc / a.gb_seg) : (int64_t)b;
       const float g0 = a.gamma[row * a.gb_bs + cc];
-      const float g = a.gamma_plus_one ? 1.0f + g0 : g0;
-      const float bt = a.beta[row * a.gb_bs + cc];
-      const float w = (u - cmean) * crstd;
-      u = w * g + bt;
+      p.g = a.gamma_plus_one ? 1.0f + g0 : g0;
+      p.beta = a.beta[row * a.gb_bs + cc];
     }
+    float u = st2_pro_affine<PRO>(v[e], p, cmean, crstd);
+    if constexpr (st2_pro_has_snake(PRO)) {
+      p.alpha = a.alpha[cc];
+      p.inv_alpha = 1.0f / p.alpha;
+    }
+    u = st2_pro_activation<PRO>(u, p, a.slope);
     u = (lok && ci < a.C) ? u * a.x_scale : 0.f;
-    // saturate to the f16 range instead of overflowing to inf (hi) / NaN (lo = u - inf): the conv then stays finite
-    // and the condition is reported through the sticky status word (so is a NaN operand, which becomes -65504)
-    const float uc = st2_clamp_f16(u);
-    sat |= uc != u;
-    const _Float16 h = (_Float16)uc;
-    hi[e] = h;
-    lo[e] = (_Float16)(uc - (float)h);
+    st2_split_f16(u, hi, lo, e, sat);  // reported through the sticky status word
   }
   if (__any(sat) && (threadIdx.x & 63) == 0) st2_raise_status(a.status, ST2_STATUS_F16_RANGE);
   const int64_t plane = (int64_t)a.xs_cg * a.Lp;
@@ -243,11 +230,6 @@ void headroom_record(int kind, const ActArgs& a, int B, hipStream_t s) {
   g_hr.push_back({kind, 0, B, a.C, a.L, a.x_scale, t_site_engine, t_site});
 }
 
-template <int PRO>
-void launch_act(const ActArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL((act_split_kernel<PRO>), dim3(st2_cdiv(a.Lp, 256), a.xs_cg, B), dim3(256), 0, s, a);
-}
-
 }  // namespace
 
 extern "C" int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L, int32_t pro,
@@ -268,9 +250,8 @@ extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int
   ST2_REQUIRE(halo >= 0 && Lp >= L + halo, "st2_act_split: Lp=%d too small for L=%d + halo=%d", Lp, L, halo);
   ST2_REQUIRE((reinterpret_cast<uintptr_t>(xs) & 15) == 0, "st2_act_split: xs must be 16-byte aligned");
   ST2_REQUIRE(pro >= ST2_PRO_NONE && pro <= ST2_PRO_COLNORM, "st2_act_split: prologue %d not supported", pro);
-  if (pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_COLNORM)
-    ST2_REQUIRE(stats && gamma && beta, "st2_act_split: prologue %d needs stats/gamma/beta", pro);
-  if (pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE) ST2_REQUIRE(alpha, "st2_act_split: snake needs alpha");
+  if (st2_pro_needs_stats(pro)) ST2_REQUIRE(stats && gamma && beta, "st2_act_split: prologue %d needs stats/gamma/beta", pro);
+  if (st2_pro_has_snake(pro)) ST2_REQUIRE(alpha, "st2_act_split: snake needs alpha");
   ST2_REQUIRE(x_scale > 0.f, "st2_act_split: x_scale must be set");
   ST2_REQUIRE(gb_seg >= 0 && (gb_seg == 0 || pro == ST2_PRO_COLNORM), "st2_act_split: gb_seg=%d is for ST2_PRO_COLNORM", gb_seg);
   ActArgs a;
@@ -282,14 +263,9 @@ extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int
   ST2_REQUIRE(!len || pro != ST2_PRO_COLNORM, "st2_act_split_len: per-row lengths are not defined for ST2_PRO_COLNORM");
   a.status = st2_status_device_ptr();
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (pro) {
-    case ST2_PRO_LEAKY: launch_act<ST2_PRO_LEAKY>(a, B, s); break;
-    case ST2_PRO_ADAIN_LEAKY: launch_act<ST2_PRO_ADAIN_LEAKY>(a, B, s); break;
-    case ST2_PRO_ADAIN_SNAKE: launch_act<ST2_PRO_ADAIN_SNAKE>(a, B, s); break;
-    case ST2_PRO_SNAKE: launch_act<ST2_PRO_SNAKE>(a, B, s); break;
-    case ST2_PRO_COLNORM: launch_act<ST2_PRO_COLNORM>(a, B, s); break;
-    default: launch_act<ST2_PRO_NONE>(a, B, s); break;
-  }
+  st2_dispatch_pro(pro, [&](auto tag) {
+    hipLaunchKernelGGL((act_split_kernel<decltype(tag)::value>), dim3(st2_cdiv(a.Lp, 256), a.xs_cg, B), dim3(256), 0, s, a);
+  });
   ST2_CHECK_LAUNCH("st2_act_split");
   if (g_headroom) {
     headroom_record(0, a, B, s);

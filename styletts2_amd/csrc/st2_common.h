@@ -45,6 +45,33 @@ __device__ __forceinline__ void st2_raise_status(int* status, int bit) {
 
 static inline int st2_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// What a conv prologue (ST2_PRO_*, st2.h) is made of and reads besides x: the one statement of it for every kernel and every
+// entry check.  (Plain chains in the order the kernels have always tested them: composing them changes the compare sequence the
+// compiler emits for a run-time `pro`.)
+#define ST2_PRO_PREDICATE static __host__ __device__ __forceinline__ constexpr bool
+ST2_PRO_PREDICATE st2_pro_is_adain(int pro) { return pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE; }
+ST2_PRO_PREDICATE st2_pro_has_leaky(int pro) { return pro == ST2_PRO_LEAKY || pro == ST2_PRO_ADAIN_LEAKY; }
+ST2_PRO_PREDICATE st2_pro_has_snake(int pro) { return pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE; }  // reads alpha
+ST2_PRO_PREDICATE st2_pro_needs_stats(int pro) {  // and gamma, beta
+  return pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_COLNORM;
+}
+ST2_PRO_PREDICATE st2_pro_has_table(int pro) {  // per-channel parameters
+  return pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE || pro == ST2_PRO_COLNORM;
+}
+
+// st2_conv1d_f16s: what its one-role launch and its warp-specialised launch both require of the LDS tile (`smem` bytes), of the
+// packed weight (C_pad input channels, blocks of BM output channels) and of the partial-sum buffer.
+static inline int st2_f16s_check_launch(const st2_conv_desc& d, int KS, int BM, int C_pad, size_t smem) {
+  ST2_REQUIRE(smem <= 160 * 1024, "st2_conv1d_f16s: tile needs %zu B of LDS (ks=%d dil=%d C_in=%d)", smem, KS, d.dil, d.C_in);
+  ST2_REQUIRE(d.wq_cin_pad == C_pad, "st2_conv1d_f16s: packed weight has %d input channels, kernel needs %d", d.wq_cin_pad,
+              C_pad);
+  ST2_REQUIRE(d.wq_co_pad % BM == 0 && d.wq_co_pad >= d.C_out, "st2_conv1d_f16s: wq_co_pad=%d must be a multiple of %d "
+              "covering C_out=%d", d.wq_co_pad, BM, d.C_out);
+  if (d.part) ST2_REQUIRE(d.part_nt >= st2_cdiv(d.L_out, 128), "st2_conv1d_f16s: part_nt=%d < %d tiles", d.part_nt,
+                          st2_cdiv(d.L_out, 128));
+  return 0;
+}
+
 // hipFuncSetAttribute (dynamic LDS above 64 KB) is a PER-DEVICE setting: every launcher keeps one bit per device ordinal
 // and kernel instantiation, so that a process driving several GPUs sets it on each of them (advisor, round 3).  The bit is
 // published only AFTER `set_attr` has returned (advisor, round 4): a second thread that finds it clear sets the attribute

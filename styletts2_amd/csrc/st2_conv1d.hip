@@ -86,7 +86,7 @@ __global__ __launch_bounds__(NT) void conv1d_mfma_kernel(const st2_conv_desc d) 
       const bool rowok = ci < d.C_in;
       RowPar p = {0.f, 1.f, 1.f, 0.f, 1.f, 1.f};
       if (rowok) {
-        if (pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE) {
+        if (st2_pro_is_adain(pro)) {
           const float* st = d.stats + ((int64_t)b * d.C_in + ci) * 2;
           p.mean = st[0];
           p.rstd = st[1];
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(NT) void conv1d_mfma_kernel(const st2_conv_desc d) 
           p.g = d.gamma_plus_one ? 1.0f + g : g;
           p.beta = d.beta[(int64_t)b * d.gb_bs + ci];
         }
-        if (pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE) {
+        if (st2_pro_has_snake(pro)) {
           p.alpha = d.alpha[ci];
           p.inv_alpha = 1.0f / p.alpha;
         }
@@ -249,10 +249,9 @@ extern "C" int st2_conv1d(const st2_conv_desc* dp, void* stream) {
   ST2_REQUIRE((reinterpret_cast<uintptr_t>(d.wt) & 15) == 0, "st2_conv1d: wt must be 16-byte aligned");
   ST2_REQUIRE(d.dil >= 1 && d.dil <= 8, "st2_conv1d: dil=%d out of range", d.dil);
   ST2_REQUIRE(d.pro >= ST2_PRO_NONE && d.pro <= ST2_PRO_COLNORM, "st2_conv1d: bad prologue %d", d.pro);
-  if (d.pro == ST2_PRO_ADAIN_LEAKY || d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_COLNORM)
+  if (st2_pro_needs_stats(d.pro))
     ST2_REQUIRE(d.stats && d.gamma && d.beta, "st2_conv1d: prologue %d needs stats/gamma/beta", d.pro);
-  if (d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_SNAKE)
-    ST2_REQUIRE(d.alpha, "st2_conv1d: snake prologue needs alpha");
+  if (st2_pro_has_snake(d.pro)) ST2_REQUIRE(d.alpha, "st2_conv1d: snake prologue needs alpha");
   ST2_REQUIRE(d.res_shift >= 0 && d.res_shift <= 1, "st2_conv1d: res_shift must be 0 or 1");
   ST2_REQUIRE(d.B <= 65535 && st2_cdiv(d.C_out, BM) <= 65535, "st2_conv1d: grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -47,10 +47,9 @@ extern "C" int st2_conv1d_f16s(const st2_conv_desc* dp, void* stream) {
   ST2_REQUIRE((reinterpret_cast<uintptr_t>(d.wq) & 15) == 0, "st2_conv1d_f16s: wq must be 16-byte aligned");
   ST2_REQUIRE(d.dil >= 1 && d.dil <= 8, "st2_conv1d_f16s: dil=%d out of range", d.dil);
   ST2_REQUIRE(d.pro >= ST2_PRO_NONE && d.pro <= ST2_PRO_COLNORM, "st2_conv1d_f16s: prologue %d not supported", d.pro);
-  if (d.pro == ST2_PRO_ADAIN_LEAKY || d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_COLNORM)
+  if (st2_pro_needs_stats(d.pro))
     ST2_REQUIRE(d.stats && d.gamma && d.beta, "st2_conv1d_f16s: prologue %d needs stats/gamma/beta", d.pro);
-  if (d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_SNAKE)
-    ST2_REQUIRE(d.alpha, "st2_conv1d_f16s: snake prologue needs alpha");
+  if (st2_pro_has_snake(d.pro)) ST2_REQUIRE(d.alpha, "st2_conv1d_f16s: snake prologue needs alpha");
   ST2_REQUIRE(d.res_shift >= 0 && d.res_shift <= 1, "st2_conv1d_f16s: res_shift must be 0 or 1");
   ST2_REQUIRE(d.x_scale > 0.f && d.out_scale > 0.f, "st2_conv1d_f16s: x_scale / out_scale must be set");
   ST2_REQUIRE(d.B <= 65535, "st2_conv1d_f16s: grid too large");

@@ -40,36 +40,11 @@ namespace {
 
 constexpr int NT = 256;
 
-struct ChanPar {  // per input channel, staged once per workgroup in LDS (32 B); xs = x_scale, 0 for the channel tail of the last chunk
-  float mean, rstd, g, beta, alpha, inv_alpha, xs, pad1;
-};
-
-// The one-role kernel's table holds the parameters of channels (2i, 2i + 1) as PAIRS (64 B per pair: the same 32 B per channel), so that
-// its prologue runs the affine and the Snake polynomial as packed-f32 ops on two adjacent channels at once (round 6).  On one SIMD
-// the prologue's VALU time ADDS to the MFMA time (tools/mfma_valu_overlap.hip) and at C <= 64 it is as large; a v_pk_fma_f32 costs
-// ~1.27 x a v_fma_f32 and does the work of two.  Same IEEE operations in the same order per channel: results are bitwise those of
-// the scalar form (and of the warp-specialised build, which keeps it).  Plain encodings and low-half broadcasts only
-// (tools/check_isa.py: an op_sel on a packed-f32 op would be the gfx950 hazard of DESIGN.md section 9).
-typedef float st2_f2 __attribute__((ext_vector_type(2)));
-struct ChanPar2 {
-  st2_f2 mean, rstd, g, beta, alpha, inv_alpha, xs, pad1;
-};
-
-static __device__ __forceinline__ st2_f2 splat2(float c) { return st2_f2{c, c}; }
-// sin(x)^2 of st2_act.h's sin_sq, two lanes at a time: the same operations in the same order per component
-static __device__ __forceinline__ st2_f2 sin_sq2(st2_f2 x) {
-  const st2_f2 n = __builtin_elementwise_rint(x * splat2(0.3183098861837907f));
-  st2_f2 r = __builtin_elementwise_fma(n, splat2(-3.1415927410125732f), x);
-  r = __builtin_elementwise_fma(n, splat2(8.742277657347586e-08f), r);
-  const st2_f2 r2 = r * r;
-  st2_f2 p = splat2(2.6000539037340786e-06f);
-  p = __builtin_elementwise_fma(p, r2, splat2(-0.00019806614727713168f));
-  p = __builtin_elementwise_fma(p, r2, splat2(0.008333017118275166f));
-  p = __builtin_elementwise_fma(p, r2, splat2(-0.16666656732559204f));
-  const st2_f2 s = __builtin_elementwise_fma(r2 * r, p, r);
-  return s * s;
-}
-static __device__ __forceinline__ st2_f2 snake2(st2_f2 v, st2_f2 alpha, st2_f2 inv_alpha) { return v + inv_alpha * sin_sq2(alpha * v); }
+// The one-role kernel's table, staged once per workgroup in LDS, holds the parameters of channels (2i, 2i + 1) as PAIRS
+// (st2_chan_par<st2_f2>, st2_act.h), so that its prologue can run the affine and the Snake polynomial as packed-f32 ops on two
+// adjacent channels at once (round 6).  On one SIMD the prologue's VALU time ADDS to the MFMA time (tools/mfma_valu_overlap.hip) and
+// at C <= 64 it is as large; a v_pk_fma_f32 costs ~1.27 x a v_fma_f32 and does the work of two.  Both forms are instantiations of
+// st2_prologue: bitwise each other, and the warp-specialised build, which keeps the scalar one.
 
 template <int KS, int CI_T, int WM, int WN, int TN>
 #ifndef ST2_F16S_OCC
@@ -133,15 +108,15 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
   // LDS: [2 buffers][2 planes hi/lo][CG][XW] slots of 16 B, then the channel parameter table
   h8* xs = reinterpret_cast<h8*>(smem_raw);
   const int plane = CG * XW;  // slots per plane
+  typedef st2_chan_par<st2_f2> ChanPar2;
   ChanPar2* par2 = reinterpret_cast<ChanPar2*>(smem_raw + (size_t)4 * plane * 16);  // pair i = channels (2i, 2i + 1)
 
   const int pro = d.pro;
-  const bool has_par = pro == ST2_PRO_ADAIN_LEAKY || pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE ||
-                       pro == ST2_PRO_COLNORM;
   const int C_pad = (d.C_in + CI_T - 1) / CI_T * CI_T;
+  const bool has_par = st2_pro_has_table(pro);
   if (has_par) {
     for (int ci = tid; ci < C_pad; ci += NT) {
-      ChanPar p = {0.f, 1.f, 1.f, 0.f, 1.f, 1.f, 0.f, 0.f};
+      st2_chan_par<float> p = ST2_CHAN_PAR_FILL;
       if (ci < d.C_in) {
         p.xs = d.x_scale;
         if (pro == ST2_PRO_COLNORM) {  // per-channel affine of a LayerNorm over channels (statistics are per position)
@@ -155,7 +130,7 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
           p.g = 1.0f + d.gamma[(int64_t)b * d.gb_bs + ci];
           p.beta = d.beta[(int64_t)b * d.gb_bs + ci];
         }
-        if (pro == ST2_PRO_ADAIN_SNAKE || pro == ST2_PRO_SNAKE) {
+        if (st2_pro_has_snake(pro)) {
           p.alpha = d.alpha[ci];
           p.inv_alpha = 1.0f / p.alpha;
         }
@@ -203,7 +178,7 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
     // k = 7 0.924 -> 0.797 ms, k = 11 1.015 -> 0.924 with both; the 64-row layout moves by -5 ... 0 %, the 128-row k = 3 layers of the
     // default step by -6 ... +6 % (profiles/r06/r06w_probe_narrow.log): they keep one channel at a time
     constexpr bool PACK = WM == 1;
-    constexpr bool TABLE = PRO == ST2_PRO_ADAIN_LEAKY || PRO == ST2_PRO_ADAIN_SNAKE || PRO == ST2_PRO_SNAKE || PRO == ST2_PRO_COLNORM;
+    constexpr bool TABLE = st2_pro_has_table(PRO);
     ChanPar2 pr[4];
     if constexpr (TABLE && HOIST) {
 #pragma unroll
@@ -231,75 +206,26 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
       for (int ep = 0; ep < 4; ++ep) {  // channels (2 ep, 2 ep + 1) of this thread's group of 8, as one packed pair
         const int ci = c0 + sg * 8 + 2 * ep;
         st2_f2 v = st2_f2{xr[r][2 * ep], xr[r][2 * ep + 1]};
+        ChanPar2 p{};
+        if constexpr (TABLE) p = par_of(ep);
+        else p.xs = st2_splat<st2_f2>(d.x_scale);  // no table: the channel tail is zeroed below
         if constexpr (PACK) {
-          if constexpr (PRO == ST2_PRO_LEAKY) {
-            v = st2_f2{leaky(v.x, d.slope), leaky(v.y, d.slope)};
-          } else if constexpr (PRO == ST2_PRO_ADAIN_LEAKY) {
-            const ChanPar2 p = par_of(ep);
-            st2_f2 u = (v - p.mean) * p.rstd;
-            u = p.g * u + p.beta;
-            v = st2_f2{leaky(u.x, d.slope), leaky(u.y, d.slope)};
-          } else if constexpr (PRO == ST2_PRO_ADAIN_SNAKE) {
-            const ChanPar2 p = par_of(ep);
-            st2_f2 u = (v - p.mean) * p.rstd;
-            u = p.g * u + p.beta;
-            v = snake2(u, p.alpha, p.inv_alpha);
-          } else if constexpr (PRO == ST2_PRO_SNAKE) {
-            const ChanPar2 p = par_of(ep);
-            v = snake2(v, p.alpha, p.inv_alpha);
-          } else if constexpr (PRO == ST2_PRO_COLNORM) {
-            const ChanPar2 p = par_of(ep);
-            // per-position statistics stay scalar: splatting crstd -- the HIGH element of the (mean, rstd) pair its load returns --
-            // would be an op_sel'd packed op (tools/check_isa.py)
-            const st2_f2 u = st2_f2{(v.x - cmean) * crstd, (v.y - cmean) * crstd};
-            v = u * p.g + p.beta;
-          }
-          if constexpr (TABLE)
-            v = v * par_of(ep).xs;
-          else
-            v = v * splat2(d.x_scale);
+          v = st2_prologue<PRO>(v, p, d.slope, cmean, crstd) * p.xs;
         } else {  // one channel at a time (the 64- / 128-row layouts: the packed form is neutral to slower there, r06w)
-          [[maybe_unused]] ChanPar2 p;
-          if constexpr (TABLE) p = par_of(ep);
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
-            float w = v[c];
-            if constexpr (PRO == ST2_PRO_LEAKY) {
-              w = leaky(w, d.slope);
-            } else if constexpr (PRO == ST2_PRO_ADAIN_LEAKY) {
-              float u = (w - p.mean[c]) * p.rstd[c];
-              u = p.g[c] * u + p.beta[c];
-              w = leaky(u, d.slope);
-            } else if constexpr (PRO == ST2_PRO_ADAIN_SNAKE) {
-              float u = (w - p.mean[c]) * p.rstd[c];
-              u = p.g[c] * u + p.beta[c];
-              w = snake(u, p.alpha[c], p.inv_alpha[c]);
-            } else if constexpr (PRO == ST2_PRO_SNAKE) {
-              w = snake(w, p.alpha[c], p.inv_alpha[c]);
-            } else if constexpr (PRO == ST2_PRO_COLNORM) {
-              const float u = (w - cmean) * crstd;
-              w = u * p.g[c] + p.beta[c];
-            }
-            if constexpr (TABLE)
-              w = w * p.xs[c];
-            else
-              w = w * d.x_scale;
-            v[c] = w;
+            const st2_chan_par<float> q = {p.mean[c], p.rstd[c], p.g[c], p.beta[c], p.alpha[c], p.inv_alpha[c], p.xs[c], 0.f};
+            v[c] = st2_prologue<PRO>((float)v[c], q, d.slope, cmean, crstd) * q.xs;
           }
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          const int e = 2 * ep + c;
           float w = c ? v.y : v.x;
           if constexpr (TABLE)
             w = lok ? w : 0.f;
           else
             w = (lok && ci + c < d.C_in) ? w : 0.f;
-          const float vc = st2_clamp_f16(w);  // saturate instead of inf / NaN, reported via st2_status()
-          sat |= vc != w;
-          const _Float16 h = (_Float16)vc;
-          hi[e] = h;
-          lo[e] = (_Float16)(vc - (float)h);
+          st2_split_f16(w, hi, lo, 2 * ep + c, sat);  // reported via st2_status()
         }
       }
       if (sat) st2_raise_status(status, ST2_STATUS_F16_RANGE);
@@ -308,26 +234,7 @@ __global__ __launch_bounds__(NT, ST2_F16S_OCC) void conv1d_f16s_kernel(const st2
     }
   };
   auto store_chunk = [&](int c0, int buf) __attribute__((always_inline)) {
-    switch (pro) {
-      case ST2_PRO_LEAKY:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_LEAKY>{});
-        break;
-      case ST2_PRO_ADAIN_LEAKY:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_ADAIN_LEAKY>{});
-        break;
-      case ST2_PRO_ADAIN_SNAKE:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_ADAIN_SNAKE>{});
-        break;
-      case ST2_PRO_SNAKE:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_SNAKE>{});
-        break;
-      case ST2_PRO_COLNORM:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_COLNORM>{});
-        break;
-      default:
-        store_chunk_as(c0, buf, std::integral_constant<int, ST2_PRO_NONE>{});
-        break;
-    }
+    st2_dispatch_pro(pro, [&](auto pro_tag) __attribute__((always_inline)) { store_chunk_as(c0, buf, pro_tag); });
   };
 
   f32x16 acc[TN];
@@ -510,22 +417,13 @@ int launch(const st2_conv_desc& d, hipStream_t s) {
   constexpr int BN = 32 * TN * WN;
   const int XW = BN + (KS - 1) * d.dil;
   const int C_pad = (d.C_in + CI_T - 1) / CI_T * CI_T;
-  const bool has_par = d.pro == ST2_PRO_ADAIN_LEAKY || d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_SNAKE ||
-                       d.pro == ST2_PRO_COLNORM;
-  const size_t smem = (size_t)4 * (CI_T / 8) * XW * 16 + (has_par ? (size_t)C_pad * 32 : 0);
-  ST2_REQUIRE(smem <= 160 * 1024, "st2_conv1d_f16s: tile needs %zu B of LDS (ks=%d dil=%d C_in=%d)", smem, KS,
-              d.dil, d.C_in);
-  ST2_REQUIRE(d.wq_cin_pad == C_pad, "st2_conv1d_f16s: packed weight has %d input channels, kernel needs %d",
-              d.wq_cin_pad, C_pad);
-  ST2_REQUIRE(d.wq_co_pad % BM == 0 && d.wq_co_pad >= d.C_out, "st2_conv1d_f16s: wq_co_pad=%d must be a multiple "
-              "of %d covering C_out=%d", d.wq_co_pad, BM, d.C_out);
+  const size_t smem = (size_t)4 * (CI_T / 8) * XW * 16 + (st2_pro_has_table(d.pro) ? (size_t)C_pad * 32 : 0);
+  if (st2_f16s_check_launch(d, KS, BM, C_pad, smem) != 0) return 1;
   static std::atomic<uint64_t> attr_done{0};  // one bit per device ordinal
   st2_once_per_device(attr_done, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_f16s_kernel<KS, CI_T, WM, WN, TN>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
-  if (d.part) ST2_REQUIRE(d.part_nt >= st2_cdiv(d.L_out, 128), "st2_conv1d_f16s: part_nt=%d < %d tiles", d.part_nt,
-                          st2_cdiv(d.L_out, 128));
   const int ksplit = d.part ? 1 : pick_ksplit(d);  // the reduction kernel does not emit statistics
   ST2_REQUIRE((int64_t)d.B * ksplit <= 65535, "st2_conv1d_f16s: grid too large");
   // rows beyond C_out inside the last co block are computed on zero weights and not stored

@@ -3,8 +3,10 @@
 // AdaIN + Snake convs (C_out <= 64: the HiFi-GAN stages at L = 120 000 / 240 000).
 //
 // One 512-thread workgroup per CU walks a contiguous range of tiles; its waves have fixed roles, one pair per SIMD:
-//   waves 0-3  consumers: LDS fragments + weight fragments -> MFMA (the k loop of conv1d_f16s_kernel, verbatim), epilogue;
-//   waves 4-7  producers: global loads two chunks ahead (two named register sets), prologue + hi/lo split one chunk ahead
+//   waves 0-3  consumers: LDS fragments + weight fragments -> MFMA (the MFMA sequence of conv1d_f16s_kernel's k loop; the weight
+//              pointer advance and the ablation hooks are this kernel's own), the shared epilogue (st2_conv_epilogue.h);
+//   waves 4-7  producers: global loads two chunks ahead (two named register sets), prologue + hi/lo split (st2_prologue,
+//              st2_split_f16 of st2_act.h: the functions conv1d_f16s_kernel and st2_act_split call) one chunk ahead
 //              into the other LDS buffer -- across tile boundaries, so a tile's fill happens under its predecessor's k loop
 //              and epilogue.
 // Phases are separated by one workgroup barrier: a tile is nchunk MFMA phases + one epilogue phase; in every phase the
@@ -74,9 +76,7 @@ constexpr int NCT = 256;        // consumer threads (waves 0-3)
 constexpr int NPR = 256;        // producer threads (waves 4-7; eight producer waves: 3-5 % faster, 30-140 spilled VGPRs)
 constexpr int NTW = NCT + NPR;  // threads per workgroup
 
-struct ChanPar {  // per input channel, staged per batch item in LDS (32 B); xs = x_scale, 0 for the channel tail of the last chunk
-  float mean, rstd, g, beta, alpha, inv_alpha, xs, pad1;
-};
+typedef st2_chan_par<float> ChanPar;  // per input channel (st2_act.h), staged per batch item in LDS
 
 // a value every lane of the wave holds, moved to an SGPR
 static __device__ __forceinline__ float wave_uniform(float v) {
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(NTW, 2) void conv1d_f16s_ws_kernel(const st2_conv_d
     // chunk that needs this one is activated one barrier later at the earliest.
     auto table_update = [&]() __attribute__((always_inline)) {
       if (tp_b != tab_b) {  // workgroup-uniform
-        ChanPar p = {0.f, 1.f, 1.f, 0.f, 1.f, 1.f, 0.f, 0.f};
+        ChanPar p = ST2_CHAN_PAR_FILL;
         if (ptid < d.C_in) {
           p.mean = tp_mean;
           p.rstd = tp_rstd;
@@ -191,7 +191,8 @@ __global__ __launch_bounds__(NTW, 2) void conv1d_f16s_ws_kernel(const st2_conv_d
         ++lt;
       }
     };
-    // prologue + hi/lo split of set SET into buffer `buf`, op for op that of conv1d_f16s_kernel / st2_act_split
+    // prologue + hi/lo split of set SET into buffer `buf`: st2_prologue / st2_split_f16 (st2_act.h), as conv1d_f16s_kernel and
+    // st2_act_split call them
     auto activate_set = [&](auto set_tag, int buf) __attribute__((always_inline)) {
       constexpr int SET = decltype(set_tag)::value;
       const int c0 = q_c0[SET];
@@ -220,22 +221,14 @@ __global__ __launch_bounds__(NTW, 2) void conv1d_f16s_ws_kernel(const st2_conv_d
         for (int e = 0; e < 8; ++e) {
           const ChanPar p = cp[e];
           float v = xq[SET][r][e];
-          float u = (v - p.mean) * p.rstd;
-          u = p.g * u + p.beta;
           if constexpr (ST2_WS_ABLATE == 1)
             v = v + p.beta;
-          else if constexpr (PRO == ST2_PRO_ADAIN_LEAKY)
-            v = leaky(u, d.slope);
           else
-            v = snake(u, p.alpha, p.inv_alpha);
+            v = st2_prologue<PRO>(v, p, d.slope, 0.f, 1.f);
           // zero padding (and the channel tail, through the table's scale) is applied AFTER the activation, as F.conv1d pads
           // the activated tensor
           v = lok ? v * p.xs : 0.f;
-          const float vc = st2_clamp_f16(v);  // saturate instead of inf / NaN, reported via st2_status()
-          sat |= vc != v;
-          const _Float16 h = (_Float16)vc;
-          hi[e] = h;
-          lo[e] = (_Float16)(vc - (float)h);
+          st2_split_f16(v, hi, lo, e, sat);  // reported via st2_status()
         }
         dst[pos] = hi;
         dst[plane + pos] = lo;
@@ -401,13 +394,7 @@ int launch_ws(const st2_conv_desc& d, hipStream_t s) {
   const int XW = BN + (KS - 1) * d.dil;
   const int C_pad = (d.C_in + CI_T - 1) / CI_T * CI_T;
   const size_t smem = (size_t)4 * (CI_T / 8) * XW * 16 + (size_t)2 * C_pad * 32;
-  ST2_REQUIRE(smem <= 160 * 1024, "st2_conv1d_f16s: tile needs %zu B of LDS (ks=%d dil=%d C_in=%d)", smem, KS, d.dil, d.C_in);
-  ST2_REQUIRE(d.wq_cin_pad == C_pad, "st2_conv1d_f16s: packed weight has %d input channels, kernel needs %d", d.wq_cin_pad,
-              C_pad);
-  ST2_REQUIRE(d.wq_co_pad % BM == 0 && d.wq_co_pad >= d.C_out, "st2_conv1d_f16s: wq_co_pad=%d must be a multiple of %d "
-              "covering C_out=%d", d.wq_co_pad, BM, d.C_out);
-  if (d.part) ST2_REQUIRE(d.part_nt >= st2_cdiv(d.L_out, 128), "st2_conv1d_f16s: part_nt=%d < %d tiles", d.part_nt,
-                          st2_cdiv(d.L_out, 128));
+  if (st2_f16s_check_launch(d, KS, BM, C_pad, smem) != 0) return 1;
   ST2_REQUIRE(C_pad <= NPR, "st2_conv1d_f16s (warp-specialised): C_in=%d exceeds %d", d.C_in, NPR);
   // one workgroup per CU: the CU count and the kernel's LDS attribute are set up once per device (a process normally drives
   // one GPU, but nothing here may assume it: cf. the capacity cache of st2_lstm_coop.hip)

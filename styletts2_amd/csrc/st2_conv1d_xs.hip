@@ -307,7 +307,7 @@ extern "C" int st2_conv_launch_plan(const st2_conv_desc* dp, int32_t want_stats,
                                     st2_conv_plan* p) {
   ST2_REQUIRE(dp && p, "st2_conv_launch_plan: null descriptor or plan");
   const st2_conv_desc& d = *dp;
-  const bool norm = d.pro == ST2_PRO_ADAIN_LEAKY || d.pro == ST2_PRO_ADAIN_SNAKE || d.pro == ST2_PRO_COLNORM;
+  const bool norm = st2_pro_needs_stats(d.pro);
   const bool prefer_fused = d.pro != ST2_PRO_NONE && (d.C_in <= FUSED_MAX_C || (d.ks <= 3 && d.C_in <= FUSED_K3_MAX_C));
   const bool xs = !force_fused && d.pad_left <= XS_HALO && d.L_in >= XS_MIN_L &&
                   (d.pro != ST2_PRO_NONE || d.C_in >= XS_MIN_C_PLAIN) && !prefer_fused;

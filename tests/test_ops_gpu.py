@@ -190,6 +190,80 @@ def test_conv1d_f16s_warp_specialised_build_is_bitwise_the_one_role_kernel(B, C_
         assert rel_err(outs["ws"][0], ref) < 3e-6
 
 
+PROLOGUE_CASES = (
+    # (pro, C, ks, pad_left, saturate).  C = 24: the 32-row layout (packed, hoisted prologue), channel tail inside the only chunk;
+    # C = 40: the 64-row layout (one channel at a time), tail in the second chunk; C = 72: the 128-row layout, tail in the third
+    [(pro, C, 1, 0, False) for pro in (R.PRO_NONE, R.PRO_LEAKY, R.PRO_ADAIN_LEAKY, R.PRO_ADAIN_SNAKE, R.PRO_SNAKE, R.PRO_COLNORM)
+     for C in (24, 40, 72)]
+    + [(R.PRO_ADAIN_SNAKE, 24, 3, 1, False), (R.PRO_ADAIN_SNAKE, 40, 3, 1, False)]  # + the warp-specialised build, halo columns
+    + [(R.PRO_LEAKY, 24, 1, 0, True)])
+
+
+@pytest.mark.parametrize("pro,C,ks,pad_left,saturate", PROLOGUE_CASES)
+def test_prologues_agree_bitwise(pro, C, ks, pad_left, saturate):
+    """The split-f16 prologue (affine, activation, operand scale, zero padding, f16 clamp, hi/lo split) of st2_act_split, of the
+    one-role fused conv and of its warp-specialised build, compared ELEMENT FOR ELEMENT: through an identity weight (W[c, c, tap]
+    = 1 packs to hi = 2^13, lo = 0 and a power-of-two row scale) every output is exactly (hi_x + lo_x) / x_scale of the one operand
+    element under that tap -- hi + lo has at most 22 significant bits and every scale is a power of two, so no rounding hides a
+    difference.  B = 2 / L = 600 crosses the 512- / 256- / 128-column tiles and gives the warp-specialised kernel both of its
+    parameter-table slots."""
+    lib = _lib.load()
+    B, L = 2, 600
+    gen = torch.Generator().manual_seed(311)
+    x = torch.randn(B, C, L, generator=gen)
+    h = torch.randn(B, 2 * C, generator=gen) * 0.3
+    alpha = torch.rand(C, generator=gen) + 0.5
+    if saturate:
+        x[1, 5, 300] = 1.0e6
+        x[0, 17, 41] = float("nan")
+    xg = g(x)
+    kw = dict(pro=pro)
+    if pro in (R.PRO_LEAKY, R.PRO_ADAIN_LEAKY):
+        kw["slope"] = 0.2
+    if pro in (R.PRO_ADAIN_LEAKY, R.PRO_ADAIN_SNAKE, R.PRO_COLNORM):
+        kw.update(stats=ops.colnorm_stats(xg) if pro == R.PRO_COLNORM else ops.instnorm_stats(xg), gamma=g(h)[:, :C],
+                  beta=g(h)[:, C:])
+    if pro in (R.PRO_ADAIN_SNAKE, R.PRO_SNAKE):
+        kw["alpha"] = g(alpha)
+    ops.status(clear=True)
+
+    def routes(tap):
+        w = torch.zeros(C, C, ks)
+        w[torch.arange(C), torch.arange(C), tap] = 1.0
+        wt = weights.pack_conv_f16s(w).to(DEV)
+        outs = {}
+
+        def done(name, out):
+            torch.cuda.synchronize()
+            outs[name] = out
+            if saturate:
+                assert ops.status(clear=True) & _lib.STATUS_F16_RANGE, name
+
+        done("act_split", ops.conv1d_xs(ops.activate(xg, **kw), wt, C, ks, pad_left=pad_left))
+        try:
+            for name, variant in (("one_role", 1), ("ws", 2)):
+                if variant == 2 and not (pro == R.PRO_ADAIN_SNAKE and ks == 3):
+                    continue  # the warp-specialised build exists for AdaIN + Snake at k = 3 / 7 / 11
+                lib.st2_conv1d_f16s_set_variant(variant)
+                with _hooks.override(conv_path="fused"):
+                    done(name, ops.conv1d(xg, wt, C, ks, pad_left=pad_left, **kw))
+        finally:
+            lib.st2_conv1d_f16s_set_variant(0)
+        for name, out in outs.items():
+            assert torch.equal(out, outs["act_split"]), (name, (out != outs["act_split"]).sum().item())
+        return outs["act_split"]
+
+    out = routes(ks // 2)
+    assert saturate or bool(torch.isfinite(out).all())
+    assert float(out.min()) < float(out.max()), "a constant output compares nothing"
+    if saturate:
+        assert out[1, 5, 300].item() == 65504.0 and out[0, 17, 41].item() == -65504.0
+    if ks > 1:  # the one on tap 0: column 0 of the output is the halo column itself -- zeroed AFTER the activation on every route
+        first = routes(0)
+        assert bool((first[:, :, 0] == 0).all()) and torch.equal(first[:, :, 1:], out[:, :, :-1])
+    assert saturate or ops.status() == 0
+
+
 @pytest.mark.parametrize("B,C_in,C_out,L,ks,dil,res", [(2, 128, 128, 2500, 11, 5, True), (1, 256, 256, 515, 3, 1, False),
                                                        (2, 64, 64, 777, 7, 3, True), (1, 32, 22, 1300, 7, 1, False),
                                                        (2, 128, 128, 48001, 11, 1, True),
