@@ -623,6 +623,51 @@ int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, i
                        int32_t taps_per_phase, int32_t fmt /* st2_pcm_format */, const int32_t* gaps, int32_t gap_cap,
                        void* out, int64_t out_capacity, int64_t* offsets, void* stream);
 
+/* ---- loudness-normalised hand-over: BS.1770 level and per-row gain (added under ABI 23, additive: two kernel-level entry
+ * points and a size helper, no new backend-table slot, no struct change, no new sticky status bit) -- *
+ * st2_wave_level: per-row integrated loudness (ITU-R BS.1770-4) and sample peak of a ragged batch at the model rate, and the
+ * per-row linear gain that brings the row to a target loudness without passing a peak ceiling.
+ *  1. Valid samples.  Row b has x[0 .. n_b), n_b = max(0, samples_per_frame * f_b - trim), f_b = frames[b] clamped to 0..T_cap
+ *     (st2_wave_pack's rule); nothing of `wave` at or past n_b is read.  A non-finite sample counts as 0.
+ *  2. K-weighting: two biquads in cascade from zero state at x[0], in fp64 -- the high shelf and the high pass of BS.1770-4,
+ *     their coefficients derived on the host in double for `sample_rate` from the analog prototypes by the bilinear transform
+ *     (at 48 kHz the standard's table).
+ *  3. Blocks.  The hop is h = sample_rate / 10 samples; e_j = sum y^2 over hop j; block k covers four hops, z_k = (e_k + ... +
+ *     e_{k+3}) / (4 h), for every k with (k + 4) h <= n_b.  A row with n_b < 4 h has one block, the whole row: z_0 = sum y^2 / n_b;
+ *     a row with n_b = 0 has none.  l_k = -0.691 + 10 log10 z_k.
+ *  4. Gates.  Absolute: l_k > -70.  Relative: l_k > -0.691 + 10 log10(mean of z over the absolutely gated blocks) - 10.
+ *     L_b = -0.691 + 10 log10(mean of z over the blocks that pass both); -inf if none does.
+ *  5. Gain.  peak_b = max |x| over the valid, finite samples;  g_b = min(10^((target[b] - L_b) / 20), 10^(max_gain_db / 20),
+ *     ceiling / peak_b) in fp64, rounded once to fp32; exactly 1.0f where target[b] is NaN (the row is left alone), where
+ *     L_b = -inf or where peak_b = 0.
+ *  6. Report.  level[b] = {L_b, peak_b, g_b, number of blocks that passed both gates}, four fp32 values (level fp32 [B][4]).
+ * A lane of the measuring kernel starts its fp64 chain from zero state W = 4 ceil(0.032 sample_rate) samples early (or at the
+ * row's first sample, then exactly): a block's energy is off by at most 2 T peak_b / sqrt(z_k) relative, T = 1.2e-12 -- 7.0e-9
+ * for a block above the absolute gate of a row that peaks at full scale.  Sums are made in a fixed order without atomics: a
+ * row's four values depend neither on the tiling nor on the row's place in the batch, bit for bit.
+ * `workspace` (8-byte aligned, st2_wave_level_workspace_bytes(B, T_cap, samples_per_frame, sample_rate) bytes; 0 for an
+ * argument <= 0 or a rate that is no multiple of 10) holds the fp64 hop energies [B][ceil(samples_per_frame T_cap / h)] and the
+ * hops' peaks.  Two launches (hop energies and peaks; gates and gain), no allocation, no synchronisation, no host read: legal
+ * under stream capture.  Returns non-zero before any launch on: every geometry refusal of st2_wave_pack (NULL wave / frames,
+ * B <= 0 or > 65535, T_cap <= 0, samples_per_frame <= 0, trim < 0, w_bs too small); NULL target / level / workspace; a workspace
+ * that is too small or misaligned; sample_rate <= 0 or not a multiple of 10, or so high that a hop does not fit LDS; ceiling
+ * outside (0, 1]; max_gain_db outside [0, 60]; wave / target / level misaligned for float.
+ *
+ * st2_wave_pack_level: st2_wave_pack_gaps with the gain in its moves.  level == NULL: the call IS st2_wave_pack_gaps, its
+ * launches and its bytes.  Otherwise every valid input sample of row b becomes fl32(x * level[b][2]) -- one fp32 multiply as
+ * the sample is loaded, before anything else the move does -- so that the packed output is exactly what st2_wave_pack_gaps
+ * writes for the input fl32(x * g_b); gaps stay the format's silence code and sample counts do not change.  Returns non-zero
+ * before any launch on every refusal of st2_wave_pack_gaps and on a level misaligned for float. */
+int64_t st2_wave_level_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame, int32_t sample_rate);
+int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                   int32_t trim, int32_t sample_rate, const float* target /* fp32 [B], device */, double ceiling,
+                   double max_gain_db, float* level /* fp32 [B][4], device */, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+int st2_wave_pack_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                        int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                        int32_t taps_per_phase, int32_t fmt /* st2_pcm_format */, const int32_t* gaps, int32_t gap_cap,
+                        void* out, int64_t out_capacity, int64_t* offsets, void* stream, const float* level);
+
 /* ---- reference clips at a client's rate and in G.711 (added under ABI 23, additive: one kernel-level entry point and its
  * size helper, no new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
  * st2_clip_ingest: the way in of a zero-shot request.  src holds B rows of N_cap samples (row b at

@@ -268,6 +268,12 @@ _SIGNATURES = {
     "st2_wave_pack_gaps": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_void_p]),
+    "st2_wave_level_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "st2_wave_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                 C.c_double, C.c_double, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_wave_pack_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, f32p]),
     "st2_clip_ingest_work_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "st2_clip_ingest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
                                   C.c_int32, C.c_float, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

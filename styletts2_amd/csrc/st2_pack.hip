@@ -36,7 +36,8 @@ template <typename OUT, int V>
 __global__ __launch_bounds__(PACK_THREADS) void wave_pack_kernel(const float* __restrict__ wave, int64_t w_bs,
                                                                  const int32_t* __restrict__ frames, int B, int T_cap, int spf,
                                                                  int trim, OUT* __restrict__ out, long long out_capacity,
-                                                                 const long long* __restrict__ offsets) {
+                                                                 const long long* __restrict__ offsets,
+                                                                 const float* __restrict__ level) {
   static_assert(V * sizeof(OUT) == 16, "one vector = one 16-byte store");
   const int b = blockIdx.y;
   const long long off = offsets[b];
@@ -45,6 +46,7 @@ __global__ __launch_bounds__(PACK_THREADS) void wave_pack_kernel(const float* __
   if (n <= 0) return;
   const float* __restrict__ src = wave + (int64_t)b * w_bs;
   OUT* __restrict__ dst = out + off;
+  const row_gain gain = pack_row_gain(level, b);
   const long long head = min(n, (long long)((16 - (int)(reinterpret_cast<uintptr_t>(dst) & 15)) & 15) / (long long)sizeof(OUT));
   const long long nvec = (n - head) / V;
   const long long v0 = (long long)blockIdx.x * (PACK_THREADS * PACK_ITERS);
@@ -55,12 +57,12 @@ __global__ __launch_bounds__(PACK_THREADS) void wave_pack_kernel(const float* __
     if (v >= nvec) break;
     const long long i = head + v * V;
     if constexpr (V == 4) {
-      const float4 a = load_f32x4(src + i);
+      const float4 a = gain(load_f32x4(src + i));
       uint4 o;
       o.x = __float_as_uint(a.x); o.y = __float_as_uint(a.y); o.z = __float_as_uint(a.z); o.w = __float_as_uint(a.w);
       *reinterpret_cast<uint4*>(dst + i) = o;
     } else {
-      const float4 a = load_f32x4(src + i), c = load_f32x4(src + i + 4);
+      const float4 a = gain(load_f32x4(src + i)), c = gain(load_f32x4(src + i + 4));
       auto two = [](float lo, float hi) { return (uint32_t)(uint16_t)pcm16(lo) | ((uint32_t)(uint16_t)pcm16(hi) << 16); };
       uint4 o;
       o.x = two(a.x, a.y); o.y = two(a.z, a.w); o.z = two(c.x, c.y); o.w = two(c.z, c.w);
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(PACK_THREADS) void wave_pack_kernel(const float* __
     if ((long long)threadIdx.x < head) i = threadIdx.x;
     else if (threadIdx.x >= 64 && t0 + (threadIdx.x - 64) < n) i = t0 + (threadIdx.x - 64);
     if (i >= 0) {
-      if constexpr (V == 4) dst[i] = src[i]; else dst[i] = pcm16(src[i]);
+      if constexpr (V == 4) dst[i] = gain(src[i]); else dst[i] = pcm16(gain(src[i]));
     }
   }
 }
@@ -98,11 +100,13 @@ int pack_move(const char* who, const pack_args& a) {
   if (a.fmt == ST2_PCM_S16) {
     const int gx = st2_cdiv(st2_cdiv(row, 8), PACK_THREADS * PACK_ITERS);
     hipLaunchKernelGGL((wave_pack_kernel<int16_t, 8>), dim3(gx, a.B), dim3(PACK_THREADS), 0, s, a.wave, a.w_bs, a.frames, a.B,
-                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<int16_t*>(a.out), (long long)a.out_capacity, offs);
+                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<int16_t*>(a.out), (long long)a.out_capacity, offs,
+                       a.level);
   } else {
     const int gx = st2_cdiv(st2_cdiv(row, 4), PACK_THREADS * PACK_ITERS);
     hipLaunchKernelGGL((wave_pack_kernel<float, 4>), dim3(gx, a.B), dim3(PACK_THREADS), 0, s, a.wave, a.w_bs, a.frames, a.B,
-                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<float*>(a.out), (long long)a.out_capacity, offs);
+                       a.T_cap, a.samples_per_frame, a.trim, reinterpret_cast<float*>(a.out), (long long)a.out_capacity, offs,
+                       a.level);
   }
   ST2_CHECK_LAUNCH(who);
   return 0;

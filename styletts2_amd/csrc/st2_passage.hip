@@ -99,6 +99,7 @@ int pack_plan(const char* who, const pack_args& a) {
                   reinterpret_cast<uintptr_t>(a.taps) % 4 == 0,
               rs ? "%s: wave / taps / out is not aligned to its sample type" : "%s: wave / out is not aligned to its sample type", who);
   const int64_t row = (int64_t)a.samples_per_frame * a.T_cap;
+  ST2_REQUIRE(reinterpret_cast<uintptr_t>(a.level) % 4 == 0, "%s: level is not aligned to float", who);
   ST2_REQUIRE(a.B == 1 || a.w_bs >= row, "%s: w_bs=%lld is less than the %lld samples of a row at capacity", who,
               (long long)a.w_bs, (long long)row);
   int tile = 0;
@@ -121,11 +122,11 @@ int pack_plan(const char* who, const pack_args& a) {
   return 0;
 }
 
-extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                                  int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
-                                  int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
-                                  int64_t out_capacity, int64_t* offsets, void* stream) {
-  const char* who = "st2_wave_pack_gaps";
+// What st2_wave_pack_gaps and st2_wave_pack_level refuse themselves, in the entry's own name, and the plan behind them
+static int pack_gaps_entry(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                           int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                           int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
+                           int64_t out_capacity, int64_t* offsets, void* stream, const float* level) {
   ST2_REQUIRE(gap_cap >= 0, "%s: gap_cap=%d must not be negative", who, gap_cap);
   ST2_REQUIRE(reinterpret_cast<uintptr_t>(gaps) % 4 == 0, "%s: gaps is not aligned to int32", who);
   if (!taps) {  // this entry's own words for what the plain move cannot do
@@ -134,5 +135,23 @@ extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t
                 "%s: format %d needs the resampling move (taps); without taps fp32 and 16-bit PCM only", who, fmt);
   }
   return pack_plan(who, pack_args{wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase, fmt, gaps,
-                                  gap_cap, out, out_capacity, offsets, stream});
+                                  gap_cap, out, out_capacity, offsets, stream, level});
+}
+
+extern "C" int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                                  int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                                  int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
+                                  int64_t out_capacity, int64_t* offsets, void* stream) {
+  return pack_gaps_entry("st2_wave_pack_gaps", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase,
+                         fmt, gaps, gap_cap, out, out_capacity, offsets, stream, nullptr);
+}
+
+// st2_wave_pack_level: st2_wave_pack_gaps whose moves multiply every input sample of row b by level[b][2],
+// the gain st2_wave_level (st2_level.hip) wrote there; level == NULL: st2_wave_pack_gaps itself.
+extern "C" int st2_wave_pack_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                                   int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
+                                   int32_t taps_per_phase, int32_t fmt, const int32_t* gaps, int32_t gap_cap, void* out,
+                                   int64_t out_capacity, int64_t* offsets, void* stream, const float* level) {
+  return pack_gaps_entry("st2_wave_pack_level", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, up, down, taps, taps_per_phase,
+                         fmt, gaps, gap_cap, out, out_capacity, offsets, stream, level);
 }

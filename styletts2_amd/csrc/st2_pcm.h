@@ -19,6 +19,21 @@ __device__ __forceinline__ long long pack_row_out_samples(const int32_t* __restr
   return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D;
 }
 
+// The per-row gain of st2_wave_pack_level (st2_level.hip): g_b = level[b][2], read once per workgroup and
+// multiplied into every input sample as it is loaded, before anything else a move does.  level == NULL: no multiply at all --
+// not one by 1.0f, which would quieten the NaN payloads the fp32 bit copy hands on -- and the move is the one it always was.
+struct row_gain {
+  bool on;
+  float g;
+  __device__ __forceinline__ float operator()(float x) const { return on ? x * g : x; }
+  __device__ __forceinline__ float4 operator()(float4 x) const {
+    return on ? make_float4(x.x * g, x.y * g, x.z * g, x.w * g) : x;
+  }
+};
+__device__ __forceinline__ row_gain pack_row_gain(const float* __restrict__ level, int b) {
+  return level ? row_gain{true, level[4 * b + 2]} : row_gain{false, 1.0f};
+}
+
 // The source of a row's aligned body starts wherever the destination's alignment puts it: 4-byte aligned only.
 struct __attribute__((packed, aligned(4))) f32x4_u {
   float v[4];
@@ -105,7 +120,7 @@ __device__ __forceinline__ float4 load_f32x4(const float* __restrict__ p) { retu
 // The pack plan (st2_passage.hip): what the three packing entries st2_wave_pack, st2_wave_resample_pack
 // and st2_wave_pack_gaps receive, and the one function that serves them -- every refusal once (`who` names the entry in the
 // message), then the row scan, the move, and the fill where there are gaps.  taps == NULL: the plain move (up = down = 1,
-// fp32 / 16-bit PCM); gaps == NULL or gap_cap == 0: no fill.
+// fp32 / 16-bit PCM); gaps == NULL or gap_cap == 0: no fill; level == NULL (every entry but st2_wave_pack_level): no gain.
 static_assert((int)ST2_PACK_F32 == (int)ST2_PCM_F32 && (int)ST2_PACK_S16 == (int)ST2_PCM_S16,
               "st2_wave_pack's format codes are the first two of st2_pcm_format: the code below tests ST2_PCM_* only");
 struct pack_args {
@@ -121,6 +136,7 @@ struct pack_args {
   int64_t out_capacity;
   int64_t* offsets;
   void* stream;
+  const float* level = nullptr;  // fp32 [B][4] of st2_wave_level: the moves multiply by level[b][2]
 };
 int pack_plan(const char* who, const pack_args& a);
 // The move launch over offsets that the scan has written on the same stream, each beside its kernel (st2_pack.hip,

@@ -38,21 +38,22 @@ __device__ __forceinline__ void pp_stage_table(float* __restrict__ tab, const fl
 }
 
 // The tile's input span of a row of n samples in format FMT, decoded, to LDS; a sample in front of the row or at / past n is
-// a SELECTED zero -- nothing of `row` at or past n is read
+// a SELECTED zero -- nothing of `row` at or past n is read.  `gain` (st2_pcm.h): the row's gain on every loaded sample; the
+// default is none.
 template <int FMT>
 __device__ __forceinline__ void pp_stage_span(float* __restrict__ xs, const typename pcm_fmt<FMT>::type* __restrict__ row,
-                                              long long n, const pp_tile& g) {
+                                              long long n, const pp_tile& g, const row_gain gain = row_gain{false, 1.0f}) {
   for (int q = threadIdx.x; q < g.n4; q += PP_THREADS) {
     const long long i = g.a0 + 4LL * q;
     float4 x;
     if (i >= 0 && i + 4 <= n) {
-      x = pcm_decode4<FMT>(row + i);
+      x = gain(pcm_decode4<FMT>(row + i));
     } else {  // an edge of the row: every sample on its own, loaded only where it is valid
       float e[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         e[r] = 0.0f;
-        if (i + r >= 0 && i + r < n) e[r] = pcm_decode<FMT>(row[i + r]);
+        if (i + r >= 0 && i + r < n) e[r] = gain(pcm_decode<FMT>(row[i + r]));
       }
       x = make_float4(e[0], e[1], e[2], e[3]);
     }

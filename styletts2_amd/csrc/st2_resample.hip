@@ -26,7 +26,7 @@ template <int FMT>
 __global__ __launch_bounds__(RS_THREADS) void wave_resample_pack_kernel(
     const float* __restrict__ wave, int64_t w_bs, const int32_t* __restrict__ frames, int B, int T_cap, int spf, int trim, int U,
     int D, const float* __restrict__ taps, int K, int tile, typename pcm_fmt<FMT>::type* __restrict__ out, long long out_capacity,
-    const long long* __restrict__ offsets) {
+    const long long* __restrict__ offsets, const float* __restrict__ level) {
   using OUT = typename pcm_fmt<FMT>::type;
   constexpr int V = 16 / (int)sizeof(OUT);
   __shared__ __attribute__((aligned(16))) float lds[RS_LDS_FLOATS];
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(RS_THREADS) void wave_resample_pack_kernel(
   unsigned char* __restrict__ ys = reinterpret_cast<unsigned char*>(lds + (RS_LDS_FLOATS - RS_OUT_FLOATS));
   // -- 1. stage
   pp_stage_table(tab, taps, U * K);
-  pp_stage_span<ST2_PCM_F32>(xs, wave + (int64_t)b * w_bs, n, tg);
+  pp_stage_span<ST2_PCM_F32>(xs, wave + (int64_t)b * w_bs, n, tg, pack_row_gain(level, b));
   __syncthreads();
   // -- 2. filter and convert
   const int mis0 = blockIdx.x == 0 ? mis : 0;  // where sample j0 lies in its 16-byte vector of the destination
@@ -95,7 +95,7 @@ int pack_resample_move(const char* who, const pack_args& a, int tile) {
     hipLaunchKernelGGL((wave_resample_pack_kernel<f()>), dim3(gx, a.B), dim3(RS_THREADS), 0, reinterpret_cast<hipStream_t>(a.stream),
                        a.wave, a.w_bs, a.frames, a.B, a.T_cap, a.samples_per_frame, a.trim, a.up, a.down, a.taps, a.taps_per_phase,
                        tile, reinterpret_cast<typename pcm_fmt<f()>::type*>(a.out), (long long)a.out_capacity,
-                       reinterpret_cast<const long long*>(a.offsets));
+                       reinterpret_cast<const long long*>(a.offsets), a.level);
   });
   ST2_CHECK_LAUNCH(who);
   return 0;

@@ -1239,10 +1239,12 @@ def _pack_operands(wave, frames, samples_per_frame, dtype, out, offsets, out_sam
     return wave, lp, B, L, spf, out, offsets
 
 
-def _wave_pack(entry, wave, frames, rate, fmt, trim, out, offsets, samples_per_frame, plain=None, gaps=None, max_gap=None):
-    """The body of the three packing wrappers; `entry` is the C entry the caller chose.  `plain`: the entry's refusal of a
+def _wave_pack(entry, wave, frames, rate, fmt, trim, out, offsets, samples_per_frame, plain=None, gaps=None, max_gap=None,
+               level=()):
+    """The body of the four packing wrappers; `entry` is the C entry the caller chose.  `plain`: the entry's refusal of a
     format outside PACK_FORMATS when there is no rate (the plain move, no table); None: the entry needs a rate.  `max_gap`
-    (the gaps entry only): `gaps` and `max_gap` are passed on, and `out` defaults to `max_gap` more samples per row."""
+    (the gaps entries only): `gaps` and `max_gap` are passed on, and `out` defaults to `max_gap` more samples per row.  `level`
+    (the level entry only): a 1-tuple of the table of `wave_level` or of None, passed on behind the stream."""
     from . import resample
     if rate is None and plain is not None:
         if fmt not in PACK_FORMATS:
@@ -1258,9 +1260,20 @@ def _wave_pack(entry, wave, frames, rate, fmt, trim, out, offsets, samples_per_f
     breaks = () if max_gap is None else (_chk_len(gaps, "gaps", B, wave), max_gap)
     U, D, K, taps = table()
     how = (code,) if entry == "st2_wave_pack" else (U, D, _ptr(taps), K, code)
+    gain = tuple(_ptr(_chk_level(t, B, wave)) for t in level)
     _lib.check(getattr(_lib.load(), entry)(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), *how, *breaks,
-                                           out.data_ptr(), out.numel(), offsets.data_ptr(), _stream()), entry)
+                                           out.data_ptr(), out.numel(), offsets.data_ptr(), _stream(), *gain), entry)
     return out, offsets
+
+
+def _chk_level(level, B, wave):
+    """A level table: None, or fp32 with 4 B entries, contiguous, on the device of `wave`."""
+    if level is None:
+        return None
+    _chk_dev(level, "level", torch.float32, level.dim() if torch.is_tensor(level) else 2)
+    if level.numel() != 4 * B or level.device != wave.device:
+        raise _lib.St2Error("level must hold [%d, 4] values on the device of wave (got %s on %s)" % (B, tuple(level.shape), level.device))
+    return level
 
 
 def wave_pack(wave, frames, trim=0, fmt="s16", out=None, offsets=None, samples_per_frame=600):
@@ -1296,6 +1309,56 @@ def wave_pack_gaps(wave, frames, gaps, max_gap, rate=None, fmt="s16", trim=0, ou
     (rate, device) designs and uploads the table, which therefore must not happen under stream capture."""
     return _wave_pack("st2_wave_pack_gaps", wave, frames, rate, fmt, trim, out, offsets, samples_per_frame,
                       plain="fmt must be one of %s without a rate, got %r", gaps=gaps, max_gap=int(max_gap))
+
+
+def wave_pack_level(wave, frames, level, gaps=None, max_gap=0, rate=None, fmt="s16", trim=0, out=None, offsets=None,
+                    samples_per_frame=600):
+    """`st2_wave_pack_level`: `wave_pack_gaps` whose moves multiply every valid sample of row b by level[b, 2], the gain
+    `wave_level` wrote there -- one fp32 multiply as the sample is loaded, so the packed output is what `wave_pack_gaps` gives
+    for the input fl32(x * g_b).  level fp32 [B, 4] on the device; None = no gain, `wave_pack_gaps` itself (NaN payloads of the
+    fp32 copy included).  Every other argument, the return value and the no-host-read rule as `wave_pack_gaps`."""
+    return _wave_pack("st2_wave_pack_level", wave, frames, rate, fmt, trim, out, offsets, samples_per_frame,
+                      plain="fmt must be one of %s without a rate, got %r", gaps=gaps, max_gap=int(max_gap), level=(level,))
+
+
+def wave_level_workspace_bytes(B, T_cap, samples_per_frame=600, sample_rate=24000):
+    """`st2_wave_level_workspace_bytes`: what `wave_level(workspace=)` needs, in bytes."""
+    return int(_lib.load().st2_wave_level_workspace_bytes(int(B), int(T_cap), int(samples_per_frame), int(sample_rate)))
+
+
+def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samples_per_frame=600, sample_rate=24000, out=None,
+               workspace=None):
+    """`st2_wave_level`: wave [B, 1, L] or [B, L] at `sample_rate` (L a multiple of `samples_per_frame`: the batch's frame
+    capacity), frames int32 [B] on the device, target fp32 [B] on the device (LUFS; NaN = leave the row alone) -> level fp32
+    [B, 4] on the device: every row's integrated loudness (ITU-R BS.1770-4, K-weighted and gated; -inf when no block passes the
+    gates), its sample peak, the linear gain min(10^((target - L) / 20), 10^(max_gain_db / 20), ceiling / peak) (exactly 1 for a
+    NaN target, L = -inf or peak = 0) and the number of gating blocks that passed, measured on the row's first max(0,
+    samples_per_frame * frames[b] - trim) samples.  `ceiling` is linear, in (0, 1]; `max_gain_db` in [0, 60].  `out`: a contiguous
+    fp32 tensor of 4 B entries to write into; `workspace`: a uint8 device tensor of `wave_level_workspace_bytes` bytes (by
+    default allocated here, from the caching allocator).  No host read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf = int(samples_per_frame)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    _chk_dev(target, "target", torch.float32, 1)
+    if target.numel() != B or target.device != wave.device:
+        raise _lib.St2Error("target must hold %d values on the device of wave" % B)
+    if out is None:
+        out = torch.empty((B, 4), device=wave.device, dtype=torch.float32)
+    _chk_level(out, B, wave)
+    need = wave_level_workspace_bytes(B, L // spf, spf, sample_rate)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    _lib.check(_lib.load().st2_wave_level(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), int(sample_rate),
+                                          target.data_ptr(), float(ceiling), float(max_gain_db), out.data_ptr(),
+                                          workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_level")
+    return out
 
 
 def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):

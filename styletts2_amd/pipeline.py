@@ -278,6 +278,72 @@ class Controls:
         return c
 
 
+class Level:
+    """Loudness normalisation of the packed hand-over (include/st2.h `st2_wave_level`): every row is
+    measured on the device (ITU-R BS.1770-4 integrated loudness and sample peak, at the model rate) and packed with the gain that
+    brings it to `target` LUFS -- never more than `max_gain_db`, and never so much that a sample passes `ceiling_db` dBFS.
+
+        target       LUFS, one value or B values; None or NaN in a row = leave this row alone    [-70, 0]
+        ceiling_db   dBFS of the largest sample magnitude after the gain                          [-20, 0]
+        max_gain_db  the most a quiet row is raised by                                             [0, 60]
+
+    Kept as one fp32 [B] device row (`target`), validated on the host like `Controls`; a tensor already on the device is not
+    read.  `ceiling` is `ceiling_db` as a linear factor."""
+
+    def __init__(self, B, target=-16.0, ceiling_db=-1.0, max_gain_db=20.0, device=None):
+        B = int(B)
+        if B <= 0:
+            raise ValueError("Level: B must be positive, got %r" % (B,))
+        ceiling_db, max_gain_db = float(ceiling_db), float(max_gain_db)
+        if not -20.0 <= ceiling_db <= 0.0:
+            raise ValueError("Level: ceiling_db must lie in [-20, 0], got %r" % (ceiling_db,))
+        if not 0.0 <= max_gain_db <= 60.0:
+            raise ValueError("Level: max_gain_db must lie in [0, 60], got %r" % (max_gain_db,))
+        on_dev = torch.is_tensor(target) and target.is_cuda
+        if device is None:
+            device = target.device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        self.B, self.ceiling_db, self.max_gain_db = B, ceiling_db, max_gain_db
+        self.ceiling = min(1.0, 10.0 ** (ceiling_db / 20.0))
+        self.target = self.row(target, B).to(device)
+
+    @staticmethod
+    def row(target, B):
+        """`target` as the fp32 [B] row the kernel reads: a device tensor as it is (unread), host values validated; None = NaN."""
+        if torch.is_tensor(target) and target.is_cuda:
+            if target.numel() != B:
+                raise ValueError("Level: target must hold %d values, got shape %s" % (B, tuple(target.shape)))
+            return target.detach().reshape(B).to(torch.float32)
+        if target is None:
+            target = float("nan")
+        if isinstance(target, (list, tuple)):
+            target = [float("nan") if v is None else float(v) for v in target]
+        rows = torch.as_tensor(target, dtype=torch.float64).reshape(-1)
+        if rows.numel() == 1:
+            rows = rows.expand(B)
+        if rows.numel() != B:
+            raise ValueError("Level: target must be one value or %d values, got %d" % (B, rows.numel()))
+        if not bool((torch.isnan(rows) | ((rows >= -70.0) & (rows <= 0.0))).all()):
+            raise ValueError("Level: target must lie in [-70, 0] LUFS (None / NaN = leave the row alone), got %s" % rows.tolist())
+        return rows.to(torch.float32)
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as a Level over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Level)
+        c.B, c.ceiling_db, c.max_gain_db, c.ceiling, c.target = j - i, self.ceiling_db, self.max_gain_db, self.ceiling, self.target[i:j]
+        return c
+
+
+def _check_level(level, B, pack, max_frames=True):
+    """What `level=` needs wherever it is given: a `Level` of the batch's rows, and a packed hand-over on the capacity-bound path
+    for the gain to be applied in."""
+    if level is None:
+        return
+    if pack is None or max_frames is None:
+        raise ValueError("level is a gain in the packed samples of the capacity-bound path: pass max_frames and pack")
+    if not isinstance(level, Level) or level.B != B:
+        raise ValueError("level must be a pipeline.Level of %d rows" % B)
+
+
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
     """What `controls=` cannot be combined with: refused before anything is launched."""
     if not isinstance(controls, Controls):
@@ -764,20 +830,25 @@ class SynthesisResult:
                packed[offsets[b] : offsets[b + 1] - g_b], its break the g_b samples behind it, and offsets[B] the length of the
                whole passage.  `marks` stay relative to their row: a position in the passage is offsets[b] + marks[b, n], and
                offsets[b + 1] - offsets[b] = marks[b, N] + g_b.
+      level    (with `level=`) fp32 [B, 4]: every row's integrated loudness in LUFS (-inf when no block
+               passed the gates), its sample peak, the linear gain its packed samples were multiplied by and the number of gating
+               blocks that passed -- measured on `wave`, which stays as the decoder made it.  Kept in the same allocation behind
+               the gaps: `to_host(level=True)` is still one copy.
     `to_host()` is the one place that waits."""
 
     def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None,
-                 marks=None, style=None, gaps=None, max_gap=0):
+                 marks=None, style=None, gaps=None, max_gap=0, level=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
         self.sample_rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
         self.marks = marks
         self.style, self.gaps, self.max_gap = style, gaps, int(max_gap)
+        self.level = level
         self._buf = buf  # offsets, marks and packed are views of this one allocation: one copy takes all
         self._host = None  # its pinned mirror, allocated by the first to_host()
 
-    def to_host(self, marks=False, passage=False):
+    def to_host(self, marks=False, passage=False, level=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -789,7 +860,10 @@ class SynthesisResult:
         would need a second wait.  `marks=True` (a result made with `marks=True`): returns (arrays, marks) with the timing marks as
         an int32 [B, N + 1] numpy array out of the same copy.  A result with `gaps` gives every row's speech WITHOUT its break,
         as a result without gaps does; `passage=True` gives instead the ONE contiguous array packed[:offsets[B]], speech and
-        breaks as a client plays them."""
+        breaks as a client plays them.  `level=True` (a result made with `level=`): the level table as a float32 [B, 4] numpy
+        array out of the same copy, behind whatever else is returned: (arrays, level) or (arrays, marks, level)."""
+        if level and self.level is None:
+            raise ValueError("this result carries no level table: ask for it with inference(..., level=Level(...))")
         if marks and self.marks is None:
             raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
         if self._buf is None:
@@ -804,8 +878,9 @@ class SynthesisResult:
         done.synchronize()
         ops.check_status()
         B = self.frames.numel()
-        layout = _HandOver(B, self.pack or "f32", 0 if self.marks is None else self.marks.numel(), self.gaps is not None)
-        offs, m, g, samples = layout.views(host)
+        layout = _HandOver(B, self.pack or "f32", 0 if self.marks is None else self.marks.numel(), self.gaps is not None,
+                           with_level=self.level is not None)
+        offs, m, g, samples, lv = layout.views(host)
         offs, samples = offs.tolist(), samples.numpy()
         if passage:
             rows = samples[:offs[B]]
@@ -814,9 +889,8 @@ class SynthesisResult:
         else:  # the breaks as the packing step counted them: clamped to 0..max_gap
             g = g.clamp(0, self.max_gap).tolist()
             rows = [samples[offs[b]:offs[b + 1] - g[b]] for b in range(B)]
-        if not marks:
-            return rows
-        return rows, m.numpy().reshape(tuple(self.marks.shape))
+        more = ((m.numpy().reshape(tuple(self.marks.shape)),) if marks else ()) + ((lv.numpy().reshape(B, 4),) if level else ())
+        return (rows,) + more if more else rows
 
 
 def _check_output(pack, sample_rate):
@@ -896,46 +970,58 @@ def _resamples(fmt, sample_rate):
 class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
-        [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | pad to 16 bytes | samples of `fmt`]
+        [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | pad to 16 bytes | samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the four
-    parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
-    its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps` and `packed` are the
-    buffer and its views (None for a part the layout does not have)."""
+    with `n_marks` = 0 / no gaps / no level the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    five parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
+    its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `packed` and `level` are
+    the buffer and its views (None for a part the layout does not have)."""
 
-    def __init__(self, B, fmt, n_marks=0, with_gaps=False):
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
+        self.with_level = bool(with_level)
         self.offsets_at = 0
         self.marks_at = 8 * (self.B + 1)
         self.gaps_at = self.marks_at + 4 * self.n_marks
-        self.samples_at = (self.gaps_at + (4 * self.B if self.with_gaps else 0) + 15) // 16 * 16
-        self.buf = self.offsets = self.marks = self.gaps = self.packed = None
+        self.level_at = self.gaps_at + (4 * self.B if self.with_gaps else 0)
+        self.samples_at = (self.level_at + (16 * self.B if self.with_level else 0) + 15) // 16 * 16
+        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = None
 
     def views(self, buf):
-        """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples) of a uint8 buffer."""
+        """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
+        None) of a uint8 buffer."""
         i32 = lambda at, n: buf[at:at + 4 * n].view(torch.int32)
         return (buf[self.offsets_at:self.marks_at].view(torch.int64), i32(self.marks_at, self.n_marks) if self.n_marks else None,
-                i32(self.gaps_at, self.B) if self.with_gaps else None, buf[self.samples_at:].view(self.dtype))
+                i32(self.gaps_at, self.B) if self.with_gaps else None, buf[self.samples_at:].view(self.dtype),
+                buf[self.level_at:self.level_at + 16 * self.B].view(torch.float32) if self.with_level else None)
 
     def allocate(self, samples, device):
         self.buf = torch.empty((self.samples_at + samples * self.dtype.itemsize,), device=device, dtype=torch.uint8)
-        self.offsets, self.marks, self.gaps, self.packed = self.views(self.buf)
+        self.offsets, self.marks, self.gaps, self.packed, self.level = self.views(self.buf)
         return self
 
 
-def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0):
+def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
-    are copied into here; else, where `_resamples`, `ops.wave_resample_pack`; else `ops.wave_pack`."""
+    are copied into here; else, where `_resamples`, `ops.wave_resample_pack`; else `ops.wave_pack`.  With `level` (a `Level`;
+    DESIGN.md section 23) `ops.wave_level` measures the rows into the header's level part -- its workspace comes from the caching
+    allocator, under capture from the graph's own pool, which lives as long as the graph -- and `ops.wave_pack_level` packs them
+    with the gains it reads there, with or without gaps and a rate."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
     room = resample.output_samples(L, U, D) + (0 if gaps is None else max_gap)
-    ho = _HandOver(B, fmt, n_marks, gaps is not None).allocate(B * room, wave.device)
+    ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None).allocate(B * room, wave.device)
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
+    if level is not None:
+        ops.wave_level(wave, frames, level.target, ceiling=level.ceiling, max_gain_db=level.max_gain_db, trim=trim,
+                       samples_per_frame=samples_per_frame, sample_rate=resample.MODEL_RATE, out=ho.level)
+        ops.wave_pack_level(wave, frames, ho.level, gaps=ho.gaps, max_gap=max_gap, rate=rate, **into)
+    elif gaps is not None:
         ops.wave_pack_gaps(wave, frames, ho.gaps, max_gap, rate=rate, **into)
     elif rate is not None:
         ops.wave_resample_pack(wave, frames, rate, **into)
@@ -944,10 +1030,11 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False, gaps=None, max_gap=0):
+def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False, gaps=None, max_gap=0, level=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `marks`: one `ops.token_marks` launch behind the packing writes the timing marks
-    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows (`_hand_over`)."""
+    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows, `level`: their loudness normalisation
+    (`_hand_over`)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     if trim is None:
@@ -957,14 +1044,16 @@ def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=F
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    ho = _hand_over(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0, gaps=gaps, max_gap=max_gap)
+    ho = _hand_over(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0, gaps=gaps, max_gap=max_gap,
+                    level=level)
     m = None
     if marks:
         m = ho.marks.view(B, N + 1)
         ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=model.decoder.kind == "hifigan", trim=trim,
                         rate=sample_rate, samples_per_frame=spf, out=m)
     return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=ho.packed, offsets=ho.offsets, buf=ho.buf,
-                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=ho.gaps, max_gap=max_gap)
+                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=ho.gaps, max_gap=max_gap,
+                           level=None if ho.level is None else ho.level.view(B, 4))
 
 
 class GraphedSynthesis:
@@ -996,11 +1085,17 @@ class GraphedSynthesis:
     row 0 alone), `s_prev` ([1, 256]: the style row 0 continues from unless its start flag is set) and `gaps` (int32 [B], zeros:
     samples of silence behind every row, clamped to 0..max_gap by the kernel).  `__call__(starts=, s_prev=, gaps=)` fills them
     (what is left out keeps its contents): one recorded graph serves any breaks up to `max_gap`, any start flags and any
-    `s_prev`.  `t` is the carry-over's weight.  Built without them, the graph records exactly what it recorded before."""
+    `s_prev`.  `t` is the carry-over's weight.  Built without them, the graph records exactly what it recorded before.
+
+    `level=True` (or a `Level`; needs `pack`): the graph records the level measurement and the gain-applying
+    pack over one more static buffer, `static["level"]` (a `Level`; at first -16 LUFS in every row, or the one given):
+    `__call__(level=)` -- a `Level`, one target or B of them, None / NaN = leave the row alone -- copies the targets into its
+    row, so one graph serves any targets; the ceiling and the gain limit are the graph's own.  Without it the graph records
+    exactly what it recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None, passage=False, max_gap=None, t=0.7):
+                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1036,6 +1131,11 @@ class GraphedSynthesis:
             self.kw["t"] = t
         if self.max_gap is not None:
             self.static["gaps"] = torch.zeros((B,), device=dev, dtype=torch.int32)
+        if level is not None and level is not False:
+            level = Level(B, device=dev) if level is True else level
+            _check_level(level, B, pack)
+            self.static["level"] = Level(B, target=level.target.to(dev).clone(), ceiling_db=level.ceiling_db,
+                                         max_gain_db=level.max_gain_db, device=dev)
         self._g = None
 
     def _run(self):
@@ -1045,6 +1145,8 @@ class GraphedSynthesis:
             more.update(passage=st["starts"], s_prev=st["s_prev"])
         if self.max_gap is not None:
             more.update(gaps=st["gaps"], max_gap=self.max_gap)
+        if st.get("level") is not None:
+            more.update(level=st["level"])
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
                          controls=st["controls"], **more, **self.kw)
@@ -1060,7 +1162,7 @@ class GraphedSynthesis:
 
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
-                 starts=None, s_prev=None, gaps=None):
+                 starts=None, s_prev=None, gaps=None, level=None):
         st = self.static
         built_by = dict(starts="passage=True", s_prev="passage=True", gaps="max_gap")  # the buffers a plain graph lacks
         for name, val in (("starts", starts), ("s_prev", s_prev), ("gaps", gaps), ("tokens", tokens), ("lengths_dev", lengths),
@@ -1076,6 +1178,13 @@ class GraphedSynthesis:
             elif name == "sine_noise":
                 val = val[:, :st[name].shape[1]]
             st[name].copy_(val.reshape(st[name].shape), non_blocking=True)
+        if level is not None:
+            if st.get("level") is None:
+                raise ValueError("this graph was built without level: pass level=True")
+            row = level.target if isinstance(level, Level) else Level.row(level, st["level"].B)
+            if row.numel() != st["level"].B:
+                raise ValueError("level must hold %d targets, got %d" % (st["level"].B, row.numel()))
+            st["level"].target.copy_(row, non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
@@ -1137,11 +1246,12 @@ def _decode_groups(model, groups, dec, main, noise_of, ready=None, first=0):
 
 
 def _check_capacity_args(tokens, *, max_frames, pack, trim, sample_rate, lengths_dev, marks, passage, gaps, max_gap, s_prev,
-                         controls, taps, front, durations, decode_streams):
+                         controls, taps, front, durations, decode_streams, level=None):
     """What `inference` refuses about the arguments of the capacity-bound path, before anything is launched, and what it
     settles on the way -> (carry, gaps, max_gap, controls): whether the rows are a passage, the breaks as `_check_gaps` hands
     them on, and the controls with the start flags of `passage=[...]` in their `t` row."""
     _check_output(pack, sample_rate)
+    _check_level(level, tokens.shape[0], pack, max_frames)
     if max_frames is None and (passage is not None or gaps is not None or max_gap is not None or s_prev is not None):
         raise ValueError("passage / gaps / max_gap / s_prev belong to the capacity-bound path: pass max_frames")
     _check_gap_args(pack, gaps, max_gap)
@@ -1170,7 +1280,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
-              sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7):
+              sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1230,11 +1340,16 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     (`ops.wave_pack_gaps`; `gap_samples(ms, sample_rate)` converts milliseconds) -- an int32 [B] device tensor, which needs
     `max_gap` (the packing step clamps to 0..max_gap and sizes its allocation by it), or a host list, whose maximum is the
     default.  `marks` stay relative to their row (`SynthesisResult`).
+
+    `level` (a `Level` of B rows, with `max_frames` and `pack`): every row is measured on the device
+    (`ops.wave_level`: BS.1770-4 integrated loudness and sample peak) and packed with the gain that brings it to its target
+    loudness under the peak ceiling (`ops.wave_pack_level`); the result carries the table as `level` and `to_host(level=True)`
+    brings it over in its one copy.  `wave` stays as the decoder made it, marks and sample counts do not move.
     """
     carry, gaps, max_gap, controls = _check_capacity_args(
         tokens, max_frames=max_frames, pack=pack, trim=trim, sample_rate=sample_rate, lengths_dev=lengths_dev, marks=marks,
         passage=passage, gaps=gaps, max_gap=max_gap, s_prev=s_prev, controls=controls, taps=taps, front=front, durations=durations,
-        decode_streams=decode_streams)
+        decode_streams=decode_streams, level=level)
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
@@ -1257,7 +1372,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
                   main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
         return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate, marks=bool(marks), gaps=gaps,
-                                max_gap=0 if gaps is None else max_gap)
+                                max_gap=0 if gaps is None else max_gap, level=level)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1326,7 +1441,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None):
+                    max_gap=None, level=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1375,7 +1490,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `inference(max_frames=, passage=True, s_prev=<the previous group's style[-1:]>)` on the caller's stream: the token counts
     come from the sentences' shapes, nothing is read back, and the return value is (list of `SynthesisResult`, one per front
     group, final style [1, 256]); `on_chunk(k, result)` is called per GROUP.  `pack`, `sample_rate`, `marks` and `gaps` (one
-    break per sentence: a host list, or an int32 device tensor with `max_gap`) are `inference`'s and need `max_frames`.
+    break per sentence: a host list, or an int32 device tensor with `max_gap`) are `inference`'s and need `max_frames`; so is
+    `level` (a `Level` of one row per SENTENCE: every sentence is normalised on its own).
     `sine_noises` rows are stacked, zero-padded, to the capacity.  Per-token controls are served here: the rows are
     right-padded to the controls' width N, which must be the longest sentence's.  `decode_streams` > 1 is refused (there is one
     decoder call per group, on the caller's stream); `overlap`, `front`, `side_stream` and `ragged_decode` have no meaning.
@@ -1389,9 +1505,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                                          step_noises=step_noises, sine_noises=sine_noises, durations=durations, trim=trim,
                                          on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch,
                                          decode_streams=decode_streams, controls=controls, max_frames=max_frames, pack=pack,
-                                         sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap)
-    if pack is not None or sample_rate is not None or marks or gaps is not None or max_gap is not None:
-        raise ValueError("pack / sample_rate / marks / gaps / max_gap belong to the capacity-bound path: pass max_frames")
+                                         sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
+                                         level=level)
+    if pack is not None or sample_rate is not None or marks or gaps is not None or max_gap is not None or level is not None:
+        raise ValueError("pack / sample_rate / marks / gaps / max_gap / level belong to the capacity-bound path: pass max_frames")
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
@@ -1470,7 +1587,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -1490,6 +1607,7 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     if gaps is not None:
         _check_gap_args(pack, gaps, max_gap)
         gaps, max_gap = _check_gaps(gaps, max_gap, K)
+    _check_level(level, K, pack)
     prepped = []
     for i, i_end in _front_chunks(front_batch, K):
         ids = list(range(i, i_end))
@@ -1508,6 +1626,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     for k, q in enumerate(prepped):
         i, j = q["ids"][0], q["ids"][-1] + 1
         more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=max_gap)
+        if level is not None:
+            more.update(level=level.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
