@@ -10,6 +10,8 @@ Differences from the notebooks, all host-side:
   * optional `durations=` forces the per-phoneme durations (throughput runs use 4 frames / phoneme so that
     every utterance is exactly 10 s) and removes the only data-dependent host sync.
 """
+import typing
+
 import torch
 
 from . import _hooks, ops, resample
@@ -331,17 +333,6 @@ class Level:
         c = object.__new__(Level)
         c.B, c.ceiling_db, c.max_gain_db, c.ceiling, c.target = j - i, self.ceiling_db, self.max_gain_db, self.ceiling, self.target[i:j]
         return c
-
-
-def _check_level(level, B, pack, max_frames=True):
-    """What `level=` needs wherever it is given: a `Level` of the batch's rows, and a packed hand-over on the capacity-bound path
-    for the gain to be applied in."""
-    if level is None:
-        return
-    if pack is None or max_frames is None:
-        raise ValueError("level is a gain in the packed samples of the capacity-bound path: pass max_frames and pack")
-    if not isinstance(level, Level) or level.B != B:
-        raise ValueError("level must be a pipeline.Level of %d rows" % B)
 
 
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
@@ -834,19 +825,23 @@ class SynthesisResult:
                passed the gates), its sample peak, the linear gain its packed samples were multiplied by and the number of gating
                blocks that passed -- measured on `wave`, which stays as the decoder made it.  Kept in the same allocation behind
                the gaps: `to_host(level=True)` is still one copy.
-    `to_host()` is the one place that waits."""
+    `to_host()` is the one place that waits.  Made with `spec` (an `_Output`, trim resolved: `trim`, `pack`, `sample_rate`, `max_gap`)
+    and `ho` (the `_HandOver` that `_hand_over` returned for it, None without `pack`: `packed`, `offsets`, `gaps`, `level`)."""
 
-    def __init__(self, wave, frames, max_frames, trim=0, pack=None, packed=None, offsets=None, buf=None, sample_rate=None,
-                 marks=None, style=None, gaps=None, max_gap=0, level=None):
+    def __init__(self, wave, frames, max_frames, spec=None, ho=None, marks=None, style=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
-        self.trim, self.pack, self.packed, self.offsets = int(trim), pack, packed, offsets
-        self.sample_rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
-        self.marks = marks
-        self.style, self.gaps, self.max_gap = style, gaps, int(max_gap)
-        self.level = level
-        self._buf = buf  # offsets, marks and packed are views of this one allocation: one copy takes all
-        self._host = None  # its pinned mirror, allocated by the first to_host()
+        self.spec = spec = _Output() if spec is None else spec
+        self.trim, self.pack, self.sample_rate, self.max_gap = int(spec.trim), spec.fmt, _rate(spec.sample_rate), spec.max_gap
+        self.marks, self.style = marks, style
+        self._take(ho)
+        self._host = None  # the buffer's pinned mirror, allocated by the first to_host()
+
+    def _take(self, ho):
+        """offsets, marks, gaps, level and packed are views of the hand-over's one allocation: one copy takes all."""
+        self._ho, self._buf = ho, None if ho is None else ho.buf
+        self.packed, self.offsets, self.gaps = (None, None, None) if ho is None else (ho.packed, ho.offsets, ho.gaps)
+        self.level = None if ho is None or ho.level is None else ho.level.view(-1, 4)
 
     def to_host(self, marks=False, passage=False, level=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
@@ -866,21 +861,17 @@ class SynthesisResult:
             raise ValueError("this result carries no level table: ask for it with inference(..., level=Level(...))")
         if marks and self.marks is None:
             raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
-        if self._buf is None:
-            ho = _hand_over(self.wave, self.frames, self.trim, self.pack or "f32", self.samples_per_frame, self.sample_rate)
-            self._buf, self.packed, self.offsets = ho.buf, ho.packed, ho.offsets
+        if self._ho is None:
+            self._take(_hand_over(self.wave, self.frames, self.trim, "f32", self.samples_per_frame))
         if self._host is None or self._host.shape != self._buf.shape:
             self._host = torch.empty(self._buf.shape, dtype=torch.uint8, pin_memory=True)
-        host = self._host
-        host.copy_(self._buf, non_blocking=True)
+        self._host.copy_(self._buf, non_blocking=True)
         done = torch.cuda.Event()
         done.record(torch.cuda.current_stream(self._buf.device))
         done.synchronize()
         ops.check_status()
         B = self.frames.numel()
-        layout = _HandOver(B, self.pack or "f32", 0 if self.marks is None else self.marks.numel(), self.gaps is not None,
-                           with_level=self.level is not None)
-        offs, m, g, samples, lv = layout.views(host)
+        offs, m, g, samples, lv = self._ho.views(self._host)  # the layout the buffer was allocated with
         offs, samples = offs.tolist(), samples.numpy()
         if passage:
             rows = samples[:offs[B]]
@@ -893,50 +884,17 @@ class SynthesisResult:
         return (rows,) + more if more else rows
 
 
-def _check_output(pack, sample_rate):
-    """The output format and rate of the capacity-bound path: `pack` one of `ops.OUTPUT_FORMATS` or None, `sample_rate` one of
-    `resample.RATES` or None -- and only with `pack`."""
-    if pack is not None and pack not in ops.OUTPUT_FORMATS:
-        raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
-    if sample_rate is not None and pack is None:
-        raise ValueError("sample_rate is the rate of the packed samples: pass pack")
-    if sample_rate is not None and sample_rate not in resample.RATES:
-        raise ValueError("sample_rate must be None or one of %s, got %r" % (list(resample.RATES), sample_rate))
+def _rate(sample_rate):
+    """The rate of the packed samples: the caller's `sample_rate`, None = the model's 24 kHz."""
+    return resample.MODEL_RATE if sample_rate is None else int(sample_rate)
 
 
 def gap_samples(ms, sample_rate=None):
     """A break of `ms` milliseconds as samples of the hand-over at `sample_rate` (None: the model's 24 kHz): rint(ms * rate /
     1000), ties to even -- the one conversion between SSML's break times and `gaps=`.  A scalar gives an int, a sequence a list."""
-    rate = resample.MODEL_RATE if sample_rate is None else int(sample_rate)
+    rate = _rate(sample_rate)
     one = lambda v: int(round(float(v) * rate / 1000.0))  # Python's round: half to even, as rint
     return [one(v) for v in ms] if isinstance(ms, (list, tuple)) else one(ms)
-
-
-def _check_gap_args(pack, gaps, max_gap):
-    """What `gaps` / `max_gap` need wherever they are given (`inference`, `synthesize_long`, `GraphedSynthesis`): a packed
-    hand-over to be silence in, and a bound that is not negative."""
-    if pack is None and (gaps is not None or max_gap is not None):
-        raise ValueError("gaps are silence in the packed samples: pass pack")
-    if max_gap is not None and int(max_gap) < 0:
-        raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
-
-
-def _check_gaps(gaps, max_gap, B):
-    """`gaps=` -> (int32 [B] tensor, host or device as given; max_gap): a host sequence defaults `max_gap` to its own maximum, a
-    device tensor is never read and needs it.  (`max_gap` itself: `_check_gap_args`.)"""
-    if torch.is_tensor(gaps) and gaps.is_cuda:
-        if max_gap is None:
-            raise ValueError("gaps on the device are never read on the host: pass max_gap, the longest break in samples")
-        if gaps.dtype != torch.int32 or gaps.numel() != B:
-            raise ValueError("gaps must be an int32 tensor of %d entries, got %s %s" % (B, gaps.dtype, tuple(gaps.shape)))
-    else:
-        gaps = torch.as_tensor(gaps).reshape(-1)
-        if gaps.numel() != B or gaps.dtype.is_floating_point or int(gaps.abs().max()) >= 2 ** 31:
-            raise ValueError("gaps must be %d whole sample counts (pipeline.gap_samples converts milliseconds)" % B)
-        if max_gap is None:
-            max_gap = max(int(gaps.max()), 0)
-        gaps = gaps.to(torch.int32)
-    return gaps, int(max_gap)
 
 
 def _passage_controls(controls, starts, B, dev):
@@ -1001,6 +959,71 @@ class _HandOver:
         return self
 
 
+class _Output(typing.NamedTuple):
+    """What the packed hand-over of ONE call is: the output options as `_output_spec` settled them, stated
+    here and read by `_decode_capacity`, which hands them to `_hand_over`, by `GraphedSynthesis` and by `SynthesisResult`."""
+    fmt: typing.Optional[str] = None          # `pack`; None: nothing is packed before the first `to_host()`
+    trim: typing.Optional[int] = 0            # samples dropped from every row's end; None until `_decode_capacity` knows the decoder
+    sample_rate: typing.Optional[int] = None  # as the caller gave it
+    rate: typing.Optional[int] = None         # the rate the packing step resamples to; None: `ops.wave_pack` serves (`_resamples`)
+    marks: bool = False
+    max_gap: int = 0                          # 0 without gaps
+
+
+def _capacity_only(names, *given):
+    """The one statement that options belong to the capacity-bound path, over the subset `names` an entry point names."""
+    if any(v is not None for v in given):
+        raise ValueError("%s belong to the capacity-bound path: pass max_frames" % names)
+
+
+def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False):
+    """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
+    every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
+    launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
+    B rows; `max_gap` not negative, and a bound of `gaps` -- a host sequence defaults it to its own maximum, a device tensor is
+    never read and needs it; and all of them but `trim` only with `pack` on the capacity-bound path.
+    `capacity`: the call has a `max_frames`.  `graph`: the caller is `GraphedSynthesis`, to which `max_frames` is no option --
+    its `marks` refusal names `pack` alone.  `trim` goes through as given: `_decode_capacity` resolves None."""
+    if pack is not None and pack not in ops.OUTPUT_FORMATS:
+        raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
+    if sample_rate is not None and pack is None:
+        raise ValueError("sample_rate is the rate of the packed samples: pass pack")
+    if sample_rate is not None and sample_rate not in resample.RATES:
+        raise ValueError("sample_rate must be None or one of %s, got %r" % (list(resample.RATES), sample_rate))
+    if level is not None and (pack is None or not capacity):
+        raise ValueError("level is a gain in the packed samples of the capacity-bound path: pass max_frames and pack")
+    if level is not None and (not isinstance(level, Level) or level.B != B):
+        raise ValueError("level must be a pipeline.Level of %d rows" % B)
+    if not capacity:
+        _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
+    if pack is None and (gaps is not None or max_gap is not None):
+        raise ValueError("gaps are silence in the packed samples: pass pack")
+    if max_gap is not None and int(max_gap) < 0:
+        raise ValueError("max_gap must not be negative, got %r" % (max_gap,))
+    if gaps is None and max_gap is not None:
+        raise ValueError("max_gap bounds `gaps`: pass gaps")
+    if torch.is_tensor(gaps) and gaps.is_cuda:
+        if max_gap is None:
+            raise ValueError("gaps on the device are never read on the host: pass max_gap, the longest break in samples")
+        if gaps.dtype != torch.int32 or gaps.numel() != B:
+            raise ValueError("gaps must be an int32 tensor of %d entries, got %s %s" % (B, gaps.dtype, tuple(gaps.shape)))
+    elif gaps is not None:
+        gaps = torch.as_tensor(gaps).reshape(-1)
+        if gaps.numel() != B or gaps.dtype.is_floating_point or int(gaps.abs().max()) >= 2 ** 31:
+            raise ValueError("gaps must be %d whole sample counts (pipeline.gap_samples converts milliseconds)" % B)
+        if max_gap is None:
+            max_gap = max(int(gaps.max()), 0)
+        gaps = gaps.to(torch.int32)
+    if marks and (not capacity or pack is None):
+        raise ValueError("marks are positions in the packed samples" + (
+            ": pass pack" if graph else " of the capacity-bound path: pass max_frames and pack"))
+    if not capacity:
+        _capacity_only("pack / trim / lengths_dev", pack, trim)
+    rate = _rate(sample_rate) if pack is not None and _resamples(pack, sample_rate) else None
+    max_gap = 0 if gaps is None else int(max_gap)
+    return _Output(pack, trim, sample_rate, rate, bool(marks), max_gap), gaps
+
+
 def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
@@ -1030,30 +1053,28 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, pack, trim, sample_rate=None, marks=False, gaps=None, max_gap=0, level=None):
-    """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `pack`, the packed samples: nothing is read
-    back, nothing is sliced on the host.  `marks`: one `ops.token_marks` launch behind the packing writes the timing marks
-    into the hand-over allocation.  `gaps` / `max_gap`: the breaks behind the rows, `level`: their loudness normalisation
-    (`_hand_over`)."""
+def _decode_capacity(model, p, sine_noise, spec, gaps, level):
+    """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
+    back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
+    into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation (`_hand_over`)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
-    if trim is None:
-        trim = 50 if model.decoder.kind == "hifigan" else 0  # Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
-    if pack is None:
-        return SynthesisResult(w, p["frames"], T_cap, trim=trim, style=p["s_pred"])
+    hifigan = model.decoder.kind == "hifigan"
+    if spec.trim is None:  # read here and nowhere else: `inference`'s default, Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
+        spec = spec._replace(trim=50 if hifigan else 0)
+    if spec.fmt is None:
+        return SynthesisResult(w, p["frames"], T_cap, spec, style=p["s_pred"])
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    ho = _hand_over(w, p["frames"], trim, pack, spf, sample_rate, n_marks=B * (N + 1) if marks else 0, gaps=gaps, max_gap=max_gap,
-                    level=level)
+    ho = _hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
+                    level)
     m = None
-    if marks:
+    if spec.marks:
         m = ho.marks.view(B, N + 1)
-        ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=model.decoder.kind == "hifigan", trim=trim,
-                        rate=sample_rate, samples_per_frame=spf, out=m)
-    return SynthesisResult(w, p["frames"], T_cap, trim=trim, pack=pack, packed=ho.packed, offsets=ho.offsets, buf=ho.buf,
-                           sample_rate=sample_rate, marks=m, style=p["s_pred"], gaps=ho.gaps, max_gap=max_gap,
-                           level=None if ho.level is None else ho.level.view(B, 4))
+        ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
+                        rate=spec.sample_rate, samples_per_frame=spf, out=m)
+    return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"])
 
 
 class GraphedSynthesis:
@@ -1102,16 +1123,17 @@ class GraphedSynthesis:
         dev = torch.device(device) if device is not None else next(model.decoder.parameters()).device
         if not _engine_path(dev):
             raise ValueError("GraphedSynthesis needs the C++ engine path (HIP device, plan_mode 'engine')")
-        _check_output(pack, sample_rate)
-        if marks and pack is None:
-            raise ValueError("marks are positions in the packed samples: pass pack")
-        if pack is not None and _resamples(pack, sample_rate):
-            resample.table(resample.MODEL_RATE if sample_rate is None else sample_rate, dev)
         self.device, self.max_frames, self.steps = dev, int(max_frames), int(diffusion_steps)
+        self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
+        level = Level(B, device=dev) if level is True else None if level is False else level
+        # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
+        gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
+        spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True)
+        if spec.rate is not None:
+            resample.table(spec.rate, dev)
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
-                       max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate)
-        if marks:
-            self.kw["marks"] = True
+                       max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
+                       max_gap=self.max_gap, t=t)
         z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
         self.static = dict(tokens=torch.zeros((B, N), device=dev, dtype=torch.int64),
                            lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=z(B, 1, 256),
@@ -1122,34 +1144,23 @@ class GraphedSynthesis:
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
         self._neutral_tok = self.static["controls"].tok_buf.clone() if tok else None
-        _check_gap_args(pack, None, max_gap)
-        self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
         if self.passage:
             starts = torch.zeros((B,), device=dev, dtype=torch.int32)
             starts[:1] = 1
             self.static.update(starts=starts, s_prev=z(1, 256))
-            self.kw["t"] = t
-        if self.max_gap is not None:
-            self.static["gaps"] = torch.zeros((B,), device=dev, dtype=torch.int32)
-        if level is not None and level is not False:
-            level = Level(B, device=dev) if level is True else level
-            _check_level(level, B, pack)
+        if gaps is not None:
+            self.static["gaps"] = gaps
+        if level is not None:
             self.static["level"] = Level(B, target=level.target.to(dev).clone(), ceiling_db=level.ceiling_db,
                                          max_gain_db=level.max_gain_db, device=dev)
         self._g = None
 
     def _run(self):
-        st = self.static
-        more = {}
-        if self.passage:
-            more.update(passage=st["starts"], s_prev=st["s_prev"])
-        if self.max_gap is not None:
-            more.update(gaps=st["gaps"], max_gap=self.max_gap)
-        if st.get("level") is not None:
-            more.update(level=st["level"])
+        st = self.static  # a buffer the graph was built without is None here, as in a call that leaves the argument out
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
-                         controls=st["controls"], **more, **self.kw)
+                         controls=st["controls"], passage=st.get("starts"), s_prev=st.get("s_prev"), gaps=st.get("gaps"),
+                         level=st.get("level"), **self.kw)
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1245,34 +1256,23 @@ def _decode_groups(model, groups, dec, main, noise_of, ready=None, first=0):
     yield from queued
 
 
-def _check_capacity_args(tokens, *, max_frames, pack, trim, sample_rate, lengths_dev, marks, passage, gaps, max_gap, s_prev,
-                         controls, taps, front, durations, decode_streams, level=None):
-    """What `inference` refuses about the arguments of the capacity-bound path, before anything is launched, and what it
-    settles on the way -> (carry, gaps, max_gap, controls): whether the rows are a passage, the breaks as `_check_gaps` hands
-    them on, and the controls with the start flags of `passage=[...]` in their `t` row."""
-    _check_output(pack, sample_rate)
-    _check_level(level, tokens.shape[0], pack, max_frames)
-    if max_frames is None and (passage is not None or gaps is not None or max_gap is not None or s_prev is not None):
-        raise ValueError("passage / gaps / max_gap / s_prev belong to the capacity-bound path: pass max_frames")
-    _check_gap_args(pack, gaps, max_gap)
-    if gaps is None and max_gap is not None:
-        raise ValueError("max_gap bounds `gaps`: pass gaps")
+def _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations, decode_streams):
+    """What `inference` refuses about the arguments of the capacity-bound path that are not about the output (`_output_spec`,
+    which it calls first), before anything is launched, and what it settles on the way -> (carry, controls): whether the rows
+    are a passage, and the controls with the start flags of `passage=[...]` in their `t` row."""
+    if max_frames is None:
+        _capacity_only("passage / gaps / max_gap / s_prev", passage, s_prev)
+        _capacity_only("pack / trim / lengths_dev", lengths_dev)
     carry = passage is not None and passage is not False
     if s_prev is not None and not carry:
         raise ValueError("s_prev is the style a passage continues from: pass passage")
-    if gaps is not None:
-        gaps, max_gap = _check_gaps(gaps, max_gap, tokens.shape[0])
     if carry and passage is not True:
         if controls is not None:
             _check_controls(controls, tokens.device, tokens.shape[0], taps, front, durations, tokens.shape[1])
         controls = _passage_controls(controls, passage, tokens.shape[0], tokens.device)
-    if marks and (max_frames is None or pack is None):
-        raise ValueError("marks are positions in the packed samples of the capacity-bound path: pass max_frames and pack")
-    if max_frames is None and (pack is not None or trim is not None or lengths_dev is not None):
-        raise ValueError("pack / trim / lengths_dev belong to the capacity-bound path: pass max_frames")
     if max_frames is not None and decode_streams:
         raise ValueError("max_frames: there is ONE decoder call, on the current stream; `decode_streams` has no meaning here")
-    return carry, gaps, max_gap, controls
+    return carry, controls
 
 
 @torch.no_grad()
@@ -1346,10 +1346,9 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     loudness under the peak ceiling (`ops.wave_pack_level`); the result carries the table as `level` and `to_host(level=True)`
     brings it over in its one copy.  `wave` stays as the decoder made it, marks and sample counts do not move.
     """
-    carry, gaps, max_gap, controls = _check_capacity_args(
-        tokens, max_frames=max_frames, pack=pack, trim=trim, sample_rate=sample_rate, lengths_dev=lengths_dev, marks=marks,
-        passage=passage, gaps=gaps, max_gap=max_gap, s_prev=s_prev, controls=controls, taps=taps, front=front, durations=durations,
-        decode_streams=decode_streams, level=level)
+    spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level)
+    carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
+                                           decode_streams)
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
@@ -1371,8 +1370,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
                   main, ready)  # allocated on the front stream, consumed on the main stream
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, pack, trim, sample_rate, marks=bool(marks), gaps=gaps,
-                                max_gap=0 if gaps is None else max_gap, level=level)
+        return _decode_capacity(model, p, sine_noise, spec, gaps, level)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1500,15 +1498,13 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
         raise ValueError("controls must be a pipeline.Controls of one row per sentence (%d)" % len(sentences))
     if max_frames is not None:
-        return _synthesize_long_capacity(model, sampler, sentences, ref_s=ref_s, alpha=alpha, beta=beta, t=t,
-                                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, noises=noises,
-                                         step_noises=step_noises, sine_noises=sine_noises, durations=durations, trim=trim,
-                                         on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch,
-                                         decode_streams=decode_streams, controls=controls, max_frames=max_frames, pack=pack,
-                                         sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-                                         level=level)
-    if pack is not None or sample_rate is not None or marks or gaps is not None or max_gap is not None or level is not None:
-        raise ValueError("pack / sample_rate / marks / gaps / max_gap / level belong to the capacity-bound path: pass max_frames")
+        return _synthesize_long_capacity(
+            model, sampler, sentences, ref_s=ref_s, alpha=alpha, beta=beta, t=t, diffusion_steps=diffusion_steps,
+            embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
+            trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
+            controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
+            level=level)
+    _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
@@ -1587,7 +1583,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level=None):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -1604,10 +1600,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     tok_ctl = controls is not None and controls.tok_buf is not None
     if tok_ctl and controls.N != max(ns_all):
         raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
-    if gaps is not None:
-        _check_gap_args(pack, gaps, max_gap)
-        gaps, max_gap = _check_gaps(gaps, max_gap, K)
-    _check_level(level, K, pack)
+    # the K sentences' output, judged once (a `max_gap` without `gaps` is not looked at, as ever); every group's slice is, again
+    spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level)
     prepped = []
     for i, i_end in _front_chunks(front_batch, K):
         ids = list(range(i, i_end))
@@ -1625,14 +1619,13 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     s_prev, results = None, []
     for k, q in enumerate(prepped):
         i, j = q["ids"][0], q["ids"][-1] + 1
-        more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=max_gap)
-        if level is not None:
-            more.update(level=level.slice(i, j))
+        more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=spec.max_gap)
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
                         pack=pack, trim=trim, sample_rate=sample_rate, marks=marks, passage=True, s_prev=s_prev, t=t,
-                        controls=None if controls is None else controls.slice(i, j), **more)
+                        controls=None if controls is None else controls.slice(i, j),
+                        level=None if level is None else level.slice(i, j), **more)
         s_prev = res.style[-1:]
         results.append(res)
         if on_chunk is not None:

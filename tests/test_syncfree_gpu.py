@@ -358,3 +358,106 @@ def test_a_row_over_capacity_is_truncated_and_reported_and_the_others_are_untouc
         #                        DURATION_SUM the expansion raised for the same row goes with it
     assert [len(r) for r in rows] == [600 * f for f in f_over]
     assert ops.status() & CAPACITY_BITS == 0
+
+
+# ---- 6. the output options together ------------------------------------------------------------------
+def test_every_output_option_at_once_equals_the_pieces_composed_by_hand():
+    """Three rows of 12, 9 and 7 tokens at a capacity three frames above the longest, 16-bit PCM at 16 kHz with marks, breaks and a
+    level: the smallest call whose header has all five parts and a pad that is not zero.  What `to_host` hands back is, byte for
+    byte, `ops.wave_level`, `ops.wave_pack_level` and `ops.token_marks` over the result's own `wave` and `frames`."""
+    from test_passage_gpu import _passage, _sub
+    P = _passage("libritts")
+    model, sampler, trim = P["model"], P["sampler"], P["trim"]
+    tk, kw = _sub(P, 0, 3)
+    B, N = tk.shape
+    front = {k: v for k, v in kw.items() if k not in ("sine_noise", "trim")}
+    need = pipeline.prepare(model, sampler, tk, allow_ragged=True, ragged_decode=True, **front)["frames_host"]
+    T, gaps = max(need) + 3, [0, 5, 3]
+    assert len(set(need)) == B
+    lv = pipeline.Level(B, target=[-20.0, None, -30.0], max_gain_db=30.0)
+    torch.cuda.synchronize()
+    ops.status(clear=True)
+    res = pipeline.inference(model, sampler, tk, max_frames=T, pack="s16", sample_rate=16000, marks=True, gaps=gaps, level=lv, **kw)
+    rows, marks, level = res.to_host(marks=True, level=True)
+    rows, marks, level = [r.copy() for r in rows], marks.copy(), level.copy()
+    assert res.frames.cpu().tolist() == need and ops.status() & CAPACITY_BITS == 0
+    assert (res.pack, res.trim, res.sample_rate, res.max_gap, res.max_frames, res.samples_per_frame) == ("s16", trim, 16000, 5, T, 600)
+    header = 8 * (B + 1) + 4 * B * (N + 1) + 4 * B + 16 * B
+    assert header % 16 and res.packed.data_ptr() - res.offsets.data_ptr() == (header + 15) // 16 * 16
+    assert res.gaps.cpu().tolist() == gaps and tuple(res.marks.shape) == (B, N + 1) and tuple(res.level.shape) == (B, 4)
+    # by hand
+    p = pipeline.prepare(model, sampler, tk, max_frames=T, **front)
+    want_lv = ops.wave_level(res.wave, res.frames, lv.target, ceiling=lv.ceiling, max_gain_db=lv.max_gain_db, trim=trim)
+    want, woff = ops.wave_pack_level(res.wave, res.frames, want_lv, gaps=torch.tensor(gaps, dtype=torch.int32, device=DEV), max_gap=5,
+                                     rate=16000, fmt="s16", trim=trim)
+    want_m = ops.token_marks(p["durations"], res.frames, T, lengths=p["token_lengths"], shift=model.decoder.kind == "hifigan",
+                             trim=trim, rate=16000)
+    torch.cuda.synchronize()
+    want, offs = want.cpu().numpy(), woff.cpu().tolist()
+    assert torch.equal(res.offsets, woff) and res.to_host(passage=True).tobytes() == want[:offs[B]].tobytes()
+    for b in range(B):
+        assert rows[b].dtype == np.int16 and rows[b].tobytes() == want[offs[b]:offs[b + 1] - gaps[b]].tobytes(), "row %d" % b
+        assert not want[offs[b + 1] - gaps[b]:offs[b + 1]].any(), "the break behind row %d" % b
+    assert marks.dtype == np.int32 and marks.tobytes() == want_m.cpu().numpy().tobytes()
+    assert level.dtype == np.float32 and level.tobytes() == want_lv.cpu().numpy().tobytes()
+    assert level[1, 2] == 1.0 and level[0, 2] != 1.0, "row 1 is left alone, row 0 is not"
+    ops.check_status()
+
+
+def test_the_constructor_and_a_device_tensor_of_gaps_refuse_what_the_table_says(monkeypatch):
+    """The rows of tests/golden/output_refusals.json that need a device: `GraphedSynthesis` refuses in `__init__`, before any
+    capture, and `inference` a device tensor of gaps without `max_gap`."""
+    import json
+    import os
+    from test_output_spec_cpu import _arg
+    from test_passage_gpu import K, STEPS, _passage, _sub  # the passage's own draws: its number of diffusion steps
+    table = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "output_refusals.json")))
+    P = _passage("libritts")
+    recorded = []
+    monkeypatch.setattr(pipeline, "_record_graph", lambda *a, **kw: recorded.append(a))
+    cases = [c for c in table if c["entry"] == "graphed"]
+    assert {c["fault"] for c in cases} == {"marks without pack", "max_gap without pack", "bad sample_rate", "level without pack"}
+    for c in cases:
+        with pytest.raises(Exception) as e:
+            pipeline.GraphedSynthesis(P["model"], P["sampler"], K, P["b"]["tokens"].shape[1], P["T"], STEPS, ref_s=P["ref_s"], **c["args"])
+        assert type(e.value).__name__ == c["raises"] and str(e.value) == c["text"], c["fault"]
+    (c,) = [c for c in table if c["entry"] == "inference_device"]
+    tk, kw = _sub(P, 0, 2)
+    with pytest.raises(Exception) as e:
+        pipeline.inference(P["model"], P["sampler"], tk, **kw, **{k: _arg(v, DEV) for k, v in c["args"].items()})
+    assert type(e.value).__name__ == c["raises"] and str(e.value) == c["text"]
+    assert not recorded
+
+
+def test_one_graph_with_breaks_and_a_level_equals_the_eager_call_at_every_replay():
+    """ONE recorded graph with `pack`, `max_gap` and `level=True`: other breaks and other targets at the second replay, and at
+    each what `to_host(level=True)` hands back is the eager `inference` call on the same static inputs, byte for byte."""
+    from test_passage_gpu import K, STEPS, _passage  # the passage's own draws: its number of diffusion steps
+    P = _passage("libritts")
+    model, sampler, b = P["model"], P["sampler"], P["b"]
+    T, N = P["T"], b["tokens"].shape[1]
+    out = dict(pack="s16", sample_rate=16000)
+    gs = pipeline.GraphedSynthesis(model, sampler, K, N, T, STEPS, ref_s=P["ref_s"], trim=P["trim"], lj_tail=False, max_gap=40,
+                                   level=True, **out)
+    ld = b["lengths"].to(torch.int32).to(DEV)
+    feed = dict(tokens=b["tokens"], lengths=ld, noise=b["noise"], step_noise=b["step_noise"], sine_noise=b["sine"])
+    eager_kw = dict(P["kw"], input_lengths=None, lengths_dev=ld, max_frames=T, **out)
+    graph = None
+    for i, (gaps, targets) in enumerate((([7, 0, 40, 3], [-20.0, -23.0, None, -30.0]), ([0, 55, 1, 9], [-35.0, None, -18.0, -27.0]))):
+        res = gs(gaps=gaps, level=targets, **(feed if i == 0 else {}))
+        graph = gs._g["graph"] if graph is None else graph
+        assert gs._g["graph"] is graph, "no re-record"
+        rows, lv = res.to_host(level=True)
+        rows, lv, whole = [r.copy() for r in rows], lv.copy(), res.to_host(passage=True).copy()
+        eager = pipeline.inference(model, sampler, b["tokens"], gaps=torch.tensor(gaps, dtype=torch.int32, device=DEV), max_gap=40,
+                                   level=pipeline.Level(K, target=targets), **eager_kw)
+        erows, elv = eager.to_host(level=True)
+        assert torch.equal(res.wave, eager.wave) and torch.equal(res.offsets, eager.offsets), "replay %d" % i
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(rows, erows)) and lv.tobytes() == elv.tobytes(), "replay %d" % i
+        assert whole.tobytes() == eager.to_host(passage=True).tobytes(), "replay %d" % i
+        offs = res.offsets.cpu().tolist()
+        assert [offs[k + 1] - offs[k] - len(rows[k]) for k in range(K)] == [min(g, 40) for g in gaps]
+        assert [bool(v == 1.0) for v in lv[:, 2]] == [t is None for t in targets]
+    torch.cuda.synchronize()
+    assert ops.status() & CAPACITY_BITS == 0
+    ops.check_status()
