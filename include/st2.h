@@ -668,6 +668,38 @@ int st2_wave_pack_level(const float* wave, int64_t w_bs, const int32_t* frames, 
                         int32_t taps_per_phase, int32_t fmt /* st2_pcm_format */, const int32_t* gaps, int32_t gap_cap,
                         void* out, int64_t out_capacity, int64_t* offsets, void* stream, const float* level);
 
+/* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
+ * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
+ * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one
+ * int64 seed per row.  A plain-C host needs no generator of its own: it fills the `noise` / `step_noise` of st2_front_args and the
+ * `noise` of st2_decoder_forward(_ragged) with this entry, on the stream the plans run on.
+ * Values.  Element i of noise stream s of a row with seed k is output (i mod 4) of the four values made from
+ *     Philox4x32-10(counter = (i div 4, 0, s, 0), key = (lo32(k), hi32(k))),    k read as uint64
+ * (Random123's generator: multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds).  A row's
+ * values depend on its seed, the stream id and i alone: not on B, not on the row's place in the batch, not on n.
+ *   ST2_NOISE_BITS    the four 32-bit words x0 .. x3 themselves, as their bit pattern (for tests and callers that want integers);
+ *   ST2_NOISE_NORMAL  fp32 standard normals, pairwise from (x0, x1) and (x2, x3): with u1 = ((x >> 8) + 0.5) 2^-24,
+ *                     r = sqrt(-2 ln u1) and a = 2 ((x' >> 8) 2^-24) -- exact in fp32 -- the pair is (r cos(pi a), r sin(pi a));
+ *                     |z| <= 5.89.  Full-precision logf / sqrtf / sincospif; within 8 2^-24 max(1, |z|) of the fp64 value.
+ * Stream ids: ST2_NOISE_SAMPLER the sampler's start noise [B][256]; ST2_NOISE_STEP + j the draws of sampler step j;
+ * ST2_NOISE_SINE the harmonic source's [B][F U][9].
+ * Layout.  out[s][b][i] at out + s * s_stride + b * b_stride + i (strides in elements) for s < S, b < B, written with noise stream
+ * stream0 + s under seeds[b] (int64 [B], device: read by the kernel, so a captured launch serves any seeds), for i in
+ * [0, min(n, counts[b] * per_count)) -- counts int32 [B] on the device, a negative one counting as 0 -- or [0, n) where counts
+ * is NULL.  Nothing else is written: padding between rows and a row's tail past its count stay as they are.  (The source noise
+ * of a ragged batch: counts = the frame counts, per_count = U * 9; st2_har_source_len reads no further.)
+ * One launch, one thread per counter, 16-byte stores where the row's base is 16-byte aligned and 4-byte stores elsewhere; no
+ * allocation, no synchronisation: legal under stream capture.  n = 0 is a successful no-op.  Returns non-zero before any launch
+ * on: NULL seeds / out; B or S outside 1..65535; n < 0 or n >= 2^34 (i div 4 is the counter's first word); an unknown kind;
+ * stream0 + S - 1 past 2^32 - 1; B > 1 with b_stride < n (or >= 2^40); S > 1 with s_stride < (B - 1) b_stride + n; counts with
+ * per_count <= 0; seeds / out / counts misaligned for its element. */
+enum st2_noise_kind { ST2_NOISE_NORMAL = 0, ST2_NOISE_BITS = 1 };
+#define ST2_NOISE_SAMPLER 0u
+#define ST2_NOISE_STEP 1u
+#define ST2_NOISE_SINE 0x10000u
+int st2_noise_fill(const int64_t* seeds, int32_t B, uint32_t stream0, int32_t S, int32_t kind /* st2_noise_kind */, float* out,
+                   int64_t s_stride, int64_t b_stride, int64_t n, const int32_t* counts, int64_t per_count, void* stream);
+
 /* ---- reference clips at a client's rate and in G.711 (added under ABI 23, additive: one kernel-level entry point and its
  * size helper, no new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
  * st2_clip_ingest: the way in of a zero-shot request.  src holds B rows of N_cap samples (row b at

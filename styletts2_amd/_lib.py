@@ -24,6 +24,8 @@ STATUS_F16_RANGE, STATUS_LSTM_TIMEOUT, STATUS_DURATION_SUM, STATUS_LSTM_RECOVERE
 STATUS_FRAME_CAPACITY = 16  # added under ABI 23: a row was truncated to the caller's frame capacity
 PACK_F32, PACK_S16 = 0, 1  # enum st2_pack_format
 PCM_F32, PCM_S16, PCM_ULAW, PCM_ALAW = range(4)  # enum st2_pcm_format (st2_wave_resample_pack)
+NOISE_NORMAL, NOISE_BITS = 0, 1  # enum st2_noise_kind (st2_noise_fill)
+NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = 0, 1, 0x10000  # ST2_NOISE_*: the noise stream ids of a synthesis (step j draws 1 + j)
 ACT_NONE, ACT_GELU, ACT_EXP_SIN, ACT_TANH, ACT_LEAKY, ACT_GELU_TANH = range(6)
 
 
@@ -274,6 +276,8 @@ _SIGNATURES = {
     "st2_wave_pack_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p, f32p]),
+    "st2_noise_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int64,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_clip_ingest_work_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "st2_clip_ingest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
                                   C.c_int32, C.c_float, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1361,6 +1361,44 @@ def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samp
     return out
 
 
+NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*
+
+
+def noise_fill(seeds, out, stream0, counts=None, per_count=None, bits=False, streams=None):
+    """`st2_noise_fill`: the noise of B requests from their seeds, drawn on the device.  seeds int64 [B] on
+    the device; `out` [B, ...] -- or, with `streams=S`, [S, B, ...] -- float32 (int32 with `bits`) on the same device, every
+    row's trailing axes dense: row b (of noise stream `stream0`, or `stream0 + s` for out[s]) receives the values 0 .. n - 1 of
+    that stream under seeds[b], n the row's element count.  Rows may be strided views (padding between them is not touched).
+    `counts` (int32 [B] on the device) with `per_count`: row b receives its first min(n, counts[b] * per_count) values only
+    and keeps the rest as it is.  `bits`: the raw 32-bit Philox words instead of normals.  Equal seeds give equal rows, bit for
+    bit, whatever B and wherever the row lies.  One launch, no host read; legal under stream capture.  Returns `out`."""
+    _chk_dev(seeds, "seeds", torch.int64, 1)
+    B = seeds.numel()
+    lp = _chk_len(counts, "counts", B, seeds)
+    if (counts is None) != (per_count is None):
+        raise _lib.St2Error("counts and per_count go together")
+    _chk_on_dev(out, "out")
+    want = torch.int32 if bits else torch.float32
+    lead = 1 if streams is None else 2
+    if out.dtype != want or out.device != seeds.device or out.dim() < lead or out.shape[lead - 1] != B or (
+            streams is not None and out.shape[0] != int(streams)):
+        raise _lib.St2Error("out must be a %s tensor of shape %s on the device of seeds (got %s %s on %s)" % (
+            want, ("[%d, ...]" % B) if streams is None else "[%d, %d, ...]" % (int(streams), B), out.dtype, tuple(out.shape), out.device))
+    n = 1
+    for d in range(out.dim() - 1, lead - 1, -1):  # the trailing axes of a row are dense, in order
+        if out.shape[d] != 1 and out.stride(d) != n:
+            raise _lib.St2Error("out: the axes behind the batch axis must be dense (shape %s, strides %s)" % (
+                tuple(out.shape), tuple(out.stride())))
+        n *= out.shape[d]
+    S = 1 if streams is None else int(streams)
+    if S == 0 or n == 0:
+        return out
+    _lib.check(_lib.load().st2_noise_fill(seeds.data_ptr(), B, int(stream0), S, _lib.NOISE_BITS if bits else _lib.NOISE_NORMAL,
+                                          out.data_ptr(), out.stride(0) if streams is not None else 0, out.stride(lead - 1), n, lp,
+                                          0 if per_count is None else int(per_count), _stream()), "st2_noise_fill")
+    return out
+
+
 def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):
     """`st2_clip_ingest`: reference clips in a client's rate and sample format -> trimmed fp32 rows at 24 kHz.  src [B, N_cap]
     on the device, of the dtype of `fmt` ("f32" float32, "s16" int16, "ulaw" / "alaw" uint8), n int32 [B] on the device (row

@@ -1112,11 +1112,18 @@ class GraphedSynthesis:
     pack over one more static buffer, `static["level"]` (a `Level`; at first -16 LUFS in every row, or the one given):
     `__call__(level=)` -- a `Level`, one target or B of them, None / NaN = leave the row alone -- copies the targets into its
     row, so one graph serves any targets; the ceiling and the gain limit are the graph's own.  Without it the graph records
-    exactly what it recorded before."""
+    exactly what it recorded before.
+
+    `seeds=True`: the graph draws its own noise.  `static["seeds"]` (int64 [B], zeros at first) takes the
+    place of the three noise buffers, which such a graph does not have; the three `ops.noise_fill` launches are recorded in the
+    graph and read the seeds on the device, so one recorded graph serves any seeds: `__call__(seeds=)` -- an int64 [B] tensor
+    or B ints -- copies them in, and a call without them replays the seeds it holds, i.e. the same rendition.  `noise` /
+    `step_noise` / `sine_noise` are refused by such a graph, `seeds` by a graph built without it, which has no such key and
+    records exactly what it recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None):
+                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1135,11 +1142,15 @@ class GraphedSynthesis:
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
         z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
+        drawn = None if seeds else True  # a seeded graph has no noise buffers: `inference(seeds=)` draws into its own
         self.static = dict(tokens=torch.zeros((B, N), device=dev, dtype=torch.int64),
-                           lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=z(B, 1, 256),
-                           step_noise=z(max(self.steps - 1, 0), B, 1, 256), sine_noise=z(B, 600 * self.max_frames, 9),
+                           lengths_dev=torch.full((B,), N, device=dev, dtype=torch.int32), noise=drawn and z(B, 1, 256),
+                           step_noise=drawn and z(max(self.steps - 1, 0), B, 1, 256),
+                           sine_noise=drawn and z(B, 600 * self.max_frames, 9),
                            ref_s=None if ref_s is None else ref_s.detach().to(dev, torch.float32).reshape(-1, 256)
                            .expand(B, -1).contiguous())
+        if seeds:
+            self.static["seeds"] = torch.zeros((B,), device=dev, dtype=torch.int64)
         tok = bool(marks) if token_controls is None else bool(token_controls)
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
@@ -1160,7 +1171,7 @@ class GraphedSynthesis:
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
                          controls=st["controls"], passage=st.get("starts"), s_prev=st.get("s_prev"), gaps=st.get("gaps"),
-                         level=st.get("level"), **self.kw)
+                         level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1173,8 +1184,15 @@ class GraphedSynthesis:
 
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
-                 starts=None, s_prev=None, gaps=None, level=None):
+                 starts=None, s_prev=None, gaps=None, level=None, seeds=None):
         st = self.static
+        if "seeds" in st and (noise is not None or step_noise is not None or sine_noise is not None):
+            raise ValueError("this graph draws noise, step_noise and sine_noise from its seeds: pass seeds, one or the other")
+        if seeds is not None:
+            if "seeds" not in st:
+                raise ValueError("this graph was built without seeds: pass seeds=True")
+            rows = seed_rows(seeds, st["seeds"].numel())
+            st["seeds"].copy_(rows if torch.is_tensor(rows) else torch.tensor(rows, dtype=torch.int64), non_blocking=True)
         built_by = dict(starts="passage=True", s_prev="passage=True", gaps="max_gap")  # the buffers a plain graph lacks
         for name, val in (("starts", starts), ("s_prev", s_prev), ("gaps", gaps), ("tokens", tokens), ("lengths_dev", lengths),
                           ("noise", noise), ("step_noise", step_noise), ("sine_noise", sine_noise), ("ref_s", ref_s)):
@@ -1275,12 +1293,56 @@ def _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, contr
     return carry, controls
 
 
+def seed_rows(seeds, K):
+    """`seeds` of K rows as the host list of K ints a sequence gives, or the int64 [K] device tensor as it is.  One int s means
+    s, s + 1, ..., s + K - 1, wrapping from 2^63 - 1 to -2^63 (the seed is 64 bits, read as unsigned by the generator)."""
+    if isinstance(seeds, int) and not isinstance(seeds, bool):
+        seeds = [(seeds + k + 2 ** 63) % 2 ** 64 - 2 ** 63 for k in range(K)]
+    if torch.is_tensor(seeds):
+        if seeds.dtype != torch.int64 or seeds.dim() != 1 or seeds.numel() != K:
+            raise ValueError("seeds must be an int64 tensor of %d entries, got %s %s" % (K, seeds.dtype, tuple(seeds.shape)))
+        return seeds if seeds.is_cuda else seeds.tolist()
+    seeds = list(seeds)
+    if len(seeds) != K or not all(isinstance(v, int) and not isinstance(v, bool) and -2 ** 63 <= v < 2 ** 63 for v in seeds):
+        raise ValueError("seeds must be %d whole numbers in the int64 range, got %r" % (K, seeds))
+    return seeds
+
+
+def _check_seeds(seeds, B, max_frames, noise, step_noise, sine_noise):
+    """What `inference` refuses about `seeds` (an input, not an output option: DESIGN.md section 25), before anything is
+    launched -> the seeds as `seed_rows` gives them."""
+    if max_frames is None:
+        _capacity_only("seeds", seeds)
+    if noise is not None or step_noise is not None or sine_noise is not None:
+        raise ValueError("seeds draw noise, step_noise and sine_noise on the device: pass one or the other")
+    return seed_rows(seeds, B)
+
+
+def _seeds_on(seeds, dev):
+    return seeds if torch.is_tensor(seeds) else torch.tensor(seeds, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def _seeded_front_noise(seeds, B, steps, dev):
+    """The sampler's start noise [B, 1, 256] and its per-step draws [steps - 1, B, 1, 256] under `seeds`: two launches."""
+    e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+    return (ops.noise_fill(seeds, e(B, 1, 256), ops.NOISE_SAMPLER),
+            ops.noise_fill(seeds, e(max(steps - 1, 0), B, 1, 256), ops.NOISE_STEP, streams=max(steps - 1, 0)))
+
+
+def _seeded_sine_noise(seeds, frames, max_frames):
+    """The harmonic source's draws [B, 600 max_frames, 9] under `seeds`: one launch behind the front, which writes row b's
+    600 frames[b] * 9 values and no more -- the ragged source kernel reads no further (st2_har_source_len)."""
+    out = torch.empty((seeds.numel(), 600 * int(max_frames), 9), device=seeds.device, dtype=torch.float32)
+    return ops.noise_fill(seeds, out, ops.NOISE_SINE, counts=frames, per_count=600 * 9)
+
+
 @torch.no_grad()
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
-              sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None):
+              sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
+              seeds=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1345,10 +1407,18 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     (`ops.wave_level`: BS.1770-4 integrated loudness and sample peak) and packed with the gain that brings it to its target
     loudness under the peak ceiling (`ops.wave_pack_level`); the result carries the table as `level` and `to_host(level=True)`
     brings it over in its one copy.  `wave` stays as the decoder made it, marks and sample counts do not move.
+
+    `seeds` (with `max_frames`): one int64 seed per row -- an int64 [B] device tensor, never read on the
+    host, or a host sequence of B ints -- instead of `noise`, `step_noise` and `sine_noise` (one or the other): the three are
+    drawn on the device by `ops.noise_fill`, three launches, under the noise stream ids of include/st2.h.  A row's draws depend
+    on its seed alone: the same seed gives the same draws in any batch and at any place in it.  Without `seeds` the call
+    issues exactly the launches it always did.
     """
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level)
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
+    if seeds is not None:
+        seeds = _seeds_on(_check_seeds(seeds, tokens.shape[0], max_frames, noise, step_noise, sine_noise), tokens.device)
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
@@ -1357,18 +1427,22 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         kw.update(max_frames=max_frames, lengths_dev=lengths_dev)
     if carry:
         kw.update(carry=True, s_prev=s_prev, t=t)
+    seeded = lambda: {} if seeds is None else dict(zip(("noise", "step_noise"), _seeded_front_noise(
+        seeds, tokens.shape[0], diffusion_steps, tokens.device)))  # drawn on the stream the front reads them on
     if front_stream is None:
-        p = prepare(model, sampler, tokens, **kw)
+        p = prepare(model, sampler, tokens, **dict(kw, **seeded()))
     else:
         main = torch.cuda.current_stream(tokens.device)
-        if inputs_on_main:
+        if inputs_on_main or seeds is not None:  # (the seeds may just have been copied in on the current stream)
             front_stream.wait_stream(main)
         with torch.cuda.stream(front_stream):
-            p = prepare(model, sampler, tokens, **kw)
+            p = prepare(model, sampler, tokens, **dict(kw, **seeded()))
             ready = torch.cuda.Event()
             ready.record(front_stream)
         _hand_off([v for g in ([p] if "groups" not in p else [g for _, g in p["groups"]]) for v in _decoder_inputs(g)],
                   main, ready)  # allocated on the front stream, consumed on the main stream
+    if seeds is not None:
+        sine_noise = _seeded_sine_noise(seeds, p["frames"], max_frames)
     if max_frames is not None:
         return _decode_capacity(model, p, sine_noise, spec, gaps, level)
     if "frames" in p:
@@ -1439,7 +1513,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None):
+                    max_gap=None, level=None, seeds=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1493,6 +1567,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `sine_noises` rows are stacked, zero-padded, to the capacity.  Per-token controls are served here: the rows are
     right-padded to the controls' width N, which must be the longest sentence's.  `decode_streams` > 1 is refused (there is one
     decoder call per group, on the caller's stream); `overlap`, `front`, `side_stream` and `ragged_decode` have no meaning.
+    `seeds` (needs `max_frames`): one seed per SENTENCE -- K ints or an int64 [K] device tensor -- or one
+    int s, which stands for s, s + 1, ..., s + K - 1 (wrapping from 2^63 - 1 to -2^63: the seed is 64 bits), instead of `noises`,
+    `step_noises` and `sine_noises`: every sentence's noise is drawn on the device from its own seed (`inference(seeds=)`), the
+    same draws whatever `front_batch` groups it with.
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
@@ -1503,8 +1581,9 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level)
+            level=level, seeds=seeds)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
+    _capacity_only("seeds", seeds)
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
@@ -1583,11 +1662,13 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
     T_cap = int(max_frames)
+    if seeds is not None:  # judged once for the K sentences; every group's slice is, again, by `inference`
+        seeds = _seeds_on(_check_seeds(seeds, K, max_frames, noises, step_noises, sine_noises), dev)
     if isinstance(decode_streams, (list, tuple)) and len(decode_streams) > 1 or \
             not isinstance(decode_streams, (list, tuple)) and decode_streams and int(decode_streams) > 1:
         raise ValueError("max_frames: there is ONE decoder call per front group, on the current stream; `decode_streams` has no "
@@ -1625,7 +1706,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
                         pack=pack, trim=trim, sample_rate=sample_rate, marks=marks, passage=True, s_prev=s_prev, t=t,
                         controls=None if controls is None else controls.slice(i, j),
-                        level=None if level is None else level.slice(i, j), **more)
+                        level=None if level is None else level.slice(i, j),
+                        seeds=None if seeds is None else seeds[i:j], **more)
         s_prev = res.style[-1:]
         results.append(res)
         if on_chunk is not None:
