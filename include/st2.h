@@ -700,6 +700,43 @@ enum st2_noise_kind { ST2_NOISE_NORMAL = 0, ST2_NOISE_BITS = 1 };
 int st2_noise_fill(const int64_t* seeds, int32_t B, uint32_t stream0, int32_t S, int32_t kind /* st2_noise_kind */, float* out,
                    int64_t s_stride, int64_t b_stride, int64_t n, const int32_t* counts, int64_t per_count, void* stream);
 
+/* ---- fit to duration: per-request frame targets apportioned on the device (added under ABI 23, additive: one kernel-level
+ * entry point, no new backend-table slot, no struct change, no new sticky status bit -- the flag column of `report` carries
+ * what a status bit would) ------------------------------------------------------------------------- *
+ * st2_durations_fit: rewrites every row of the integer durations (int64 [B][N], N <= 512, as the duration head or a caller made
+ * them) to a stated total of frames, between the front and st2_frames_from_durations.  Everything that takes its timing from
+ * the durations -- the frame counts, the expansion, the timing marks, the per-token prosody spans -- follows with no change.
+ * All integer arithmetic; a row's result depends on that row alone.
+ *   len     int32 [B] or NULL: the rows' token counts, clamped to 0..N; NULL = N.
+ *   target  int32 [B]: the frame targets; <= 0 leaves the row alone.
+ *   hold    uint8 [B][N] or NULL: non-zero = this token keeps its duration.  NULL = no token is held.
+ *   out     int64 [B][N]; may be dur itself (in place), must not overlap it otherwise.
+ *   report  int32 [B][4] or NULL: {S, T', flag, number of tokens n < n_b with out[n] != dur[n]} per row.
+ * Per row b, with n_b the clamped length:
+ *   1. target[b] <= 0: all N entries of out equal dur's; report {S, S, 0, 0}, S as in step 2.
+ *   2. v_n = max(dur[n], 1) for n < n_b, S = sum of min(v_n, 2^31) (a term is saturated so that no caller-made duration wraps
+ *      the sum; S <= 2^31 - 1 is exact either way), reported as min(S, 2^31 - 1).  In a fitted row the entries n >= n_b of out
+ *      are 0, as the duration head writes them.  n_b = 0: the row is all zeros, report {0, 0, 2, 0}.  S > 2^31 - 1: the row
+ *      is copied as in step 1, report {2^31 - 1, 2^31 - 1, 3, 0}.
+ *   3. Held tokens: base_n = v_n, m_n = 0.  Free tokens: base_n = 1, m_n = v_n - 1 -- no token drops under one frame; the
+ *      excess over that frame is what stretches and shrinks.  lo = sum of base_n.
+ *   4. lo > T_cap: the row is copied as in step 1, report {S, S, 3, 0}.  Else T' = min(max(target[b], lo), T_cap) and
+ *      flag = 0 if T' == target[b], else 1: the target was infeasible and the nearest feasible total was taken.
+ *   5. R = T' - lo, M = sum of m_n.  M = 0 (every free token is one frame long): m_n = 1 for the free tokens, M = their count.
+ *      No free token at all: the row is copied as in step 1, report {S, S, 2, 0}.
+ *   6. Largest remainders: q_n = floor(R m_n / M), r_n = (R m_n) mod M, K = R - sum of q_n; the K tokens with m_n > 0 that
+ *      have the largest r_n, ties to the LOWER index, get one frame more: out[n] = base_n + q_n + [extra].  (R m_n < 2^62.)
+ *   7. report[b] = {S, T', flag, changed}.
+ * Then: the row sums to T' exactly; T' = target wherever lo <= target <= T_cap; T' = S returns the row's v_n; held tokens
+ * are unchanged; among free tokens dur[a] < dur[b] implies out[a] <= out[b].
+ * One launch, one workgroup of 256 threads per row, at most two tokens per thread, read into registers before anything is
+ * written (in place is legal); block sums in a fixed order; a token's rank is a count over the row's (r, -index) keys in LDS.
+ * No atomics, no allocation, no synchronisation: legal under stream capture.  len, target and hold are read by the kernel: a
+ * captured launch serves any of them.  Returns non-zero before any launch on: NULL dur / target / out; B outside 1..65535;
+ * N outside 1..512; T_cap <= 0; dur / out not 8-byte aligned, len / target / report not 4-byte aligned. */
+int st2_durations_fit(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* target, const uint8_t* hold,
+                      int32_t T_cap, int64_t* out, int32_t* report, void* stream);
+
 /* ---- reference clips at a client's rate and in G.711 (added under ABI 23, additive: one kernel-level entry point and its
  * size helper, no new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
  * st2_clip_ingest: the way in of a zero-shot request.  src holds B rows of N_cap samples (row b at

@@ -278,6 +278,8 @@ _SIGNATURES = {
                                       C.c_void_p, f32p]),
     "st2_noise_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_durations_fit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "st2_clip_ingest_work_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "st2_clip_ingest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
                                   C.c_int32, C.c_float, C.c_int32, f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1399,6 +1399,44 @@ def noise_fill(seeds, out, stream0, counts=None, per_count=None, bits=False, str
     return out
 
 
+FIT_OK, FIT_NEAREST, FIT_NOTHING_FREE, FIT_REFUSED = range(4)  # the flag column of st2_durations_fit's report (st2.h)
+
+
+def durations_fit(dur, target, T_cap, lengths=None, hold=None, out=None, report=None):
+    """`st2_durations_fit`: every row of the integer durations rewritten to a stated total of frames (the
+    value definition is include/st2.h's).  dur int64 [B, N] on the device, N <= 512; target int32 [B] on the device (<= 0
+    leaves the row alone); `lengths` int32 [B] on the device or None (= N); `hold` bool / uint8 [B, N] on the device or None:
+    non-zero = the token keeps its duration; `out` int64 [B, N], None = a new tensor, `dur` itself = in place; `report` int32
+    [B, 4], None = a new tensor: {S, T', flag, tokens changed} per row.  One launch, no host read; legal under stream
+    capture.  Returns (out, report)."""
+    _chk_dev(dur, "dur", torch.int64, 2)
+    B, N = dur.shape
+    lp = _chk_len(lengths, "lengths", B, dur)
+    tp = _chk_len(target, "target", B, dur)
+    if target is None:
+        raise _lib.St2Error("target must be an int32 tensor of %d entries (got None)" % B)
+    hp = 0
+    if hold is not None:
+        _chk_on_dev(hold, "hold")
+        if hold.dtype not in (torch.bool, torch.uint8) or tuple(hold.shape) != (B, N) or not hold.is_contiguous() \
+                or hold.device != dur.device:
+            raise _lib.St2Error("hold must be a contiguous bool / uint8 [%d, %d] tensor on the device of dur (got %s %s on %s)" % (
+                B, N, hold.dtype, tuple(hold.shape), hold.device))
+        hp = hold.data_ptr()
+    if out is None:
+        out = torch.empty_like(dur)
+    _chk_dev(out, "out", torch.int64, 2)
+    if report is None:
+        report = torch.empty((B, 4), device=dur.device, dtype=torch.int32)
+    _chk_dev(report, "report", torch.int32, 2)
+    if out.shape != dur.shape or out.device != dur.device or tuple(report.shape) != (B, 4) or report.device != dur.device:
+        raise _lib.St2Error("out must be [%d, %d] and report [%d, 4] on the device of dur (got %s on %s, %s on %s)" % (
+            B, N, B, tuple(out.shape), out.device, tuple(report.shape), report.device))
+    _lib.check(_lib.load().st2_durations_fit(dur.data_ptr(), B, N, lp, tp, hp, int(T_cap), out.data_ptr(), report.data_ptr(),
+                                             _stream()), "st2_durations_fit")
+    return out, report
+
+
 def clip_ingest(src, n, rate, fmt, top_db=30.0, L_cap=None, L_min=0, out=None, want_start=True, want_flags=True):
     """`st2_clip_ingest`: reference clips in a client's rate and sample format -> trimmed fp32 rows at 24 kHz.  src [B, N_cap]
     on the device, of the dtype of `fmt` ("f32" float32, "s16" int16, "ulaw" / "alaw" uint8), n int32 [B] on the device (row

@@ -595,7 +595,7 @@ class GraphedFront:
 def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
             ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, lj_tail=None, s_prev=None, t=0.7,
             taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False,
-            ragged_decode=False, max_frames=None, controls=None):
+            ragged_decode=False, max_frames=None, controls=None, fit=None):
     """Everything in front of the decoder: text encoder, PL-BERT, style diffusion, style mixing, duration and
     prosody prediction, alignment expansion.  Returns the decoder's inputs {asr, F0, N, ref} plus the mixed style
     vector `s_pred` [B, 256] (what LFinference hands to the next sentence) and the durations.
@@ -643,9 +643,16 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     then one launch), pitch and energy are applied to F0 / N right behind every prosody call (`ops.prosody_controls`).  Nothing
     of it is read on the host; None takes the code paths without it.  Its per-token rows go the same two
     ways: the rate through `st2_front_forward_tok`, pitch and energy through `ops.prosody_controls_tok` right behind
-    `ops.prosody_controls`."""
+    `ops.prosody_controls`.
+
+    `fit` (with `max_frames`): (targets int32 [B] on the device, hold bool / uint8 [B, N] on the device or
+    None) -- the durations, predicted or forced, are rewritten to the targets by ONE launch (`ops.durations_fit`) right in front
+    of `ops.frames_from_durations`; the fitted tensor is what the frame counts, the prosody call, the controls' per-token spans
+    and the result's `durations` see, and the result carries the launch's report as `fit` (int32 [B, 4], device)."""
     dev = tokens.device
     B, N = tokens.shape
+    if max_frames is None:
+        _capacity_only("fit_frames / fit_hold", fit)
     if controls is not None:
         _check_controls(controls, dev, B, taps, front, durations, N)
     if max_frames is not None:
@@ -702,10 +709,13 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         else:
             durations, len_arg = durations.long().to(dev), None  # the caller's: pad-token frames count like any other
         durations = durations.contiguous()
+        fitted = {}
+        if fit is not None:  # out of place: forced durations are the caller's tensor
+            durations, fitted["fit"] = ops.durations_fit(durations, fit[0], T_cap, lengths=len_arg, hold=fit[1])
         frames = ops.frames_from_durations(durations, len_arg, T_cap)
         d_cm = d.transpose(-1, -2).contiguous()
         return dict(out, durations=durations, **prosody(whole, durations, T_cap, frames), frames=frames, max_frames=T_cap,
-                    token_lengths=len_arg)
+                    token_lengths=len_arg, **fitted)
     if durations is None:
         durations = f["durations"]
         tot = durations.sum(dim=1).tolist()  # the path's one data-dependent host sync: the frame counts
@@ -825,15 +835,20 @@ class SynthesisResult:
                passed the gates), its sample peak, the linear gain its packed samples were multiplied by and the number of gating
                blocks that passed -- measured on `wave`, which stays as the decoder made it.  Kept in the same allocation behind
                the gaps: `to_host(level=True)` is still one copy.
+      fit      (with `fit_frames=`) int32 [B, 4]: {the row's frames before the fit, its frames after,
+               flag, the number of tokens whose duration changed}; flag 0 = the target was met, 1 = it was infeasible and the
+               nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
+               as it was (its held tokens alone exceed the capacity, or a forced total beyond 2^31 - 1).  A small tensor of its
+               own, NOT a part of the hand-over allocation: reading it (`result.fit.cpu()`) is a copy of its own.
     `to_host()` is the one place that waits.  Made with `spec` (an `_Output`, trim resolved: `trim`, `pack`, `sample_rate`, `max_gap`)
     and `ho` (the `_HandOver` that `_hand_over` returned for it, None without `pack`: `packed`, `offsets`, `gaps`, `level`)."""
 
-    def __init__(self, wave, frames, max_frames, spec=None, ho=None, marks=None, style=None):
+    def __init__(self, wave, frames, max_frames, spec=None, ho=None, marks=None, style=None, fit=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
         self.spec = spec = _Output() if spec is None else spec
         self.trim, self.pack, self.sample_rate, self.max_gap = int(spec.trim), spec.fmt, _rate(spec.sample_rate), spec.max_gap
-        self.marks, self.style = marks, style
+        self.marks, self.style, self.fit = marks, style, fit
         self._take(ho)
         self._host = None  # the buffer's pinned mirror, allocated by the first to_host()
 
@@ -1063,7 +1078,7 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level):
     if spec.trim is None:  # read here and nowhere else: `inference`'s default, Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
         spec = spec._replace(trim=50 if hifigan else 0)
     if spec.fmt is None:
-        return SynthesisResult(w, p["frames"], T_cap, spec, style=p["s_pred"])
+        return SynthesisResult(w, p["frames"], T_cap, spec, style=p["s_pred"], fit=p.get("fit"))
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
@@ -1074,7 +1089,7 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level):
         m = ho.marks.view(B, N + 1)
         ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
                         rate=spec.sample_rate, samples_per_frame=spf, out=m)
-    return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"])
+    return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"], fit=p.get("fit"))
 
 
 class GraphedSynthesis:
@@ -1119,11 +1134,17 @@ class GraphedSynthesis:
     graph and read the seeds on the device, so one recorded graph serves any seeds: `__call__(seeds=)` -- an int64 [B] tensor
     or B ints -- copies them in, and a call without them replays the seeds it holds, i.e. the same rendition.  `noise` /
     `step_noise` / `sine_noise` are refused by such a graph, `seeds` by a graph built without it, which has no such key and
-    records exactly what it recorded before."""
+    records exactly what it recorded before.
+
+    `fit=True`: the graph records the one `ops.durations_fit` launch over two more static buffers,
+    `static["fit_frames"]` (int32 [B], zeros: every row left alone) and `static["fit_hold"]` (uint8 [B, N], zeros: no token
+    held), both read on the device, so one recorded graph serves any targets: `__call__(fit_frames=, fit_hold=)` copies them in
+    (what is left out keeps its contents) and the result carries `fit`.  A graph built without it has neither key, refuses both
+    arguments and records exactly what it recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False):
+                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1151,6 +1172,9 @@ class GraphedSynthesis:
                            .expand(B, -1).contiguous())
         if seeds:
             self.static["seeds"] = torch.zeros((B,), device=dev, dtype=torch.int64)
+        if fit:
+            self.static.update(fit_frames=torch.zeros((B,), device=dev, dtype=torch.int32),
+                               fit_hold=torch.zeros((B, N), device=dev, dtype=torch.uint8))
         tok = bool(marks) if token_controls is None else bool(token_controls)
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
@@ -1171,7 +1195,8 @@ class GraphedSynthesis:
         return inference(self.model, self.sampler, st["tokens"], noise=st["noise"], step_noise=st["step_noise"],
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
                          controls=st["controls"], passage=st.get("starts"), s_prev=st.get("s_prev"), gaps=st.get("gaps"),
-                         level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}))
+                         level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}),
+                         **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1184,8 +1209,17 @@ class GraphedSynthesis:
 
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
-                 starts=None, s_prev=None, gaps=None, level=None, seeds=None):
+                 starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None):
         st = self.static
+        if fit_frames is not None or fit_hold is not None:
+            if "fit_frames" not in st:
+                raise ValueError("this graph was built without fit: pass fit=True")
+            rows, hold = _check_fit(st["fit_frames"] if fit_frames is None else fit_frames, fit_hold, *st["fit_hold"].shape,
+                                    self.max_frames)  # as `inference` judges them; a hold alone goes with the targets held here
+            if fit_frames is not None:
+                st["fit_frames"].copy_(rows if torch.is_tensor(rows) else torch.tensor(rows, dtype=torch.int32), non_blocking=True)
+            if hold is not None:
+                st["fit_hold"].copy_(hold, non_blocking=True)
         if "seeds" in st and (noise is not None or step_noise is not None or sine_noise is not None):
             raise ValueError("this graph draws noise, step_noise and sine_noise from its seeds: pass seeds, one or the other")
         if seeds is not None:
@@ -1336,13 +1370,59 @@ def _seeded_sine_noise(seeds, frames, max_frames):
     return ops.noise_fill(seeds, out, ops.NOISE_SINE, counts=frames, per_count=600 * 9)
 
 
+def fit_frames(seconds, trim=0):
+    """A length of `seconds` as the frame target of `inference(fit_frames=)`: round((24000 seconds +
+    trim) / 600), ties to even, at least 1 -- the row then hands over 600 T - `trim` samples at 24 kHz, `trim` being the
+    samples the hand-over drops from the row's end (`inference(trim=)`: by default 50 for a HiFi-GAN decoder, 0 for iSTFTNet).
+    One frame is 600 samples, 25 ms: that is the granularity, a target lands within 12.5 ms of the length asked for.  What is
+    fitted is everything the durations hold: the LJSpeech flow's five tail frames on the last token and forced `durations=`
+    are part of the total.  A scalar gives an int, a sequence a list."""
+    one = lambda s: max(int(round((resample.MODEL_RATE * float(s) + trim) / 600.0)), 1)
+    return one(seconds) if isinstance(seconds, (int, float)) else [one(s) for s in seconds]
+
+
+def _check_fit(fit_frames, fit_hold, B, N, max_frames):
+    """What `inference` refuses about `fit_frames` / `fit_hold` (inputs, not output options: DESIGN.md section 26), before
+    anything is launched -> (the targets as a host list of B ints or the int32 [B] device tensor as it is, fit_hold).  A host
+    list is judged here -- no negative entry, none above `max_frames` --; a device tensor is never read: the kernel clamps its
+    entries to what is feasible and says so in the report's flag."""
+    if max_frames is None:
+        _capacity_only("fit_frames / fit_hold", fit_frames, fit_hold)
+    if fit_frames is None:
+        raise ValueError("fit_hold marks the tokens that fit_frames leaves as they are: pass fit_frames")
+    if torch.is_tensor(fit_frames) and fit_frames.is_cuda:
+        if fit_frames.dtype != torch.int32 or fit_frames.dim() != 1 or fit_frames.numel() != B:
+            raise ValueError("fit_frames must be an int32 tensor of %d entries, got %s %s" % (B, fit_frames.dtype, tuple(fit_frames.shape)))
+    else:
+        rows = fit_frames.tolist() if torch.is_tensor(fit_frames) and fit_frames.dim() == 1 else fit_frames
+        rows = list(rows) if isinstance(rows, (list, tuple)) else None
+        if rows is None or len(rows) != B or not all(isinstance(v, int) and not isinstance(v, bool) for v in rows):
+            raise ValueError("fit_frames must be %d whole frame counts (pipeline.fit_frames converts seconds), got %r" % (B, fit_frames))
+        if any(v < 0 or v > int(max_frames) for v in rows):
+            raise ValueError("fit_frames must lie in 0..max_frames = %d (0 leaves the row alone), got %r" % (int(max_frames), rows))
+        fit_frames = rows
+    if fit_hold is not None and (not torch.is_tensor(fit_hold) or not fit_hold.is_cuda or fit_hold.dtype not in (torch.bool, torch.uint8)
+                                 or tuple(fit_hold.shape) != (B, N)):
+        raise ValueError("fit_hold must be a bool / uint8 device tensor of shape [%d, %s], got %s" % (
+            B, N, "%s %s on %s" % (fit_hold.dtype, tuple(fit_hold.shape), fit_hold.device) if torch.is_tensor(fit_hold)
+            else type(fit_hold).__name__))
+    return fit_frames, fit_hold
+
+
+def _fit_on(fit, dev):
+    """`_check_fit`'s pair with the targets on the device: what `prepare(fit=)` takes."""
+    rows, hold = fit
+    rows = rows if torch.is_tensor(rows) else torch.tensor(rows, dtype=torch.int32).to(dev, non_blocking=True)
+    return rows, None if hold is None else hold.contiguous()
+
+
 @torch.no_grad()
 def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
               ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, sine_noise=None, lj_tail=None,
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None):
+              seeds=None, fit_frames=None, fit_hold=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1413,12 +1493,25 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     drawn on the device by `ops.noise_fill`, three launches, under the noise stream ids of include/st2.h.  A row's draws depend
     on its seed alone: the same seed gives the same draws in any batch and at any place in it.  Without `seeds` the call
     issues exactly the launches it always did.
+
+    `fit_frames` (with `max_frames`): "say this in exactly T frames" -- a host sequence of B whole frame
+    counts, or an int32 [B] device tensor, which is never read on the host; 0 leaves the row alone (`pipeline.fit_frames`
+    converts seconds).  One launch (`ops.durations_fit`) between the front and the frame counts rewrites every row's integer
+    durations -- predicted or forced -- to its target by largest-remainder apportionment of the excess over one frame per
+    token; the frame counts, the expansion, the marks, the per-token prosody spans and the result's `durations` all follow.
+    `fit_hold` (bool / uint8 [B, N] on the device): tokens that keep their duration.  A host target is refused when it is
+    negative or above `max_frames`; a feasible target (at least one frame per free token plus the held ones) is met exactly,
+    any other is replaced by the nearest feasible total.  The result carries `fit`, int32 [B, 4]: {frames before, frames
+    after, flag, tokens changed} per row.  Without the two arguments the call issues exactly the launches it always did.
     """
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level)
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
         seeds = _seeds_on(_check_seeds(seeds, tokens.shape[0], max_frames, noise, step_noise, sine_noise), tokens.device)
+    fit = None
+    if fit_frames is not None or fit_hold is not None:
+        fit = _fit_on(_check_fit(fit_frames, fit_hold, tokens.shape[0], tokens.shape[1], max_frames), tokens.device)
     kw = dict(input_lengths=input_lengths, noise=noise, diffusion_steps=diffusion_steps,
               embedding_scale=embedding_scale, ref_s=ref_s, alpha=alpha, beta=beta, durations=durations,
               step_noise=step_noise, lj_tail=lj_tail, taps=taps, allow_ragged=True, total_frames=total_frames,
@@ -1427,13 +1520,15 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         kw.update(max_frames=max_frames, lengths_dev=lengths_dev)
     if carry:
         kw.update(carry=True, s_prev=s_prev, t=t)
+    if fit is not None:
+        kw.update(fit=fit)
     seeded = lambda: {} if seeds is None else dict(zip(("noise", "step_noise"), _seeded_front_noise(
         seeds, tokens.shape[0], diffusion_steps, tokens.device)))  # drawn on the stream the front reads them on
     if front_stream is None:
         p = prepare(model, sampler, tokens, **dict(kw, **seeded()))
     else:
         main = torch.cuda.current_stream(tokens.device)
-        if inputs_on_main or seeds is not None:  # (the seeds may just have been copied in on the current stream)
+        if inputs_on_main or seeds is not None or fit is not None:  # (seeds / targets may just have been copied in on the current stream)
             front_stream.wait_stream(main)
         with torch.cuda.stream(front_stream):
             p = prepare(model, sampler, tokens, **dict(kw, **seeded()))
@@ -1513,7 +1608,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None, seeds=None):
+                    max_gap=None, level=None, seeds=None, fit_frames=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1571,6 +1666,9 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     int s, which stands for s, s + 1, ..., s + K - 1 (wrapping from 2^63 - 1 to -2^63: the seed is 64 bits), instead of `noises`,
     `step_noises` and `sine_noises`: every sentence's noise is drawn on the device from its own seed (`inference(seeds=)`), the
     same draws whatever `front_batch` groups it with.
+    `fit_frames` (needs `max_frames`): one frame target per SENTENCE -- K whole frame counts or an int32 [K]
+    device tensor, 0 = leave the sentence alone --: every sentence's durations are fitted to its own target
+    (`inference(fit_frames=)`); the breaks between sentences are not part of it.
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
@@ -1581,9 +1679,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds)
+            level=level, seeds=seeds, fit_frames=fit_frames)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     _capacity_only("seeds", seeds)
+    _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
     multispeaker = ref_s is not None
@@ -1662,13 +1761,15 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
     T_cap = int(max_frames)
     if seeds is not None:  # judged once for the K sentences; every group's slice is, again, by `inference`
         seeds = _seeds_on(_check_seeds(seeds, K, max_frames, noises, step_noises, sine_noises), dev)
+    if fit_frames is not None:  # likewise: a host list stays on the host, every group uploads its own slice
+        fit_frames, _ = _check_fit(fit_frames, None, K, None, max_frames)
     if isinstance(decode_streams, (list, tuple)) and len(decode_streams) > 1 or \
             not isinstance(decode_streams, (list, tuple)) and decode_streams and int(decode_streams) > 1:
         raise ValueError("max_frames: there is ONE decoder call per front group, on the current stream; `decode_streams` has no "
@@ -1707,7 +1808,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
                         pack=pack, trim=trim, sample_rate=sample_rate, marks=marks, passage=True, s_prev=s_prev, t=t,
                         controls=None if controls is None else controls.slice(i, j),
                         level=None if level is None else level.slice(i, j),
-                        seeds=None if seeds is None else seeds[i:j], **more)
+                        seeds=None if seeds is None else seeds[i:j],
+                        fit_frames=None if fit_frames is None else fit_frames[i:j], **more)
         s_prev = res.style[-1:]
         results.append(res)
         if on_chunk is not None:
