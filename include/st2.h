@@ -657,7 +657,35 @@ int st2_wave_pack_gaps(const float* wave, int64_t w_bs, const int32_t* frames, i
  * launches and its bytes.  Otherwise every valid input sample of row b becomes fl32(x * level[b][2]) -- one fp32 multiply as
  * the sample is loaded, before anything else the move does -- so that the packed output is exactly what st2_wave_pack_gaps
  * writes for the input fl32(x * g_b); gaps stay the format's silence code and sample counts do not change.  Returns non-zero
- * before any launch on every refusal of st2_wave_pack_gaps and on a level misaligned for float. */
+ * before any launch on every refusal of st2_wave_pack_gaps and on a level misaligned for float.
+ *
+ * st2_wave_level_ex: st2_wave_level with a true-peak ceiling and / or one gain per passage (additive under ABI 23).  It takes
+ * st2_wave_level's arguments and, behind the stream, `taps` (fp32 [up][taps_per_phase] on the device; NULL = sample peaks) and
+ * `start` (int32 [B] on the device; NULL = every row its own group).  With both NULL the call IS st2_wave_level: its two
+ * launches, its bytes, its refusals under its name.
+ *  True peak (ITU-R BS.1770-4 Annex 2: the peak of the signal oversampled to at least 192 kHz -- up = 8 at 24 kHz).  With
+ *     U = up, K = taps_per_phase and the row's cleaned samples x (rule 1; x = 0 in front of the row and at or past n_b),
+ *         y[j] = sum_{k = 0}^{K - 1} taps[j mod U][k] * x[j div U - (K - 1) div 2 + k]      for j in [0, U n_b)
+ *     -- st2_wave_resample_pack's sum with down = 1, the same fp32 fmaf chain from 0, k ascending -- and
+ *         tp_b = max(peak_b, max_j |y[j]|);   tp_b = 0 for an empty or all-zero row.
+ *     The sample peak stays in the maximum: phase 0 of a table whose cutoff lies below Nyquist is not the identity, and the
+ *     reading must never fall below st2_wave_level's.  tp_b takes peak_b's place in rule 5, and level[b][1] reports it.  A
+ *     maximum does not depend on order: tp_b depends neither on the tiling nor on the row's place in the batch, bit for bit.
+ *     Limit of the measurement: a steady sine of frequency f reads at least cos(pi f / (U sample_rate)) of its crest (0.9952
+ *     at a quarter of the rate with U = 8), less the table's passband ripple; content in the table's transition band (with
+ *     the package's table: 0.85 to 1.0 of Nyquist, 10.2 to 12 kHz) is attenuated by the table and under-read.  The peak is the
+ *     model-rate signal's: what a resampling hand-over or a G.711 conversion adds behind it is not covered.
+ *  Passage scope.  A group is a row with start[b] != 0 and the rows with start[b] == 0 behind it; row 0 begins a group
+ *     whatever its flag.  The group's blocks are the blocks of its rows, each row's by rule 3 from zero filter state at its own
+ *     x[0], in row order; blocks never span two rows.  Both gates and L run over that one list; the peak (sample or true) is
+ *     the maximum over the group's rows; the target is the group's first row's (NaN = the whole group is left alone).  Every row
+ *     of the group gets the same four values {L_group, peak_group, g_group, blocks passed in the group}, bit for bit; a group
+ *     of one row is st2_wave_level's row, bit for bit.
+ * With `taps` one launch more, between the two: one workgroup per (hop, row) stages the table and the hop's span (K - 1 samples
+ * of halo) in LDS, every lane makes all U phases of its input positions, and one lane folds the hop's maximum into the hop's
+ * peak slot -- the workspace is st2_wave_level's (st2_wave_level_ex_workspace_bytes forwards).  Returns non-zero before any
+ * launch, under its own name, on: every refusal of st2_wave_level; with `taps`, up outside 1..1024, taps_per_phase outside
+ * 1..512, a table that does not fit LDS beside one hop, taps misaligned for float; start misaligned for int32. */
 int64_t st2_wave_level_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame, int32_t sample_rate);
 int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
                    int32_t trim, int32_t sample_rate, const float* target /* fp32 [B], device */, double ceiling,
@@ -667,6 +695,11 @@ int st2_wave_pack_level(const float* wave, int64_t w_bs, const int32_t* frames, 
                         int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, const float* taps,
                         int32_t taps_per_phase, int32_t fmt /* st2_pcm_format */, const int32_t* gaps, int32_t gap_cap,
                         void* out, int64_t out_capacity, int64_t* offsets, void* stream, const float* level);
+int64_t st2_wave_level_ex_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame, int32_t sample_rate);
+int st2_wave_level_ex(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                      int32_t trim, int32_t sample_rate, const float* target, double ceiling, double max_gain_db, float* level,
+                      void* workspace, int64_t workspace_bytes, void* stream, const float* taps /* fp32 [up][taps_per_phase] */,
+                      int32_t up, int32_t taps_per_phase, const int32_t* start /* int32 [B], device */);
 
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *

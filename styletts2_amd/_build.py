@@ -33,6 +33,9 @@ EXTRA_FLAGS.update({"st2_lstm.hip": ["-fno-slp-vectorize"], "st2_lstm_coop.hip":
 # The polyphase FMA chains of st2_polyphase.h (one per output sample, k ascending), on the way out and on the way in, gain
 # nothing from packing two of them, and a pair that shares a tap in an odd register would be that same encoding.
 EXTRA_FLAGS.update({"st2_resample.hip": ["-fno-slp-vectorize"], "st2_ingest.hip": ["-fno-slp-vectorize"]})
+# The true-peak launch of st2_level.hip runs those chains several to a lane over one shared tap: packed two and two, the tap of
+# an odd phase is that encoding (the gate refused the one-phase build).  The unit's other two kernels are fp64 and scalar.
+EXTRA_FLAGS.update({"st2_level.hip": ["-fno-slp-vectorize"]})
 
 
 def _hipcc():

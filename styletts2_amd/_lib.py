@@ -273,6 +273,10 @@ _SIGNATURES = {
     "st2_wave_level_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "st2_wave_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
                                  C.c_double, C.c_double, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_wave_level_ex_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "st2_wave_level_ex": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p,
+                                    C.c_double, C.c_double, f32p, C.c_void_p, C.c_int64, C.c_void_p, f32p, C.c_int32, C.c_int32,
+                                    C.c_void_p]),
     "st2_wave_pack_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p, f32p]),

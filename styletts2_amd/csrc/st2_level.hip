@@ -21,9 +21,12 @@
 // Launch 2, one wave per row: the blocks from the hop energies, both gates (in the linear domain: l_k > -70 is z_k > 10^-6.9309,
 // the relative gate z_k > mean / 10), loudness and gain in fp64 with one rounding to fp32, lane-strided sums folded by a fixed
 // shuffle tree.
+//
+// st2_wave_level_ex adds, with a table, the true-peak launch between the two (below, at its kernel) and, with start flags, the
+// gate kernel's group loop: the rows of a passage as one programme with one gain.  With neither it is st2_wave_level.
 #include <cmath>
 
-#include "st2_pcm.h"
+#include "st2_polyphase.h"
 
 namespace {
 
@@ -46,8 +49,6 @@ struct kw_state {
     return w;
   }
 };
-
-__device__ __forceinline__ float finite_or_zero(float x) { return fabsf(x) <= 3.402823466e38f ? x : 0.0f; }  // NaN: false
 
 __global__ __launch_bounds__(LV_THREADS) void level_hops_kernel(const float* __restrict__ wave, int64_t w_bs,
                                                                 const int32_t* __restrict__ frames, int T_cap, int spf, int trim,
@@ -112,56 +113,148 @@ __global__ __launch_bounds__(LV_THREADS) void level_hops_kernel(const float* __r
   }
 }
 
+// The true-peak launch (st2_wave_level_ex with a table), between launch 1 and the gate: one workgroup per
+// (hop, row), the grid sized by the capacity.  It stages the table [U][K] and the hop's input span -- the hop and K - 1 samples
+// of halo, zeros selected outside the row, a non-finite sample as 0 -- and every lane makes all the phases of TP_J input
+// positions PP_THREADS apart: per tap it reads its TP_J staged samples once (consecutive lanes read consecutive words: no
+// bank conflict) and PB table words at wave-uniform addresses (broadcasts) for TP_J PB accumulators.  Every output is
+// st2_polyphase.h's chain -- fp32 fmaf from 0, k ascending -- and a maximum does not depend on order, so the hop's reading is
+// the same wherever the row lies.  One lane folds it into the hop's slot of `peaks`, which launch 1 wrote before it in stream
+// order: no atomics, and the gate reads max(sample peak, interpolated peak) where it read the sample peak.
+constexpr int TP_J = 5;  // 10 positions per lane at 24 kHz (h = 2400): two full passes
+
+template <int PB>  // phases per pass: 8 where U is a multiple of 8, else 1
+__global__ __launch_bounds__(PP_THREADS) void level_true_peak_kernel(const float* __restrict__ wave, int64_t w_bs,
+                                                                     const int32_t* __restrict__ frames, int T_cap, int spf, int trim,
+                                                                     int h, const float* __restrict__ taps, int U, int K,
+                                                                     int nhop_cap, float* __restrict__ peaks) {
+  __shared__ __attribute__((aligned(16))) float lds[LV_LDS_FLOATS];
+  __shared__ float part[PP_THREADS / 64];
+  const int b = blockIdx.y;
+  const long long n = pack_row_samples(frames, b, T_cap, spf, trim);
+  const long long t0 = (long long)blockIdx.x * h;  // the hop's first input position
+  if (t0 >= n) return;                              // behind the row's end
+  const int len = (int)min((long long)h, n - t0);
+  float* __restrict__ tab = lds;
+  float* __restrict__ xs = lds + pp_round4(U * K);  // the host checked that the span fits behind the table
+  const pp_tile g = pp_tile_of(t0 * U, len * U, U, 1, K);  // outputs [U t0, U (t0 + len)): phase 0 of position t0 first
+  pp_stage_table(tab, taps, U * K);
+  pp_stage_span<ST2_PCM_F32, true>(xs, wave + (int64_t)b * w_bs, n, g);
+  __syncthreads();
+  float m = 0.0f;
+  for (int q0 = threadIdx.x; q0 < len; q0 += PP_THREADS * TP_J) {
+    const float* __restrict__ xw[TP_J];  // xw[j][k] = x[c_j - (K - 1) / 2 + k]; a position past the hop's end reads q0's window
+    bool valid[TP_J];
+#pragma unroll
+    for (int j = 0; j < TP_J; ++j) {
+      valid[j] = q0 + j * PP_THREADS < len;
+      xw[j] = xs + g.x0 + (valid[j] ? q0 + j * PP_THREADS : q0);
+    }
+    for (int p0 = 0; p0 < U; p0 += PB) {
+      const float* __restrict__ tp = tab + p0 * K;
+      float acc[TP_J][PB];
+#pragma unroll
+      for (int j = 0; j < TP_J; ++j)
+#pragma unroll
+        for (int p = 0; p < PB; ++p) acc[j][p] = 0.0f;
+#pragma unroll 2
+      for (int k = 0; k < K; ++k) {
+        float t[PB];
+#pragma unroll
+        for (int p = 0; p < PB; ++p) t[p] = tp[p * K + k];
+#pragma unroll
+        for (int j = 0; j < TP_J; ++j) {
+          const float x = xw[j][k];
+#pragma unroll
+          for (int p = 0; p < PB; ++p) acc[j][p] = fmaf(t[p], x, acc[j][p]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < TP_J; ++j)
+#pragma unroll
+        for (int p = 0; p < PB; ++p)
+          if (valid[j]) m = fmaxf(m, fabsf(acc[j][p]));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
+  if (threadIdx.x % 64 == 0) part[threadIdx.x / 64] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < PP_THREADS / 64; ++w) m = fmaxf(m, part[w]);
+    const long long at = (long long)b * nhop_cap + blockIdx.x;  // the slot launch 1 wrote: t0 < n
+    peaks[at] = fmaxf(peaks[at], m);
+  }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
   return __shfl(v, 0, 64);
 }
 
+// GROUPED (st2_wave_level_ex with start flags): row b's wave measures its whole group -- the flagged row at or in front of b
+// and the unflagged rows behind it -- as one programme: the blocks of the group's rows in row order, every row's by its own
+// rule, one peak, one target (the first row's).  Every lane's sums run over the rows in row order and, within a row, over the
+// blocks it takes in a row of its own, so a group of one row is the ungrouped kernel operation for operation, and the rows of
+// a group, which all run this one sequence over the same data, agree bit for bit.
+template <bool GROUPED>
 __global__ __launch_bounds__(64) void level_gate_kernel(const int32_t* __restrict__ frames, int T_cap, int spf, int trim, int h,
                                                         int nhop_cap, const double* __restrict__ energy,
                                                         const float* __restrict__ peaks, const float* __restrict__ target,
-                                                        double abs_thr, double ceiling, double max_gain,
-                                                        float* __restrict__ level) {
+                                                        const int32_t* __restrict__ start, double abs_thr, double ceiling,
+                                                        double max_gain, float* __restrict__ level) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const long long n = pack_row_samples(frames, b, T_cap, spf, trim);
-  const int nh = (int)((n + h - 1) / h);  // hops that hold samples, the last one perhaps in part
-  const double* __restrict__ e = energy + (long long)b * nhop_cap;
+  int r0 = b, r1 = b;
+  if constexpr (GROUPED) {
+    while (r0 > 0 && start[r0] == 0) --r0;  // row 0 begins a group whatever its flag
+    while (r1 + 1 < (int)gridDim.x && start[r1 + 1] == 0) ++r1;
+  }
   float pk = 0.0f;
-  for (int j = lane; j < nh; j += 64) pk = fmaxf(pk, peaks[(long long)b * nhop_cap + j]);
+  for (int r = r0; r <= r1; ++r) {
+    const long long n = pack_row_samples(frames, r, T_cap, spf, trim);
+    const int nh = (int)((n + h - 1) / h);  // hops that hold samples, the last one perhaps in part
+    for (int j = lane; j < nh; j += 64) pk = fmaxf(pk, peaks[(long long)r * nhop_cap + j]);
+  }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) pk = fmaxf(pk, __shfl_down(pk, off, 64));
   pk = __shfl(pk, 0, 64);
-  const bool whole = n < 4LL * h;  // the short-row rule: one block, the whole row
-  const int nb = whole ? (n > 0 ? 1 : 0) : (int)(n / h) - 3;
-  double z_whole = 0.0;
-  if (whole && n > 0) {
-    double s = 0.0;
-    for (int j = lane; j < nh; j += 64) s += e[j];
-    z_whole = wave_sum(s) / (double)n;
-  }
-  auto z_of = [&](int k) { return whole ? z_whole : (e[k] + e[k + 1] + e[k + 2] + e[k + 3]) / (double)(4 * h); };
+  // the blocks of rows r0 .. r1 above the absolute gate and, with `relative`, above rel_thr: this lane's share of their sum and count
+  auto gate = [&](bool relative, double rel_thr, double& sum, double& count) {
+    for (int r = r0; r <= r1; ++r) {
+      const long long n = pack_row_samples(frames, r, T_cap, spf, trim);
+      const int nh = (int)((n + h - 1) / h);
+      const double* __restrict__ e = energy + (long long)r * nhop_cap;
+      const bool whole = n < 4LL * h;  // the short-row rule: one block, the whole row
+      const int nb = whole ? (n > 0 ? 1 : 0) : (int)(n / h) - 3;
+      double z_whole = 0.0;
+      if (whole && n > 0) {
+        double s = 0.0;
+        for (int j = lane; j < nh; j += 64) s += e[j];
+        z_whole = wave_sum(s) / (double)n;
+      }
+      for (int k = lane; k < nb; k += 64) {
+        const double z = whole ? z_whole : (e[k] + e[k + 1] + e[k + 2] + e[k + 3]) / (double)(4 * h);
+        if (z > abs_thr && (!relative || z > rel_thr)) { sum += z; count += 1.0; }
+      }
+    }
+  };
   double sum = 0.0, count = 0.0;
-  for (int k = lane; k < nb; k += 64) {
-    const double z = z_of(k);
-    if (z > abs_thr) { sum += z; count += 1.0; }
-  }
+  gate(false, 0.0, sum, count);
   sum = wave_sum(sum);
   count = wave_sum(count);
   double L = -INFINITY, passed = 0.0;
   if (count > 0.0) {
     const double rel_thr = sum / count / 10.0;  // -10 LU under the mean of the absolutely gated blocks
     sum = 0.0; count = 0.0;
-    for (int k = lane; k < nb; k += 64) {
-      const double z = z_of(k);
-      if (z > abs_thr && z > rel_thr) { sum += z; count += 1.0; }
-    }
+    gate(true, rel_thr, sum, count);
     sum = wave_sum(sum);
     passed = wave_sum(count);
     if (passed > 0.0) L = LV_OFFSET + 10.0 * log10(sum / passed);
   }
   if (lane == 0) {
-    const float tg = target[b];
+    const float tg = target[r0];  // the group's target is its first row's
     double g = 1.0;
     if (tg == tg && passed > 0.0 && pk > 0.0f) g = fmin(fmin(pow(10.0, ((double)tg - L) / 20.0), max_gain), ceiling / (double)pk);
     float* __restrict__ o = level + 4 * b;
@@ -210,10 +303,12 @@ extern "C" int64_t st2_wave_level_workspace_bytes(int32_t B, int32_t T_cap, int3
   return ((int64_t)B * nhop * (int64_t)(sizeof(double) + sizeof(float)) + 15) / 16 * 16;
 }
 
-extern "C" int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
-                              int32_t samples_per_frame, int32_t trim, int32_t sample_rate, const float* target, double ceiling,
-                              double max_gain_db, float* level, void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "st2_wave_level";
+// Both entries: every refusal under the entry's name `who`, then the launches.  taps == NULL: sample peaks, no third launch;
+// start == NULL: every row its own group.  With both NULL these are st2_wave_level's two launches.
+static int level_plan(const char* who, const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                      int32_t samples_per_frame, int32_t trim, int32_t sample_rate, const float* target, double ceiling,
+                      double max_gain_db, float* level, void* workspace, int64_t workspace_bytes, void* stream, const float* taps,
+                      int32_t up, int32_t taps_per_phase, const int32_t* start) {
   ST2_REQUIRE(wave && frames, "%s: wave / frames is NULL", who);
   ST2_REQUIRE(B > 0 && B <= 65535 && T_cap > 0 && samples_per_frame > 0, "%s: bad geometry (B=%d, T_cap=%d, samples_per_frame=%d)",
               who, B, T_cap, samples_per_frame);
@@ -238,6 +333,14 @@ extern "C" int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* fr
               who, sample_rate, LV_LDS_FLOATS * 4);
   const int64_t nhop = (row + h - 1) / h;
   ST2_REQUIRE(nhop <= (1 << 24), "%s: a row of %lld samples is too long", who, (long long)row);
+  if (taps) {
+    if (pp_check(who, up, 1, taps_per_phase, ST2_PCM_F32)) return 1;
+    const long long fit = (long long)pp_round4(up * taps_per_phase) + pp_span_cap((long long)h * up, up, 1, taps_per_phase);
+    ST2_REQUIRE(fit <= LV_LDS_FLOATS, "%s: the table (up=%d, taps_per_phase=%d) does not fit the %d bytes of LDS beside one hop of %d samples",
+                who, up, taps_per_phase, LV_LDS_FLOATS * 4, h);
+    ST2_REQUIRE(reinterpret_cast<uintptr_t>(taps) % 4 == 0, "%s: taps is not aligned to float", who);
+  }
+  ST2_REQUIRE(reinterpret_cast<uintptr_t>(start) % 4 == 0, "%s: start is not aligned to int32", who);
 
   const kw_coef c = level_coefficients((double)sample_rate);
   double* energy = reinterpret_cast<double*>(workspace);
@@ -246,8 +349,36 @@ extern "C" int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* fr
   hipLaunchKernelGGL(level_hops_kernel, dim3(st2_cdiv(nhop, R), B), dim3(LV_THREADS), 0, s, wave, w_bs, frames, T_cap,
                      samples_per_frame, trim, h, W, R, c, (int)nhop, energy, peaks);
   ST2_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(level_gate_kernel, dim3(B), dim3(64), 0, s, frames, T_cap, samples_per_frame, trim, h, (int)nhop, energy, peaks,
-                     target, std::pow(10.0, (LV_ABS_GATE - LV_OFFSET) / 10.0), ceiling, std::pow(10.0, max_gain_db / 20.0), level);
+  if (taps) {  // folds the interpolated maxima into the hops' peaks, behind launch 1 in stream order
+    auto tp = up % 8 == 0 ? level_true_peak_kernel<8> : level_true_peak_kernel<1>;
+    hipLaunchKernelGGL(tp, dim3(nhop, B), dim3(PP_THREADS), 0, s, wave, w_bs, frames, T_cap, samples_per_frame, trim, h, taps, up,
+                       taps_per_phase, (int)nhop, peaks);
+    ST2_CHECK_LAUNCH(who);
+  }
+  auto gate = start ? level_gate_kernel<true> : level_gate_kernel<false>;
+  hipLaunchKernelGGL(gate, dim3(B), dim3(64), 0, s, frames, T_cap, samples_per_frame, trim, h, (int)nhop, energy, peaks, target, start,
+                     std::pow(10.0, (LV_ABS_GATE - LV_OFFSET) / 10.0), ceiling, std::pow(10.0, max_gain_db / 20.0), level);
   ST2_CHECK_LAUNCH(who);
   return 0;
+}
+
+extern "C" int st2_wave_level(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                              int32_t samples_per_frame, int32_t trim, int32_t sample_rate, const float* target, double ceiling,
+                              double max_gain_db, float* level, void* workspace, int64_t workspace_bytes, void* stream) {
+  return level_plan("st2_wave_level", wave, w_bs, frames, B, T_cap, samples_per_frame, trim, sample_rate, target, ceiling, max_gain_db,
+                    level, workspace, workspace_bytes, stream, nullptr, 0, 0, nullptr);
+}
+
+// st2_wave_level_ex (st2.h): st2_wave_level with a true-peak table and / or start flags; without either it IS st2_wave_level.
+// The true-peak launch writes into the hops' peak slots, so the workspace is st2_wave_level's.
+extern "C" int64_t st2_wave_level_ex_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame, int32_t sample_rate) {
+  return st2_wave_level_workspace_bytes(B, T_cap, samples_per_frame, sample_rate);
+}
+
+extern "C" int st2_wave_level_ex(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap,
+                                 int32_t samples_per_frame, int32_t trim, int32_t sample_rate, const float* target, double ceiling,
+                                 double max_gain_db, float* level, void* workspace, int64_t workspace_bytes, void* stream,
+                                 const float* taps, int32_t up, int32_t taps_per_phase, const int32_t* start) {
+  return level_plan(taps || start ? "st2_wave_level_ex" : "st2_wave_level", wave, w_bs, frames, B, T_cap, samples_per_frame, trim,
+                    sample_rate, target, ceiling, max_gain_db, level, workspace, workspace_bytes, stream, taps, up, taps_per_phase, start);
 }

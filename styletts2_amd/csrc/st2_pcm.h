@@ -19,6 +19,9 @@ __device__ __forceinline__ long long pack_row_out_samples(const int32_t* __restr
   return (pack_row_samples(frames, b, T_cap, spf, trim) * U + D - 1) / D;
 }
 
+// What the level measurement reads for a sample (st2_level.hip; st2_polyphase.h's cleaning option): a non-finite one counts as 0
+__device__ __forceinline__ float finite_or_zero(float x) { return fabsf(x) <= 3.402823466e38f ? x : 0.0f; }  // NaN: false
+
 // The per-row gain of st2_wave_pack_level (st2_level.hip): g_b = level[b][2], read once per workgroup and
 // multiplied into every input sample as it is loaded, before anything else a move does.  level == NULL: no multiply at all --
 // not one by 1.0f, which would quieten the NaN payloads the fp32 bit copy hands on -- and the move is the one it always was.

@@ -39,8 +39,9 @@ __device__ __forceinline__ void pp_stage_table(float* __restrict__ tab, const fl
 
 // The tile's input span of a row of n samples in format FMT, decoded, to LDS; a sample in front of the row or at / past n is
 // a SELECTED zero -- nothing of `row` at or past n is read.  `gain` (st2_pcm.h): the row's gain on every loaded sample; the
-// default is none.
-template <int FMT>
+// default is none.  CLEAN (the true-peak launch of st2_level.hip; off for the two resamplers): a non-finite sample is staged
+// as 0.
+template <int FMT, bool CLEAN = false>
 __device__ __forceinline__ void pp_stage_span(float* __restrict__ xs, const typename pcm_fmt<FMT>::type* __restrict__ row,
                                               long long n, const pp_tile& g, const row_gain gain = row_gain{false, 1.0f}) {
   for (int q = threadIdx.x; q < g.n4; q += PP_THREADS) {
@@ -57,6 +58,7 @@ __device__ __forceinline__ void pp_stage_span(float* __restrict__ xs, const type
       }
       x = make_float4(e[0], e[1], e[2], e[3]);
     }
+    if constexpr (CLEAN) x = make_float4(finite_or_zero(x.x), finite_or_zero(x.y), finite_or_zero(x.z), finite_or_zero(x.w));
     *reinterpret_cast<float4*>(xs + 4 * q) = x;
   }
 }

@@ -1322,12 +1322,13 @@ def wave_pack_level(wave, frames, level, gaps=None, max_gap=0, rate=None, fmt="s
 
 
 def wave_level_workspace_bytes(B, T_cap, samples_per_frame=600, sample_rate=24000):
-    """`st2_wave_level_workspace_bytes`: what `wave_level(workspace=)` needs, in bytes."""
-    return int(_lib.load().st2_wave_level_workspace_bytes(int(B), int(T_cap), int(samples_per_frame), int(sample_rate)))
+    """`st2_wave_level_ex_workspace_bytes`: what `wave_level(workspace=)` needs, in bytes, with or without `true_peak` / `starts`
+    (the true-peak launch writes into the hops' peak slots: the size is `st2_wave_level_workspace_bytes`')."""
+    return int(_lib.load().st2_wave_level_ex_workspace_bytes(int(B), int(T_cap), int(samples_per_frame), int(sample_rate)))
 
 
 def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samples_per_frame=600, sample_rate=24000, out=None,
-               workspace=None):
+               workspace=None, true_peak=None, starts=None):
     """`st2_wave_level`: wave [B, 1, L] or [B, L] at `sample_rate` (L a multiple of `samples_per_frame`: the batch's frame
     capacity), frames int32 [B] on the device, target fp32 [B] on the device (LUFS; NaN = leave the row alone) -> level fp32
     [B, 4] on the device: every row's integrated loudness (ITU-R BS.1770-4, K-weighted and gated; -inf when no block passes the
@@ -1335,7 +1336,12 @@ def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samp
     NaN target, L = -inf or peak = 0) and the number of gating blocks that passed, measured on the row's first max(0,
     samples_per_frame * frames[b] - trim) samples.  `ceiling` is linear, in (0, 1]; `max_gain_db` in [0, 60].  `out`: a contiguous
     fp32 tensor of 4 B entries to write into; `workspace`: a uint8 device tensor of `wave_level_workspace_bytes` bytes (by
-    default allocated here, from the caching allocator).  No host read; legal under stream capture."""
+    default allocated here, from the caching allocator).  No host read; legal under stream capture.
+    With `true_peak` or `starts` the call is `st2_wave_level_ex`.  `true_peak`: (U, K, taps fp32 [U, K] on the device), what
+    `resample.true_peak_table` returns -- the peak the ceiling acts on, and level[b, 1], is the larger of the sample peak and
+    the peak of the row interpolated U times (BS.1770-4 Annex 2), one launch more.  `starts`: int32 [B] on the device, 1 where
+    a passage begins (row 0 begins one whatever its flag) -- the rows of a passage are measured as one programme and get one
+    gain: the same four values in every row of it."""
     lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
     _chk(wave, "wave")
     if wave.dim() == 3 and wave.shape[1] == 1:
@@ -1355,9 +1361,19 @@ def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samp
     if workspace is None:
         workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
     _chk_dev(workspace, "workspace", torch.uint8, 1)
-    _lib.check(_lib.load().st2_wave_level(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), int(sample_rate),
-                                          target.data_ptr(), float(ceiling), float(max_gain_db), out.data_ptr(),
-                                          workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_level")
+    args = (wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), int(sample_rate), target.data_ptr(), float(ceiling),
+            float(max_gain_db), out.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream())
+    if true_peak is None and starts is None:
+        _lib.check(_lib.load().st2_wave_level(*args), "st2_wave_level")
+        return out
+    U, K, taps = (0, 0, None) if true_peak is None else true_peak
+    if taps is not None:
+        _chk_dev(taps, "true_peak taps", torch.float32, 2)
+        if tuple(taps.shape) != (int(U), int(K)) or taps.device != wave.device:
+            raise _lib.St2Error("true_peak must be (U, K, taps [U, K] on the device of wave), got (%r, %r, %s on %s)"
+                                % (U, K, tuple(taps.shape), taps.device))
+    sp = _chk_len(starts, "starts", B, wave)
+    _lib.check(_lib.load().st2_wave_level_ex(*args, _ptr(taps), int(U), int(K), sp), "st2_wave_level_ex")
     return out
 
 

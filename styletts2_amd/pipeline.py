@@ -280,7 +280,19 @@ class Controls:
         return c
 
 
-class Level:
+class _LevelOptions(type):
+    """`Level(B, ..., true_peak=False, scope="row")`: the two options of the measurement are keyword arguments of the constructor
+    call, judged and stored here, in front of `Level.__init__`, whose own parameter list is the rows' and stays as it is."""
+
+    def __call__(cls, *args, true_peak=False, scope="row", **kw):
+        if scope not in Level.SCOPES:
+            raise ValueError("Level: scope must be one of %s, got %r" % (list(Level.SCOPES), scope))
+        self = super().__call__(*args, **kw)
+        self.true_peak, self.scope = bool(true_peak), scope
+        return self
+
+
+class Level(metaclass=_LevelOptions):
     """Loudness normalisation of the packed hand-over (include/st2.h `st2_wave_level`): every row is
     measured on the device (ITU-R BS.1770-4 integrated loudness and sample peak, at the model rate) and packed with the gain that
     brings it to `target` LUFS -- never more than `max_gain_db`, and never so much that a sample passes `ceiling_db` dBFS.
@@ -288,9 +300,16 @@ class Level:
         target       LUFS, one value or B values; None or NaN in a row = leave this row alone    [-70, 0]
         ceiling_db   dBFS of the largest sample magnitude after the gain                          [-20, 0]
         max_gain_db  the most a quiet row is raised by                                             [0, 60]
+        true_peak    the ceiling holds on the true peak (BS.1770-4 Annex 2: the row interpolated 8 x, to 192 kHz) and not
+                     on the sample peak, which at 24 kHz reads a crest between two samples up to 3 dB low
+        scope        "row": every row on its own; "passage": the rows of a passage (`passage=`) are one programme -- their
+                     gating blocks are gated together and they get ONE gain, the first row's target deciding
 
     Kept as one fp32 [B] device row (`target`), validated on the host like `Controls`; a tensor already on the device is not
     read.  `ceiling` is `ceiling_db` as a linear factor."""
+
+    SCOPES = ("row", "passage")
+    true_peak, scope = False, "row"
 
     def __init__(self, B, target=-16.0, ceiling_db=-1.0, max_gain_db=20.0, device=None):
         B = int(B)
@@ -332,6 +351,7 @@ class Level:
         """Rows i .. j-1 as a Level over the same memory (long-form: a front group's sentences)."""
         c = object.__new__(Level)
         c.B, c.ceiling_db, c.max_gain_db, c.ceiling, c.target = j - i, self.ceiling_db, self.max_gain_db, self.ceiling, self.target[i:j]
+        c.true_peak, c.scope = self.true_peak, self.scope
         return c
 
 
@@ -934,6 +954,17 @@ def _passage_controls(controls, starts, B, dev):
     return c
 
 
+def _passage_starts(passage, B, dev):
+    """The start flags of a call's `passage` as the int32 [B] device row `ops.wave_level(starts=)` reads: None / True = the rows
+    are one passage, [1, 0, ..., 0]; flags = the caller's, nonzero = 1.  A device tensor of flags is never read on the host."""
+    if passage is None or passage is True:
+        flag = torch.zeros((B,), dtype=torch.int32, device=dev)
+        flag[:1] = 1
+        return flag
+    flag = passage if torch.is_tensor(passage) else torch.as_tensor(passage)
+    return (flag.reshape(-1) != 0).to(device=dev, dtype=torch.int32)
+
+
 def _resamples(fmt, sample_rate):
     """True when the packing step is `ops.wave_resample_pack`: another rate than the model's, or a G.711 format.  24 kHz fp32 /
     16-bit PCM stays `ops.wave_pack`."""
@@ -991,14 +1022,17 @@ def _capacity_only(names, *given):
         raise ValueError("%s belong to the capacity-bound path: pass max_frames" % names)
 
 
-def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False):
+def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False,
+                 passage=None, front_groups=1):
     """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
     every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
     launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
     B rows; `max_gap` not negative, and a bound of `gaps` -- a host sequence defaults it to its own maximum, a device tensor is
     never read and needs it; and all of them but `trim` only with `pack` on the capacity-bound path.
     `capacity`: the call has a `max_frames`.  `graph`: the caller is `GraphedSynthesis`, to which `max_frames` is no option --
-    its `marks` refusal names `pack` alone.  `trim` goes through as given: `_decode_capacity` resolves None."""
+    its `marks` refusal names `pack` alone.  `trim` goes through as given: `_decode_capacity` resolves None.  `passage`: the
+    call's `passage`, and `front_groups`: the front calls `synthesize_long` cuts the passage into -- what a `Level` of
+    scope "passage" is judged by, and looked at for nothing else."""
     if pack is not None and pack not in ops.OUTPUT_FORMATS:
         raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
     if sample_rate is not None and pack is None:
@@ -1009,6 +1043,11 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
         raise ValueError("level is a gain in the packed samples of the capacity-bound path: pass max_frames and pack")
     if level is not None and (not isinstance(level, Level) or level.B != B):
         raise ValueError("level must be a pipeline.Level of %d rows" % B)
+    if level is not None and level.scope == "passage" and (passage is None or passage is False):
+        raise ValueError("level of scope 'passage' is one gain for the rows of a passage: pass passage")
+    if level is not None and level.scope == "passage" and front_groups > 1:
+        raise ValueError("level of scope 'passage' is one gain for the rows of ONE call, and front_batch cuts this passage into %d: "
+                         "pass front_batch=0" % front_groups)
     if not capacity:
         _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
     if pack is None and (gaps is not None or max_gap is not None):
@@ -1039,14 +1078,16 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     return _Output(pack, trim, sample_rate, rate, bool(marks), max_gap), gaps
 
 
-def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None):
+def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None, starts=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
     are copied into here; else, where `_resamples`, `ops.wave_resample_pack`; else `ops.wave_pack`.  With `level` (a `Level`;
     DESIGN.md section 23) `ops.wave_level` measures the rows into the header's level part -- its workspace comes from the caching
     allocator, under capture from the graph's own pool, which lives as long as the graph -- and `ops.wave_pack_level` packs them
-    with the gains it reads there, with or without gaps and a rate."""
+    with the gains it reads there, with or without gaps and a rate.  A `Level` with `true_peak` has `ops.wave_level` read the
+    table of `resample.true_peak_table`; one of scope "passage" has it read `starts` (int32 [B] on the device, 1 where a
+    passage begins; None = the rows are one passage).  A plain `Level` passes neither argument on."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
@@ -1056,8 +1097,13 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
     if level is not None:
+        more = {}
+        if level.true_peak:
+            more.update(true_peak=resample.true_peak_table(wave.device))
+        if level.scope == "passage":
+            more.update(starts=_passage_starts(starts, B, wave.device))
         ops.wave_level(wave, frames, level.target, ceiling=level.ceiling, max_gain_db=level.max_gain_db, trim=trim,
-                       samples_per_frame=samples_per_frame, sample_rate=resample.MODEL_RATE, out=ho.level)
+                       samples_per_frame=samples_per_frame, sample_rate=resample.MODEL_RATE, out=ho.level, **more)
         ops.wave_pack_level(wave, frames, ho.level, gaps=ho.gaps, max_gap=max_gap, rate=rate, **into)
     elif gaps is not None:
         ops.wave_pack_gaps(wave, frames, ho.gaps, max_gap, rate=rate, **into)
@@ -1068,10 +1114,11 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, spec, gaps, level):
+def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
-    into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation (`_hand_over`)."""
+    into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation, `starts`: the call's `passage`
+    for a level of scope "passage" (`_hand_over`)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     hifigan = model.decoder.kind == "hifigan"
@@ -1083,7 +1130,7 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level):
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
     ho = _hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
-                    level)
+                    level, starts)
     m = None
     if spec.marks:
         m = ho.marks.view(B, N + 1)
@@ -1156,9 +1203,11 @@ class GraphedSynthesis:
         level = Level(B, device=dev) if level is True else None if level is False else level
         # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
         gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
-        spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True)
+        spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage)
         if spec.rate is not None:
             resample.table(spec.rate, dev)
+        if level is not None and level.true_peak:
+            resample.true_peak_table(dev)  # as the rate's table: made before the capture that reads it
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1187,7 +1236,7 @@ class GraphedSynthesis:
             self.static["gaps"] = gaps
         if level is not None:
             self.static["level"] = Level(B, target=level.target.to(dev).clone(), ceiling_db=level.ceiling_db,
-                                         max_gain_db=level.max_gain_db, device=dev)
+                                         max_gain_db=level.max_gain_db, device=dev, true_peak=level.true_peak, scope=level.scope)
         self._g = None
 
     def _run(self):
@@ -1504,7 +1553,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     any other is replaced by the nearest feasible total.  The result carries `fit`, int32 [B, 4]: {frames before, frames
     after, flag, tokens changed} per row.  Without the two arguments the call issues exactly the launches it always did.
     """
-    spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level)
+    spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
+                              passage=passage)
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
@@ -1539,7 +1589,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     if seeds is not None:
         sine_noise = _seeded_sine_noise(seeds, p["frames"], max_frames)
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, spec, gaps, level)
+        return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage)
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1783,9 +1833,11 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     if tok_ctl and controls.N != max(ns_all):
         raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
     # the K sentences' output, judged once (a `max_gap` without `gaps` is not looked at, as ever); every group's slice is, again
-    spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level)
+    chunks = _front_chunks(front_batch, K)
+    spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level, passage=True,
+                              front_groups=len(chunks))
     prepped = []
-    for i, i_end in _front_chunks(front_batch, K):
+    for i, i_end in chunks:
         ids = list(range(i, i_end))
         ns = ns_all[i:i_end]
         npad = max(ns_all) if tok_ctl else max(ns)

@@ -82,15 +82,15 @@ def output_samples(n, up, down):
 _TABLES = {}
 
 
-def _device_table(key, rate, device, make, name):
+def _device_table(key, rate, device, make, name, call=None):
     dev = torch.device(device)
     key = key + (int(rate), dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     hit = _TABLES.get(key)
     if hit is None:
         U, D, taps = make(rate)
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the %d Hz filter table must exist before a stream capture: call resample.%s(%d, device) "
-                               "first" % (rate, name, rate))
+            raise RuntimeError("the %d Hz filter table must exist before a stream capture: call resample.%s first"
+                               % (rate, call or "%s(%d, device)" % (name, rate)))
         hit = _TABLES[key] = (U, D, taps.shape[1], torch.from_numpy(taps).to(dev))
     return hit
 
@@ -103,3 +103,15 @@ def table(rate, device):
 def input_table(rate, device):
     """`table` of the way in (`design_input`), under cache keys of its own."""
     return _device_table(("in",), rate, device, design_input, "input_table")
+
+
+TRUE_PEAK_UP = 8  # ITU-R BS.1770-4 Annex 2 reads the peak at 192 kHz or above: 8 x the model's 24 kHz
+
+
+def true_peak_table(device):
+    """-> (8, K, taps fp32 [8, K] on `device`): the interpolation table of the true-peak measurement (`ops.wave_level(true_peak=)`;
+    DESIGN.md section 23) -- the design of every other table here at the ratio 8 / 1 (K = 82), under a cache key of its own,
+    designed and uploaded on first use and, like `table`, never under stream capture."""
+    U, _, K, taps = _device_table(("tp",), MODEL_RATE * TRUE_PEAK_UP, device, lambda rate: _kaiser_table(TRUE_PEAK_UP, 1),
+                                  "true_peak_table", call="true_peak_table(device)")
+    return U, K, taps

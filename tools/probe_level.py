@@ -1,4 +1,5 @@
-"""`st2_wave_level` and the gain in the packing moves at the headline's size, rows of 10 s: device time per
+"""`st2_wave_level`, with and without the true-peak launch and the passage scope of `st2_wave_level_ex`, and the gain in the
+packing moves at the headline's size, rows of 10 s: device time per
 call from events around `--calls` back-to-back calls, after a warm-up, the legs taking turns over `--rounds` rounds, in one
 process.  One JSON line per leg: min / median / max of the rounds in microseconds and the bytes the leg reads (by arithmetic: the
 level call reads every valid sample once, 4 bytes each).  Needs a HIP device; there is nothing to fall back to.
@@ -39,6 +40,15 @@ def main():
         work = torch.empty((ops.wave_level_workspace_bytes(B, T_CAP, SPF),), dtype=torch.uint8, device=dev)
         legs["wave_level B=%d" % B] = (B, lambda w=wave, f=frames, t=target, lv=level, ws=work: ops.wave_level(
             w, f, t, ceiling=0.89, out=lv, workspace=ws))
+        tp = resample.true_peak_table(dev)
+        starts = torch.zeros((B,), dtype=torch.int32, device=dev)
+        starts[::4] = 1  # passages of four sentences
+        legs["wave_level true_peak B=%d" % B] = (B, lambda w=wave, f=frames, t=target, lv=level, ws=work, tp=tp: ops.wave_level(
+            w, f, t, ceiling=0.89, out=lv, workspace=ws, true_peak=tp))
+        legs["wave_level passage B=%d" % B] = (B, lambda w=wave, f=frames, t=target, lv=level, ws=work, st=starts: ops.wave_level(
+            w, f, t, ceiling=0.89, out=lv, workspace=ws, starts=st))
+        legs["wave_level true_peak passage B=%d" % B] = (B, lambda w=wave, f=frames, t=target, lv=level, ws=work, tp=tp, st=starts:
+                                                         ops.wave_level(w, f, t, ceiling=0.89, out=lv, workspace=ws, true_peak=tp, starts=st))
         if B != 32:
             continue
         ops.wave_level(wave, frames, target, ceiling=0.89, out=level, workspace=work)
