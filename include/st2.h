@@ -701,6 +701,48 @@ int st2_wave_level_ex(const float* wave, int64_t w_bs, const int32_t* frames, in
                       void* workspace, int64_t workspace_bytes, void* stream, const float* taps /* fp32 [up][taps_per_phase] */,
                       int32_t up, int32_t taps_per_phase, const int32_t* start /* int32 [B], device */);
 
+/* ---- look-ahead peak limiter of the hand-over (added under ABI 23, additive: one kernel-level entry point and two helpers, no
+ * new backend-table slot, no struct change, no new sticky status bit) ---------------------------------- *
+ * st2_wave_limit: the rows of st2_wave_level_ex, driven above the ceiling by up to drive_db and brought back under it by a
+ * zero-phase gain that is a sliding minimum (the hold) under an FIR smoother.  It takes what st2_wave_level_ex took -- the same
+ * wave, frames, trim, target, ceiling (c below), max_gain_db, start and taps [U = up][K = taps_per_phase], NULL as there -- and
+ * the `level` table that call wrote (read, never modified), drive_db in [0, 24], a half window W in samples, 1..1024, and `win`,
+ * fp32 [2 W + 1] on the device, non-negative and summing to 1.  Row b's valid samples are st2_wave_level's rule 1: x[0 .. n_b),
+ * cleaned (a non-finite sample counts as 0).
+ *  1. Drive gain.  g'_b = min(10^((t - L) / 20), 10^(max_gain_db / 20), 10^(drive_db / 20) * c / peak) in fp64, rounded once to
+ *     fp32; L = level[b][0] and peak = level[b][1] as they stand there in fp32, t the target of the first row of b's group
+ *     (start as in st2_wave_level_ex; NULL = every row its own group).  Where t is NaN, L = -inf or peak = 0 the row is LEFT
+ *     ALONE: its valid samples are copied bit for bit, NaN payloads intact, and limit[b] = {1, 1}.  drive_db bounds how deep
+ *     the limiter ever digs: q >= 10^(-drive_db / 20) up to rounding wherever `peak` covers the envelope.
+ *  2. Envelope.  e[i] = |x[i]|; with taps, e[i] = max(|x[i]|, max_{p < U} |y[U i + p]|), y st2_wave_level_ex's interpolation
+ *     (the same fp32 fmaf chain from 0, k ascending).
+ *  3. Required gain.  r[i] = min(1, c / (e[i] g'_b)) evaluated in fp64 and rounded once to fp32; 1 where e[i] = 0 and 1 for i
+ *     outside [0, n_b).
+ *  4. Hold.  m[j] = min_{|d| <= W} r[j + d].
+ *  5. Smooth.  s[i] = 1 - sum_{k = 0}^{2 W} win[k] * (1 - m[i - W + k]): 1 - m in fp32, the sum an fp32 fmaf chain from 0, k
+ *     ascending, the last difference in fp32.  Every window of m that s[i] reads contains i, so s[i] <= r[i] up to the rounding
+ *     of sum win; q[i] = min(s[i], r[i]) makes that exact.
+ *  6. Output.  out[i] = fl32(fl32(x[i] * g'_b) * q[i]) for i in [0, n_b), fp32 in wave's layout (row stride w_bs); nothing at or
+ *     past n_b is written.  limit[b] = {g'_b, min_i q[i]} (fp32 [B][2]; 1 for a row without samples).
+ * Every output sample is a function of the 4 W + 1 samples around it and a minimum does not depend on order: a row's output and
+ * its two numbers depend neither on the tiling nor on the row's place in the batch, bit for bit.
+ * `workspace` (float-aligned, st2_wave_limit_workspace_bytes(B, T_cap, samples_per_frame) bytes; 0 for an argument <= 0) begins
+ * with r as fp32 [B][samples_per_frame T_cap] (entries [0, n_b) of a row that is not left alone), followed by the tiles' minima
+ * and the rows' gains.  st2_wave_limit_tile(): the samples of a tile.  Four launches (gain; envelope and r; hold, smoother and
+ * product; the rows' minima), no allocation, no synchronisation, no host read: legal under stream capture.  Returns non-zero
+ * before any launch on: every refusal of st2_wave_level_ex about geometry (NULL wave / frames, B <= 0 or > 65535, T_cap <= 0,
+ * samples_per_frame <= 0, trim < 0, w_bs too small), ceiling, max_gain_db and, with taps, the table; NULL or misaligned level /
+ * target / out / limit / win / workspace, misaligned taps / start; out overlapping wave; a workspace that is too small; W outside
+ * 1..1024; drive_db outside [0, 24]; a tile whose halo does not fit LDS. */
+int32_t st2_wave_limit_tile(void);
+int64_t st2_wave_limit_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame);
+int st2_wave_limit(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                   int32_t trim, const float* target /* fp32 [B], device */, double ceiling, double max_gain_db,
+                   const float* level /* fp32 [B][4] of st2_wave_level(_ex) */, const float* taps /* fp32 [up][taps_per_phase] */,
+                   int32_t up, int32_t taps_per_phase, const int32_t* start /* int32 [B], device */, double drive_db, int32_t W,
+                   const float* win /* fp32 [2 W + 1], device */, float* out, float* limit /* fp32 [B][2], device */,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
  * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one

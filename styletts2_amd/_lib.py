@@ -280,6 +280,11 @@ _SIGNATURES = {
     "st2_wave_pack_level": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                       C.c_void_p, f32p]),
+    "st2_wave_limit_tile": (C.c_int32, []),
+    "st2_wave_limit_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "st2_wave_limit": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_double,
+                                 C.c_double, f32p, f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_int32, f32p, f32p, f32p,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_noise_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_durations_fit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,

@@ -1377,6 +1377,68 @@ def wave_level(wave, frames, target, ceiling=1.0, max_gain_db=20.0, trim=0, samp
     return out
 
 
+LIMIT_TILE = 2048  # st2_wave_limit_tile(): the samples of a tile of the limiter's launches (tests place events at its edges)
+
+
+def wave_limit_workspace_bytes(B, T_cap, samples_per_frame=600):
+    """`st2_wave_limit_workspace_bytes`: what `wave_limit(workspace=)` needs, in bytes.  The workspace begins with the required
+    gain r as fp32 [B, samples_per_frame * T_cap]."""
+    return int(_lib.load().st2_wave_limit_workspace_bytes(int(B), int(T_cap), int(samples_per_frame)))
+
+
+def wave_limit(wave, frames, level, target, win, ceiling=1.0, max_gain_db=20.0, drive_db=6.0, trim=0, samples_per_frame=600,
+               out=None, limit=None, workspace=None, true_peak=None, starts=None):
+    """`st2_wave_limit`: the look-ahead peak limiter behind `wave_level`.  wave, frames, target, ceiling,
+    max_gain_db, trim, samples_per_frame, true_peak and starts as `wave_level` got them, `level` the fp32 [B, 4] table it wrote,
+    `win` fp32 [2 W + 1] on the device (`resample.limit_window`; W is read from its length), `drive_db` in [0, 24] -> (out, limit):
+    `out` fp32 with the shape and strides of wave as [B, L] -- every valid sample times the row's drive gain g' = min(target gain,
+    max gain, 10^(drive_db / 20) ceiling / peak) and times q, the smoothed sliding minimum of the gain the sample's neighbourhood
+    of 2 W samples either side needs to stay at or under the ceiling; samples at or past a row's end are not written -- and `limit`
+    fp32 [B, 2] = {g', min q} per row.  A row whose target is NaN, whose loudness is -inf or whose peak is 0 is copied bit for
+    bit, {1, 1}.  `workspace`: a uint8 device tensor of `wave_limit_workspace_bytes` bytes (by default from the caching
+    allocator).  No host read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf = int(samples_per_frame)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    _chk_dev(target, "target", torch.float32, 1)
+    _chk_dev(win, "win", torch.float32, 1)
+    _chk_level(level, B, wave)
+    if target.numel() != B or target.device != wave.device or win.device != wave.device or win.numel() % 2 == 0:
+        raise _lib.St2Error("target must hold %d values and win 2 W + 1, both on the device of wave" % B)
+    if out is None:
+        out = torch.empty_strided((B, L), (wave.stride(0), 1), device=wave.device, dtype=torch.float32)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (B, L) or out.device != wave.device or (B > 1 and out.stride(0) != wave.stride(0)):
+        raise _lib.St2Error("out must be [%d, %d] with the row stride of wave, on its device (got %s)" % (B, L, tuple(out.shape)))
+    if limit is None:
+        limit = torch.empty((B, 2), device=wave.device, dtype=torch.float32)
+    _chk_dev(limit, "limit", torch.float32, limit.dim() if torch.is_tensor(limit) else 2)
+    if limit.numel() != 2 * B or limit.device != wave.device:
+        raise _lib.St2Error("limit must hold [%d, 2] values on the device of wave" % B)
+    need = wave_limit_workspace_bytes(B, L // spf, spf)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    U, K, taps = (0, 0, None) if true_peak is None else true_peak
+    if taps is not None:
+        _chk_dev(taps, "true_peak taps", torch.float32, 2)
+        if tuple(taps.shape) != (int(U), int(K)) or taps.device != wave.device:
+            raise _lib.St2Error("true_peak must be (U, K, taps [U, K] on the device of wave), got (%r, %r, %s on %s)"
+                                % (U, K, tuple(taps.shape), taps.device))
+    sp = _chk_len(starts, "starts", B, wave)
+    _lib.check(_lib.load().st2_wave_limit(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), target.data_ptr(),
+                                          float(ceiling), float(max_gain_db), level.data_ptr(), _ptr(taps), int(U), int(K), sp,
+                                          float(drive_db), win.numel() // 2, win.data_ptr(), out.data_ptr(), limit.data_ptr(),
+                                          workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_limit")
+    return out, limit
+
+
 NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*
 
 

@@ -281,14 +281,24 @@ class Controls:
 
 
 class _LevelOptions(type):
-    """`Level(B, ..., true_peak=False, scope="row")`: the two options of the measurement are keyword arguments of the constructor
-    call, judged and stored here, in front of `Level.__init__`, whose own parameter list is the rows' and stays as it is."""
+    """`Level(B, ..., true_peak=False, scope="row", limiter=False, drive_db=6.0, window_ms=8.0)`: the options of the measurement
+    and of the limiter are keyword arguments of the constructor call, judged and stored here, in front of `Level.__init__`, whose
+    own parameter list is the rows' and stays as it is.  The limiter's three are instance attributes only where they differ from
+    the class's defaults: a `Level` made without them is the object it always was."""
 
-    def __call__(cls, *args, true_peak=False, scope="row", **kw):
+    def __call__(cls, *args, true_peak=False, scope="row", limiter=False, drive_db=6.0, window_ms=8.0, **kw):
         if scope not in Level.SCOPES:
             raise ValueError("Level: scope must be one of %s, got %r" % (list(Level.SCOPES), scope))
+        drive_db, window_ms = float(drive_db), float(window_ms)
+        if not 0.0 <= drive_db <= 24.0:
+            raise ValueError("Level: drive_db must lie in [0, 24], got %r" % (drive_db,))
+        if not 0.5 <= window_ms <= 40.0:
+            raise ValueError("Level: window_ms must lie in [0.5, 40], got %r" % (window_ms,))
         self = super().__call__(*args, **kw)
         self.true_peak, self.scope = bool(true_peak), scope
+        for name, value in (("limiter", bool(limiter)), ("drive_db", drive_db), ("window_ms", window_ms)):
+            if value != getattr(Level, name):
+                setattr(self, name, value)
         return self
 
 
@@ -304,12 +314,24 @@ class Level(metaclass=_LevelOptions):
                      on the sample peak, which at 24 kHz reads a crest between two samples up to 3 dB low
         scope        "row": every row on its own; "passage": the rows of a passage (`passage=`) are one programme -- their
                      gating blocks are gated together and they get ONE gain, the first row's target deciding
+        limiter      a look-ahead peak limiter holds the ceiling (`ops.wave_limit`): the row's gain may pass
+                     ceiling / peak by up to `drive_db`, and a zero-phase gain -- the sliding minimum of what each sample needs,
+                     smoothed by a Hann window of 2 W + 1 samples -- brings the peaks back under it
+        drive_db     the most the limiter ever digs, and so the most a row's gain passes ceiling / peak by     [0, 24]
+        window_ms    the half window: W = round(window_ms * 24) samples.  8 ms holds for 16 ms, longer than a pitch period
+                     down to 62 Hz, so that the gain does not ride a voiced waveform                        [0.5, 40]
 
     Kept as one fp32 [B] device row (`target`), validated on the host like `Controls`; a tensor already on the device is not
     read.  `ceiling` is `ceiling_db` as a linear factor."""
 
     SCOPES = ("row", "passage")
     true_peak, scope = False, "row"
+    limiter, drive_db, window_ms = False, 6.0, 8.0
+
+    @property
+    def W(self):
+        """The limiter's half window in samples at the model rate."""
+        return int(round(self.window_ms * resample.MODEL_RATE / 1000.0))
 
     def __init__(self, B, target=-16.0, ceiling_db=-1.0, max_gain_db=20.0, device=None):
         B = int(B)
@@ -352,7 +374,12 @@ class Level(metaclass=_LevelOptions):
         c = object.__new__(Level)
         c.B, c.ceiling_db, c.max_gain_db, c.ceiling, c.target = j - i, self.ceiling_db, self.max_gain_db, self.ceiling, self.target[i:j]
         c.true_peak, c.scope = self.true_peak, self.scope
+        c.__dict__.update({k: v for k, v in self.__dict__.items() if k in ("limiter", "drive_db", "window_ms")})
         return c
+
+    def options(self):
+        """The keyword options of this Level, as its constructor takes them (what a copy over other rows is made with)."""
+        return dict(true_peak=self.true_peak, scope=self.scope, limiter=self.limiter, drive_db=self.drive_db, window_ms=self.window_ms)
 
 
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
@@ -877,8 +904,9 @@ class SynthesisResult:
         self._ho, self._buf = ho, None if ho is None else ho.buf
         self.packed, self.offsets, self.gaps = (None, None, None) if ho is None else (ho.packed, ho.offsets, ho.gaps)
         self.level = None if ho is None or ho.level is None else ho.level.view(-1, 4)
+        self.limit = None if ho is None or ho.limit is None else ho.limit.view(-1, 2)
 
-    def to_host(self, marks=False, passage=False, level=False):
+    def to_host(self, marks=False, passage=False, level=False, limit=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -891,9 +919,13 @@ class SynthesisResult:
         an int32 [B, N + 1] numpy array out of the same copy.  A result with `gaps` gives every row's speech WITHOUT its break,
         as a result without gaps does; `passage=True` gives instead the ONE contiguous array packed[:offsets[B]], speech and
         breaks as a client plays them.  `level=True` (a result made with `level=`): the level table as a float32 [B, 4] numpy
-        array out of the same copy, behind whatever else is returned: (arrays, level) or (arrays, marks, level)."""
+        array out of the same copy, behind whatever else is returned: (arrays, level) or (arrays, marks, level).  `limit=True` (a
+        result made with a limiting `Level`): the limiter's {drive gain, smallest gain factor} as a float32 [B, 2] numpy array, out
+        of the same copy, last."""
         if level and self.level is None:
             raise ValueError("this result carries no level table: ask for it with inference(..., level=Level(...))")
+        if limit and self.limit is None:
+            raise ValueError("this result carries no limit table: ask for it with inference(..., level=Level(..., limiter=True))")
         if marks and self.marks is None:
             raise ValueError("this result carries no timing marks: ask for them with inference(..., marks=True)")
         if self._ho is None:
@@ -916,6 +948,8 @@ class SynthesisResult:
             g = g.clamp(0, self.max_gap).tolist()
             rows = [samples[offs[b]:offs[b + 1] - g[b]] for b in range(B)]
         more = ((m.numpy().reshape(tuple(self.marks.shape)),) if marks else ()) + ((lv.numpy().reshape(B, 4),) if level else ())
+        if limit:
+            more += (self._ho.limit_view(self._host).numpy().reshape(B, 2),)
         return (rows,) + more if more else rows
 
 
@@ -974,22 +1008,29 @@ def _resamples(fmt, sample_rate):
 class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
-        [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | pad to 16 bytes | samples of `fmt`]
+        [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | limit float32 [2 B] |
+         pad to 16 bytes | samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps / no level the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    with `n_marks` = 0 / no gaps / no level / no limit the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
     five parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
     its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `packed` and `level` are
     the buffer and its views (None for a part the layout does not have)."""
 
-    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False):
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
-        self.with_level = bool(with_level)
+        self.with_level, self.with_limit = bool(with_level), bool(with_limit)
         self.offsets_at = 0
         self.marks_at = 8 * (self.B + 1)
         self.gaps_at = self.marks_at + 4 * self.n_marks
         self.level_at = self.gaps_at + (4 * self.B if self.with_gaps else 0)
-        self.samples_at = (self.level_at + (16 * self.B if self.with_level else 0) + 15) // 16 * 16
-        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = None
+        self.limit_at = self.level_at + (16 * self.B if self.with_level else 0)
+        self.samples_at = (self.limit_at + (8 * self.B if self.with_limit else 0) + 15) // 16 * 16
+        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = None
+
+    def limit_view(self, buf):
+        """The sixth part, float32 [2 B] (`ops.wave_limit`'s {g', min q} per row), of a uint8 buffer of this
+        layout, or None.  Apart from `views`, whose five parts stay the five they were."""
+        return buf[self.limit_at:self.limit_at + 8 * self.B].view(torch.float32) if self.with_limit else None
 
     def views(self, buf):
         """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
@@ -1002,6 +1043,7 @@ class _HandOver:
     def allocate(self, samples, device):
         self.buf = torch.empty((self.samples_at + samples * self.dtype.itemsize,), device=device, dtype=torch.uint8)
         self.offsets, self.marks, self.gaps, self.packed, self.level = self.views(self.buf)
+        self.limit = self.limit_view(self.buf)
         return self
 
 
@@ -1087,12 +1129,15 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     allocator, under capture from the graph's own pool, which lives as long as the graph -- and `ops.wave_pack_level` packs them
     with the gains it reads there, with or without gaps and a rate.  A `Level` with `true_peak` has `ops.wave_level` read the
     table of `resample.true_peak_table`; one of scope "passage" has it read `starts` (int32 [B] on the device, 1 where a
-    passage begins; None = the rows are one passage).  A plain `Level` passes neither argument on."""
+    passage begins; None = the rows are one passage).  A plain `Level` passes neither argument on.  A `Level` with `limiter`
+    (DESIGN.md section 27): measure as above, then `ops.wave_limit` into a buffer of the caching allocator with {g', min q} into
+    the header's limit part, then the wrapper a call WITHOUT a level takes, over the limited rows."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
     room = resample.output_samples(L, U, D) + (0 if gaps is None else max_gap)
-    ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None).allocate(B * room, wave.device)
+    limiting = level is not None and level.limiter
+    ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting).allocate(B * room, wave.device)
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
@@ -1104,8 +1149,16 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
             more.update(starts=_passage_starts(starts, B, wave.device))
         ops.wave_level(wave, frames, level.target, ceiling=level.ceiling, max_gain_db=level.max_gain_db, trim=trim,
                        samples_per_frame=samples_per_frame, sample_rate=resample.MODEL_RATE, out=ho.level, **more)
+    if limiting:
+        # the limited rows in a buffer of the caching allocator (under capture: the graph's pool), then the packing wrappers
+        # below as they are, without a level: the packed bytes are what they give for that input
+        wave, _ = ops.wave_limit(wave, frames, ho.level, level.target, resample.limit_window(level.W, wave.device),
+                                 ceiling=level.ceiling, max_gain_db=level.max_gain_db, drive_db=level.drive_db, trim=trim,
+                                 samples_per_frame=samples_per_frame, limit=ho.limit, **more)
+    elif level is not None:
         ops.wave_pack_level(wave, frames, ho.level, gaps=ho.gaps, max_gap=max_gap, rate=rate, **into)
-    elif gaps is not None:
+        return ho
+    if gaps is not None:
         ops.wave_pack_gaps(wave, frames, ho.gaps, max_gap, rate=rate, **into)
     elif rate is not None:
         ops.wave_resample_pack(wave, frames, rate, **into)
@@ -1208,6 +1261,8 @@ class GraphedSynthesis:
             resample.table(spec.rate, dev)
         if level is not None and level.true_peak:
             resample.true_peak_table(dev)  # as the rate's table: made before the capture that reads it
+        if level is not None and level.limiter:
+            resample.limit_window(level.W, dev)  # and the limiter's window
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1236,7 +1291,7 @@ class GraphedSynthesis:
             self.static["gaps"] = gaps
         if level is not None:
             self.static["level"] = Level(B, target=level.target.to(dev).clone(), ceiling_db=level.ceiling_db,
-                                         max_gain_db=level.max_gain_db, device=dev, true_peak=level.true_peak, scope=level.scope)
+                                         max_gain_db=level.max_gain_db, device=dev, **level.options())
         self._g = None
 
     def _run(self):

@@ -115,3 +115,24 @@ def true_peak_table(device):
     U, _, K, taps = _device_table(("tp",), MODEL_RATE * TRUE_PEAK_UP, device, lambda rate: _kaiser_table(TRUE_PEAK_UP, 1),
                                   "true_peak_table", call="true_peak_table(device)")
     return U, K, taps
+
+
+LIMIT_MAX_W = 1024  # st2_wave_limit's largest half window
+
+
+def limit_window_design(W):
+    """-> fp32 [2 W + 1]: the smoother of the look-ahead limiter (`ops.wave_limit`) -- a Hann window over
+    2 W + 1 points without its two zero end points, normalised to sum 1 in fp64 and then rounded: every weight positive."""
+    W = int(W)
+    if not 1 <= W <= LIMIT_MAX_W:
+        raise ValueError("the limiter's half window must be 1..%d samples, got %r" % (LIMIT_MAX_W, W))
+    k = np.arange(1, 2 * W + 2, dtype=np.float64)
+    h = 0.5 - 0.5 * np.cos(2.0 * np.pi * k / (2 * W + 2))
+    return (h / h.sum()).astype(np.float32)
+
+
+def limit_window(W, device):
+    """-> win fp32 [2 W + 1] on `device`: `limit_window_design(W)`, one copy per (W, device), designed and uploaded on first use and,
+    like `table`, never under stream capture."""
+    _, _, _, win = _device_table(("lim",), int(W), device, lambda w: (1, 1, limit_window_design(w)[None, :]), "limit_window")
+    return win[0]
