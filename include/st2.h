@@ -447,7 +447,8 @@ int st2_colnorm_apply(const float* x, int64_t x_bs, int32_t x_cs, const float* s
  * G [B][2*4H][N]: input projections W_ih x_t + b_ih + b_hh for both directions (rows 0..4H-1 forward,
  * 4H..8H-1 reverse; PyTorch gate order i,f,g,o), produced by st2_conv1d (k=1).  whh_t [2][H][4H] is
  * W_hh transposed per direction.  lengths [B] int32 (NULL = all N): packed-sequence semantics, outputs
- * beyond the length are zero.  Y [B][2H][N] (rows 0..H-1 forward h_t, H..2H-1 reverse).
+ * beyond the length are zero; a device length is clamped to 0..N where it is read (both kernels), so a bad value
+ * gives an all-zero or a full row, never an access outside the row.  Y [B][2H][N] (rows 0..H-1 forward h_t, H..2H-1 reverse).
  * Replaces nn.LSTM(bidirectional=True) + pack/pad: models.py:300,314-327 (TextEncoder),
  * :450,523-528,545-566 (duration LSTM / DurationEncoder), :453,498 (shared F0/N LSTM). */
 int st2_lstm_bidir(const float* G, int64_t g_bs, int32_t g_cs, const float* whh_t, const int32_t* lengths,

@@ -34,7 +34,8 @@ __global__ __launch_bounds__(H) void lstm_recurrence_kernel(const float* __restr
     if (__hip_atomic_load(cond, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
     if (j == 0 && b == 0 && dir == 0) st2_raise_status(gstatus, ST2_STATUS_LSTM_RECOVERED);
   }
-  const int len = lengths ? min(lengths[b], N) : N;
+  // clamped to 0..N: a bad device value gives an all-zero or a full row, never a write in front of the row
+  const int len = lengths ? max(min(lengths[b], N), 0) : N;
   const float* Gb = G + (int64_t)b * g_bs + (int64_t)(dir * 4 * H) * g_cs;
   const float* W = whh_t + (int64_t)dir * H * 4 * H;
   float* Yb = Y + (int64_t)b * y_bs + (int64_t)(dir * H + j) * y_cs;

@@ -93,12 +93,14 @@ __global__ __launch_bounds__(256) void lstm_coop_kernel(const float* __restrict_
   // ---- update-role state ------------------------------------------------------------------------------
   const int b = blk * U + uu;
   const bool live = uu < U && b < B;
-  const int len = live ? (lengths ? min(lengths[b], N) : N) : 0;
+  // device lengths are clamped to 0..N here and in `maxlen`: a bad value gives an all-zero or a full row, never a write in
+  // front of the row
+  const int len = live ? (lengths ? max(min(lengths[b], N), 0) : N) : 0;
   int maxlen = 0;  // steps this group runs = longest sequence in the block (same value in all 8 workgroups)
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int bb = blk * U + u;
-    if (bb < B) maxlen = max(maxlen, lengths ? min(lengths[bb], N) : N);
+    if (bb < B) maxlen = max(maxlen, lengths ? max(min(lengths[bb], N), 0) : N);
   }
   const float* Gb = G + (int64_t)(live ? b : 0) * g_bs + (int64_t)(dir * 4 * H + hu) * g_cs;
   float* Yb = Y + (int64_t)(live ? b : 0) * y_bs + (int64_t)(dir * H + hu) * y_cs;

@@ -1018,7 +1018,8 @@ def test_lstm_coop_exchange_variants_agree(xch):
 def test_lstm_bidir_matches_torch_lstm(B, N, ragged, mode, monkeypatch):
     """Input projection on st2_conv1d + the recurrence kernel == nn.LSTM(bidirectional) with pack/pad semantics, for
     both recurrence kernels: `coop` = st2_lstm_bidir_coop (register-resident W_hh over 8 CUs per group; utterance
-    blocks of 1 / 4 / 8, partial blocks, ragged lengths inside a block), `single` = st2_lstm_bidir."""
+    blocks of 1 (B = 1) and 4 (B = 2 .. 32), partial blocks, ragged lengths inside a block; the blocks of 2 and 8 are in
+    tests/test_lstm_edges_gpu.py), `single` = st2_lstm_bidir."""
     from styletts2_amd.text import EngineLSTM
     monkeypatch.setattr(_hooks, "lstm", mode)
     torch.manual_seed(N)
