@@ -327,6 +327,7 @@ int st2_style_fc(const float* s, int32_t B, int32_t K, const float* wt, const fl
  * out[b,co,l] = bias[co] + phases[b][((l+pad)%s)*C + co][(l+pad)/s] + add[b,co,l]
  * for l in [0,L_raw); if reflect_left the result is shifted right by one sample and
  * out[.,.,0] = value at raw index 1 (nn.ReflectionPad1d((1,0))).  L_out = L_raw + reflect_left.
+ * Columns q >= Lq read as 0 (the transposed conv's zero padding); 0 <= pad, 1 <= stride <= 64 (anything else is refused).
  * Replaces: Modules/istftnet.py:364-368 (ups[i], reflection_pad, + x_source),
  *           Modules/hifigan.py:333-334.
  */

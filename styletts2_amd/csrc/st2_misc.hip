@@ -321,6 +321,8 @@ extern "C" int st2_convt_interleave_stats_len(const float* phases, int64_t p_bs,
               "st2_convt_interleave: bad arguments");
   ST2_REQUIRE(reflect_left == 0 || (reflect_left == 1 && L_raw >= 2), "st2_convt_interleave: bad reflect_left");
   ST2_REQUIRE(stride <= 64, "st2_convt_interleave: stride %d too large", stride);
+  // (l + pad) / stride must be a floor: with pad < 0 it truncates toward zero and the staged window is indexed from the wrong column
+  ST2_REQUIRE(pad >= 0, "st2_convt_interleave: pad %d is negative", pad);
   const int L_out = L_raw + reflect_left;
   const int nt = st2_cdiv(L_out, CVT_TILE);
   if (part) ST2_REQUIRE(part_nt >= nt && (reinterpret_cast<uintptr_t>(part) & 7) == 0,
