@@ -745,6 +745,57 @@ int st2_wave_limit(const float* wave, int64_t w_bs, const int32_t* frames, int32
                    const float* win /* fp32 [2 W + 1], device */, float* out, float* limit /* fp32 [B][2], device */,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- edges: lead and tail silence trimmed on the way out (added under ABI 23, additive: two kernel-level entry points and two
+ * helpers, no new backend-table slot, no struct change, no new sticky status bit) ------------------------ *
+ * st2_wave_edges: the way out's counterpart of st2_clip_ingest's trim.  It takes st2_wave_level's geometry (wave, w_bs, frames,
+ * B, T_cap, samples_per_frame, trim) and, all on the device and read by the kernels -- a captured launch serves any values --
+ * top_db fp32 [B], keep int32 [B][2] (samples of lead and of tail to keep outside the detected bounds) and ramp fp32 [F],
+ * F in 0..4096 (NULL with F = 0), rising and non-negative; it writes `out`, fp32 in wave's layout (row stride w_bs), not
+ * overlapping wave, and edges int32 [B][2].
+ *  1. Valid samples.  Row b's valid samples are st2_wave_level's rule 1: x[0 .. n_b), n_b = max(0, frames[b] * samples_per_frame
+ *     - trim), frames clamped to 0..T_cap.  A non-finite sample counts as 0 for the measurement.
+ *  2. Detection.  Rule 3 of st2_clip_ingest, verbatim, over the row's n_b samples with top_db[b]: 2048-sample frames with hop
+ *     512, centred and zero-padded, f = 0 .. n_b div 512; e_f = max(sum / 2048, 1e-10) from the sums of squares of the row's
+ *     512-sample blocks -- every block by one wave, lane l the samples l, l + 64, ... ascending by fmaf from 0, the 64 partial
+ *     sums by a butterfly; e_f = ((s[f - 2] + s[f - 1]) + (s[f] + s[f + 1])) / 2048 in fp32 --; frame f is non-silent iff
+ *     e_f > max_f e_f * (float) 10^(-top_db / 10) (the power in double, rounded once), the maximal frame whatever the rounding.
+ *     start = 512 * the first non-silent frame, end = min(n_b, 512 * (the last one + 1)).  The row is LEFT ALONE (start = 0,
+ *     end = n_b) where top_db[b] is NaN or <= 0 or the row is empty; an all-zero row has every frame at the floor, so every
+ *     frame is the maximal one and the rule itself gives start = 0, end = n_b.
+ *  3. Pads.  head = max(0, start - max(0, keep[b][0])), stop = min(n_b, end + max(0, keep[b][1])), count = stop - head, in
+ *     integers (64-bit inside: no keep overflows).
+ *  4. Move and fade.  out[b][i] = x[head + i] for i < count, the bits copied, NaN payloads included, except inside a fade: with
+ *     F > 0 and f = min(F, count div 2) the first f samples are multiplied by ramp[i] only if head > 0, the last f by
+ *     ramp[count - 1 - i] only if stop < n_b, each one fp32 multiply (f + f <= count: no sample takes both).  Nothing at or past
+ *     out[b][count] is written.
+ *  5. Result.  edges[b] = {head, count}.
+ *  6. Independence.  The block sums have one fixed order, the maximum and the first / last frame do not depend on order, and
+ *     the move accumulates nothing: a row's output and its two numbers depend neither on the tiling nor on the row's place in
+ *     the batch, bit for bit.
+ * `workspace` (float-aligned, st2_wave_edges_workspace_bytes(B, T_cap, samples_per_frame) bytes; 0 for an argument <= 0) holds
+ * the block sums, fp32 [B][4 ceil(samples_per_frame T_cap / tile)].  st2_wave_edges_tile(): the samples of a tile of the sums'
+ * launch.  Three launches (block sums; per row the maximum, the bounds and the pads; the move), no atomics, no allocation, no
+ * synchronisation, no host read: legal under stream capture.  Returns non-zero before any launch on: NULL wave / frames, B <= 0
+ * or > 65535, T_cap <= 0, samples_per_frame <= 0, trim < 0, a row at capacity beyond the int32 edges, w_bs too small; NULL
+ * top_db / keep / out / edges / workspace; F outside 0..4096 or F > 0 with a NULL ramp; wave / top_db / out / ramp / workspace
+ * misaligned for float, frames / keep / edges for int32; out overlapping wave; a workspace that is too small. */
+int32_t st2_wave_edges_tile(void);
+int64_t st2_wave_edges_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame);
+int st2_wave_edges(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                   int32_t trim, const float* top_db /* fp32 [B], device */, const int32_t* keep /* int32 [B][2], device */,
+                   const float* ramp /* fp32 [F], device */, int32_t F, float* out, int32_t* edges /* int32 [B][2], device */,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+/* st2_token_marks_edges: st2_token_marks for rows that st2_wave_edges cut before they were packed.  It takes st2_token_marks's
+ * arguments and, in front of the stream, `edges` (int32 [B][2] on the device, {head, count} as st2_wave_edges wrote them; a
+ * negative entry counts as 0).  The boundaries are st2_token_marks's, by the one boundary rule; with s = min(samples_per_frame *
+ * bound[b][n], n_smp) as there, marks[b][n] = (clamp(s - head, 0, count) * up + down - 1) div down: a token that lies in the
+ * removed lead sits at 0, one in the removed tail at the row's end, and marks[b][N] is still the row's packed sample count,
+ * ceil(count up / down).  bound_out is st2_token_marks's, in decoder frames of the uncut row.  One launch.  Returns non-zero
+ * before any launch on every refusal of st2_token_marks and on a NULL or misaligned edges. */
+int st2_token_marks_edges(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* frames, int32_t T_cap,
+                          int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, int32_t* marks,
+                          int32_t* bound_out, const int32_t* edges /* int32 [B][2], device */, void* stream);
+
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
  * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one

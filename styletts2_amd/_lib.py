@@ -285,6 +285,10 @@ _SIGNATURES = {
     "st2_wave_limit": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_double,
                                  C.c_double, f32p, f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_int32, f32p, f32p, f32p,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_wave_edges_tile": (C.c_int32, []),
+    "st2_wave_edges_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "st2_wave_edges": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_void_p, f32p,
+                                 C.c_int32, f32p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_noise_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_durations_fit": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
@@ -303,6 +307,8 @@ _SIGNATURES = {
     "st2_prosody_controls": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, f32p, f32p, C.c_void_p, C.c_void_p]),
     "st2_token_marks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "st2_token_marks_edges": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "st2_duration_head_rate_tok": (C.c_int, [f32p, C.c_int64, C.c_int32, f32p, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_int32, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "st2_prosody_controls_tok": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, f32p,

@@ -4,11 +4,13 @@
 // effects.trim rule and handed over as fp32 rows with their device lengths: three launches, no host read and no allocation, so
 // the call is legal under stream capture and runs straight into the style path.
 #include "st2_polyphase.h"
+#include "st2_trim.h"
 
 namespace {
 
 constexpr int IN_THREADS = PP_THREADS;
-constexpr int IN_HOP = 512;         // the trim's hop: a frame of 2048 samples is four block sums
+constexpr int IN_HOP = TRIM_HOP;    // the trim's hop (st2_trim.h): a frame of 2048 samples is four block sums
+static_assert(IN_THREADS == TRIM_THREADS, "the trim rule's functions are written for this workgroup");
 constexpr int IN_TILE_MAX = 1024;   // output samples of a workgroup, a multiple of IN_HOP; rows of `work` are padded to it
 constexpr int IN_LDS_BYTES = 63 * 1024;
 
@@ -24,8 +26,7 @@ __device__ __forceinline__ long long in_row_samples(const int32_t* __restrict__ 
 // of squares of the tile's 512-sample blocks into `sums`:
 //   1. the phase table and the tile's decoded input span [c(j0) - h, c(j1 - 1) - h + K) go to LDS (st2_polyphase.h);
 //   2. lane l makes the samples j0 + l, j0 + l + 256, ... by the chain of st2_polyphase.h;
-//   3. the tile leaves with one 16-byte store per lane and pass; wave w sums the squares of block w, lane l the samples
-//      l, l + 64, ... ascending, then the 64 partial sums by a butterfly: one fixed order, no atomics.
+//   3. the tile leaves with one 16-byte store per lane and pass, and its block sums by the rule of st2_trim.h.
 // A workgroup whose tile lies behind the row's end leaves before any barrier: the grid is sized by the capacity.
 template <int FMT>
 __global__ __launch_bounds__(IN_THREADS) void ingest_resample_kernel(
@@ -55,33 +56,11 @@ __global__ __launch_bounds__(IN_THREADS) void ingest_resample_kernel(
   float* __restrict__ dst = work + (int64_t)b * wk_bs + j0;  // 16-byte aligned: wk_bs and j0 are multiples of 512
   for (int q = threadIdx.x; 4 * q < tile; q += IN_THREADS)
     *reinterpret_cast<float4*>(dst + 4 * q) = *reinterpret_cast<const float4*>(ys + 4 * q);
-  const int lane = threadIdx.x & 63;
-  for (int blk = threadIdx.x >> 6; blk * IN_HOP < tile; blk += IN_THREADS / 64) {
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < IN_HOP / 64; ++i) {
-      const float v = ys[blk * IN_HOP + i * 64 + lane];
-      s = fmaf(v, v, s);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (lane == 0) sums[(int64_t)b * nb_row + (j0 / IN_HOP) + blk] = s;
-  }
+  trim_block_sums(ys, tile, sums + (int64_t)b * nb_row + j0 / IN_HOP);
 }
 
-// Reductions of the bounds kernel over its 256 lanes: a butterfly inside each wave, the four wave results through LDS.
-template <class T, class F>
-__device__ __forceinline__ T in_block_reduce(T v, T* __restrict__ slot, F op) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-  __syncthreads();  // the slots of the reduction before this one have been read
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return op(op(slot[0], slot[1]), op(slot[2], slot[3]));
-}
-
-// Launch two, one workgroup per row: frame energies from the block sums, their maximum, the first and last non-silent frame,
-// the minimum-length rule; writes len / start / flags and the row's start for the gather.
+// Launch two, one workgroup per row: the bounds from the block sums (st2_trim.h: frame energies, their maximum, the first and
+// last non-silent frame), the minimum-length rule; writes len / start / flags and the row's start for the gather.
 __global__ __launch_bounds__(IN_THREADS) void ingest_bounds_kernel(const int32_t* __restrict__ n_in, int N_cap, int U, int D,
                                                                    int L_cap, float threshold /* < 0: no trim */, int L_min,
                                                                    const float* __restrict__ sums, int nb_row,
@@ -94,28 +73,7 @@ __global__ __launch_bounds__(IN_THREADS) void ingest_bounds_kernel(const int32_t
   const int m = (int)min((long long)L_cap, full);
   int s0 = 0, s1 = m;
   if (threshold >= 0.0f) {
-    const int nblk = (m + IN_HOP - 1) / IN_HOP, nf = m / IN_HOP + 1;
-    const float* __restrict__ s = sums + (int64_t)b * nb_row;
-    auto block = [&](int i) { return i >= 0 && i < nblk ? s[i] : 0.0f; };
-    auto energy = [&](int f) {
-      return fmaxf(((block(f - 2) + block(f - 1)) + (block(f) + block(f + 1))) * (1.0f / 2048.0f), 1e-10f);
-    };
-    float top = 0.0f;
-    for (int f = threadIdx.x; f < nf; f += IN_THREADS) top = fmaxf(top, energy(f));
-    top = in_block_reduce(top, slot_f, [](float a, float c) { return fmaxf(a, c); });
-    const float lim = top * threshold;
-    int first = 0x7fffffff, last = -1;
-    for (int f = threadIdx.x; f < nf; f += IN_THREADS) {
-      const float e = energy(f);
-      if (e > lim || e >= top) {  // the maximal frame is non-silent whatever the rounding of `lim`
-        first = min(first, f);
-        last = max(last, f);
-      }
-    }
-    first = in_block_reduce(first, slot_i, [](int a, int c) { return min(a, c); });
-    last = in_block_reduce(last, slot_i, [](int a, int c) { return max(a, c); });
-    s0 = IN_HOP * first;
-    s1 = (int)min((long long)m, (long long)IN_HOP * (last + 1));
+    trim_bounds(sums + (int64_t)b * nb_row, m, threshold, slot_f, slot_i, &s0, &s1);
   }
   if (threadIdx.x != 0) return;
   int fl = full > L_cap ? 1 : 0;
@@ -200,7 +158,7 @@ extern "C" int st2_clip_ingest(const void* src, int64_t src_bs, const int32_t* n
                        up, down, taps, taps_per_phase, tile, L_cap, rows, wk_bs, sums, nb_row);
   });
   ST2_CHECK_LAUNCH("st2_clip_ingest (resample)");
-  const float threshold = top_db > 0.0f ? (float)pow(10.0, -(double)top_db / 10.0) : -1.0f;
+  const float threshold = top_db > 0.0f ? trim_threshold(top_db) : -1.0f;
   hipLaunchKernelGGL(ingest_bounds_kernel, dim3(B), dim3(IN_THREADS), 0, s, n, N_cap, up, down, L_cap, threshold, L_min, sums,
                      nb_row, len, start, flags, cut);
   ST2_CHECK_LAUNCH("st2_clip_ingest (bounds)");

@@ -27,10 +27,13 @@ __device__ __forceinline__ void scan_durations(const long long* __restrict__ db,
 }
 
 // One wave per row.  bound[n] = the first frame of token n (st2.h "the boundary rule"), marks[n] = the first output sample at
-// or after that frame's time in the row's packed samples.
+// or after that frame's time in the row's packed samples.  EDGES (st2_token_marks_edges): the row was cut to the `count` samples
+// from `head` on (st2_wave_edges) before it was packed, and a boundary's sample is clamp(s - head, 0, count) of them.
+template <bool EDGES>
 __global__ __launch_bounds__(64) void token_marks_kernel(const long long* __restrict__ dur, int N, const int32_t* __restrict__ len,
                                                          const int32_t* __restrict__ frames, int T_cap, int shift, int spf, int trim,
-                                                         int U, int D, int32_t* __restrict__ marks, int32_t* __restrict__ bound_out) {
+                                                         int U, int D, int32_t* __restrict__ marks, int32_t* __restrict__ bound_out,
+                                                         const int32_t* __restrict__ edges) {
   __shared__ int cum[512];
   const int b = blockIdx.x;
   const int n_b = len ? min(max(len[b], 0), N) : N;
@@ -46,7 +49,8 @@ __global__ __launch_bounds__(64) void token_marks_kernel(const long long* __rest
       const int c = cum[n - 1];
       bound = min(T_b, c == 0 ? 0 : c + (shift ? 1 : 0));
     }
-    const long long s = min((long long)spf * bound, n_smp);
+    long long s = min((long long)spf * bound, n_smp);
+    if constexpr (EDGES) s = min(max(s - edges[2 * b], 0LL), (long long)max(edges[2 * b + 1], 0));
     marks[(int64_t)b * (N + 1) + n] = (int32_t)((s * U + D - 1) / D);
     if (bound_out) bound_out[(int64_t)b * (N + 1) + n] = bound;
   }
@@ -106,24 +110,41 @@ __global__ __launch_bounds__(TOK_THREADS) void prosody_controls_tok_kernel(float
 
 extern "C" int st2_sizeof_token_controls(void) { return (int)sizeof(st2_token_controls); }
 
+// Both entries: every refusal under the entry's name `who`, then the one launch.  edges == NULL: st2_token_marks.
+static int marks_plan(const char* who, const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* frames,
+                      int32_t T_cap, int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, int32_t* marks,
+                      int32_t* bound_out, const int32_t* edges, void* stream) {
+  ST2_REQUIRE(dur && marks, "%s: dur / marks is NULL", who);
+  ST2_REQUIRE(B > 0 && N > 0 && T_cap > 0 && samples_per_frame > 0, "%s: bad geometry (B=%d, N=%d, T_cap=%d, samples_per_frame=%d)", who,
+              B, N, T_cap, samples_per_frame);
+  ST2_REQUIRE(N <= 512, "%s: N=%d tokens exceed the 512 of PL-BERT's position table", who, N);
+  ST2_REQUIRE(up >= 1 && up <= 1024 && down >= 1 && down <= 1024, "%s: up=%d / down=%d must lie in 1..1024", who, up, down);
+  ST2_REQUIRE(trim >= 0, "%s: trim=%d must not be negative", who, trim);
+  // ceil(spf T_cap U / D) <= INT32_MAX  <=>  spf T_cap <= floor(INT32_MAX D / U)
+  ST2_REQUIRE((int64_t)samples_per_frame * T_cap <= (int64_t)INT32_MAX * down / up,
+              "%s: a row at capacity (%d frames of %d samples at %d / %d) does not fit the int32 marks", who, T_cap, samples_per_frame,
+              up, down);
+  auto kernel = edges ? token_marks_kernel<true> : token_marks_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(dur), N,
+                     len, frames, T_cap, shift ? 1 : 0, samples_per_frame, trim, up, down, marks, bound_out, edges);
+  ST2_CHECK_LAUNCH(who);
+  return 0;
+}
+
 extern "C" int st2_token_marks(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* frames, int32_t T_cap,
                                int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, int32_t* marks,
                                int32_t* bound_out, void* stream) {
-  ST2_REQUIRE(dur && marks, "st2_token_marks: dur / marks is NULL");
-  ST2_REQUIRE(B > 0 && N > 0 && T_cap > 0 && samples_per_frame > 0,
-              "st2_token_marks: bad geometry (B=%d, N=%d, T_cap=%d, samples_per_frame=%d)", B, N, T_cap, samples_per_frame);
-  ST2_REQUIRE(N <= 512, "st2_token_marks: N=%d tokens exceed the 512 of PL-BERT's position table", N);
-  ST2_REQUIRE(up >= 1 && up <= 1024 && down >= 1 && down <= 1024, "st2_token_marks: up=%d / down=%d must lie in 1..1024", up, down);
-  ST2_REQUIRE(trim >= 0, "st2_token_marks: trim=%d must not be negative", trim);
-  // ceil(spf T_cap U / D) <= INT32_MAX  <=>  spf T_cap <= floor(INT32_MAX D / U)
-  ST2_REQUIRE((int64_t)samples_per_frame * T_cap <= (int64_t)INT32_MAX * down / up,
-              "st2_token_marks: a row at capacity (%d frames of %d samples at %d / %d) does not fit the int32 marks", T_cap,
-              samples_per_frame, up, down);
-  hipLaunchKernelGGL(token_marks_kernel, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                     reinterpret_cast<const long long*>(dur), N, len, frames, T_cap, shift ? 1 : 0, samples_per_frame, trim, up, down,
-                     marks, bound_out);
-  ST2_CHECK_LAUNCH("st2_token_marks");
-  return 0;
+  return marks_plan("st2_token_marks", dur, B, N, len, frames, T_cap, shift, samples_per_frame, trim, up, down, marks, bound_out,
+                    nullptr, stream);
+}
+
+// st2_token_marks_edges (st2.h): the marks of rows that st2_wave_edges cut, relative to the cut row
+extern "C" int st2_token_marks_edges(const int64_t* dur, int32_t B, int32_t N, const int32_t* len, const int32_t* frames,
+                                     int32_t T_cap, int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down,
+                                     int32_t* marks, int32_t* bound_out, const int32_t* edges, void* stream) {
+  ST2_REQUIRE(edges && reinterpret_cast<uintptr_t>(edges) % 4 == 0, "st2_token_marks_edges: edges is NULL or not aligned to int32");
+  return marks_plan("st2_token_marks_edges", dur, B, N, len, frames, T_cap, shift, samples_per_frame, trim, up, down, marks,
+                    bound_out, edges, stream);
 }
 
 extern "C" int st2_prosody_controls_tok(float* f0, float* n, int64_t bs, int32_t B, int32_t L, const int64_t* dur, int32_t N,

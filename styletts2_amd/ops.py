@@ -1176,7 +1176,7 @@ def frames_from_durations(dur, lengths_dev, T_cap):
 
 
 def token_marks(dur, frames, T_cap, lengths=None, shift=False, trim=0, rate=None, samples_per_frame=600, out=None,
-                want_bound=False):
+                want_bound=False, _edges=None):
     """`st2_token_marks`: where every token starts in its row's packed samples, without a host read.  dur int64 [B, N] on the
     device, frames int32 [B] on the device (None: every row has T_cap frames), lengths int32 [B] on the device or None ->
     int32 [B, N + 1]: marks[b, n] is the first sample of token n among the row's samples as `wave_pack` (rate None or 24000) /
@@ -1195,9 +1195,30 @@ def token_marks(dur, frames, T_cap, lengths=None, shift=False, trim=0, rate=None
     if tuple(out.shape) != (B, N + 1) or out.device != dur.device:
         raise _lib.St2Error("out must be [%d, %d] on the device of dur (got %s on %s)" % (B, N + 1, tuple(out.shape), out.device))
     bound = torch.empty((B, N + 1), device=dur.device, dtype=torch.int32) if want_bound else None
-    _lib.check(_lib.load().st2_token_marks(dur.data_ptr(), B, N, lp, fp, int(T_cap), 1 if shift else 0, int(samples_per_frame),
-                                           int(trim), U, D, out.data_ptr(), _ptr(bound), _stream()), "st2_token_marks")
+    entry, more = ("st2_token_marks", ()) if _edges is None else ("st2_token_marks_edges", (_edges.data_ptr(),))
+    _lib.check(getattr(_lib.load(), entry)(dur.data_ptr(), B, N, lp, fp, int(T_cap), 1 if shift else 0, int(samples_per_frame),
+                                           int(trim), U, D, out.data_ptr(), _ptr(bound), *more, _stream()), entry)
     return (out, bound) if want_bound else out
+
+
+def _chk_edges(edges, B, like):
+    """An edges table: int32 with 2 B entries, contiguous, on the device of `like`."""
+    _chk_dev(edges, "edges", torch.int32, edges.dim() if torch.is_tensor(edges) else 2)
+    if edges.numel() != 2 * B or edges.device != like.device:
+        raise _lib.St2Error("edges must hold [%d, 2] values on the device of its rows (got %s on %s)"
+                            % (B, tuple(edges.shape), edges.device))
+    return edges
+
+
+def token_marks_edges(dur, frames, T_cap, edges, lengths=None, shift=False, trim=0, rate=None, samples_per_frame=600, out=None,
+                      want_bound=False):
+    """`st2_token_marks_edges`: `token_marks` for rows that `wave_edges` cut before they were packed.  edges int32 [B, 2] on the
+    device, {head, count} as `wave_edges` wrote them; every other argument and the return value as `token_marks`.  A boundary at
+    sample s of the uncut row is at clamp(s - head, 0, count) of the cut one, so marks[b, N] is still the row's packed sample
+    count.  One launch, no host read."""
+    _chk_dev(dur, "dur", torch.int64, 2)
+    return token_marks(dur, frames, T_cap, lengths=lengths, shift=shift, trim=trim, rate=rate, samples_per_frame=samples_per_frame,
+                       out=out, want_bound=want_bound, _edges=_chk_edges(edges, dur.shape[0], dur))
 
 
 OUTPUT_FORMATS = {"f32": (_lib.PCM_F32, torch.float32), "s16": (_lib.PCM_S16, torch.int16),
@@ -1437,6 +1458,59 @@ def wave_limit(wave, frames, level, target, win, ceiling=1.0, max_gain_db=20.0, 
                                           float(drive_db), win.numel() // 2, win.data_ptr(), out.data_ptr(), limit.data_ptr(),
                                           workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_limit")
     return out, limit
+
+
+EDGES_TILE = 2048  # st2_wave_edges_tile(): the samples of a tile of the block sums' launch (tests place events at its edges)
+
+
+def wave_edges_workspace_bytes(B, T_cap, samples_per_frame=600):
+    """`st2_wave_edges_workspace_bytes`: what `wave_edges(workspace=)` needs, in bytes: the rows' 512-sample block sums."""
+    return int(_lib.load().st2_wave_edges_workspace_bytes(int(B), int(T_cap), int(samples_per_frame)))
+
+
+def wave_edges(wave, frames, top_db, keep, ramp=None, trim=0, samples_per_frame=600, out=None, edges=None, workspace=None):
+    """`st2_wave_edges`: lead and tail silence trimmed on the device.  wave, frames, trim and
+    samples_per_frame as `wave_level` takes them; top_db fp32 [B] on the device (librosa's `effects.trim` threshold in dB under
+    the row's loudest frame; NaN or <= 0 = leave the row alone), keep int32 [B, 2] on the device (samples of lead and of tail to
+    keep outside the detected bounds; negative = 0), `ramp` fp32 [F] on the device (`resample.edge_ramp`; F <= 4096; None = no
+    fade) -> (out, edges): `out` fp32 with the shape and strides of wave as [B, L] -- row b's samples head .. head + count - 1
+    moved to its front, bit for bit but for the fade: min(F, count // 2) samples times the ramp at an edge that was cut, none at
+    an edge that was not; samples at or past `count` are not written -- and `edges` int32 [B, 2] = {head, count} per row.
+    `workspace`: a uint8 device tensor of `wave_edges_workspace_bytes` bytes (by default from the caching allocator).  No host
+    read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf = int(samples_per_frame)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    _chk_dev(top_db, "top_db", torch.float32, 1)
+    _chk_dev(keep, "keep", torch.int32, keep.dim() if torch.is_tensor(keep) else 2)
+    if top_db.numel() != B or keep.numel() != 2 * B or top_db.device != wave.device or keep.device != wave.device:
+        raise _lib.St2Error("top_db must hold %d values and keep [%d, 2], both on the device of wave" % (B, B))
+    if ramp is not None:
+        _chk_dev(ramp, "ramp", torch.float32, 1)
+        if ramp.device != wave.device:
+            raise _lib.St2Error("ramp must live on the device of wave")
+    if out is None:
+        out = torch.empty_strided((B, L), (wave.stride(0), 1), device=wave.device, dtype=torch.float32)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (B, L) or out.device != wave.device or (B > 1 and out.stride(0) != wave.stride(0)):
+        raise _lib.St2Error("out must be [%d, %d] with the row stride of wave, on its device (got %s)" % (B, L, tuple(out.shape)))
+    if edges is None:
+        edges = torch.empty((B, 2), device=wave.device, dtype=torch.int32)
+    _chk_edges(edges, B, wave)
+    need = wave_edges_workspace_bytes(B, L // spf, spf)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    _lib.check(_lib.load().st2_wave_edges(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), top_db.data_ptr(),
+                                          keep.data_ptr(), _ptr(ramp), 0 if ramp is None else ramp.numel(), out.data_ptr(),
+                                          edges.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_edges")
+    return out, edges
 
 
 NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*

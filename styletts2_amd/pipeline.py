@@ -10,6 +10,7 @@ Differences from the notebooks, all host-side:
   * optional `durations=` forces the per-phoneme durations (throughput runs use 4 frames / phoneme so that
     every utterance is exactly 10 s) and removes the only data-dependent host sync.
 """
+import functools
 import typing
 
 import torch
@@ -380,6 +381,79 @@ class Level(metaclass=_LevelOptions):
     def options(self):
         """The keyword options of this Level, as its constructor takes them (what a copy over other rows is made with)."""
         return dict(true_peak=self.true_peak, scope=self.scope, limiter=self.limiter, drive_db=self.drive_db, window_ms=self.window_ms)
+
+
+class Edges:
+    """Lead and tail silence trimmed from every row of the packed hand-over (include/st2.h
+    `st2_wave_edges`): the speech of every row is found on the device by librosa's `effects.trim` rule -- the rule the clip
+    ingest trims reference clips by -- and the row is cut to it before anything else of the hand-over runs.
+
+        top_db    dB under the row's loudest frame below which a frame is silence, one value or B values;
+                  None or NaN in a row = leave this row alone                                              (0, 120]
+        lead_ms   speech onsets are soft: this much is kept in front of the first non-silent frame        [0, 500]
+        tail_ms   and this much behind the last one                                                        [0, 500]
+        fade_ms   a raised-cosine fade over an edge that was cut (never over one that was not); at most
+                  `resample.EDGE_MAX_F` samples                                                            [0, 500]
+
+    Kept as one fp32 [B] device row (`top_db`) and one int32 [B, 2] device table (`keep`, samples at the model rate), validated
+    on the host like `Level`; a `top_db` tensor already on the device is not read.  `F` is the fade in samples."""
+
+    def __init__(self, B, top_db=40.0, lead_ms=10.0, tail_ms=30.0, fade_ms=2.0, device=None):
+        B = int(B)
+        if B <= 0:
+            raise ValueError("Edges: B must be positive, got %r" % (B,))
+        times = {}
+        for name, v in (("lead_ms", lead_ms), ("tail_ms", tail_ms), ("fade_ms", fade_ms)):
+            v = float(v)
+            if not 0.0 <= v <= 500.0:
+                raise ValueError("Edges: %s must lie in [0, 500], got %r" % (name, v))
+            times[name] = v
+        F = self.samples(times["fade_ms"])
+        if F > resample.EDGE_MAX_F:
+            raise ValueError("Edges: fade_ms=%r is %d samples, the fade holds %d at most" % (times["fade_ms"], F, resample.EDGE_MAX_F))
+        on_dev = torch.is_tensor(top_db) and top_db.is_cuda
+        if device is None:
+            device = top_db.device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        self.B, self.F = B, F
+        self.lead_ms, self.tail_ms, self.fade_ms = times["lead_ms"], times["tail_ms"], times["fade_ms"]
+        self.top_db = self.row(top_db, B).to(device)
+        self.keep = torch.tensor([[self.samples(self.lead_ms), self.samples(self.tail_ms)]] * B, dtype=torch.int32).to(device)
+
+    @staticmethod
+    def samples(ms):
+        """Milliseconds as samples at the model rate: `gap_samples`' rounding."""
+        return int(round(float(ms) * resample.MODEL_RATE / 1000.0))
+
+    @staticmethod
+    def row(top_db, B):
+        """`top_db` as the fp32 [B] row the kernel reads: a device tensor as it is (unread), host values validated; None = NaN."""
+        if torch.is_tensor(top_db) and top_db.is_cuda:
+            if top_db.numel() != B:
+                raise ValueError("Edges: top_db must hold %d values, got shape %s" % (B, tuple(top_db.shape)))
+            return top_db.detach().reshape(B).to(torch.float32)
+        if top_db is None:
+            top_db = float("nan")
+        if isinstance(top_db, (list, tuple)):
+            top_db = [float("nan") if v is None else float(v) for v in top_db]
+        rows = torch.as_tensor(top_db, dtype=torch.float64).reshape(-1)
+        if rows.numel() == 1:
+            rows = rows.expand(B)
+        if rows.numel() != B:
+            raise ValueError("Edges: top_db must be one value or %d values, got %d" % (B, rows.numel()))
+        if not bool((torch.isnan(rows) | ((rows > 0.0) & (rows <= 120.0))).all()):
+            raise ValueError("Edges: top_db must lie in (0, 120] dB (None / NaN = leave the row alone), got %s" % rows.tolist())
+        return rows.to(torch.float32)
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as an Edges over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Edges)
+        c.B, c.F, c.lead_ms, c.tail_ms, c.fade_ms = j - i, self.F, self.lead_ms, self.tail_ms, self.fade_ms
+        c.top_db, c.keep = self.top_db[i:j], self.keep[i:j]
+        return c
+
+    def options(self):
+        """The three times of this Edges, as its constructor takes them (what a copy over other rows is made with)."""
+        return dict(lead_ms=self.lead_ms, tail_ms=self.tail_ms, fade_ms=self.fade_ms)
 
 
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
@@ -882,6 +956,9 @@ class SynthesisResult:
                passed the gates), its sample peak, the linear gain its packed samples were multiplied by and the number of gating
                blocks that passed -- measured on `wave`, which stays as the decoder made it.  Kept in the same allocation behind
                the gaps: `to_host(level=True)` is still one copy.
+      edges    (with `edges=`) int32 [B, 2]: {head, count} at the model rate -- row b's packed samples are
+               wave[b, 0, head : head + count], faded at an edge that was cut, through the rest of the hand-over; offsets, marks
+               and the level are those of the cut rows.  Kept in the same allocation: `to_host(edges=True)` is still one copy.
       fit      (with `fit_frames=`) int32 [B, 4]: {the row's frames before the fit, its frames after,
                flag, the number of tokens whose duration changed}; flag 0 = the target was met, 1 = it was infeasible and the
                nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
@@ -905,8 +982,9 @@ class SynthesisResult:
         self.packed, self.offsets, self.gaps = (None, None, None) if ho is None else (ho.packed, ho.offsets, ho.gaps)
         self.level = None if ho is None or ho.level is None else ho.level.view(-1, 4)
         self.limit = None if ho is None or ho.limit is None else ho.limit.view(-1, 2)
+        self.edges = None if ho is None or ho.edges is None else ho.edges.view(-1, 2)
 
-    def to_host(self, marks=False, passage=False, level=False, limit=False):
+    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -921,7 +999,10 @@ class SynthesisResult:
         breaks as a client plays them.  `level=True` (a result made with `level=`): the level table as a float32 [B, 4] numpy
         array out of the same copy, behind whatever else is returned: (arrays, level) or (arrays, marks, level).  `limit=True` (a
         result made with a limiting `Level`): the limiter's {drive gain, smallest gain factor} as a float32 [B, 2] numpy array, out
-        of the same copy, last."""
+        of the same copy, behind those.  `edges=True` (a result made with `edges=`): {head, count} per row as an int32 [B, 2] numpy
+        array, out of the same copy, last."""
+        if edges and self.edges is None:
+            raise ValueError("this result carries no edges table: ask for it with inference(..., edges=Edges(...))")
         if level and self.level is None:
             raise ValueError("this result carries no level table: ask for it with inference(..., level=Level(...))")
         if limit and self.limit is None:
@@ -950,6 +1031,8 @@ class SynthesisResult:
         more = ((m.numpy().reshape(tuple(self.marks.shape)),) if marks else ()) + ((lv.numpy().reshape(B, 4),) if level else ())
         if limit:
             more += (self._ho.limit_view(self._host).numpy().reshape(B, 2),)
+        if edges:
+            more += (self._ho.edges_view(self._host).numpy().reshape(B, 2),)
         return (rows,) + more if more else rows
 
 
@@ -1009,28 +1092,34 @@ class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
         [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | limit float32 [2 B] |
-         pad to 16 bytes | samples of `fmt`]
+         edges int32 [2 B] | pad to 16 bytes | samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps / no level / no limit the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    with `n_marks` = 0 / no gaps / no level / no limit / no edges the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
     five parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
     its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `packed` and `level` are
     the buffer and its views (None for a part the layout does not have)."""
 
-    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False):
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
-        self.with_level, self.with_limit = bool(with_level), bool(with_limit)
+        self.with_level, self.with_limit, self.with_edges = bool(with_level), bool(with_limit), bool(with_edges)
         self.offsets_at = 0
         self.marks_at = 8 * (self.B + 1)
         self.gaps_at = self.marks_at + 4 * self.n_marks
         self.level_at = self.gaps_at + (4 * self.B if self.with_gaps else 0)
         self.limit_at = self.level_at + (16 * self.B if self.with_level else 0)
-        self.samples_at = (self.limit_at + (8 * self.B if self.with_limit else 0) + 15) // 16 * 16
-        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = None
+        self.edges_at = self.limit_at + (8 * self.B if self.with_limit else 0)
+        self.samples_at = (self.edges_at + (8 * self.B if self.with_edges else 0) + 15) // 16 * 16
+        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = self.edges = None
 
     def limit_view(self, buf):
         """The sixth part, float32 [2 B] (`ops.wave_limit`'s {g', min q} per row), of a uint8 buffer of this
         layout, or None.  Apart from `views`, whose five parts stay the five they were."""
         return buf[self.limit_at:self.limit_at + 8 * self.B].view(torch.float32) if self.with_limit else None
+
+    def edges_view(self, buf):
+        """The seventh part, int32 [2 B] (`ops.wave_edges`'s {head, count} per row), of a uint8 buffer of this
+        layout, or None.  Apart from `views`, as `limit_view` is."""
+        return buf[self.edges_at:self.edges_at + 8 * self.B].view(torch.int32) if self.with_edges else None
 
     def views(self, buf):
         """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
@@ -1044,6 +1133,7 @@ class _HandOver:
         self.buf = torch.empty((self.samples_at + samples * self.dtype.itemsize,), device=device, dtype=torch.uint8)
         self.offsets, self.marks, self.gaps, self.packed, self.level = self.views(self.buf)
         self.limit = self.limit_view(self.buf)
+        self.edges = self.edges_view(self.buf)
         return self
 
 
@@ -1065,7 +1155,7 @@ def _capacity_only(names, *given):
 
 
 def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False,
-                 passage=None, front_groups=1):
+                 passage=None, front_groups=1, edges=None):
     """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
     every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
     launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
@@ -1074,7 +1164,8 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     `capacity`: the call has a `max_frames`.  `graph`: the caller is `GraphedSynthesis`, to which `max_frames` is no option --
     its `marks` refusal names `pack` alone.  `trim` goes through as given: `_decode_capacity` resolves None.  `passage`: the
     call's `passage`, and `front_groups`: the front calls `synthesize_long` cuts the passage into -- what a `Level` of
-    scope "passage" is judged by, and looked at for nothing else."""
+    scope "passage" is judged by, and looked at for nothing else.  `edges`: an `Edges` of the B rows, judged here and handed on by
+    the caller (the spec does not carry it, as it does not carry `level`)."""
     if pack is not None and pack not in ops.OUTPUT_FORMATS:
         raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
     if sample_rate is not None and pack is None:
@@ -1090,6 +1181,10 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     if level is not None and level.scope == "passage" and front_groups > 1:
         raise ValueError("level of scope 'passage' is one gain for the rows of ONE call, and front_batch cuts this passage into %d: "
                          "pass front_batch=0" % front_groups)
+    if edges is not None and (pack is None or not capacity):
+        raise ValueError("edges are cut from the packed samples of the capacity-bound path: pass max_frames and pack")
+    if edges is not None and (not isinstance(edges, Edges) or edges.B != B):
+        raise ValueError("edges must be a pipeline.Edges of %d rows" % B)
     if not capacity:
         _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
     if pack is None and (gaps is not None or max_gap is not None):
@@ -1121,6 +1216,13 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
 
 
 def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None, starts=None):
+    """The hand-over without an edge trim: `_hand_over_edges` with `edges=None`, under the name and the parameter list it has
+    always had."""
+    return _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate, n_marks, gaps, max_gap, level, starts)
+
+
+def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None,
+                     starts=None, edges=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
@@ -1131,13 +1233,21 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     table of `resample.true_peak_table`; one of scope "passage" has it read `starts` (int32 [B] on the device, 1 where a
     passage begins; None = the rows are one passage).  A plain `Level` passes neither argument on.  A `Level` with `limiter`
     (DESIGN.md section 27): measure as above, then `ops.wave_limit` into a buffer of the caching allocator with {g', min q} into
-    the header's limit part, then the wrapper a call WITHOUT a level takes, over the limited rows."""
+    the header's limit part, then the wrapper a call WITHOUT a level takes, over the limited rows.  With `edges` (an `Edges`;
+    DESIGN.md section 28) `ops.wave_edges` runs FIRST, into a buffer of the caching allocator with {head, count} into the header's
+    edges part, and everything above runs unchanged over the cut rows: their sample counts are the frame counts of rows of
+    one-sample frames, nothing trimmed -- frames = count, samples_per_frame = 1, trim = 0."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
     room = resample.output_samples(L, U, D) + (0 if gaps is None else max_gap)
     limiting = level is not None and level.limiter
-    ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting).allocate(B * room, wave.device)
+    ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting,
+                   with_edges=edges is not None).allocate(B * room, wave.device)
+    if edges is not None:
+        wave, _ = ops.wave_edges(wave, frames, edges.top_db, edges.keep, resample.edge_ramp(edges.F, wave.device) if edges.F else None,
+                                 trim=trim, samples_per_frame=samples_per_frame, edges=ho.edges)
+        frames, trim, samples_per_frame = ho.edges.view(B, 2)[:, 1].contiguous(), 0, 1  # the counts as a row of their own
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
@@ -1167,11 +1277,11 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None):
+def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
     into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation, `starts`: the call's `passage`
-    for a level of scope "passage" (`_hand_over`)."""
+    for a level of scope "passage" (`_hand_over`), `edges`: their trim (`_hand_over_edges`; the marks are then `ops.token_marks_edges`')."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     hifigan = model.decoder.kind == "hifigan"
@@ -1182,13 +1292,15 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None):
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    ho = _hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
-                    level, starts)
+    hand_over = _hand_over if edges is None else functools.partial(_hand_over_edges, edges=edges)
+    ho = hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
+                   level, starts)
     m = None
     if spec.marks:
         m = ho.marks.view(B, N + 1)
-        ops.token_marks(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
-                        rate=spec.sample_rate, samples_per_frame=spf, out=m)
+        marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
+        marks_of(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
+                 rate=spec.sample_rate, samples_per_frame=spf, out=m)
     return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"], fit=p.get("fit"))
 
 
@@ -1240,11 +1352,17 @@ class GraphedSynthesis:
     `static["fit_frames"]` (int32 [B], zeros: every row left alone) and `static["fit_hold"]` (uint8 [B, N], zeros: no token
     held), both read on the device, so one recorded graph serves any targets: `__call__(fit_frames=, fit_hold=)` copies them in
     (what is left out keeps its contents) and the result carries `fit`.  A graph built without it has neither key, refuses both
-    arguments and records exactly what it recorded before."""
+    arguments and records exactly what it recorded before.
+
+    `edges=True` (or an `Edges`; needs `pack`): the graph records the trim in front of the hand-over over one
+    more static buffer, `static["edges"]` (an `Edges`; at first 40 dB in every row, or the one given): `__call__(edges=)` -- an
+    `Edges`, one `top_db` or B of them, None / NaN = leave the row alone -- copies the thresholds into its row, so one graph
+    serves any thresholds; the pads and the fade are the graph's own.  Without it the graph records exactly what it recorded
+    before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False):
+                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1254,15 +1372,19 @@ class GraphedSynthesis:
         self.device, self.max_frames, self.steps = dev, int(max_frames), int(diffusion_steps)
         self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
         level = Level(B, device=dev) if level is True else None if level is False else level
+        edges = Edges(B, device=dev) if edges is True else None if edges is False else edges
         # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
         gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
-        spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage)
+        spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage,
+                               **({} if edges is None else {"edges": edges}))
         if spec.rate is not None:
             resample.table(spec.rate, dev)
         if level is not None and level.true_peak:
             resample.true_peak_table(dev)  # as the rate's table: made before the capture that reads it
         if level is not None and level.limiter:
             resample.limit_window(level.W, dev)  # and the limiter's window
+        if edges is not None and edges.F:
+            resample.edge_ramp(edges.F, dev)  # and the fade of a cut edge
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1292,6 +1414,8 @@ class GraphedSynthesis:
         if level is not None:
             self.static["level"] = Level(B, target=level.target.to(dev).clone(), ceiling_db=level.ceiling_db,
                                          max_gain_db=level.max_gain_db, device=dev, **level.options())
+        if edges is not None:
+            self.static["edges"] = Edges(B, top_db=edges.top_db.to(dev).clone(), device=dev, **edges.options())
         self._g = None
 
     def _run(self):
@@ -1300,7 +1424,8 @@ class GraphedSynthesis:
                          sine_noise=st["sine_noise"], ref_s=st["ref_s"], lengths_dev=st["lengths_dev"],
                          controls=st["controls"], passage=st.get("starts"), s_prev=st.get("s_prev"), gaps=st.get("gaps"),
                          level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}),
-                         **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}))
+                         **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}),
+                         **({"edges": st["edges"]} if "edges" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1313,7 +1438,7 @@ class GraphedSynthesis:
 
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
-                 starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None):
+                 starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None):
         st = self.static
         if fit_frames is not None or fit_hold is not None:
             if "fit_frames" not in st:
@@ -1352,6 +1477,13 @@ class GraphedSynthesis:
             if row.numel() != st["level"].B:
                 raise ValueError("level must hold %d targets, got %d" % (st["level"].B, row.numel()))
             st["level"].target.copy_(row, non_blocking=True)
+        if edges is not None:
+            if st.get("edges") is None:
+                raise ValueError("this graph was built without edges: pass edges=True")
+            row = edges.top_db if isinstance(edges, Edges) else Edges.row(edges, st["edges"].B)
+            if row.numel() != st["edges"].B:
+                raise ValueError("edges must hold %d thresholds, got %d" % (st["edges"].B, row.numel()))
+            st["edges"].top_db.copy_(row, non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
@@ -1526,7 +1658,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None, fit_frames=None, fit_hold=None):
+              seeds=None, fit_frames=None, fit_hold=None, edges=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1607,9 +1739,15 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     negative or above `max_frames`; a feasible target (at least one frame per free token plus the held ones) is met exactly,
     any other is replaced by the nearest feasible total.  The result carries `fit`, int32 [B, 4]: {frames before, frames
     after, flag, tokens changed} per row.  Without the two arguments the call issues exactly the launches it always did.
+
+    `edges` (an `Edges` of B rows, with `max_frames` and `pack`): the silence the model makes in front of and
+    behind every row's speech is trimmed on the device (`ops.wave_edges`, the first step of the hand-over), so that `gaps` are
+    the pauses a listener hears and `marks[b, 0]` / `marks[b, N]` bracket speech.  Level, limiter, gaps, resampling and G.711 run
+    over the cut rows; the result carries {head, count} as `edges` and `to_host(edges=True)` brings them over in its one copy.
+    `wave` stays as the decoder made it.  Without `edges` the call issues exactly the launches it always did.
     """
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
-                              passage=passage)
+                              passage=passage, **({} if edges is None else {"edges": edges}))
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
@@ -1644,7 +1782,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     if seeds is not None:
         sine_noise = _seeded_sine_noise(seeds, p["frames"], max_frames)
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage)
+        return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage, **({} if edges is None else {"edges": edges}))
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1713,7 +1851,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None, seeds=None, fit_frames=None):
+                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1774,6 +1912,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `fit_frames` (needs `max_frames`): one frame target per SENTENCE -- K whole frame counts or an int32 [K]
     device tensor, 0 = leave the sentence alone --: every sentence's durations are fitted to its own target
     (`inference(fit_frames=)`); the breaks between sentences are not part of it.
+    `edges` (needs `max_frames` and `pack`): an `Edges` of one row per SENTENCE: every sentence is cut to its
+    speech (`inference(edges=)`), so that the breaks of `gaps` are the pauses between sentences.
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
@@ -1784,8 +1924,9 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds, fit_frames=fit_frames)
+            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
+    _capacity_only("edges", edges)
     _capacity_only("seeds", seeds)
     _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
@@ -1866,7 +2007,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -1890,7 +2031,7 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     # the K sentences' output, judged once (a `max_gap` without `gaps` is not looked at, as ever); every group's slice is, again
     chunks = _front_chunks(front_batch, K)
     spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level, passage=True,
-                              front_groups=len(chunks))
+                              front_groups=len(chunks), **({} if edges is None else {"edges": edges}))
     prepped = []
     for i, i_end in chunks:
         ids = list(range(i, i_end))
@@ -1909,6 +2050,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     for k, q in enumerate(prepped):
         i, j = q["ids"][0], q["ids"][-1] + 1
         more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=spec.max_gap)
+        if edges is not None:
+            more.update(edges=edges.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,

@@ -136,3 +136,22 @@ def limit_window(W, device):
     like `table`, never under stream capture."""
     _, _, _, win = _device_table(("lim",), int(W), device, lambda w: (1, 1, limit_window_design(w)[None, :]), "limit_window")
     return win[0]
+
+
+EDGE_MAX_F = 4096  # st2_wave_edges's longest fade
+
+
+def edge_ramp_design(F):
+    """-> fp32 [F]: the fade of a cut edge (`ops.wave_edges`) -- the rising half of a raised cosine sampled
+    at the half points, ramp[i] = 0.5 - 0.5 cos(pi (i + 0.5) / F): strictly inside (0, 1), rising, and ramp[i] + ramp[F - 1 - i] = 1."""
+    F = int(F)
+    if not 1 <= F <= EDGE_MAX_F:
+        raise ValueError("the edge fade must be 1..%d samples, got %r" % (EDGE_MAX_F, F))
+    return (0.5 - 0.5 * np.cos(np.pi * (np.arange(F, dtype=np.float64) + 0.5) / F)).astype(np.float32)
+
+
+def edge_ramp(F, device):
+    """-> ramp fp32 [F] on `device`: `edge_ramp_design(F)`, one copy per (F, device), designed and uploaded on first use and, like
+    `table`, never under stream capture."""
+    _, _, _, ramp = _device_table(("edge",), int(F), device, lambda f: (1, 1, edge_ramp_design(f)[None, :]), "edge_ramp")
+    return ramp[0]
