@@ -796,6 +796,58 @@ int st2_token_marks_edges(const int64_t* dur, int32_t B, int32_t N, const int32_
                           int32_t shift, int32_t samples_per_frame, int32_t trim, int32_t up, int32_t down, int32_t* marks,
                           int32_t* bound_out, const int32_t* edges /* int32 [B][2], device */, void* stream);
 
+/* ---- breaks: silence spliced into a row at token spans (added under ABI 23, additive: two kernel-level entry points and one
+ * helper, no new backend-table slot, no struct change, no new sticky status bit) ------------------------- *
+ * st2_wave_breaks: a pause INSIDE a row.  It takes st2_wave_edges's geometry (wave, w_bs, frames, B, T_cap, samples_per_frame,
+ * trim) and its ramp (fp32 [F], F in 0..4096, NULL with F = 0), and, on the device and read by the kernels, pos int32 [B][N + 1]
+ * (the tokens' boundaries in samples of THIS row: st2_token_marks(_edges) at up = down = 1) and brk int32 [B][N] (samples of
+ * silence wanted inside token n; <= 0 = none); max_break is a host number, the most silence one row takes, and sizes the grids.
+ * It writes `out` (fp32, row stride o_bs >= samples_per_frame T_cap + max_break, not overlapping wave), ins int32 [B][N], cuts
+ * int32 [B][N] and breaks int32 [B][2].
+ *  1. Valid samples.  Row b's valid samples are st2_wave_level's rule 1: x[0 .. n_b).  A non-finite sample counts as 0 for the
+ *     measurement only.  The boundaries are q[0] = 0, q[N] = n_b, q[i] = clamp(pos[b][i], 0, n_b) otherwise, then made monotone
+ *     by a running maximum, q[i] = max(q[i - 1], q[i]); token n's span is [q[n], q[n + 1]).
+ *  2. Block energies.  s[k] is the sum of squares of the row's samples [64 k, 64 k + 64), zeros at and past n_b: lane l of a
+ *     wave squares sample 64 k + l (one fp32 multiply), and the 64 squares are folded by a butterfly, t[l] += t[l ^ off] for
+ *     off = 32, 16, ..., 1 in fp32.  The window energy is e_k = s[k - 1] + s[k] in fp32: 128 samples, 5.3 ms.
+ *  3. Cut.  For token n with a break and span [p0, p1) the candidates are the k with 64 (k - 1) >= p0 and 64 (k + 1) <= p1; the
+ *     cut is c = 64 k for the smallest e_k, the smallest such k among equal ones.  Without a candidate (a span that holds no
+ *     aligned window, or an empty one) c = (p0 + p1) div 2.  p0 <= c <= p1, so the cuts of a row do not decrease.
+ *  4. Cap.  In token order, with w_n = max(brk[b][n], 0): ins[b][n] = min(w_n, max_break - the silence inserted in front of
+ *     token n) (the sum of the w in 64 bits).  ins[b][n] = 0 -- nothing asked for, or the cap reached -- makes no cut:
+ *     cuts[b][n] = -1 and no fade; else cuts[b][n] = c.
+ *  5. Move, fade and fill.  The m cuts of the row divide it into m + 1 segments (a segment between two equal cuts is empty).
+ *     Every segment is copied, bit for bit, NaN payloads included, to its place plus the silence in front of it, and ins[b][n]
+ *     samples of +0.0f follow cut n.  With f = min(F, (a segment's length) div 2), the last f samples of a segment that ends
+ *     at a cut are multiplied by ramp[0 .. f) counted back from the cut, the first f samples of a segment that starts at one by
+ *     ramp[0 .. f) counted from it: one fp32 multiply each, f + f <= the length, so no sample takes two.  The row's own ends
+ *     are not faded (that is st2_wave_edges's).  count' = n_b + the silence inserted; nothing at or past out[b][count'] is
+ *     written.  A row without a break is a bit copy of its n_b samples.
+ *  6. Result.  breaks[b] = {count', the silence inserted}.
+ *  7. Independence.  The block sums have one fixed order, the minimum and its tie rule do not depend on order, the scan is in
+ *     integers and the move accumulates nothing: a row's output and its numbers depend neither on the tiling nor on the row's
+ *     place in the batch, bit for bit.
+ * `workspace` (float-aligned, st2_wave_breaks_workspace_bytes(B, T_cap, samples_per_frame, N) bytes; 0 for an argument <= 0 or
+ * N > 512) holds the block sums and one segment table per row.  Three launches (block sums; per row the boundaries, the cap,
+ * the cuts and the table; the move), no atomics, no allocation, no synchronisation, no host read: legal under stream capture.
+ * Returns non-zero before any launch on every refusal of st2_wave_edges that applies (NULL wave / frames / out / workspace, bad
+ * geometry, trim < 0, w_bs too small, F outside 0..4096 or F > 0 with a NULL ramp, misaligned wave / out / ramp / workspace or
+ * frames, out overlapping wave, a workspace that is too small) and on: NULL or misaligned pos / brk / ins / cuts / breaks; N
+ * outside 1..512; max_break < 0; o_bs too small; a row at capacity with max_break beyond the int32 counts. */
+int64_t st2_wave_breaks_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame, int32_t N);
+int st2_wave_breaks(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                    int32_t trim, const int32_t* pos /* int32 [B][N + 1], device */, const int32_t* brk /* int32 [B][N], device */,
+                    int32_t N, int32_t max_break, const float* ramp /* fp32 [F], device */, int32_t F, float* out, int64_t o_bs,
+                    int32_t* ins /* int32 [B][N], device */, int32_t* cuts /* int32 [B][N], device */,
+                    int32_t* breaks /* int32 [B][2], device */, void* workspace, int64_t workspace_bytes, void* stream);
+/* st2_token_marks_breaks: the timing marks of rows that st2_wave_breaks spliced silence into.  pos and ins as that entry read and
+ * wrote them (a negative entry counts as 0): marks[b][n] = min(((pos[b][n] + sum_{m < n} ins[b][m]) * up + down - 1) div down,
+ * INT32_MAX), in 64 bits, n = 0 .. N.  Token n's own break lies inside [marks[b][n], marks[b][n + 1]), and with pos[b][N] = n_b
+ * marks[b][N] is the row's packed sample count, ceil(count' up / down).  One launch, one wave per row.  Returns non-zero before
+ * the launch on a NULL or misaligned pos / ins / marks, B <= 0, N outside 1..512, up or down outside 1..1024. */
+int st2_token_marks_breaks(const int32_t* pos, const int32_t* ins, int32_t B, int32_t N, int32_t up, int32_t down,
+                           int32_t* marks /* int32 [B][N + 1], device */, void* stream);
+
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
  * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one

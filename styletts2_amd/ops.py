@@ -1513,6 +1513,97 @@ def wave_edges(wave, frames, top_db, keep, ramp=None, trim=0, samples_per_frame=
     return out, edges
 
 
+def _chk_tok_int(t, name, B, N, like):
+    """A per-token int32 table of the breaks (include/st2.h `st2_wave_breaks`): [B, N] entries, contiguous, on the device of `like`."""
+    _chk_dev(t, name, torch.int32, t.dim() if torch.is_tensor(t) else 2)
+    if t.numel() != B * N or t.device != like.device:
+        raise _lib.St2Error("%s must hold [%d, %d] values on the device of its rows (got %s on %s)" % (name, B, N, tuple(t.shape), t.device))
+    return t
+
+
+def wave_breaks_workspace_bytes(B, T_cap, samples_per_frame=600, N=1):
+    """`st2_wave_breaks_workspace_bytes`: what `wave_breaks(workspace=)` needs, in bytes: the rows' 64-sample block sums and their
+    segment tables."""
+    return int(_lib.load().st2_wave_breaks_workspace_bytes(int(B), int(T_cap), int(samples_per_frame), int(N)))
+
+
+def wave_breaks(wave, frames, pos, brk, max_break, ramp=None, trim=0, samples_per_frame=600, out=None, ins=None, cuts=None,
+                breaks=None, workspace=None):
+    """`st2_wave_breaks`: silence spliced into rows at token spans, on the device.  wave, frames, trim and
+    samples_per_frame as `wave_edges` takes them; pos int32 [B, N + 1] on the device (the tokens' boundaries in samples of this
+    row: `token_marks` / `token_marks_edges` without a rate), brk int32 [B, N] on the device (samples of silence inside token n;
+    <= 0 = none), `max_break` (host int: the most silence one row takes; it sizes `out` and the grids), `ramp` fp32 [F] on the
+    device (`resample.edge_ramp`; None = no fade) -> (out, ins, cuts, breaks): `out` fp32 [B, L + max_break] (row stride a
+    multiple of 4) -- every row cut at the quietest 128-sample window inside each named token's span, both sides faded, the
+    silence between them; samples at or past the row's new count are not written --, `ins` int32 [B, N] (silence inserted per
+    token, after the cap), `cuts` int32 [B, N] (the cut's place in the input row, -1 = none) and `breaks` int32 [B, 2] = {the
+    row's new count, the silence inserted}.  `workspace`: a uint8 device tensor of `wave_breaks_workspace_bytes` bytes (by
+    default from the caching allocator).  No host read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf, max_break = int(samples_per_frame), int(max_break)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    if max_break < 0:
+        raise _lib.St2Error("max_break must not be negative, got %d" % max_break)
+    _chk_dev(brk, "brk", torch.int32, 2)
+    N = brk.shape[1]
+    if brk.shape[0] != B or brk.device != wave.device:
+        raise _lib.St2Error("brk must be [%d, N] on the device of wave (got %s on %s)" % (B, tuple(brk.shape), brk.device))
+    _chk_dev(pos, "pos", torch.int32, 2)
+    if tuple(pos.shape) != (B, N + 1) or pos.device != wave.device:
+        raise _lib.St2Error("pos must be [%d, %d] on the device of wave (got %s on %s)" % (B, N + 1, tuple(pos.shape), pos.device))
+    if ramp is not None:
+        _chk_dev(ramp, "ramp", torch.float32, 1)
+        if ramp.device != wave.device:
+            raise _lib.St2Error("ramp must live on the device of wave")
+    room = L + max_break
+    if out is None:
+        out = torch.empty((B, (room + 3) // 4 * 4), device=wave.device, dtype=torch.float32)[:, :room]
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (B, room) or out.device != wave.device:
+        raise _lib.St2Error("out must be [%d, %d] on the device of wave (got %s on %s)" % (B, room, tuple(out.shape), out.device))
+    ins = torch.empty((B, N), device=wave.device, dtype=torch.int32) if ins is None else ins
+    cuts = torch.empty((B, N), device=wave.device, dtype=torch.int32) if cuts is None else cuts
+    breaks = torch.empty((B, 2), device=wave.device, dtype=torch.int32) if breaks is None else breaks
+    _chk_tok_int(ins, "ins", B, N, wave)
+    _chk_tok_int(cuts, "cuts", B, N, wave)
+    _chk_tok_int(breaks, "breaks", B, 2, wave)
+    need = wave_breaks_workspace_bytes(B, L // spf, spf, N)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    _lib.check(_lib.load().st2_wave_breaks(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), pos.data_ptr(),
+                                           brk.data_ptr(), N, max_break, _ptr(ramp), 0 if ramp is None else ramp.numel(),
+                                           out.data_ptr(), out.stride(0), ins.data_ptr(), cuts.data_ptr(), breaks.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_breaks")
+    return out, ins, cuts, breaks
+
+
+def token_marks_breaks(pos, ins, rate=None, out=None):
+    """`st2_token_marks_breaks`: the timing marks of rows that `wave_breaks` spliced silence into.  pos int32 [B, N + 1] on the
+    device (what `wave_breaks` was given), ins int32 [B, N] on the device (what it inserted) -> int32 [B, N + 1]: marks[b, n] =
+    ceil((pos[b, n] + sum_{m < n} ins[b, m]) U / D) at `rate` (None or 24000: U = D = 1), so token n's own break lies inside
+    [marks[n], marks[n + 1]) and marks[b, N] is the row's packed sample count.  One launch, no host read."""
+    from . import resample
+    _chk_dev(pos, "pos", torch.int32, 2)
+    B, N = pos.shape[0], pos.shape[1] - 1
+    _chk_tok_int(ins, "ins", B, max(N, 0), pos)
+    U, D = resample.ratio(resample.MODEL_RATE if rate is None else rate)
+    if out is None:
+        out = torch.empty((B, N + 1), device=pos.device, dtype=torch.int32)
+    _chk_dev(out, "out", torch.int32, 2)
+    if tuple(out.shape) != (B, N + 1) or out.device != pos.device:
+        raise _lib.St2Error("out must be [%d, %d] on the device of pos (got %s on %s)" % (B, N + 1, tuple(out.shape), out.device))
+    _lib.check(_lib.load().st2_token_marks_breaks(pos.data_ptr(), ins.data_ptr(), B, N, U, D, out.data_ptr(), _stream()),
+               "st2_token_marks_breaks")
+    return out
+
+
 NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*
 
 

@@ -456,6 +456,86 @@ class Edges:
         return dict(lead_ms=self.lead_ms, tail_ms=self.tail_ms, fade_ms=self.fade_ms)
 
 
+def break_samples(ms):
+    """A break of `ms` milliseconds as samples at the model's 24 kHz, the rate `breaks=` counts in whatever the hand-over's:
+    `gap_samples`' rounding.  A scalar gives an int, a sequence (of sequences) a list."""
+    return [break_samples(v) for v in ms] if isinstance(ms, (list, tuple)) else gap_samples(ms)
+
+
+class Breaks:
+    """Pauses INSIDE the rows of the packed hand-over (include/st2.h `st2_wave_breaks`): SSML's
+    `<break time=.../>` in the middle of a sentence.  The caller names a token per pause -- normally a space or a punctuation
+    token, where the model pauses anyway --; the row is cut at the quietest place inside that token's samples, both sides of the
+    cut are faded and digital silence of the stated length is spliced in, on the device, before anything else of the hand-over.
+
+        ms / samples   the pause inside token n of row b, [B, N], in milliseconds or in samples at 24 kHz (one of the two;
+                       neither = no pause yet, e.g. a graph's static table); <= 0 = none
+        fade_ms        the raised-cosine fade on either side of a cut; at most `resample.EDGE_MAX_F` samples      [0, 500]
+        max_ms         the most silence ONE row takes: it sizes the output and the grids; what a row asks for
+                       beyond it is dropped in token order                                                         [0, 60000]
+
+    Kept as one int32 [B, N] device table (`samples`), `max_break` (samples, a host int) and `F` (the fade in samples),
+    validated on the host like `Edges`; a table already on the device is taken unread."""
+
+    def __init__(self, B, N, ms=None, samples=None, fade_ms=2.0, max_ms=2000.0, device=None):
+        B, N = int(B), int(N)
+        if B <= 0 or not 1 <= N <= 512:
+            raise ValueError("Breaks: B must be positive and N lie in 1..512, got B=%r, N=%r" % (B, N))
+        if ms is not None and samples is not None:
+            raise ValueError("Breaks: pass ms or samples, not both")
+        fade_ms, max_ms = float(fade_ms), float(max_ms)
+        if not 0.0 <= fade_ms <= 500.0:
+            raise ValueError("Breaks: fade_ms must lie in [0, 500], got %r" % (fade_ms,))
+        if not 0.0 <= max_ms <= 60000.0:
+            raise ValueError("Breaks: max_ms must lie in [0, 60000], got %r" % (max_ms,))
+        F = Edges.samples(fade_ms)
+        if F > resample.EDGE_MAX_F:
+            raise ValueError("Breaks: fade_ms=%r is %d samples, the fade holds %d at most" % (fade_ms, F, resample.EDGE_MAX_F))
+        on_dev = torch.is_tensor(samples) and samples.is_cuda
+        if device is None:
+            device = samples.device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        self.B, self.N, self.F, self.fade_ms, self.max_ms = B, N, F, fade_ms, max_ms
+        self.max_break = Edges.samples(max_ms)
+        self.samples = self.table(ms, samples, B, N).to(device)
+
+    @staticmethod
+    def table(ms, samples, B, N):
+        """The pauses as the int32 [B, N] table the kernel reads: a device tensor as it is (unread), host values validated."""
+        if torch.is_tensor(samples) and samples.is_cuda:
+            if samples.dtype != torch.int32 or tuple(samples.shape) != (B, N):
+                raise ValueError("Breaks: samples on the device must be an int32 [%d, %d] tensor, got %s %s"
+                                 % (B, N, samples.dtype, tuple(samples.shape)))
+            return samples.detach().contiguous()
+        if ms is None and samples is None:
+            return torch.zeros((B, N), dtype=torch.int32)
+        if ms is not None:
+            t = torch.as_tensor(ms, dtype=torch.float64)
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("Breaks: ms must be finite")
+            t = torch.round(t * (resample.MODEL_RATE / 1000.0))  # half to even, as `gap_samples`
+        else:
+            t = torch.as_tensor(samples)
+            if t.dtype.is_floating_point:
+                raise ValueError("Breaks: samples must be whole sample counts (pipeline.break_samples converts milliseconds)")
+            t = t.to(torch.float64)
+        if tuple(t.shape) != (B, N):
+            raise ValueError("Breaks: the pauses must be [%d, %d] values, got shape %s" % (B, N, tuple(t.shape)))
+        if float(t.abs().max()) >= 2.0 ** 31:
+            raise ValueError("Breaks: a pause does not fit int32")
+        return t.to(torch.int32)
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as a Breaks over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Breaks)
+        c.B, c.N, c.F, c.fade_ms, c.max_ms, c.max_break = j - i, self.N, self.F, self.fade_ms, self.max_ms, self.max_break
+        c.samples = self.samples[i:j]
+        return c
+
+    def options(self):
+        """The two times of this Breaks, as its constructor takes them (what a copy over other rows is made with)."""
+        return dict(fade_ms=self.fade_ms, max_ms=self.max_ms)
+
+
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
     """What `controls=` cannot be combined with: refused before anything is launched."""
     if not isinstance(controls, Controls):
@@ -959,6 +1039,8 @@ class SynthesisResult:
       edges    (with `edges=`) int32 [B, 2]: {head, count} at the model rate -- row b's packed samples are
                wave[b, 0, head : head + count], faded at an edge that was cut, through the rest of the hand-over; offsets, marks
                and the level are those of the cut rows.  Kept in the same allocation: `to_host(edges=True)` is still one copy.
+      breaks   (with `breaks=`) int32 [B, 2]: {the row's samples with its pauses, the silence inserted} at the
+               model rate.  Kept in the same allocation: `to_host(breaks=True)` is still one copy.
       fit      (with `fit_frames=`) int32 [B, 4]: {the row's frames before the fit, its frames after,
                flag, the number of tokens whose duration changed}; flag 0 = the target was met, 1 = it was infeasible and the
                nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
@@ -983,8 +1065,9 @@ class SynthesisResult:
         self.level = None if ho is None or ho.level is None else ho.level.view(-1, 4)
         self.limit = None if ho is None or ho.limit is None else ho.limit.view(-1, 2)
         self.edges = None if ho is None or ho.edges is None else ho.edges.view(-1, 2)
+        self.breaks = None if ho is None or ho.breaks is None else ho.breaks.view(-1, 2)
 
-    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False):
+    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False, breaks=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -1000,7 +1083,10 @@ class SynthesisResult:
         array out of the same copy, behind whatever else is returned: (arrays, level) or (arrays, marks, level).  `limit=True` (a
         result made with a limiting `Level`): the limiter's {drive gain, smallest gain factor} as a float32 [B, 2] numpy array, out
         of the same copy, behind those.  `edges=True` (a result made with `edges=`): {head, count} per row as an int32 [B, 2] numpy
-        array, out of the same copy, last."""
+        array, out of the same copy, behind those.  `breaks=True` (a result made with `breaks=`): {the row's samples with its pauses,
+        the silence inserted} at the model rate as an int32 [B, 2] numpy array, out of the same copy, last."""
+        if breaks and self.breaks is None:
+            raise ValueError("this result carries no breaks table: ask for it with inference(..., breaks=Breaks(...))")
         if edges and self.edges is None:
             raise ValueError("this result carries no edges table: ask for it with inference(..., edges=Edges(...))")
         if level and self.level is None:
@@ -1033,6 +1119,8 @@ class SynthesisResult:
             more += (self._ho.limit_view(self._host).numpy().reshape(B, 2),)
         if edges:
             more += (self._ho.edges_view(self._host).numpy().reshape(B, 2),)
+        if breaks:
+            more += (self._ho.breaks_view(self._host).numpy().reshape(B, 2),)
         return (rows,) + more if more else rows
 
 
@@ -1092,24 +1180,26 @@ class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
         [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | limit float32 [2 B] |
-         edges int32 [2 B] | pad to 16 bytes | samples of `fmt`]
+         edges int32 [2 B] | breaks int32 [2 B] | pad to 16 bytes | samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps / no level / no limit / no edges the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    with `n_marks` = 0 / no gaps / no level / no limit / no edges / no breaks the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
     five parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
     its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `packed` and `level` are
     the buffer and its views (None for a part the layout does not have)."""
 
-    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False):
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False, with_breaks=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
         self.with_level, self.with_limit, self.with_edges = bool(with_level), bool(with_limit), bool(with_edges)
+        self.with_breaks = bool(with_breaks)
         self.offsets_at = 0
         self.marks_at = 8 * (self.B + 1)
         self.gaps_at = self.marks_at + 4 * self.n_marks
         self.level_at = self.gaps_at + (4 * self.B if self.with_gaps else 0)
         self.limit_at = self.level_at + (16 * self.B if self.with_level else 0)
         self.edges_at = self.limit_at + (8 * self.B if self.with_limit else 0)
-        self.samples_at = (self.edges_at + (8 * self.B if self.with_edges else 0) + 15) // 16 * 16
-        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = self.edges = None
+        self.breaks_at = self.edges_at + (8 * self.B if self.with_edges else 0)
+        self.samples_at = (self.breaks_at + (8 * self.B if self.with_breaks else 0) + 15) // 16 * 16
+        self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = self.edges = self.breaks = None
 
     def limit_view(self, buf):
         """The sixth part, float32 [2 B] (`ops.wave_limit`'s {g', min q} per row), of a uint8 buffer of this
@@ -1120,6 +1210,11 @@ class _HandOver:
         """The seventh part, int32 [2 B] (`ops.wave_edges`'s {head, count} per row), of a uint8 buffer of this
         layout, or None.  Apart from `views`, as `limit_view` is."""
         return buf[self.edges_at:self.edges_at + 8 * self.B].view(torch.int32) if self.with_edges else None
+
+    def breaks_view(self, buf):
+        """The eighth part, int32 [2 B] (`ops.wave_breaks`'s {count', silence inserted} per row), of a uint8
+        buffer of this layout, or None.  Apart from `views`, as `limit_view` is."""
+        return buf[self.breaks_at:self.breaks_at + 8 * self.B].view(torch.int32) if self.with_breaks else None
 
     def views(self, buf):
         """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
@@ -1134,6 +1229,7 @@ class _HandOver:
         self.offsets, self.marks, self.gaps, self.packed, self.level = self.views(self.buf)
         self.limit = self.limit_view(self.buf)
         self.edges = self.edges_view(self.buf)
+        self.breaks = self.breaks_view(self.buf)
         return self
 
 
@@ -1155,7 +1251,7 @@ def _capacity_only(names, *given):
 
 
 def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False,
-                 passage=None, front_groups=1, edges=None):
+                 passage=None, front_groups=1, edges=None, breaks=None, N=None):
     """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
     every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
     launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
@@ -1165,7 +1261,8 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     its `marks` refusal names `pack` alone.  `trim` goes through as given: `_decode_capacity` resolves None.  `passage`: the
     call's `passage`, and `front_groups`: the front calls `synthesize_long` cuts the passage into -- what a `Level` of
     scope "passage" is judged by, and looked at for nothing else.  `edges`: an `Edges` of the B rows, judged here and handed on by
-    the caller (the spec does not carry it, as it does not carry `level`)."""
+    the caller (the spec does not carry it, as it does not carry `level`).  `breaks`: a `Breaks` of the B rows and of the call's `N`
+    tokens (None: the caller has no token count to judge by), likewise."""
     if pack is not None and pack not in ops.OUTPUT_FORMATS:
         raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
     if sample_rate is not None and pack is None:
@@ -1185,6 +1282,10 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
         raise ValueError("edges are cut from the packed samples of the capacity-bound path: pass max_frames and pack")
     if edges is not None and (not isinstance(edges, Edges) or edges.B != B):
         raise ValueError("edges must be a pipeline.Edges of %d rows" % B)
+    if breaks is not None and (pack is None or not capacity):
+        raise ValueError("breaks are spliced into the packed samples of the capacity-bound path: pass max_frames and pack")
+    if breaks is not None and (not isinstance(breaks, Breaks) or breaks.B != B or (N is not None and breaks.N != N)):
+        raise ValueError("breaks must be a pipeline.Breaks of %d rows%s" % (B, "" if N is None else " of %d tokens" % N))
     if not capacity:
         _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
     if pack is None and (gaps is not None or max_gap is not None):
@@ -1222,7 +1323,7 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
 
 
 def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None,
-                     starts=None, edges=None):
+                     starts=None, edges=None, breaks=None, tokens=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
@@ -1236,18 +1337,33 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     the header's limit part, then the wrapper a call WITHOUT a level takes, over the limited rows.  With `edges` (an `Edges`;
     DESIGN.md section 28) `ops.wave_edges` runs FIRST, into a buffer of the caching allocator with {head, count} into the header's
     edges part, and everything above runs unchanged over the cut rows: their sample counts are the frame counts of rows of
-    one-sample frames, nothing trimmed -- frames = count, samples_per_frame = 1, trim = 0."""
+    one-sample frames, nothing trimmed -- frames = count, samples_per_frame = 1, trim = 0.  With `breaks` (a `Breaks`; DESIGN.md
+    section 29) `ops.wave_breaks` runs behind the trim and in front of everything else, in the same manner: the tokens' boundaries
+    in samples of the (cut) rows come from one `ops.token_marks` / `ops.token_marks_edges` launch without a rate over `tokens`
+    (that wrapper's dur, T_cap, lengths and shift), the rows with their silence go to a buffer of the caching allocator of
+    `max_break` more samples per row, {count', inserted} into the header's breaks part, and the rest runs over frames = count'.
+    The boundaries and the inserted silence stay with the hand-over (`pos`, `ins`) for the marks."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
     room = resample.output_samples(L, U, D) + (0 if gaps is None else max_gap)
+    if breaks is not None:
+        room += resample.output_samples(breaks.max_break, U, D)
     limiting = level is not None and level.limiter
     ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting,
-                   with_edges=edges is not None).allocate(B * room, wave.device)
+                   with_edges=edges is not None, **({} if breaks is None else {"with_breaks": True})).allocate(B * room, wave.device)
     if edges is not None:
         wave, _ = ops.wave_edges(wave, frames, edges.top_db, edges.keep, resample.edge_ramp(edges.F, wave.device) if edges.F else None,
                                  trim=trim, samples_per_frame=samples_per_frame, edges=ho.edges)
         frames, trim, samples_per_frame = ho.edges.view(B, 2)[:, 1].contiguous(), 0, 1  # the counts as a row of their own
+    if breaks is not None:  # the boundaries in the decoder's geometry (`tokens`), moved by the trim above where there is one
+        marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
+        ho.pos = marks_of(tokens["dur"], tokens["frames"], tokens["T_cap"], lengths=tokens["lengths"], shift=tokens["shift"],
+                          trim=tokens["trim"], samples_per_frame=tokens["samples_per_frame"])
+        wave, ho.ins, _, _ = ops.wave_breaks(wave, frames, ho.pos, breaks.samples, breaks.max_break,
+                                             resample.edge_ramp(breaks.F, wave.device) if breaks.F else None, trim=trim,
+                                             samples_per_frame=samples_per_frame, breaks=ho.breaks)
+        frames, trim, samples_per_frame = ho.breaks.view(B, 2)[:, 0].contiguous(), 0, 1
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
@@ -1277,11 +1393,12 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None):
+def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None, breaks=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
     into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation, `starts`: the call's `passage`
-    for a level of scope "passage" (`_hand_over`), `edges`: their trim (`_hand_over_edges`; the marks are then `ops.token_marks_edges`')."""
+    for a level of scope "passage" (`_hand_over`), `edges`: their trim (`_hand_over_edges`; the marks are then `ops.token_marks_edges`'),
+    `breaks`: the pauses inside them (`_hand_over_edges`; the marks are then `ops.token_marks_breaks`')."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     hifigan = model.decoder.kind == "hifigan"
@@ -1293,10 +1410,17 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
     hand_over = _hand_over if edges is None else functools.partial(_hand_over_edges, edges=edges)
+    if breaks is not None:
+        if breaks.N != N:
+            raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (B, N))
+        hand_over = functools.partial(_hand_over_edges, edges=edges, breaks=breaks, tokens=dict(
+            dur=dur, frames=p["frames"], T_cap=T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim, samples_per_frame=spf))
     ho = hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
                    level, starts)
     m = None
-    if spec.marks:
+    if spec.marks and breaks is not None:
+        m = ops.token_marks_breaks(ho.pos, ho.ins, rate=spec.sample_rate, out=ho.marks.view(B, N + 1))
+    elif spec.marks:
         m = ho.marks.view(B, N + 1)
         marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
         marks_of(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
@@ -1358,11 +1482,18 @@ class GraphedSynthesis:
     more static buffer, `static["edges"]` (an `Edges`; at first 40 dB in every row, or the one given): `__call__(edges=)` -- an
     `Edges`, one `top_db` or B of them, None / NaN = leave the row alone -- copies the thresholds into its row, so one graph
     serves any thresholds; the pads and the fade are the graph's own.  Without it the graph records exactly what it recorded
-    before."""
+    before.
+
+    `breaks=True` (or a `Breaks`; needs `pack`) with `max_break_ms` (the cap of the silence in one row, 2 000 by
+    default): the graph records the pauses inside the rows over one more static buffer, `static["breaks"]` (a `Breaks`; at first
+    no pause anywhere, or the table given): `__call__(breaks=)` -- a `Breaks` or an int [B, N] table of samples at 24 kHz --
+    copies the table into it, so one graph serves any pauses up to the cap; the cap and the fade are the graph's own.  Without
+    it the graph records exactly what it recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
-                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None):
+                 token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None,
+                 breaks=None, max_break_ms=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1373,10 +1504,19 @@ class GraphedSynthesis:
         self.passage, self.max_gap = bool(passage), None if max_gap is None else int(max_gap)
         level = Level(B, device=dev) if level is True else None if level is False else level
         edges = Edges(B, device=dev) if edges is True else None if edges is False else edges
+        if max_break_ms is not None and not breaks:
+            raise ValueError("max_break_ms bounds `breaks`: pass breaks=True")
+        if breaks is True:
+            breaks = Breaks(B, N, device=dev, **({} if max_break_ms is None else {"max_ms": max_break_ms}))
+        elif breaks is False:
+            breaks = None
+        elif isinstance(breaks, Breaks) and max_break_ms is not None and Edges.samples(max_break_ms) != breaks.max_break:
+            raise ValueError("max_break_ms=%r is not the cap of the Breaks given (%r ms)" % (max_break_ms, breaks.max_ms))
         # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
         gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
         spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage,
-                               **({} if edges is None else {"edges": edges}))
+                               **({} if edges is None else {"edges": edges}),
+                               **({} if breaks is None else {"breaks": breaks, "N": N}))
         if spec.rate is not None:
             resample.table(spec.rate, dev)
         if level is not None and level.true_peak:
@@ -1385,6 +1525,8 @@ class GraphedSynthesis:
             resample.limit_window(level.W, dev)  # and the limiter's window
         if edges is not None and edges.F:
             resample.edge_ramp(edges.F, dev)  # and the fade of a cut edge
+        if breaks is not None and breaks.F:
+            resample.edge_ramp(breaks.F, dev)  # and that of a pause's two sides
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1416,6 +1558,8 @@ class GraphedSynthesis:
                                          max_gain_db=level.max_gain_db, device=dev, **level.options())
         if edges is not None:
             self.static["edges"] = Edges(B, top_db=edges.top_db.to(dev).clone(), device=dev, **edges.options())
+        if breaks is not None:
+            self.static["breaks"] = Breaks(B, N, samples=breaks.samples.to(dev).clone(), device=dev, **breaks.options())
         self._g = None
 
     def _run(self):
@@ -1425,7 +1569,8 @@ class GraphedSynthesis:
                          controls=st["controls"], passage=st.get("starts"), s_prev=st.get("s_prev"), gaps=st.get("gaps"),
                          level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}),
                          **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}),
-                         **({"edges": st["edges"]} if "edges" in st else {}))
+                         **({"edges": st["edges"]} if "edges" in st else {}),
+                         **({"breaks": st["breaks"]} if "breaks" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1438,7 +1583,8 @@ class GraphedSynthesis:
 
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
-                 starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None):
+                 starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None,
+                 breaks=None):
         st = self.static
         if fit_frames is not None or fit_hold is not None:
             if "fit_frames" not in st:
@@ -1484,6 +1630,14 @@ class GraphedSynthesis:
             if row.numel() != st["edges"].B:
                 raise ValueError("edges must hold %d thresholds, got %d" % (st["edges"].B, row.numel()))
             st["edges"].top_db.copy_(row, non_blocking=True)
+        if breaks is not None:
+            if st.get("breaks") is None:
+                raise ValueError("this graph was built without breaks: pass breaks=True")
+            own = st["breaks"]
+            if isinstance(breaks, Breaks) and (breaks.B, breaks.N) != (own.B, own.N):
+                raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (own.B, own.N))
+            table = breaks.samples if isinstance(breaks, Breaks) else Breaks.table(None, breaks, own.B, own.N)
+            own.samples.copy_(table, non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
@@ -1658,7 +1812,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None, fit_frames=None, fit_hold=None, edges=None):
+              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1745,9 +1899,17 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     the pauses a listener hears and `marks[b, 0]` / `marks[b, N]` bracket speech.  Level, limiter, gaps, resampling and G.711 run
     over the cut rows; the result carries {head, count} as `edges` and `to_host(edges=True)` brings them over in its one copy.
     `wave` stays as the decoder made it.  Without `edges` the call issues exactly the launches it always did.
+
+    `breaks` (a `Breaks` of B rows of N tokens, with `max_frames` and `pack`): pauses INSIDE the rows --
+    `breaks.samples[b, n]` samples of digital silence at 24 kHz inside token n of row b, spliced in on the device at the quietest
+    place of that token's samples, both sides faded (`ops.wave_breaks`, behind the trim of `edges` and in front of everything
+    else of the hand-over).  The marks are those of the rows with their pauses: token n's pause lies inside [marks[b, n],
+    marks[b, n + 1]).  The result carries {samples with the pauses, silence inserted} as `breaks`.  `fit_frames` keeps meaning
+    frames of speech: the pauses come on top.  Without `breaks` the call issues exactly the launches it always did.
     """
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
-                              passage=passage, **({} if edges is None else {"edges": edges}))
+                              passage=passage, **({} if edges is None else {"edges": edges}),
+                              **({} if breaks is None else {"breaks": breaks, "N": tokens.shape[1]}))
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
@@ -1782,7 +1944,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     if seeds is not None:
         sine_noise = _seeded_sine_noise(seeds, p["frames"], max_frames)
     if max_frames is not None:
-        return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage, **({} if edges is None else {"edges": edges}))
+        return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage, **({} if edges is None else {"edges": edges}),
+                                **({} if breaks is None else {"breaks": breaks}))
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -1851,7 +2014,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None):
+                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -1914,6 +2077,9 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     (`inference(fit_frames=)`); the breaks between sentences are not part of it.
     `edges` (needs `max_frames` and `pack`): an `Edges` of one row per SENTENCE: every sentence is cut to its
     speech (`inference(edges=)`), so that the breaks of `gaps` are the pauses between sentences.
+    `breaks` (needs `max_frames` and `pack`): a `Breaks` of one row per SENTENCE, its N the longest sentence's
+    token count -- shorter sentences are right-padded to it, as with per-token controls --: the pauses inside the sentences
+    (`inference(breaks=)`).
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
@@ -1924,9 +2090,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges)
+            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     _capacity_only("edges", edges)
+    _capacity_only("breaks", breaks)
     _capacity_only("seeds", seeds)
     _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
@@ -2007,7 +2174,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
-                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None):
+                              controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None,
+                              breaks=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -2025,13 +2193,14 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     if trim is None:
         trim = 100 if ref_s is not None else 0
     ns_all = [s.numel() for s in sentences]
-    tok_ctl = controls is not None and controls.tok_buf is not None
-    if tok_ctl and controls.N != max(ns_all):
+    tok_ctl = controls is not None and controls.tok_buf is not None or breaks is not None  # rows as wide as the longest sentence
+    if tok_ctl and controls is not None and controls.tok_buf is not None and controls.N != max(ns_all):
         raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
     # the K sentences' output, judged once (a `max_gap` without `gaps` is not looked at, as ever); every group's slice is, again
     chunks = _front_chunks(front_batch, K)
     spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level, passage=True,
-                              front_groups=len(chunks), **({} if edges is None else {"edges": edges}))
+                              front_groups=len(chunks), **({} if edges is None else {"edges": edges}),
+                              **({} if breaks is None else {"breaks": breaks, "N": max(ns_all)}))
     prepped = []
     for i, i_end in chunks:
         ids = list(range(i, i_end))
@@ -2052,6 +2221,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
         more = {} if gaps is None else dict(gaps=gaps[i:j], max_gap=spec.max_gap)
         if edges is not None:
             more.update(edges=edges.slice(i, j))
+        if breaks is not None:
+            more.update(breaks=breaks.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
