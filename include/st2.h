@@ -848,6 +848,59 @@ int st2_wave_breaks(const float* wave, int64_t w_bs, const int32_t* frames, int3
 int st2_token_marks_breaks(const int32_t* pos, const int32_t* ins, int32_t B, int32_t N, int32_t up, int32_t down,
                            int32_t* marks /* int32 [B][N + 1], device */, void* stream);
 
+/* ---- dynamics: a speech compressor in the hand-over (added under ABI 23, additive: one kernel-level entry point and three
+ * helpers, no new backend-table slot, no struct change, no new sticky status bit) ------------------------ *
+ * st2_wave_dynamics: the dynamic range of a row reduced by a feed-forward compressor with a soft knee, instant attack under a
+ * zero-phase look-ahead, and a release that is linear in dB.  It takes st2_wave_edges's geometry (wave, w_bs, frames, B, T_cap,
+ * samples_per_frame, trim) and, on the device and read by the kernels, params fp32 [B][4] = {threshold_db, slope, knee_db,
+ * makeup_db} with slope = 1 - 1 / ratio; the kernels clamp slope to [0, 1], knee_db to [0, 40] and makeup_db to [-24, 24].  A
+ * NaN in any of the four, or a threshold that is not finite, means the row is left alone.  Host numbers: the half window A in
+ * blocks of 64 samples, 0..64; win fp32 [2 A + 1] on the device, non-negative weights that sum to 1 (NULL with A = 0, where the
+ * smoother is the identity); the release rho > 0 in dB per block.  It writes `out` (fp32, row stride o_bs, not overlapping
+ * wave), dyn fp32 [B][2] and the workspace.  With T, slope, Wk, makeup the row's clamped parameters as fp64:
+ *  1. Valid samples.  st2_wave_level's rule 1: x[0 .. n_b).  A row that is left alone, or whose n_b = 0, is copied bit for bit,
+ *     NaN payloads intact, and its dyn[b] = {0, 0}.
+ *  2. Block sums.  st2_wave_breaks's rule 2, bit for bit and by the same kernel: s[k], k = 0 .. K - 1, K = ceil(n_b / 64); a
+ *     non-finite sample counts as 0, zeros past n_b.  A sum that overflowed to +inf counts as FLT_MAX.
+ *  3. Detector.  E[k] = fl32(fl32(s[k - 1] + s[k]) + s[k + 1]), a missing neighbour as 0, +inf as FLT_MAX; L[k] =
+ *     10 log10((double)E[k] / 192) in fp64, -inf at E[k] = 0: a centred RMS over 192 samples, 8 ms.  The first block and the
+ *     last, partial one are divided by 192 like the others: the edges of a row read up to 4.8 dB low, and never high.
+ *  4. Static curve, fp64, o = L[k] - T: c[k] = 0 where 2 o <= -Wk; c[k] = (slope * (u * u)) / (2 Wk) with u = o + Wk / 2 where
+ *     |2 o| < Wk; c[k] = slope * o otherwise (the soft knee of Giannoulis, Massberg and Reiss, JAES 2012).  c >= 0.
+ *  5. Release.  g[k] = max_{m <= k} (c[m] - (k - m) rho), evaluated as g[k] = P[k] - fl64(k * rho) with P the running maximum
+ *     of z[m] = c[m] + fl64(m * rho): one fp64 multiply and one add each, and a maximum has no rounding, so no result depends
+ *     on how the scan is cut.
+ *  6. Attack.  The hold m[k] = max_{|d| <= A} g[k + d], entries outside 0 .. K - 1 absent; the smoother d[k] = sum_j win[j]
+ *     m[k - A + j] as the fp64 chain d = d + fl64((double)win[j] * m[.]) from 0 with j ascending, an entry outside the row
+ *     taking the nearest valid one; d'[k] = max(d[k], g[k]).  Every window d[k] reads contains k, so no block is ever reduced
+ *     by less than the release envelope -- and so the static curve -- asks.
+ *  7. Gain per block.  lin[k] = fl32(10^((makeup - d'[k]) / 20)), pow in fp64, rounded once.
+ *  8. Gain per sample, fp32: linear between the block centres 64 k + 31.5.  For sample i between the centres of blocks k and
+ *     k + 1, t = (2 (i - 64 k) - 63) / 128 (exact) and gain = fmaf(t, lin[k + 1] - lin[k], lin[k]); in front of the first
+ *     centre gain = lin[0], behind the last gain = lin[K - 1].  out[i] = fl32(x[i] * gain) on the valid samples, with x itself:
+ *     a NaN stays a NaN.  Nothing at or past out[b][n_b] is written.
+ *  9. Result.  dyn[b] = {max_k d'[k], the number of blocks with d'[k] > 0}, both as fp32: a maximum and a count, no sum across
+ *     samples, no atomics.  A row's output and its two numbers depend neither on the tiling nor on the row's place in the
+ *     batch, bit for bit.
+ * A row whose level never reaches T - Wk / 2, with makeup = 0, has lin = 1 everywhere and comes out bit for bit; slope = 0 is
+ * the identity times the make-up gain.  Everything is fixed but the last ulp of log10 and pow.
+ * `workspace` (float-aligned, st2_wave_dynamics_workspace_bytes(B, T_cap, samples_per_frame) bytes; 0 for an argument <= 0)
+ * begins with lin fp32 [B][Kcap], then s fp32 [B][Kcap], Kcap = ceil(samples_per_frame T_cap / 64); entries at or past a row's
+ * K are not written.  st2_wave_dynamics_tile(): the samples of a tile of the apply launch; st2_wave_dynamics_chunk(): the
+ * blocks of a chunk of the per-row launch.  Three launches (block sums; per row rules 3 to 7 and 9; apply), no atomics, no
+ * allocation, no synchronisation, no host read: legal under stream capture.
+ * Returns non-zero before any launch on every refusal of st2_wave_edges about the geometry (NULL wave / frames, bad B / T_cap /
+ * samples_per_frame, trim < 0, a row too long for int32, w_bs too small) and on: o_bs too small; NULL params / out / dyn /
+ * workspace; A outside 0..64; win NULL with A > 0; rho not finite or <= 0; a pointer that is not aligned to 4 bytes; out
+ * overlapping wave; a workspace that is too small. */
+int32_t st2_wave_dynamics_tile(void);
+int32_t st2_wave_dynamics_chunk(void);
+int64_t st2_wave_dynamics_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame);
+int st2_wave_dynamics(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                      int32_t trim, const float* params /* fp32 [B][4], device */, int32_t A,
+                      const float* win /* fp32 [2 A + 1], device */, double rho, float* out, int64_t o_bs,
+                      float* dyn /* fp32 [B][2], device */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
  * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one

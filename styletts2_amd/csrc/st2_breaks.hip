@@ -7,7 +7,7 @@
 //
 // Launch 1, one workgroup per (tile of BR_TILE samples, row): the tile goes to LDS with 16-byte loads, a non-finite sample and
 //   everything at or past n_b as 0; wave w squares block w, w + 4, ... one sample per lane and folds the 64 squares by a
-//   butterfly: one read of the valid samples.
+//   butterfly: one read of the valid samples (st2_blocksums.h, which st2_dynamics.hip launches too).
 // Launch 2, one workgroup per row: the boundaries clamped and made monotone, the cap and the exclusive scan of `ins` by wave 0,
 //   then a wave per token with a break for the arg-min over its candidates; the row's segment table goes to the workspace.
 // Launch 3, one workgroup per (BR_MOVE output samples, row): the table goes to LDS, a lane finds the segment of each of its four
@@ -17,13 +17,10 @@
 //   place in the batch.
 #include <initializer_list>
 
-#include "st2_pcm.h"
+#include "st2_blocksums.h"
 
 namespace {
 
-constexpr int BR_THREADS = 256;
-constexpr int BR_BLOCK = 64;                      // samples of a block sum: one per lane
-constexpr int BR_TILE = 2048;                     // samples of a workgroup of launch 1: eight blocks per wave
 constexpr int BR_VEC = 4;                         // 4-sample vectors of a lane of launch 3, BR_THREADS apart
 constexpr int BR_MOVE = BR_THREADS * 4 * BR_VEC;  // output samples of a workgroup of launch 3
 constexpr int BR_MAX_F = 4096;
@@ -31,48 +28,11 @@ constexpr int BR_MAX_N = 512;
 // A row's table in the workspace: {m, count'} and two pad words, then a[0 .. m + 1] (a segment's first source sample; a[m + 1] =
 // n_b) and d[0 .. m] (its first output sample), m <= 512 cuts
 constexpr int BR_TAB_A = 4, BR_TAB_D = BR_TAB_A + BR_MAX_N + 2, BR_TAB = BR_TAB_D + BR_MAX_N + 2;
-static_assert(BR_TILE % (4 * BR_THREADS) == 0 && BR_TILE % BR_BLOCK == 0 && BR_TAB % 4 == 0, "whole vectors, whole blocks");
+static_assert(BR_TAB % 4 == 0, "whole vectors");
 
 struct __attribute__((packed, aligned(4))) u32x4_u {
   uint32_t v[4];
 };
-
-__global__ __launch_bounds__(BR_THREADS) void breaks_sums_kernel(const float* __restrict__ wave, int64_t w_bs,
-                                                                 const int32_t* __restrict__ frames, int T_cap, int spf, int trim,
-                                                                 float* __restrict__ sums, int nb_row) {
-  __shared__ __attribute__((aligned(16))) float ys[BR_TILE];
-  const int b = blockIdx.y;
-  const long long n = pack_row_samples(frames, b, T_cap, spf, trim);
-  const long long j0 = (long long)blockIdx.x * BR_TILE;
-  if (j0 >= n) return;  // behind the row's end: the grid is sized by the capacity
-  const float* __restrict__ src = wave + (int64_t)b * w_bs;
-#pragma unroll
-  for (int q = threadIdx.x; 4 * q < BR_TILE; q += BR_THREADS) {
-    const long long i = j0 + 4LL * q;
-    float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (i + 4 <= n) {
-      const float4 x = load_f32x4(src + i);
-      e[0] = x.x; e[1] = x.y; e[2] = x.z; e[3] = x.w;
-    } else {  // the row's end: every sample on its own, loaded only where it is valid
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (i + r < n) e[r] = src[i + r];
-    }
-    *reinterpret_cast<float4*>(ys + 4 * q) =
-        make_float4(finite_or_zero(e[0]), finite_or_zero(e[1]), finite_or_zero(e[2]), finite_or_zero(e[3]));
-  }
-  __syncthreads();
-  // blocks j0 / 64 .. + 31 of the row: all lie below nb_row, which is sized by the capacity rounded up to the tile
-  float* __restrict__ out = sums + (int64_t)b * nb_row + j0 / BR_BLOCK;
-  const int lane = threadIdx.x & 63;
-  for (int blk = threadIdx.x >> 6; blk * BR_BLOCK < BR_TILE; blk += BR_THREADS / 64) {
-    const float v = ys[blk * BR_BLOCK + lane];
-    float s = v * v;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (lane == 0) out[blk] = s;
-  }
-}
 
 // Inclusive 64-lane scans of one chunk, by one wave
 __device__ __forceinline__ long long wave_scan_add(long long v) {
@@ -312,7 +272,7 @@ extern "C" int st2_wave_breaks(const float* wave, int64_t w_bs, const int32_t* f
   int32_t* tables = reinterpret_cast<int32_t*>(sums + (int64_t)B * nb_row);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(breaks_sums_kernel, dim3(st2_cdiv(row, BR_TILE), B), dim3(BR_THREADS), 0, s, wave, w_bs, frames, T_cap,
-                     samples_per_frame, trim, sums, nb_row);
+                     samples_per_frame, trim, sums, nb_row, nb_row);
   ST2_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(breaks_plan_kernel, dim3(B), dim3(BR_THREADS), 0, s, frames, T_cap, samples_per_frame, trim, pos, brk, N,
                      max_break, sums, nb_row, ins, cuts, breaks, tables);

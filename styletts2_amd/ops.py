@@ -1604,6 +1604,64 @@ def token_marks_breaks(pos, ins, rate=None, out=None):
     return out
 
 
+DYNAMICS_BLOCK = 64  # the grid of the compressor's detector and gain (st2_wave_breaks's blocks)
+DYNAMICS_TILE = 4096  # st2_wave_dynamics_tile(): the samples of a tile of the apply launch (tests place row ends at its edges)
+DYNAMICS_CHUNK = 1024  # st2_wave_dynamics_chunk(): the blocks of a chunk of the per-row launch
+
+
+def wave_dynamics_workspace_bytes(B, T_cap, samples_per_frame=600):
+    """`st2_wave_dynamics_workspace_bytes`: what `wave_dynamics(workspace=)` needs, in bytes.  The workspace begins with the
+    gains per block `lin` as fp32 [B, Kcap], then the block sums `s` as fp32 [B, Kcap], Kcap = ceil(samples_per_frame T_cap / 64)."""
+    return int(_lib.load().st2_wave_dynamics_workspace_bytes(int(B), int(T_cap), int(samples_per_frame)))
+
+
+def wave_dynamics(wave, frames, params, win, *, A, rho, trim=0, samples_per_frame=600, out=None, dynamics=None, workspace=None):
+    """`st2_wave_dynamics`: a speech compressor over the rows of a ragged batch, on the device.  wave, frames,
+    trim and samples_per_frame as `wave_edges` takes them; params fp32 [B, 4] on the device = {threshold_db, slope = 1 - 1 / ratio,
+    knee_db, makeup_db} per row (a NaN in a row = leave it alone); `A` the half window of the attack in blocks of 64 samples,
+    0..64 (the library refuses another), with `win` fp32 [2 A + 1] on the device (`resample.limit_window(A, device)`; None with A = 0); `rho` the release in dB
+    per block -> (out, dyn): `out` fp32 [B, L] (by default with the row stride of wave) -- every valid sample times the gain the
+    contract of include/st2.h states; samples at or past a row's end are not written -- and `dyn` fp32 [B, 2] = {the deepest gain
+    reduction in dB, the number of 64-sample blocks that were reduced} per row.  `workspace`: a uint8 device tensor of
+    `wave_dynamics_workspace_bytes` bytes (by default from the caching allocator).  No host read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf, A = int(samples_per_frame), int(A)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    _chk_dev(params, "params", torch.float32, 2)
+    if tuple(params.shape) != (B, 4) or params.device != wave.device:
+        raise _lib.St2Error("params must be [%d, 4] on the device of wave (got %s on %s)" % (B, tuple(params.shape), params.device))
+    if (win is None) != (A == 0):
+        raise _lib.St2Error("win must be None with A = 0 and 2 A + 1 weights otherwise")
+    if win is not None:
+        _chk_dev(win, "win", torch.float32, 1)
+        if win.numel() != 2 * A + 1 or win.device != wave.device:
+            raise _lib.St2Error("win must hold 2 A + 1 = %d weights on the device of wave (got %d on %s)" % (2 * A + 1, win.numel(), win.device))
+    if out is None:
+        out = torch.empty_strided((B, L), (wave.stride(0), 1), device=wave.device, dtype=torch.float32)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (B, L) or out.device != wave.device:
+        raise _lib.St2Error("out must be [%d, %d] on the device of wave (got %s on %s)" % (B, L, tuple(out.shape), out.device))
+    if dynamics is None:
+        dynamics = torch.empty((B, 2), device=wave.device, dtype=torch.float32)
+    _chk_dev(dynamics, "dynamics", torch.float32, dynamics.dim() if torch.is_tensor(dynamics) else 2)
+    if dynamics.numel() != 2 * B or dynamics.device != wave.device:
+        raise _lib.St2Error("dynamics must hold [%d, 2] values on the device of wave" % B)
+    need = wave_dynamics_workspace_bytes(B, L // spf, spf)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    _lib.check(_lib.load().st2_wave_dynamics(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), params.data_ptr(), A,
+                                             _ptr(win), float(rho), out.data_ptr(), out.stride(0), dynamics.data_ptr(),
+                                             workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_dynamics")
+    return out, dynamics
+
+
 NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*
 
 

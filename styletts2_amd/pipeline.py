@@ -536,6 +536,105 @@ class Breaks:
         return dict(fade_ms=self.fade_ms, max_ms=self.max_ms)
 
 
+class Dynamics:
+    """A speech compressor over every row of the packed hand-over (include/st2.h `st2_wave_dynamics`):
+    what a hosted TTS service offers as an SSML dynamic-range-compression effect, for callers on a phone line or in a car, where the
+    quiet half of a sentence is lost.  A feed-forward compressor with a soft knee on a centred 8 ms RMS, instant attack under a
+    zero-phase look-ahead and a release that is linear in dB; it runs behind `breaks` and in front of `level`, so the loudness
+    target holds on the compressed programme and the limiter sees compressed peaks.
+
+        threshold_db       the level above which the gain falls, one value or B values;
+                           None or NaN in a row = leave this row alone                                       [-70, 0]
+        ratio              dB of input per dB of output above the threshold; `float("inf")` = a limiter's curve  [1, inf]
+        knee_db            the width of the soft knee around the threshold                                    [0, 40]
+        makeup_db          a gain behind the compressor                                                       [-24, 24]
+        attack_ms          the half width of the look-ahead: A = round(attack_ms * 24 / 64) blocks of 64 samples  [0, 170]
+        release_db_per_s   how fast the gain comes back: rho = release_db_per_s * 64 / 24000 dB per block       [1, 2000]
+
+    The first four are kept as one fp32 [B, 4] device table (`params` = {threshold_db, 1 - 1 / ratio, knee_db, makeup_db}),
+    validated on the host like `Controls` and `Level`; a tensor already on the device is not read.  `A` and `rho` are host
+    numbers."""
+
+    RANGES = (("threshold_db", -70.0, 0.0), ("ratio", 1.0, float("inf")), ("knee_db", 0.0, 40.0), ("makeup_db", -24.0, 24.0))
+
+    def __init__(self, B, threshold_db=-24.0, ratio=3.0, knee_db=6.0, makeup_db=0.0, attack_ms=8.0, release_db_per_s=80.0,
+                 device=None):
+        B = int(B)
+        if B <= 0:
+            raise ValueError("Dynamics: B must be positive, got %r" % (B,))
+        attack_ms, release_db_per_s = float(attack_ms), float(release_db_per_s)
+        if not 0.0 <= attack_ms <= 170.0:
+            raise ValueError("Dynamics: attack_ms must lie in [0, 170], got %r" % (attack_ms,))
+        if not 1.0 <= release_db_per_s <= 2000.0:
+            raise ValueError("Dynamics: release_db_per_s must lie in [1, 2000], got %r" % (release_db_per_s,))
+        given = (threshold_db, ratio, knee_db, makeup_db)
+        if device is None:
+            on_dev = [v for v in given if torch.is_tensor(v) and v.is_cuda]
+            device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        self.B, self.attack_ms, self.release_db_per_s = B, attack_ms, release_db_per_s
+        self.params = self.table(B, *given, device=device)
+
+    @property
+    def A(self):
+        """The half window of the attack in blocks of `ops.DYNAMICS_BLOCK` samples."""
+        return int(round(self.attack_ms * (resample.MODEL_RATE / 1000.0) / ops.DYNAMICS_BLOCK))
+
+    @property
+    def rho(self):
+        """The release in dB per block."""
+        return self.release_db_per_s * ops.DYNAMICS_BLOCK / resample.MODEL_RATE
+
+    @staticmethod
+    def column(name, v, B, lo, hi):
+        """One of the four settings as the fp32 [B] column of the table: a device tensor as it is (unread), host values validated;
+        None = NaN where that means something (`threshold_db`).  `ratio` is stored as the slope 1 - 1 / ratio."""
+        if torch.is_tensor(v) and v.is_cuda:
+            if v.numel() != B:
+                raise ValueError("Dynamics: %s must hold %d values, got shape %s" % (name, B, tuple(v.shape)))
+            v = v.detach().reshape(B).to(torch.float32)
+            return 1.0 - 1.0 / v if name == "ratio" else v
+        free = name == "threshold_db"  # the one setting that may be missing in a row
+        if v is None:
+            if not free:
+                raise ValueError("Dynamics: %s must be a number, got None" % name)
+            v = float("nan")
+        if isinstance(v, (list, tuple)):
+            v = [float("nan") if e is None and free else e for e in v]
+            if any(e is None for e in v):
+                raise ValueError("Dynamics: %s must be numbers, got %r" % (name, v))
+        rows = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
+        if rows.numel() == 1:
+            rows = rows.expand(B)
+        if rows.numel() != B:
+            raise ValueError("Dynamics: %s must be one value or %d values, got %d" % (name, B, rows.numel()))
+        ok = (rows >= lo) & (rows <= hi)
+        if free:
+            ok = ok | torch.isnan(rows)
+        if not bool(ok.all()):
+            raise ValueError("Dynamics: %s must lie in [%g, %g]%s, got %s"
+                             % (name, lo, hi, " (None / NaN = leave the row alone)" if free else "", rows.tolist()))
+        if name == "ratio":
+            rows = 1.0 - 1.0 / rows
+        return rows.to(torch.float32)
+
+    @staticmethod
+    def table(B, threshold_db, ratio, knee_db, makeup_db, device):
+        """The four settings as the fp32 [B, 4] table the kernels read, on `device`."""
+        cols = [Dynamics.column(name, v, B, lo, hi).to(device)
+                for (name, lo, hi), v in zip(Dynamics.RANGES, (threshold_db, ratio, knee_db, makeup_db))]
+        return torch.stack(cols, dim=1).contiguous()
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as a Dynamics over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Dynamics)
+        c.B, c.attack_ms, c.release_db_per_s, c.params = j - i, self.attack_ms, self.release_db_per_s, self.params[i:j]
+        return c
+
+    def options(self):
+        """The two times of this Dynamics, as its constructor takes them (what a copy over other rows is made with)."""
+        return dict(attack_ms=self.attack_ms, release_db_per_s=self.release_db_per_s)
+
+
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
     """What `controls=` cannot be combined with: refused before anything is launched."""
     if not isinstance(controls, Controls):
@@ -1041,6 +1140,9 @@ class SynthesisResult:
                and the level are those of the cut rows.  Kept in the same allocation: `to_host(edges=True)` is still one copy.
       breaks   (with `breaks=`) int32 [B, 2]: {the row's samples with its pauses, the silence inserted} at the
                model rate.  Kept in the same allocation: `to_host(breaks=True)` is still one copy.
+      dynamics (with `dynamics=`) float32 [B, 2]: {the deepest gain reduction in dB, the number of 64-sample
+               blocks that were reduced}; {0, 0} for a row left alone.  Kept in the same allocation: `to_host(dynamics=True)` is
+               still one copy.
       fit      (with `fit_frames=`) int32 [B, 4]: {the row's frames before the fit, its frames after,
                flag, the number of tokens whose duration changed}; flag 0 = the target was met, 1 = it was infeasible and the
                nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
@@ -1066,8 +1168,9 @@ class SynthesisResult:
         self.limit = None if ho is None or ho.limit is None else ho.limit.view(-1, 2)
         self.edges = None if ho is None or ho.edges is None else ho.edges.view(-1, 2)
         self.breaks = None if ho is None or ho.breaks is None else ho.breaks.view(-1, 2)
+        self.dynamics = None if ho is None or ho.dynamics is None else ho.dynamics.view(-1, 2)
 
-    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False, breaks=False):
+    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False, breaks=False, dynamics=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -1084,7 +1187,11 @@ class SynthesisResult:
         result made with a limiting `Level`): the limiter's {drive gain, smallest gain factor} as a float32 [B, 2] numpy array, out
         of the same copy, behind those.  `edges=True` (a result made with `edges=`): {head, count} per row as an int32 [B, 2] numpy
         array, out of the same copy, behind those.  `breaks=True` (a result made with `breaks=`): {the row's samples with its pauses,
-        the silence inserted} at the model rate as an int32 [B, 2] numpy array, out of the same copy, last."""
+        the silence inserted} at the model rate as an int32 [B, 2] numpy array, out of the same copy, behind those.  `dynamics=True` (a
+        result made with `dynamics=`): {deepest reduction in dB, blocks reduced} per row as a float32 [B, 2] numpy array, out of the
+        same copy, last."""
+        if dynamics and self.dynamics is None:
+            raise ValueError("this result carries no dynamics table: ask for it with inference(..., dynamics=Dynamics(...))")
         if breaks and self.breaks is None:
             raise ValueError("this result carries no breaks table: ask for it with inference(..., breaks=Breaks(...))")
         if edges and self.edges is None:
@@ -1121,6 +1228,8 @@ class SynthesisResult:
             more += (self._ho.edges_view(self._host).numpy().reshape(B, 2),)
         if breaks:
             more += (self._ho.breaks_view(self._host).numpy().reshape(B, 2),)
+        if dynamics:
+            more += (self._ho.dynamics_view(self._host).numpy().reshape(B, 2),)
         return (rows,) + more if more else rows
 
 
@@ -1180,14 +1289,16 @@ class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
         [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | limit float32 [2 B] |
-         edges int32 [2 B] | breaks int32 [2 B] | pad to 16 bytes | samples of `fmt`]
+         edges int32 [2 B] | breaks int32 [2 B] | dynamics float32 [2 B] | pad to 16 bytes | samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps / no level / no limit / no edges / no breaks the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
-    five parts (`samples_at` is the header's size); `views(buf)` gives the parts of a byte buffer of this layout, on the device or
-    its pinned mirror; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `packed` and `level` are
-    the buffer and its views (None for a part the layout does not have)."""
+    with `n_marks` = 0 / no gaps / no level / no limit / no edges / no breaks / no dynamics the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    nine parts (`samples_at` is the header's size); `views(buf)` gives the first four parts and the samples of a byte buffer of
+    this layout, on the device or its pinned mirror, `limit_view`, `edges_view`, `breaks_view` and `dynamics_view` the later
+    ones; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `level`, `limit`, `edges`, `breaks`,
+    `dynamics` and `packed` are the buffer and its views (None for a part the layout does not have)."""
 
-    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False, with_breaks=False):
+    def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False, with_breaks=False,
+                 with_dynamics=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
         self.with_level, self.with_limit, self.with_edges = bool(with_level), bool(with_limit), bool(with_edges)
         self.with_breaks = bool(with_breaks)
@@ -1198,8 +1309,11 @@ class _HandOver:
         self.limit_at = self.level_at + (16 * self.B if self.with_level else 0)
         self.edges_at = self.limit_at + (8 * self.B if self.with_limit else 0)
         self.breaks_at = self.edges_at + (8 * self.B if self.with_edges else 0)
-        self.samples_at = (self.breaks_at + (8 * self.B if self.with_breaks else 0) + 15) // 16 * 16
+        self.with_dynamics = bool(with_dynamics)
+        self.dynamics_at = self.breaks_at + (8 * self.B if self.with_breaks else 0)
+        self.samples_at = (self.dynamics_at + (8 * self.B if self.with_dynamics else 0) + 15) // 16 * 16
         self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = self.edges = self.breaks = None
+        self.dynamics = None
 
     def limit_view(self, buf):
         """The sixth part, float32 [2 B] (`ops.wave_limit`'s {g', min q} per row), of a uint8 buffer of this
@@ -1216,9 +1330,14 @@ class _HandOver:
         buffer of this layout, or None.  Apart from `views`, as `limit_view` is."""
         return buf[self.breaks_at:self.breaks_at + 8 * self.B].view(torch.int32) if self.with_breaks else None
 
+    def dynamics_view(self, buf):
+        """The ninth part, float32 [2 B] (`ops.wave_dynamics`'s {deepest reduction, blocks reduced} per row),
+        of a uint8 buffer of this layout, or None.  Apart from `views`, as `limit_view` is."""
+        return buf[self.dynamics_at:self.dynamics_at + 8 * self.B].view(torch.float32) if self.with_dynamics else None
+
     def views(self, buf):
         """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
-        None) of a uint8 buffer."""
+        None) of a uint8 buffer: the parts the layout began with.  The later parts have a view function each."""
         i32 = lambda at, n: buf[at:at + 4 * n].view(torch.int32)
         return (buf[self.offsets_at:self.marks_at].view(torch.int64), i32(self.marks_at, self.n_marks) if self.n_marks else None,
                 i32(self.gaps_at, self.B) if self.with_gaps else None, buf[self.samples_at:].view(self.dtype),
@@ -1230,6 +1349,7 @@ class _HandOver:
         self.limit = self.limit_view(self.buf)
         self.edges = self.edges_view(self.buf)
         self.breaks = self.breaks_view(self.buf)
+        self.dynamics = self.dynamics_view(self.buf)
         return self
 
 
@@ -1251,7 +1371,7 @@ def _capacity_only(names, *given):
 
 
 def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False,
-                 passage=None, front_groups=1, edges=None, breaks=None, N=None):
+                 passage=None, front_groups=1, edges=None, breaks=None, N=None, dynamics=None):
     """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
     every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
     launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
@@ -1262,7 +1382,7 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     call's `passage`, and `front_groups`: the front calls `synthesize_long` cuts the passage into -- what a `Level` of
     scope "passage" is judged by, and looked at for nothing else.  `edges`: an `Edges` of the B rows, judged here and handed on by
     the caller (the spec does not carry it, as it does not carry `level`).  `breaks`: a `Breaks` of the B rows and of the call's `N`
-    tokens (None: the caller has no token count to judge by), likewise."""
+    tokens (None: the caller has no token count to judge by), likewise.  `dynamics`: a `Dynamics` of the B rows, likewise."""
     if pack is not None and pack not in ops.OUTPUT_FORMATS:
         raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
     if sample_rate is not None and pack is None:
@@ -1286,6 +1406,10 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
         raise ValueError("breaks are spliced into the packed samples of the capacity-bound path: pass max_frames and pack")
     if breaks is not None and (not isinstance(breaks, Breaks) or breaks.B != B or (N is not None and breaks.N != N)):
         raise ValueError("breaks must be a pipeline.Breaks of %d rows%s" % (B, "" if N is None else " of %d tokens" % N))
+    if dynamics is not None and (pack is None or not capacity):
+        raise ValueError("dynamics compress the packed samples of the capacity-bound path: pass max_frames and pack")
+    if dynamics is not None and (not isinstance(dynamics, Dynamics) or dynamics.B != B):
+        raise ValueError("dynamics must be a pipeline.Dynamics of %d rows" % B)
     if not capacity:
         _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
     if pack is None and (gaps is not None or max_gap is not None):
@@ -1323,7 +1447,7 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
 
 
 def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None,
-                     starts=None, edges=None, breaks=None, tokens=None):
+                     starts=None, edges=None, breaks=None, tokens=None, dynamics=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
@@ -1342,7 +1466,10 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     in samples of the (cut) rows come from one `ops.token_marks` / `ops.token_marks_edges` launch without a rate over `tokens`
     (that wrapper's dur, T_cap, lengths and shift), the rows with their silence go to a buffer of the caching allocator of
     `max_break` more samples per row, {count', inserted} into the header's breaks part, and the rest runs over frames = count'.
-    The boundaries and the inserted silence stay with the hand-over (`pos`, `ins`) for the marks."""
+    The boundaries and the inserted silence stay with the hand-over (`pos`, `ins`) for the marks.  With `dynamics` (a `Dynamics`;
+    DESIGN.md section 30) `ops.wave_dynamics` runs behind the breaks and in front of the level, into a buffer of the caching
+    allocator with {deepest reduction, blocks reduced} into the header's dynamics part: sample counts do not change, so frames,
+    trim and samples_per_frame go on as they came, and the loudness target holds on the compressed programme."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
@@ -1351,7 +1478,8 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
         room += resample.output_samples(breaks.max_break, U, D)
     limiting = level is not None and level.limiter
     ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting,
-                   with_edges=edges is not None, **({} if breaks is None else {"with_breaks": True})).allocate(B * room, wave.device)
+                   with_edges=edges is not None, **({} if breaks is None else {"with_breaks": True}),
+                   **({} if dynamics is None else {"with_dynamics": True})).allocate(B * room, wave.device)
     if edges is not None:
         wave, _ = ops.wave_edges(wave, frames, edges.top_db, edges.keep, resample.edge_ramp(edges.F, wave.device) if edges.F else None,
                                  trim=trim, samples_per_frame=samples_per_frame, edges=ho.edges)
@@ -1364,6 +1492,10 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
                                              resample.edge_ramp(breaks.F, wave.device) if breaks.F else None, trim=trim,
                                              samples_per_frame=samples_per_frame, breaks=ho.breaks)
         frames, trim, samples_per_frame = ho.breaks.view(B, 2)[:, 0].contiguous(), 0, 1
+    if dynamics is not None:
+        A = dynamics.A
+        wave, _ = ops.wave_dynamics(wave, frames, dynamics.params, resample.limit_window(A, wave.device) if A else None, A=A,
+                                    rho=dynamics.rho, trim=trim, samples_per_frame=samples_per_frame, dynamics=ho.dynamics)
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
@@ -1393,12 +1525,13 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None, breaks=None):
+def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None, breaks=None, dynamics=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
     into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation, `starts`: the call's `passage`
     for a level of scope "passage" (`_hand_over`), `edges`: their trim (`_hand_over_edges`; the marks are then `ops.token_marks_edges`'),
-    `breaks`: the pauses inside them (`_hand_over_edges`; the marks are then `ops.token_marks_breaks`')."""
+    `breaks`: the pauses inside them (`_hand_over_edges`; the marks are then `ops.token_marks_breaks`'), `dynamics`: their compressor
+    (`_hand_over_edges`; it moves no sample, so the marks are what they are without it)."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     hifigan = model.decoder.kind == "hifigan"
@@ -1409,12 +1542,15 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
-    hand_over = _hand_over if edges is None else functools.partial(_hand_over_edges, edges=edges)
+    more = {} if edges is None else {"edges": edges}  # the optional stages of the hand-over; none: `_hand_over` as ever
     if breaks is not None:
         if breaks.N != N:
             raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (B, N))
-        hand_over = functools.partial(_hand_over_edges, edges=edges, breaks=breaks, tokens=dict(
-            dur=dur, frames=p["frames"], T_cap=T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim, samples_per_frame=spf))
+        more.update(breaks=breaks, tokens=dict(dur=dur, frames=p["frames"], T_cap=T_cap, lengths=p.get("token_lengths"), shift=hifigan,
+                                               trim=spec.trim, samples_per_frame=spf))
+    if dynamics is not None:
+        more.update(dynamics=dynamics)
+    hand_over = functools.partial(_hand_over_edges, **more) if more else _hand_over
     ho = hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
                    level, starts)
     m = None
@@ -1488,12 +1624,18 @@ class GraphedSynthesis:
     default): the graph records the pauses inside the rows over one more static buffer, `static["breaks"]` (a `Breaks`; at first
     no pause anywhere, or the table given): `__call__(breaks=)` -- a `Breaks` or an int [B, N] table of samples at 24 kHz --
     copies the table into it, so one graph serves any pauses up to the cap; the cap and the fade are the graph's own.  Without
-    it the graph records exactly what it recorded before."""
+    it the graph records exactly what it recorded before.
+
+    `dynamics=True` (or a `Dynamics`; needs `pack`): the graph records the compressor over one more static
+    buffer, `static["dynamics"]` (a `Dynamics`; at first the defaults in every row, or the one given): `__call__(dynamics=)` -- a
+    `Dynamics` of B rows -- copies its table into it, so one graph serves any thresholds, ratios, knees and make-up gains;
+    `attack_ms` and `release_db_per_s` are the graph's own, fixed at construction.  Without it the graph records exactly what it
+    recorded before."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
                  token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None,
-                 breaks=None, max_break_ms=None):
+                 breaks=None, max_break_ms=None, dynamics=None):
         from .diffusion import GraphedSampler
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
@@ -1512,11 +1654,13 @@ class GraphedSynthesis:
             breaks = None
         elif isinstance(breaks, Breaks) and max_break_ms is not None and Edges.samples(max_break_ms) != breaks.max_break:
             raise ValueError("max_break_ms=%r is not the cap of the Breaks given (%r ms)" % (max_break_ms, breaks.max_ms))
+        dynamics = Dynamics(B, device=dev) if dynamics is True else None if dynamics is False else dynamics
         # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
         gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
         spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage,
                                **({} if edges is None else {"edges": edges}),
-                               **({} if breaks is None else {"breaks": breaks, "N": N}))
+                               **({} if breaks is None else {"breaks": breaks, "N": N}),
+                               **({} if dynamics is None else {"dynamics": dynamics}))
         if spec.rate is not None:
             resample.table(spec.rate, dev)
         if level is not None and level.true_peak:
@@ -1527,6 +1671,8 @@ class GraphedSynthesis:
             resample.edge_ramp(edges.F, dev)  # and the fade of a cut edge
         if breaks is not None and breaks.F:
             resample.edge_ramp(breaks.F, dev)  # and that of a pause's two sides
+        if dynamics is not None and dynamics.A:
+            resample.limit_window(dynamics.A, dev)  # and the compressor's look-ahead window
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1560,6 +1706,9 @@ class GraphedSynthesis:
             self.static["edges"] = Edges(B, top_db=edges.top_db.to(dev).clone(), device=dev, **edges.options())
         if breaks is not None:
             self.static["breaks"] = Breaks(B, N, samples=breaks.samples.to(dev).clone(), device=dev, **breaks.options())
+        if dynamics is not None:
+            own = self.static["dynamics"] = dynamics.slice(0, B)
+            own.params = dynamics.params.to(dev).clone()
         self._g = None
 
     def _run(self):
@@ -1570,7 +1719,8 @@ class GraphedSynthesis:
                          level=st.get("level"), **self.kw, **({"seeds": st["seeds"]} if "seeds" in st else {}),
                          **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}),
                          **({"edges": st["edges"]} if "edges" in st else {}),
-                         **({"breaks": st["breaks"]} if "breaks" in st else {}))
+                         **({"breaks": st["breaks"]} if "breaks" in st else {}),
+                         **({"dynamics": st["dynamics"]} if "dynamics" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1584,7 +1734,7 @@ class GraphedSynthesis:
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
                  starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None,
-                 breaks=None):
+                 breaks=None, dynamics=None):
         st = self.static
         if fit_frames is not None or fit_hold is not None:
             if "fit_frames" not in st:
@@ -1638,6 +1788,16 @@ class GraphedSynthesis:
                 raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (own.B, own.N))
             table = breaks.samples if isinstance(breaks, Breaks) else Breaks.table(None, breaks, own.B, own.N)
             own.samples.copy_(table, non_blocking=True)
+        if dynamics is not None:
+            if st.get("dynamics") is None:
+                raise ValueError("this graph was built without dynamics: pass dynamics=True")
+            own = st["dynamics"]
+            if not isinstance(dynamics, Dynamics) or dynamics.B != own.B:
+                raise ValueError("dynamics must be a pipeline.Dynamics of %d rows" % own.B)
+            if dynamics.options() != own.options():
+                raise ValueError("attack_ms and release_db_per_s are the graph's own (%r); the Dynamics given has %r"
+                                 % (own.options(), dynamics.options()))
+            own.params.copy_(dynamics.params, non_blocking=True)
         if controls is not None:
             if not isinstance(controls, Controls) or controls.B != st["controls"].B:
                 raise ValueError("controls must be a pipeline.Controls of %d rows" % st["controls"].B)
@@ -1812,7 +1972,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None):
+              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None, dynamics=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -1906,10 +2066,16 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     else of the hand-over).  The marks are those of the rows with their pauses: token n's pause lies inside [marks[b, n],
     marks[b, n + 1]).  The result carries {samples with the pauses, silence inserted} as `breaks`.  `fit_frames` keeps meaning
     frames of speech: the pauses come on top.  Without `breaks` the call issues exactly the launches it always did.
+
+    `dynamics` (a `Dynamics` of B rows, with `max_frames` and `pack`): a compressor over every row, on the
+    device (`ops.wave_dynamics`, behind `breaks` and in front of `level`, so a loudness target holds on the compressed programme
+    and the limiter sees compressed peaks).  No sample moves: marks, gaps, resampling and G.711 run unchanged.  The result carries
+    {deepest reduction in dB, blocks reduced} as `dynamics`.  Without it the call issues exactly the launches it always did.
     """
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
                               passage=passage, **({} if edges is None else {"edges": edges}),
-                              **({} if breaks is None else {"breaks": breaks, "N": tokens.shape[1]}))
+                              **({} if breaks is None else {"breaks": breaks, "N": tokens.shape[1]}),
+                              **({} if dynamics is None else {"dynamics": dynamics}))
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
@@ -1945,7 +2111,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         sine_noise = _seeded_sine_noise(seeds, p["frames"], max_frames)
     if max_frames is not None:
         return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage, **({} if edges is None else {"edges": edges}),
-                                **({} if breaks is None else {"breaks": breaks}))
+                                **({} if breaks is None else {"breaks": breaks}),
+                                **({} if dynamics is None else {"dynamics": dynamics}))
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -2014,7 +2181,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None):
+                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None, dynamics=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -2080,6 +2247,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `breaks` (needs `max_frames` and `pack`): a `Breaks` of one row per SENTENCE, its N the longest sentence's
     token count -- shorter sentences are right-padded to it, as with per-token controls --: the pauses inside the sentences
     (`inference(breaks=)`).
+    `dynamics` (needs `max_frames` and `pack`): a `Dynamics` of one row per SENTENCE: the compressor over every
+    sentence (`inference(dynamics=)`).
     """
     dev = sentences[0].device
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
@@ -2090,10 +2259,11 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks)
+            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks, dynamics=dynamics)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     _capacity_only("edges", edges)
     _capacity_only("breaks", breaks)
+    _capacity_only("dynamics", dynamics)
     _capacity_only("seeds", seeds)
     _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
@@ -2175,7 +2345,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
                               controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None,
-                              breaks=None):
+                              breaks=None, dynamics=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -2200,7 +2370,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     chunks = _front_chunks(front_batch, K)
     spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level, passage=True,
                               front_groups=len(chunks), **({} if edges is None else {"edges": edges}),
-                              **({} if breaks is None else {"breaks": breaks, "N": max(ns_all)}))
+                              **({} if breaks is None else {"breaks": breaks, "N": max(ns_all)}),
+                              **({} if dynamics is None else {"dynamics": dynamics}))
     prepped = []
     for i, i_end in chunks:
         ids = list(range(i, i_end))
@@ -2223,6 +2394,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
             more.update(edges=edges.slice(i, j))
         if breaks is not None:
             more.update(breaks=breaks.slice(i, j))
+        if dynamics is not None:
+            more.update(dynamics=dynamics.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
