@@ -1331,6 +1331,35 @@ int st2_prosody_controls_tok(float* f0, float* n, int64_t bs, int32_t B, int32_t
                              int32_t shift, const float* tok_f0_scale, const float* tok_n_shift, const int32_t* frames,
                              void* stream);
 
+/* Intonation (added under ABI 23): a request's pitch RANGE and pitch CONTOUR, applied in place to the
+ * prosody predictor's F0 curve (fp32 [B][L], row stride bs, L = 2 T_cap even) in front of st2_prosody_controls[_tok].  Row b
+ * has T_b = clamp(frames[b], 0, L / 2) frames (L / 2 without frames) and len_b = 2 T_b columns; nothing at or past len_b is read
+ * or written.
+ *  1. Voiced.  Column l < len_b is voiced iff f0[l] is finite and f0[l] > voiced_hz (the harmonic source's rule).  n_v = their
+ *     number, m = (sum over them of log2((double)f0[l])) / n_v in fp64.  A row with n_v = 0 is left alone, bit for bit.
+ *  2. Range.  r_b = range[b] clamped to [0, 4]; NaN or a NULL row = 1.  q = tok_range[b][idx(b, l div 2)] clamped to [0, 4], NaN
+ *     = 1 (NULL: 1), idx the token of st2_prosody_controls_tok for the same dur / shift.  r = min(r_b * q, 4) in fp32.
+ *  3. Contour.  contour is fp32 [B][K][2], 0 <= K <= 8, of points (p, v): p a position as a share of the row's own frames, v an
+ *     offset in semitones.  A point with a NaN p or v is unused; p is clamped to [0, 1] and then raised to the largest used p in
+ *     front of it, v is clamped to [-24, 24].  At frame t, x = (t + 0.5) / T_b in fp64 and j = the number of used points with
+ *     p <= x: c = the first v for j = 0, the last v for j = the number of used points, and otherwise
+ *     c = v[j-1] + (v[j] - v[j-1]) * ((x - p[j-1]) / (p[j] - p[j-1])) in fp64 in that order: coincident points are a step.  No
+ *     used point: c = 0.
+ *  4. Output.  A voiced column with r == 1.0f and c == 0.0 keeps its bits.  Any other voiced column becomes
+ *     fl32(min(max(exp2((m + (double)r * (log2 f0 - m)) + c / 12.0), lo_hz), hi_hz)).  Unvoiced columns keep their bits; as
+ *     lo_hz > voiced_hz, a voiced column stays voiced.
+ *  5. pitch (fp32 [B][4] or NULL) = {exp2(m) in Hz, n_v, the smallest and the largest output over the voiced columns};
+ *     {NaN, 0, NaN, NaN} for n_v = 0.
+ * Everything is fixed but the last ulp of fp64 log2 / exp2 and the order of the fp64 sum.  One launch, one workgroup of 256
+ * threads per row, no atomics, no allocation, no synchronisation, no host read: legal under stream capture.  range, tok_range,
+ * contour (or K = 0) and pitch all absent: returns 0 without a launch; pitch alone: the launch measures and writes no f0.
+ * Returns non-zero before any launch on: NULL f0; B outside 1..65535; L <= 0 or odd; bs < L with B > 1; tok_range without dur;
+ * N outside 1..512 with tok_range; K outside 0..8; NULL contour with K > 0; voiced_hz outside (0, 1000]; not voiced_hz < lo_hz
+ * < hi_hz <= 20000. */
+int st2_pitch_shape(float* f0, int64_t bs, int32_t B, int32_t L, const int32_t* frames, const float* range,
+                    const float* tok_range, const int64_t* dur, int32_t N, int32_t shift, const float* contour, int32_t K,
+                    float voiced_hz, float lo_hz, float hi_hz, float* pitch /* [B][4] or NULL */, void* stream);
+
 /* st2_front_forward_ctl with a per-token rate: tok->speed (fp32 [B][N], device) makes the duration head
  * st2_duration_head_rate_tok (`durations` must then be non-NULL).  A NULL `tok`, or one whose member is NULL, is
  * st2_front_forward_ctl, which is this call with NULL.  Refused while a debug backend is installed, as `ctl` is. */

@@ -323,6 +323,8 @@ _SIGNATURES = {
                                              C.c_void_p, C.c_int32, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "st2_prosody_controls_tok": (C.c_int, [f32p, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, f32p,
                                            f32p, C.c_void_p, C.c_void_p]),
+    "st2_pitch_shape": (C.c_int, [f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, f32p, f32p, C.c_void_p, C.c_int32, C.c_int32,
+                                  f32p, C.c_int32, C.c_float, C.c_float, C.c_float, f32p, C.c_void_p]),
     "st2_sizeof_token_controls": (C.c_int, []),
     "st2_front_forward_tok": (C.c_int, [C.c_void_p, C.POINTER(FrontArgs), C.POINTER(ControlRows), C.POINTER(TokenControlRows),
                                         C.c_void_p, C.c_int64, C.c_void_p]),

@@ -5,26 +5,9 @@
 // (The third token control, the duration head with a per-token rate, is an instantiation of duration_head_kernel in
 // st2_glue.hip.)
 #include "st2_common.h"
+#include "st2_tokens.h"
 
 namespace {
-
-// c[i + 1] = min(T_cap, sum_{m <= i, m < n_b} dur[m]) into cum[i], i < N <= 512: the expansion kernel's chunked 64-lane scan
-// by ONE wave (the caller's first 64 threads), with every duration clamped to 0..T_cap first -- the saturated sum is that of
-// the unclamped 64-bit one, and 512 terms of at most 2^31 cannot wrap.
-__device__ __forceinline__ void scan_durations(const long long* __restrict__ db, int N, int n_b, int T_cap, int* cum) {
-  long long carry = 0;
-  for (int base = 0; base < N; base += 64) {
-    const int i = base + (int)threadIdx.x;
-    long long v = i < n_b ? min(max(db[i], 0LL), (long long)T_cap) : 0LL;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long u = __shfl_up(v, off, 64);
-      if ((int)threadIdx.x >= off) v += u;
-    }
-    if (i < N) cum[i] = (int)min(v + carry, (long long)T_cap);
-    carry += __shfl(v, 63, 64);
-  }
-}
 
 // One wave per row.  bound[n] = the first frame of token n (st2.h "the boundary rule"), marks[n] = the first output sample at
 // or after that frame's time in the row's packed samples.  EDGES (st2_token_marks_edges): the row was cut to the `count` samples
@@ -82,13 +65,7 @@ __global__ __launch_bounds__(TOK_THREADS) void prosody_controls_tok_kernel(float
   for (int it = 0; it < TOK_COLS / 2 / TOK_THREADS; ++it) {
     const int t = t0 + it * TOK_THREADS + (int)threadIdx.x;
     if (t >= T_b) break;
-    const int ts = shift ? max(t - 1, 0) : t;
-    int lo = 0, hi = N;  // first m with cum[m] > ts: idx(b, t) of the expansion kernel
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cum[mid] <= ts) lo = mid + 1; else hi = mid;
-    }
-    const int idx = min(lo, N - 1);
+    const int idx = token_of_frame(cum, N, t, shift);
     const int l = 2 * t;
     if (scr) {
       const float v = scr[idx];

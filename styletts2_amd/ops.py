@@ -1118,6 +1118,53 @@ def prosody_controls_tok(f0, n, dur, tok_f0_scale=None, tok_n_shift=None, frames
     return f0, n
 
 
+PITCH_POINTS = 8  # the most contour points of a row (`st2_pitch_shape`)
+
+
+def pitch_shape(f0, range=None, tok_range=None, dur=None, contour=None, frames=None, shift=False, voiced_hz=10.0, lo_hz=40.0,
+                hi_hz=1100.0, pitch=None):
+    """`st2_pitch_shape`, in place (include/st2.h): the voiced columns of f0[b, :2 * frames[b]] move around
+    the row's own voiced mean of log2 F0 -- the deviation times range[b] * tok_range[b, idx(b, l // 2)] (each clamped to [0, 4],
+    NaN = 1, the product capped at 4) plus the contour's semitones at the frame's place in the row -- and are clamped to
+    [lo_hz, hi_hz]; unvoiced columns (not finite, or <= voiced_hz) and everything at or past a row's end keep their bits.  f0
+    [B, L] fp32, L even; range fp32 [B], tok_range fp32 [B, N] with dur int64 [B, N], contour fp32 [B, K, 2] of (position in
+    [0, 1], semitones in [-24, 24]) points, K <= 8, a NaN point unused; frames int32 [B]; all on the device of f0, any of them
+    None.  `pitch` (fp32 [B, 4] on the device, or True to have one made): {mean in Hz, voiced columns, lowest, highest output} per
+    row.  Returns `pitch` or None.  One launch; none when there is nothing to apply and nothing to report."""
+    B = _nb(f0, 2)
+    fp = _chk_len(frames, "frames", B, f0)
+    N = dur.shape[1] if torch.is_tensor(dur) and dur.dim() == 2 else tok_range.shape[1] if torch.is_tensor(tok_range) and \
+        tok_range.dim() == 2 else -1
+    rp, tp = _chk_row(range, "range", B, f0), _chk_tok_row(tok_range, "tok_range", B, N, f0)
+    K = 0
+    if contour is not None:
+        if not torch.is_tensor(contour) or contour.dtype != torch.float32:
+            raise _lib.St2Error("contour must be a float32 tensor (got %s)" % (
+                contour.dtype if torch.is_tensor(contour) else type(contour).__name__))
+        if contour.dim() != 3 or contour.shape[0] != B or contour.shape[2] != 2 or not contour.is_contiguous():
+            raise _lib.St2Error("contour must be a contiguous [%d, K, 2] tensor (got shape %s)" % (B, tuple(contour.shape)))
+        if not contour.is_cuda or not torch.is_tensor(f0) or contour.device != f0.device:
+            raise _lib.St2Error("contour must live on the device of the tensor it describes (%s, got %s)" % (
+                f0.device if torch.is_tensor(f0) else None, contour.device))
+        K = contour.shape[1]
+    lib = _lib.load()
+    _chk(f0, "f0", 2)
+    if f0.stride(1) != 1:
+        raise _lib.St2Error("f0 must have unit stride along its columns (got strides %s)" % (tuple(f0.stride()),))
+    if dur is not None:
+        _chk_dev(dur, "dur", torch.int64, 2)
+        if dur.shape[0] != B or dur.device != f0.device:
+            raise _lib.St2Error("dur must hold %d rows on the device of f0 (got %s on %s)" % (B, tuple(dur.shape), dur.device))
+    if pitch is True:
+        pitch = torch.empty((B, 4), device=f0.device, dtype=torch.float32)
+    elif pitch is not None:
+        _chk_out(pitch, "pitch", (B, 4), f0)
+    _lib.check(lib.st2_pitch_shape(f0.data_ptr(), f0.stride(0), B, f0.shape[1], fp, rp, tp, _ptr(dur), max(N, 0), 1 if shift else 0,
+                                   _ptr(contour) if K else 0, K, float(voiced_hz), float(lo_hz), float(hi_hz), _ptr(pitch), _stream()),
+               "st2_pitch_shape")
+    return pitch
+
+
 def expand_by_durations(x, dur, T, shift=False, out=None, lengths=None):
     """`st2_expand_by_durations`: x [B, C, N], dur int64 [B, N] (rows sum to T) -> [B, C, T].  `lengths` (int32 [B] on the
     device, `st2_expand_by_durations_len`): row b's durations sum to lengths[b], its columns from there on are exact zeros."""

@@ -635,6 +635,147 @@ class Dynamics:
         return dict(attack_ms=self.attack_ms, release_db_per_s=self.release_db_per_s)
 
 
+class Intonation:
+    """A request's intonation (include/st2.h `st2_pitch_shape`): SSML's `<prosody range= contour=>`, applied
+    on the device to the prosody predictor's F0 curve around every row's own voiced mean, in front of the flat pitch scales of
+    `Controls`.
+
+        range      how far the voice moves around its mean: 0 = monotone, 1 = as predicted, 2 = twice as lively;
+                   a float, B values or a device tensor [B]                                                       [0, 4]
+        contour    a glide over the sentence: per row at most `K` (position, semitones) pairs, the position a share of the row's
+                   own frames -- a list of B such lists, ONE list of pairs for every row, or a device tensor [B, K, 2];
+                   linear between the points, flat outside them, two points at one position are a step      [0, 1] x [-24, 24]
+        tok_range  token n's range on top of the row's (the product is capped at 4): a float, a [B, N] array or a device
+                   tensor                                                                                          [0, 4]
+
+    Host values are validated here (ValueError: finite, in range, positions ascending); a tensor already on the device is never
+    read: the kernel clamps it (NaN = absent, a point with a NaN is unused).  Each table is one fp32 device tensor made by ONE host
+    -> device copy; rows with fewer than `K` points are padded with NaN.  `voiced_hz` is the voiced rule's threshold (the
+    harmonic source's 10 Hz).  The F0 curve is kept inside [LO_HZ, HI_HZ]."""
+    RANGE = (0.0, 4.0)
+    SEMITONES = (-24.0, 24.0)
+    LO_HZ, HI_HZ = 40.0, 1100.0
+
+    def __init__(self, B, range=None, contour=None, tok_range=None, N=None, K=8, voiced_hz=10.0, device=None):
+        B, K, voiced_hz = int(B), int(K), float(voiced_hz)
+        if B <= 0:
+            raise ValueError("Intonation: B must be positive, got %r" % (B,))
+        if not 0 <= K <= ops.PITCH_POINTS:
+            raise ValueError("Intonation: K must lie in 0..%d, got %r" % (ops.PITCH_POINTS, K))
+        if not 0.0 < voiced_hz < self.LO_HZ:
+            raise ValueError("Intonation: voiced_hz must lie in (0, %g), got %r" % (self.LO_HZ, voiced_hz))
+        if device is None:
+            on_dev = [v for v in (range, contour, tok_range) if torch.is_tensor(v) and v.is_cuda]
+            device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        if N is None and tok_range is not None:
+            shape = tuple(tok_range.shape) if torch.is_tensor(tok_range) else tuple(torch.as_tensor(tok_range).shape)
+            if len(shape) != 2:
+                raise ValueError("Intonation: tok_range needs N (the batch's token width) or a [B, N] array")
+            N = shape[1]
+        if N is not None and not 0 < int(N) <= 512:
+            raise ValueError("Intonation: N must lie in 1..512, got %r" % (N,))
+        self.B, self.K, self.voiced_hz, self.N = B, K, voiced_hz, None if N is None else int(N)
+        self.device = torch.empty(0, device=device).device  # with its index, as a tensor's
+        self.range = self._rows("range", range, (B,), device)
+        self.tok_range = None if self.N is None else self._rows("tok_range", 1.0 if tok_range is None else tok_range, (B, self.N), device)
+        self.contour = self._points(contour, B, K, device)
+
+    @staticmethod
+    def _rows(name, v, shape, device):
+        """`range` ([B]) or `tok_range` ([B, N]) as its fp32 device tensor; None stays None."""
+        if v is None:
+            return None
+        dims = "%d" % shape if len(shape) == 1 else "[%d, %d]" % shape
+        if torch.is_tensor(v) and v.is_cuda:  # never read: clamped where the kernel reads it
+            if (v.numel() != shape[0]) if len(shape) == 1 else (tuple(v.shape) != shape):
+                raise ValueError("Intonation: %s must hold %s values, got shape %s" % (name, dims, tuple(v.shape)))
+            return v.detach().reshape(shape).to(device=device, dtype=torch.float32).contiguous()
+        rows = torch.as_tensor(v, dtype=torch.float64)
+        if len(shape) == 1:
+            rows = rows.reshape(-1)
+        if rows.numel() == 1:
+            rows = rows.reshape((1,) * len(shape)).expand(shape)
+        if tuple(rows.shape) != shape:
+            raise ValueError("Intonation: %s must be one value or %s values, got shape %s" % (name, dims, tuple(rows.shape)))
+        lo, hi = Intonation.RANGE
+        if not bool((torch.isfinite(rows) & (rows >= lo) & (rows <= hi)).all()):
+            raise ValueError("Intonation: %s must lie in [%g, %g]%s" % (name, lo, hi, ", got %s" % rows.tolist() if len(shape) == 1 else ""))
+        return rows.to(torch.float32).contiguous().to(device)  # ONE host -> device copy
+
+    @staticmethod
+    def _points(contour, B, K, device):
+        """`contour` as its fp32 [B, K, 2] device tensor, short rows padded with NaN; None stays None."""
+        if contour is None:
+            return None
+        if torch.is_tensor(contour) and contour.is_cuda:  # never read
+            if tuple(contour.shape) != (B, K, 2):
+                raise ValueError("Intonation: contour must be [%d, %d, 2], got shape %s" % (B, K, tuple(contour.shape)))
+            return contour.detach().to(device=device, dtype=torch.float32).contiguous()
+        rows = contour.tolist() if torch.is_tensor(contour) else list(contour)
+        pair = lambda e: isinstance(e, (list, tuple)) and len(e) == 2 and not any(isinstance(x, (list, tuple)) for x in e)
+        if all(pair(e) for e in rows):
+            rows = [rows] * B  # one list of points for every row
+        if len(rows) != B:
+            raise ValueError("Intonation: contour must be one list of (position, semitones) pairs or %d of them, got %d" % (B, len(rows)))
+        host = torch.full((B, K, 2), float("nan"), dtype=torch.float32)
+        (s_lo, s_hi) = Intonation.SEMITONES
+        for b, pts in enumerate(rows):
+            pts = [] if pts is None else list(pts)
+            if len(pts) > K:
+                raise ValueError("Intonation: contour row %d has %d points, at most K = %d fit" % (b, len(pts), K))
+            if not all(isinstance(e, (list, tuple)) and len(e) == 2 for e in pts):
+                raise ValueError("Intonation: contour row %d must be (position, semitones) pairs, got %r" % (b, pts))
+            last = 0.0
+            for k, (p, v) in enumerate(pts):
+                p, v = float(p), float(v)
+                if not (0.0 <= p <= 1.0) or not (s_lo <= v <= s_hi):
+                    raise ValueError("Intonation: contour point (%r, %r) of row %d must lie in [0, 1] x [%g, %g]" % (p, v, b, s_lo, s_hi))
+                if p < last:
+                    raise ValueError("Intonation: contour positions of row %d must ascend, got %r" % (b, [float(e[0]) for e in pts]))
+                host[b, k, 0], host[b, k, 1], last = p, v, p
+        return host.to(device)  # ONE host -> device copy
+
+    @classmethod
+    def neutral(cls, B, N=None, K=8, voiced_hz=10.0, device=None):
+        """Every table present and neutral: range 1, no point (all NaN), with `N` the token ranges 1.  Equals the call without the
+        object bit for bit."""
+        return cls(B, range=1.0, contour=[], tok_range=None if N is None else 1.0, N=N, K=K, voiced_hz=voiced_hz, device=device)
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as an Intonation over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Intonation)
+        c.B, c.K, c.voiced_hz, c.N, c.device = j - i, self.K, self.voiced_hz, self.N, self.device
+        c.range, c.tok_range, c.contour = (None if v is None else v[i:j] for v in (self.range, self.tok_range, self.contour))
+        return c
+
+
+def _check_intonation(intonation, dev, B, taps, front, N):
+    """What `intonation=` cannot be combined with: `_check_controls`' refusals, before anything is launched."""
+    if not isinstance(intonation, Intonation):
+        raise ValueError("intonation must be a pipeline.Intonation, got %s" % type(intonation).__name__)
+    if front is not None:
+        raise ValueError("intonation cannot be combined with front= (a GraphedFront records no prosody call); use GraphedSynthesis, "
+                         "which reads the tables from static buffers")
+    if _hooks.plan != "engine":
+        raise ValueError("intonation needs the C++ engine plans: the per-kernel Python plans (plan='python') have no twin of the "
+                         "pitch kernel")
+    if dev.type != "cuda" or taps is not None:
+        raise ValueError("intonation needs the C++ engine path (HIP device, no taps)")
+    if intonation.B != B or intonation.device != dev:
+        raise ValueError("intonation describes %d rows on %s, the batch has %d on %s" % (intonation.B, intonation.device, B, dev))
+    if intonation.tok_range is not None and N is not None and intonation.N != N:
+        raise ValueError("intonation holds per-token rows of %d tokens, the batch is %d wide" % (intonation.N, N))
+
+
+def _pitch_shape(intonation, F0, dur, frames=None, sel=None, shift=False):
+    """The rows' range and contour applied in place to the prosody call's F0 curve: one launch -> its `pitch` report [b, 4]."""
+    pick = lambda v: None if v is None else v if sel is None else sel(v).contiguous()
+    tok = pick(intonation.tok_range)
+    return ops.pitch_shape(F0, range=pick(intonation.range), tok_range=tok, dur=None if tok is None else dur.contiguous(),
+                           contour=pick(intonation.contour) if intonation.K else None, frames=frames, shift=shift,
+                           voiced_hz=intonation.voiced_hz, lo_hz=Intonation.LO_HZ, hi_hz=Intonation.HI_HZ, pitch=True)
+
+
 def _check_controls(controls, dev, B, taps, front, durations, N=None):
     """What `controls=` cannot be combined with: refused before anything is launched."""
     if not isinstance(controls, Controls):
@@ -895,7 +1036,7 @@ class GraphedFront:
 def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_steps=5, embedding_scale=1.0,
             ref_s=None, alpha=0.3, beta=0.7, durations=None, step_noise=None, lj_tail=None, s_prev=None, t=0.7,
             taps=None, allow_ragged=False, total_frames=None, lengths_dev=None, front=None, carry=False, group_events=False,
-            ragged_decode=False, max_frames=None, controls=None, fit=None):
+            ragged_decode=False, max_frames=None, controls=None, fit=None, intonation=None):
     """Everything in front of the decoder: text encoder, PL-BERT, style diffusion, style mixing, duration and
     prosody prediction, alignment expansion.  Returns the decoder's inputs {asr, F0, N, ref} plus the mixed style
     vector `s_pred` [B, 256] (what LFinference hands to the next sentence) and the durations.
@@ -948,13 +1089,21 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
     `fit` (with `max_frames`): (targets int32 [B] on the device, hold bool / uint8 [B, N] on the device or
     None) -- the durations, predicted or forced, are rewritten to the targets by ONE launch (`ops.durations_fit`) right in front
     of `ops.frames_from_durations`; the fitted tensor is what the frame counts, the prosody call, the controls' per-token spans
-    and the result's `durations` see, and the result carries the launch's report as `fit` (int32 [B, 4], device)."""
+    and the result's `durations` see, and the result carries the launch's report as `fit` (int32 [B, 4], device).
+
+    `intonation` (an `Intonation`; C++ engine path, no taps, no `front=`): per-row pitch range, per-token
+    range and contour, applied to F0 by ONE launch (`ops.pitch_shape`) right behind every prosody call and in front of the
+    controls' flat pitch scales: the model's own curve is shaped first.  The result carries the launch's report as `pitch` (fp32
+    [B, 4], device: {voiced mean in Hz, voiced columns, lowest, highest F0}), a tensor of its own.  Nothing of it is read on the
+    host; None takes the code paths without it.  A batch split into `groups` carries each group's report in the group."""
     dev = tokens.device
     B, N = tokens.shape
     if max_frames is None:
         _capacity_only("fit_frames / fit_hold", fit)
     if controls is not None:
         _check_controls(controls, dev, B, taps, front, durations, N)
+    if intonation is not None:
+        _check_intonation(intonation, dev, B, taps, front, N)
     if max_frames is not None:
         if int(max_frames) <= 0:
             raise ValueError("max_frames must be a positive frame count, got %r" % (max_frames,))
@@ -998,8 +1147,11 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         channel-major copy where it always did.  hifigan: one-frame right shift, Demo/Inference_LibriTTS.ipynb:306-319."""
         asr, F0_pred, N_pred = _front_engine(model, dev).prosody_forward(sel(d_cm), sel(t_en), dur, sel(s), T, shift=hifigan,
                                                                          frames=frames)
+        shaped = {}
+        if intonation is not None:
+            shaped["pitch"] = _pitch_shape(intonation, F0_pred, dur, frames=frames, sel=sel, shift=hifigan)
         _prosody_controls(controls, F0_pred, N_pred, dur, frames=frames, sel=sel, shift=hifigan)
-        return dict(asr=asr, F0=F0_pred, N=N_pred)
+        return dict(asr=asr, F0=F0_pred, N=N_pred, **shaped)
 
     if max_frames is not None:  # capacity-bound: no host read of the durations, one ragged prosody call at T = max_frames
         T_cap = int(max_frames)
@@ -1055,7 +1207,7 @@ def prepare(model, sampler, tokens, input_lengths=None, noise=None, diffusion_st
         g = expand(list(range(B)))
         if taps is not None:
             taps.update(F0=g["F0"], N=g["N"], asr=g["asr"], en=g["en"])
-        out.update(asr=g["asr"], F0=g["F0"], N=g["N"])
+        out.update(asr=g["asr"], F0=g["F0"], N=g["N"], **({"pitch": g["pitch"]} if "pitch" in g else {}))
         return out
     if not allow_ragged:
         raise ValueError("utterances of one call must have equal total duration; bucket them, pass `durations`, or "
@@ -1148,15 +1300,18 @@ class SynthesisResult:
                nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
                as it was (its held tokens alone exceed the capacity, or a forced total beyond 2^31 - 1).  A small tensor of its
                own, NOT a part of the hand-over allocation: reading it (`result.fit.cpu()`) is a copy of its own.
+      pitch    (with `intonation=`) fp32 [B, 4]: {the row's voiced mean F0 in Hz (geometric), its voiced
+               columns, the lowest and the highest F0 after the range and the contour}; {NaN, 0, NaN, NaN} for a row without a
+               voiced column.  Like `fit` a small tensor of its own.
     `to_host()` is the one place that waits.  Made with `spec` (an `_Output`, trim resolved: `trim`, `pack`, `sample_rate`, `max_gap`)
     and `ho` (the `_HandOver` that `_hand_over` returned for it, None without `pack`: `packed`, `offsets`, `gaps`, `level`)."""
 
-    def __init__(self, wave, frames, max_frames, spec=None, ho=None, marks=None, style=None, fit=None):
+    def __init__(self, wave, frames, max_frames, spec=None, ho=None, marks=None, style=None, fit=None, pitch=None):
         self.wave, self.frames, self.max_frames = wave, frames, int(max_frames)
         self.samples_per_frame = wave.shape[-1] // self.max_frames
         self.spec = spec = _Output() if spec is None else spec
         self.trim, self.pack, self.sample_rate, self.max_gap = int(spec.trim), spec.fmt, _rate(spec.sample_rate), spec.max_gap
-        self.marks, self.style, self.fit = marks, style, fit
+        self.marks, self.style, self.fit, self.pitch = marks, style, fit, pitch
         self._take(ho)
         self._host = None  # the buffer's pinned mirror, allocated by the first to_host()
 
@@ -1538,7 +1693,7 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges
     if spec.trim is None:  # read here and nowhere else: `inference`'s default, Demo/Inference_LibriTTS.ipynb:325 `[..., :-50]`
         spec = spec._replace(trim=50 if hifigan else 0)
     if spec.fmt is None:
-        return SynthesisResult(w, p["frames"], T_cap, spec, style=p["s_pred"], fit=p.get("fit"))
+        return SynthesisResult(w, p["frames"], T_cap, spec, style=p["s_pred"], fit=p.get("fit"), pitch=p.get("pitch"))
     dur = p["durations"]
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
@@ -1561,7 +1716,7 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges
         marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
         marks_of(dur, p["frames"], T_cap, lengths=p.get("token_lengths"), shift=hifigan, trim=spec.trim,
                  rate=spec.sample_rate, samples_per_frame=spf, out=m)
-    return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"], fit=p.get("fit"))
+    return SynthesisResult(w, p["frames"], T_cap, spec, ho, marks=m, style=p["s_pred"], fit=p.get("fit"), pitch=p.get("pitch"))
 
 
 class GraphedSynthesis:
@@ -1630,13 +1785,24 @@ class GraphedSynthesis:
     buffer, `static["dynamics"]` (a `Dynamics`; at first the defaults in every row, or the one given): `__call__(dynamics=)` -- a
     `Dynamics` of B rows -- copies its table into it, so one graph serves any thresholds, ratios, knees and make-up gains;
     `attack_ms` and `release_db_per_s` are the graph's own, fixed at construction.  Without it the graph records exactly what it
-    recorded before."""
+    recorded before.
+
+    `intonation=True` (or an `Intonation`, whose `K` and `voiced_hz` are taken): the graph records the one
+    `ops.pitch_shape` launch over one more static object, `static["intonation"]` (an `Intonation` with every table present and
+    neutral: range 1, no contour point, and -- with `token_controls` or `marks` -- token ranges of 1): `__call__(intonation=)`
+    copies the caller's tables in, a table it lacks and a call without the argument reset to neutral, so one graph serves any
+    ranges and contours; `K` and `voiced_hz` are the graph's own.  The result carries `pitch`.  Without it the graph records
+    exactly what it recorded before and refuses the argument."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
                  token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None,
-                 breaks=None, max_break_ms=None, dynamics=None):
+                 breaks=None, max_break_ms=None, dynamics=None, intonation=None):
         from .diffusion import GraphedSampler
+        if intonation is not None and not isinstance(intonation, (bool, Intonation)):
+            raise ValueError("intonation must be True or a pipeline.Intonation, got %s" % type(intonation).__name__)
+        if isinstance(intonation, Intonation) and intonation.B != B:
+            raise ValueError("intonation must be a pipeline.Intonation of %d rows" % B)
         self.model = model
         self.sampler = sampler.sampler if isinstance(sampler, GraphedSampler) else sampler  # one graph, not two nested
         dev = torch.device(device) if device is not None else next(model.decoder.parameters()).device
@@ -1693,6 +1859,9 @@ class GraphedSynthesis:
         self.static["controls"] = Controls.neutral(B, device=dev, N=N if tok else None)  # NaN weights: the call's own scalars
         self._neutral = self.static["controls"].buf.clone()
         self._neutral_tok = self.static["controls"].tok_buf.clone() if tok else None
+        if intonation is not None and intonation is not False:
+            own = {} if intonation is True else dict(K=intonation.K, voiced_hz=intonation.voiced_hz)
+            self.static["intonation"] = Intonation.neutral(B, N=N if tok else None, device=dev, **own)
         if self.passage:
             starts = torch.zeros((B,), device=dev, dtype=torch.int32)
             starts[:1] = 1
@@ -1720,7 +1889,8 @@ class GraphedSynthesis:
                          **({"fit_frames": st["fit_frames"], "fit_hold": st["fit_hold"]} if "fit_frames" in st else {}),
                          **({"edges": st["edges"]} if "edges" in st else {}),
                          **({"breaks": st["breaks"]} if "breaks" in st else {}),
-                         **({"dynamics": st["dynamics"]} if "dynamics" in st else {}))
+                         **({"dynamics": st["dynamics"]} if "dynamics" in st else {}),
+                         **({"intonation": st["intonation"]} if "intonation" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1734,8 +1904,26 @@ class GraphedSynthesis:
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
                  starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None,
-                 breaks=None, dynamics=None):
+                 breaks=None, dynamics=None, intonation=None):
         st = self.static
+        if intonation is not None and "intonation" not in st:
+            raise ValueError("this graph was built without intonation: pass intonation=True")
+        if "intonation" in st:
+            own = st["intonation"]
+            if intonation is not None:
+                if not isinstance(intonation, Intonation) or intonation.B != own.B:
+                    raise ValueError("intonation must be a pipeline.Intonation of %d rows" % own.B)
+                if (intonation.K, intonation.voiced_hz) != (own.K, own.voiced_hz):
+                    raise ValueError("K and voiced_hz are the graph's own (%r); the Intonation given has %r"
+                                     % ((own.K, own.voiced_hz), (intonation.K, intonation.voiced_hz)))
+                if intonation.tok_range is not None and own.tok_range is None:
+                    raise ValueError("per-token ranges need a graph built with token_controls=True (or marks=True)")
+                if intonation.tok_range is not None and intonation.N != own.N:
+                    raise ValueError("intonation holds per-token rows of %d tokens, this graph's are %d wide" % (intonation.N, own.N))
+            for name, absent in (("range", 1.0), ("contour", float("nan")), ("tok_range", 1.0)):
+                mine, given = getattr(own, name), None if intonation is None else getattr(intonation, name)
+                if mine is not None:
+                    mine.fill_(absent) if given is None else mine.copy_(given, non_blocking=True)
         if fit_frames is not None or fit_hold is not None:
             if "fit_frames" not in st:
                 raise ValueError("this graph was built without fit: pass fit=True")
@@ -1972,7 +2160,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None, dynamics=None):
+              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None, dynamics=None, intonation=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -2071,7 +2259,13 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     device (`ops.wave_dynamics`, behind `breaks` and in front of `level`, so a loudness target holds on the compressed programme
     and the limiter sees compressed peaks).  No sample moves: marks, gaps, resampling and G.711 run unchanged.  The result carries
     {deepest reduction in dB, blocks reduced} as `dynamics`.  Without it the call issues exactly the launches it always did.
+
+    `intonation` (an `Intonation` of B rows; with and without `max_frames`): per-row pitch range, per-token
+    range and pitch contour on the device, see `prepare`; on the capacity-bound path the result carries the report as `pitch`.
+    Without it the call issues exactly the launches it always did.
     """
+    if intonation is not None:
+        _check_intonation(intonation, tokens.device, tokens.shape[0], taps, front, tokens.shape[1])
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
                               passage=passage, **({} if edges is None else {"edges": edges}),
                               **({} if breaks is None else {"breaks": breaks, "N": tokens.shape[1]}),
@@ -2093,6 +2287,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
         kw.update(carry=True, s_prev=s_prev, t=t)
     if fit is not None:
         kw.update(fit=fit)
+    if intonation is not None:
+        kw.update(intonation=intonation)
     seeded = lambda: {} if seeds is None else dict(zip(("noise", "step_noise"), _seeded_front_noise(
         seeds, tokens.shape[0], diffusion_steps, tokens.device)))  # drawn on the stream the front reads them on
     if front_stream is None:
@@ -2181,7 +2377,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     embedding_scale=1.0, noises=None, step_noises=None, sine_noises=None, durations=None, trim=None,
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
-                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None, dynamics=None):
+                    max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None, dynamics=None,
+                    intonation=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -2249,8 +2446,13 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     (`inference(breaks=)`).
     `dynamics` (needs `max_frames` and `pack`): a `Dynamics` of one row per SENTENCE: the compressor over every
     sentence (`inference(dynamics=)`).
+    `intonation` (with and without `max_frames`): an `Intonation` of one row per SENTENCE, sliced per front
+    group: every sentence's own pitch range and contour (`prepare(intonation=)`).  Its per-token ranges are served with
+    `max_frames` only, under the rule of the per-token controls: N is the longest sentence's token count.
     """
     dev = sentences[0].device
+    if intonation is not None and (not isinstance(intonation, Intonation) or intonation.B != len(sentences)):
+        raise ValueError("intonation must be a pipeline.Intonation of one row per sentence (%d)" % len(sentences))
     if controls is not None and (not isinstance(controls, Controls) or controls.B != len(sentences)):
         raise ValueError("controls must be a pipeline.Controls of one row per sentence (%d)" % len(sentences))
     if max_frames is not None:
@@ -2259,7 +2461,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks, dynamics=dynamics)
+            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks, dynamics=dynamics, intonation=intonation)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     _capacity_only("edges", edges)
     _capacity_only("breaks", breaks)
@@ -2268,6 +2470,10 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
         raise ValueError("per-token controls are not served on the long-form path (sentences differ in width)")
+    if intonation is not None:
+        if intonation.tok_range is not None:
+            raise ValueError("per-token ranges are not served on the long-form path (sentences differ in width): pass max_frames")
+        _check_intonation(intonation, dev, len(sentences), None, front, None)
     multispeaker = ref_s is not None
     if trim is None:
         trim = 100 if multispeaker else 0
@@ -2312,7 +2518,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                   embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta, lj_tail=False, s_prev=s_prev, t=t,
                   step_noise=q["step_noise"], durations=q["dur"], total_frames=q["frames"], lengths_dev=q["lens_dev"],
                   front=front, carry=len(ids) > 1, allow_ragged=True, group_events=use_streams and len(ids) > 1,
-                  ragged_decode=ragged_decode, controls=None if controls is None else controls.slice(ids[0], ids[-1] + 1))
+                  ragged_decode=ragged_decode, controls=None if controls is None else controls.slice(ids[0], ids[-1] + 1),
+                  **({} if intonation is None else {"intonation": intonation.slice(ids[0], ids[-1] + 1)}))
         if use_streams:
             with torch.cuda.stream(side):
                 p = prepare(model, sampler, q["tokens"], **kw)
@@ -2345,7 +2552,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
                               controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None,
-                              breaks=None, dynamics=None):
+                              breaks=None, dynamics=None, intonation=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -2364,6 +2571,9 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
         trim = 100 if ref_s is not None else 0
     ns_all = [s.numel() for s in sentences]
     tok_ctl = controls is not None and controls.tok_buf is not None or breaks is not None  # rows as wide as the longest sentence
+    if intonation is not None:
+        _check_intonation(intonation, dev, K, None, front, max(ns_all) if intonation.tok_range is not None else None)
+        tok_ctl = tok_ctl or intonation.tok_range is not None
     if tok_ctl and controls is not None and controls.tok_buf is not None and controls.N != max(ns_all):
         raise ValueError("controls hold per-token rows of %d tokens, the longest sentence has %d" % (controls.N, max(ns_all)))
     # the K sentences' output, judged once (a `max_gap` without `gaps` is not looked at, as ever); every group's slice is, again
@@ -2396,6 +2606,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
             more.update(breaks=breaks.slice(i, j))
         if dynamics is not None:
             more.update(dynamics=dynamics.slice(i, j))
+        if intonation is not None:
+            more.update(intonation=intonation.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
