@@ -901,6 +901,53 @@ int st2_wave_dynamics(const float* wave, int64_t w_bs, const int32_t* frames, in
                       const float* win /* fp32 [2 A + 1], device */, double rho, float* out, int64_t o_bs,
                       float* dyn /* fp32 [B][2], device */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- volume: per-request and per-token gain envelopes in the hand-over (added under ABI 23, additive: one kernel-level entry
+ * point and one helper, no new backend-table slot, no struct change, no new sticky status bit) --------- *
+ * st2_wave_volume: SSML's <prosody volume=> and the loudness of <emphasis> -- one gain in dB per row and one per token, smoothed
+ * on the 64-sample grid and applied as st2_wave_dynamics applies its gain.  It takes st2_wave_edges's geometry (wave, w_bs,
+ * frames, B, T_cap, samples_per_frame, trim) and, on the device and read by the kernels:
+ *   pos      int32 [B][N + 1]: the tokens' boundaries in samples of THIS row, not decreasing (what st2_wave_breaks is given, or
+ *            st2_token_marks_breaks's marks at up = down = 1 for rows that entry spliced silence into); N in 1..512;
+ *   lengths  int32 [B] or NULL: the rows' token counts, Nb = clamp(lengths[b], 0, N); NULL = N;
+ *   db       fp32 [B] or NULL: row b's gain in dB;       tok_db  fp32 [B][N] or NULL: token n's gain in dB, on top of the row's.
+ * Host numbers: the half window A in blocks of 64 samples, 0..64, and win fp32 [2 A + 1] on the device (the limiter's window,
+ * non-negative weights that sum to 1); win is NULL if and only if A = 0.  It writes `out` (fp32, row stride o_bs, not overlapping
+ * wave), vol fp32 [B][2] and the workspace.  With n = n_b the row's valid samples (st2_wave_level's rule 1) and K = ceil(n / 64):
+ *  1. Cleaning.  clean(v) = 0 for a NaN, else min(max(v, -60), +20), in fp32: -inf is -60, +inf is +20.  A NULL table is 0.
+ *  2. Wanted gain per block.  For block k, c = min(64 k + 32, n - 1); idx is the largest i in [0, Nb) with pos[b][i] <= c, or 0
+ *     if there is none (a binary search: where pos decreases, whichever of its candidates the search meets) -- so a token of no
+ *     samples is skipped, and of several boundaries at one sample the last token owns what follows.  d[k] =
+ *     min(max((double)clean(db[b]) + (double)clean(tok_db[b][idx]), -60), +20); with Nb = 0 the token term is 0.
+ *  3. Smoothing, fp64: acc = 0; for j = -A .. A in order acc = acc + fl64((double)win[j + A] * (d[clamp(k + j, 0, K - 1)] -
+ *     d[k])); e[k] = d[k] + acc.  A stretch of equal d wider than the window gives e = d exactly, d = 0 all around e = 0.
+ *  4. Gain per block.  lin[k] = 0.0f where e[k] <= -60 (SSML's "silent"), else fl32(10^(e[k] / 20)), pow in fp64, rounded once;
+ *     e = 0 gives exactly 1.0f.
+ *  5. Gain per sample: st2_wave_dynamics's rule 8, bit for bit -- linear between the block centres 64 k + 31.5, block indices
+ *     clamped to [0, K - 1], gain = fmaf(t, lin[ka + 1] - lin[ka], lin[ka]) with t = (2 (i - 64 ka) - 63) / 128, out[i] =
+ *     fl32(x[i] * gain) with x itself.
+ *  6. Kept words.  Samples 4 v .. 4 v + 3 of a row lie between the same two block centres; where both of those gains are exactly
+ *     1.0f the samples are moved as 32-bit words, NaN payloads as they are.  Every 0 dB stretch of a row keeps its bits, and
+ *     a call whose tables are all 0 (or NULL) is a bit copy of the valid samples.
+ *  7. Nothing at or past out[b][n] is written.
+ *  8. Report.  vol[b] = {max |out[b][i]| over i < n with a NaN ignored as by fmaxf, 0 for an empty row; the number of k < K with
+ *     lin[k] != 1.0f, as fp32}: a maximum and a count of integers, so no bit depends on how the reduction is cut, and a row's
+ *     output and its two numbers depend neither on the tiling nor on the row's place in the batch.
+ * Everything is fixed but the last ulp of pow.
+ * `workspace` (float-aligned, st2_wave_volume_workspace_bytes(B, T_cap, samples_per_frame) bytes; 0 for an argument <= 0) begins
+ * with lin fp32 [B][Kcap], Kcap = ceil(samples_per_frame T_cap / 64) (entries at or past a row's K are not written); the
+ * partials of the report follow.  Three launches (gains per (256 blocks, row); apply per (4096 samples, row); the report per
+ * row), no atomics, no allocation, no synchronisation, no host read: legal under stream capture.
+ * Returns non-zero before any launch on every refusal of st2_wave_dynamics about the geometry, out, the workspace and the window
+ * (NULL wave / frames, bad B / T_cap / samples_per_frame, trim < 0, a row too long for int32, w_bs or o_bs too small, A outside
+ * 0..64, win NULL with A > 0, out overlapping wave, a workspace that is too small) and on: win given with A = 0; NULL pos / out /
+ * vol / workspace; N outside 1..512; a pointer that is not aligned to 4 bytes. */
+int64_t st2_wave_volume_workspace_bytes(int32_t B, int32_t T_cap, int32_t samples_per_frame);
+int st2_wave_volume(const float* wave, int64_t w_bs, const int32_t* frames, int32_t B, int32_t T_cap, int32_t samples_per_frame,
+                    int32_t trim, const int32_t* pos /* int32 [B][N + 1], device */, const int32_t* lengths /* int32 [B] or NULL */,
+                    int32_t N, const float* db /* fp32 [B] or NULL, device */, const float* tok_db /* fp32 [B][N] or NULL, device */,
+                    int32_t A, const float* win /* fp32 [2 A + 1], device */, float* out, int64_t o_bs,
+                    float* vol /* fp32 [B][2], device */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- per-request seeds: counter-based noise drawn on the device (added under ABI 23, additive: one kernel-level entry point,
  * no new backend-table slot, no struct change, no new sticky status bit) ----------------------------- *
  * st2_noise_fill: the model's randomness -- the sampler's start noise, its per-step draws, the harmonic source's draws -- from one

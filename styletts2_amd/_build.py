@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libst2_hip.so")
 SOURCES = ["st2_api.hip", "st2_conv1d.hip", "st2_conv1d_f16s.hip", "st2_conv1d_f16s_k0.hip", "st2_conv1d_f16s_k1.hip",
            "st2_conv1d_f16s_k2.hip", "st2_conv1d_f16s_w0.hip", "st2_conv1d_f16s_w1.hip", "st2_conv1d_f16s_w2.hip",
            "st2_conv1d_xs.hip", "st2_conv1d_xs_k0.hip", "st2_conv1d_xs_k1.hip",
-           "st2_conv1d_xs_k2.hip", "st2_conv1d_xs_k3.hip", "st2_actsplit.hip", "st2_norm.hip", "st2_misc.hip", "st2_glue.hip", "st2_pack.hip", "st2_resample.hip", "st2_passage.hip", "st2_level.hip", "st2_limit.hip", "st2_edges.hip", "st2_breaks.hip", "st2_dynamics.hip", "st2_rng.hip", "st2_fit.hip", "st2_ingest.hip", "st2_controls.hip", "st2_marks.hip", "st2_intonation.hip", "st2_style.hip", "st2_engine.hip", "st2_source.hip", "st2_attention.hip", "st2_lstm.hip", "st2_lstm_coop.hip", "st2_probe.hip", "st2_probe_conv.hip"]
+           "st2_conv1d_xs_k2.hip", "st2_conv1d_xs_k3.hip", "st2_actsplit.hip", "st2_norm.hip", "st2_misc.hip", "st2_glue.hip", "st2_pack.hip", "st2_resample.hip", "st2_passage.hip", "st2_level.hip", "st2_limit.hip", "st2_edges.hip", "st2_breaks.hip", "st2_dynamics.hip", "st2_volume.hip", "st2_rng.hip", "st2_fit.hip", "st2_ingest.hip", "st2_controls.hip", "st2_marks.hip", "st2_intonation.hip", "st2_style.hip", "st2_engine.hip", "st2_source.hip", "st2_attention.hip", "st2_lstm.hip", "st2_lstm_coop.hip", "st2_probe.hip", "st2_probe_conv.hip"]
 # -ffp-contract=off: the SineGen phase path must reproduce ATen-CPU rounding (no implicit FMA);
 # fused multiply-adds are written explicitly (fmaf) where wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
@@ -47,6 +47,8 @@ EXTRA_FLAGS.update({"st2_breaks.hip": ["-fno-slp-vectorize"]})
 # st2_dynamics.hip launches st2_breaks.hip's block sums (st2_blocksums.h) and must run them as that unit does; its gain is four
 # fmaf and four products to a lane over two shared LDS words, pairs of which could be that encoding again.
 EXTRA_FLAGS.update({"st2_dynamics.hip": ["-fno-slp-vectorize"]})
+# st2_volume.hip's apply launch is st2_dynamics.hip's: four fmaf and four products to a lane over two shared LDS words.
+EXTRA_FLAGS.update({"st2_volume.hip": ["-fno-slp-vectorize"]})
 # st2_intonation.hip shapes the two columns of a frame side by side in fp64 and takes their fp32 minimum and maximum: nothing
 # there gains from packing, and a pair of fp32 results in odd registers could be that encoding once more.
 EXTRA_FLAGS.update({"st2_intonation.hip": ["-fno-slp-vectorize"]})

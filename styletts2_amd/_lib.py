@@ -298,6 +298,9 @@ _SIGNATURES = {
     "st2_wave_dynamics_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "st2_wave_dynamics": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int32, f32p,
                                     C.c_double, f32p, C.c_int64, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "st2_wave_volume_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "st2_wave_volume": (C.c_int, [f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_int32, f32p, f32p, C.c_int32, f32p, f32p, C.c_int64, f32p, C.c_void_p, C.c_int64, C.c_void_p]),
     "st2_token_marks_breaks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "st2_noise_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.c_int64, C.c_int64, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_void_p]),

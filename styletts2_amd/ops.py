@@ -1709,6 +1709,75 @@ def wave_dynamics(wave, frames, params, win, *, A, rho, trim=0, samples_per_fram
     return out, dynamics
 
 
+VOLUME_BLOCK = 64  # the grid of the volume envelope (st2_wave_breaks's blocks)
+VOLUME_TILE = 4096  # the samples of a tile of the apply launch (tests place row ends at its edges)
+VOLUME_DB = (-60.0, 20.0)  # what the kernels clamp a gain in dB to; at or under the lower end a block is silent
+
+
+def wave_volume_workspace_bytes(B, T_cap, samples_per_frame=600):
+    """`st2_wave_volume_workspace_bytes`: what `wave_volume(workspace=)` needs, in bytes.  The workspace begins with the gains per
+    block `lin` as fp32 [B, Kcap], Kcap = ceil(samples_per_frame T_cap / 64)."""
+    return int(_lib.load().st2_wave_volume_workspace_bytes(int(B), int(T_cap), int(samples_per_frame)))
+
+
+def wave_volume(wave, frames, pos, db, tok_db, win, *, A, lengths=None, trim=0, samples_per_frame=600, out=None, volume=None,
+                workspace=None):
+    """`st2_wave_volume`: one gain in dB per row and one per token, smoothed and applied on the device.
+    wave, frames, trim and samples_per_frame as `wave_edges` takes them; pos int32 [B, N + 1] on the device (the tokens'
+    boundaries in samples of this row: what `wave_breaks` is given, or `token_marks_breaks` without a rate behind it); `db` fp32
+    [B] and `tok_db` fp32 [B, N] on the device, either may be None (NaN = 0 dB; clamped to `VOLUME_DB`; -60 = silent); `lengths`
+    int32 [B] on the device or None; `A` the half window of the ramp in blocks of 64 samples, 0..64, with `win` fp32 [2 A + 1] on
+    the device (`resample.limit_window(A, device)`; None if and only if A = 0) -> (out, vol): `out` fp32 [B, L] (by default with
+    the row stride of wave) -- every valid sample times the gain the contract of include/st2.h states, a stretch at 0 dB bit for
+    bit; samples at or past a row's end are not written -- and `vol` fp32 [B, 2] = {the peak of the row's output, the number of
+    64-sample blocks whose gain is not 1}.  `workspace`: a uint8 device tensor of `wave_volume_workspace_bytes` bytes (by default
+    from the caching allocator).  No host read; legal under stream capture."""
+    lp = _chk_len(frames, "frames", wave.shape[0] if torch.is_tensor(wave) and wave.dim() in (2, 3) else -1, wave)
+    _chk(wave, "wave")
+    if wave.dim() == 3 and wave.shape[1] == 1:
+        wave = wave[:, 0]
+    _chk(wave, "wave", 2)
+    B, L = wave.shape
+    spf, A = int(samples_per_frame), int(A)
+    if spf <= 0 or L < spf or L % spf:
+        raise _lib.St2Error("wave rows of %d samples are not a whole number of %d-sample frames" % (L, spf))
+    _chk_dev(pos, "pos", torch.int32, 2)
+    N = pos.shape[1] - 1
+    if pos.shape[0] != B or N < 1 or pos.device != wave.device:
+        raise _lib.St2Error("pos must be [%d, N + 1] on the device of wave (got %s on %s)" % (B, tuple(pos.shape), pos.device))
+    np_ = _chk_len(lengths, "lengths", B, wave)
+    for t, name, shape in ((db, "db", (B,)), (tok_db, "tok_db", (B, N))):
+        if t is None:
+            continue
+        _chk_dev(t, name, torch.float32, len(shape))
+        if tuple(t.shape) != shape or t.device != wave.device:
+            raise _lib.St2Error("%s must be %s on the device of wave (got %s on %s)" % (name, list(shape), tuple(t.shape), t.device))
+    if (win is None) != (A == 0):
+        raise _lib.St2Error("win must be None with A = 0 and 2 A + 1 weights otherwise")
+    if win is not None:
+        _chk_dev(win, "win", torch.float32, 1)
+        if win.numel() != 2 * A + 1 or win.device != wave.device:
+            raise _lib.St2Error("win must hold 2 A + 1 = %d weights on the device of wave (got %d on %s)" % (2 * A + 1, win.numel(), win.device))
+    if out is None:
+        out = torch.empty_strided((B, L), (wave.stride(0), 1), device=wave.device, dtype=torch.float32)
+    _chk(out, "out", 2)
+    if tuple(out.shape) != (B, L) or out.device != wave.device:
+        raise _lib.St2Error("out must be [%d, %d] on the device of wave (got %s on %s)" % (B, L, tuple(out.shape), out.device))
+    if volume is None:
+        volume = torch.empty((B, 2), device=wave.device, dtype=torch.float32)
+    _chk_dev(volume, "volume", torch.float32, volume.dim() if torch.is_tensor(volume) else 2)
+    if volume.numel() != 2 * B or volume.device != wave.device:
+        raise _lib.St2Error("volume must hold [%d, 2] values on the device of wave" % B)
+    need = wave_volume_workspace_bytes(B, L // spf, spf)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), device=wave.device, dtype=torch.uint8)
+    _chk_dev(workspace, "workspace", torch.uint8, 1)
+    _lib.check(_lib.load().st2_wave_volume(wave.data_ptr(), wave.stride(0), lp, B, L // spf, spf, int(trim), pos.data_ptr(), np_, N,
+                                           _ptr(db), _ptr(tok_db), A, _ptr(win), out.data_ptr(), out.stride(0), volume.data_ptr(),
+                                           workspace.data_ptr(), workspace.numel(), _stream()), "st2_wave_volume")
+    return out, volume
+
+
 NOISE_SAMPLER, NOISE_STEP, NOISE_SINE = _lib.NOISE_SAMPLER, _lib.NOISE_STEP, _lib.NOISE_SINE  # st2.h ST2_NOISE_*
 
 

@@ -635,6 +635,134 @@ class Dynamics:
         return dict(attack_ms=self.attack_ms, release_db_per_s=self.release_db_per_s)
 
 
+class Volume:
+    """A request's volume (include/st2.h `st2_wave_volume`): SSML's `<prosody volume=>` and the loudness
+    part of `<emphasis>` -- one gain in dB per row and one per token on top of it, applied on the device to the rows of the packed
+    hand-over behind `dynamics` and in front of `level`: a compressor does not undo an emphasis, a loudness target holds on the
+    programme as voiced and the limiter sees the boosted peaks.
+
+        db        the row's gain in dB: a float, B values or a device tensor [B]; None = no table            [-60, +20]
+        tok_db    token n's gain in dB on top of the row's (the sum is kept inside the same range): a float, a [B, N] array
+                  or a device tensor; None = no table (with `N`: a table of zeros)                            [-60, +20]
+        ramp_ms   the half width of the ramp between two gains: A = round(ramp_ms * 24 / 64) blocks of 64 samples, 0..64;
+                  0 = the bare linear interpolation between block centres, 2.7 ms                              [0, 170]
+
+    -60 dB, or `float("-inf")`, is SSML's `silent`: exact zeros.  A stretch at 0 dB keeps its bits.  Host values are validated
+    here (ValueError: no NaN, inside the range); a tensor already on the device is never read: the kernel cleans it (NaN = 0 dB,
+    clamped to the range).  Each table is one fp32 device tensor made by ONE host -> device copy.
+
+    With `Level(scope="row")` a row's `db` is cancelled by the normalisation -- the level is measured behind this stage -- and the
+    differences between tokens survive; with `scope="passage"` a quiet sentence stays quiet beside its neighbours."""
+    RANGE = ops.VOLUME_DB
+
+    def __init__(self, B, N=None, db=None, tok_db=None, ramp_ms=8.0, device=None):
+        B, ramp_ms = int(B), float(ramp_ms)
+        if B <= 0:
+            raise ValueError("Volume: B must be positive, got %r" % (B,))
+        if not 0.0 <= ramp_ms <= 170.0:  # NaN: refused
+            raise ValueError("Volume: ramp_ms must lie in [0, 170], got %r" % (ramp_ms,))
+        if device is None:
+            on_dev = [v for v in (db, tok_db) if torch.is_tensor(v) and v.is_cuda]
+            device = on_dev[0].device if on_dev else ("cuda" if torch.cuda.is_available() else "cpu")
+        if N is None and tok_db is not None:
+            shape = tuple(tok_db.shape) if torch.is_tensor(tok_db) else tuple(torch.as_tensor(tok_db).shape)
+            if len(shape) != 2:
+                raise ValueError("Volume: tok_db needs N (the batch's token width) or a [B, N] array")
+            N = shape[1]
+        if N is not None and not 0 < int(N) <= 512:
+            raise ValueError("Volume: N must lie in 1..512, got %r" % (N,))
+        self.B, self.N, self.ramp_ms = B, None if N is None else int(N), ramp_ms
+        if not 0 <= self.A <= 64:
+            raise ValueError("Volume: ramp_ms=%r is a half window of %d blocks, outside 0..64" % (ramp_ms, self.A))
+        self.device = torch.empty(0, device=device).device  # with its index, as a tensor's
+        self.db = self._rows("db", db, (B,), device)
+        self.tok_db = None if self.N is None else self._rows("tok_db", 0.0 if tok_db is None else tok_db, (B, self.N), device)
+
+    @property
+    def A(self):
+        """The half window of the ramp in blocks of `ops.VOLUME_BLOCK` samples."""
+        return int(round(self.ramp_ms * (resample.MODEL_RATE / 1000.0) / ops.VOLUME_BLOCK))
+
+    @staticmethod
+    def _rows(name, v, shape, device):
+        """`db` ([B]) or `tok_db` ([B, N]) as its fp32 device tensor; None stays None."""
+        if v is None:
+            return None
+        dims = "%d" % shape if len(shape) == 1 else "[%d, %d]" % shape
+        if torch.is_tensor(v) and v.is_cuda:  # never read: cleaned where the kernel reads it
+            if (v.numel() != shape[0]) if len(shape) == 1 else (tuple(v.shape) != shape):
+                raise ValueError("Volume: %s must hold %s values, got shape %s" % (name, dims, tuple(v.shape)))
+            return v.detach().reshape(shape).to(device=device, dtype=torch.float32).contiguous()
+        try:
+            rows = torch.as_tensor(v, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("Volume: %s must be numbers, got %r" % (name, v)) from None
+        if len(shape) == 1:
+            rows = rows.reshape(-1)
+        if rows.numel() == 1:
+            rows = rows.reshape((1,) * len(shape)).expand(shape)
+        if tuple(rows.shape) != shape:
+            raise ValueError("Volume: %s must be one value or %s values, got shape %s" % (name, dims, tuple(rows.shape)))
+        lo, hi = Volume.RANGE
+        if not bool((((rows >= lo) & (rows <= hi)) | (rows == float("-inf"))).all()):
+            raise ValueError("Volume: %s must lie in [%g, %g] dB (-inf = silent)%s" % (name, lo, hi, ", got %s" % rows.tolist()
+                                                                                     if len(shape) == 1 else ""))
+        return rows.to(torch.float32).contiguous().to(device)  # ONE host -> device copy
+
+    @classmethod
+    def neutral(cls, B, N=None, ramp_ms=8.0, device=None):
+        """Every table present and 0 dB (with `N` the per-token one too).  Equals the call without the object bit for bit."""
+        return cls(B, N=N, db=0.0, tok_db=None if N is None else 0.0, ramp_ms=ramp_ms, device=device)
+
+    def slice(self, i, j):
+        """Rows i .. j-1 as a Volume over the same memory (long-form: a front group's sentences)."""
+        c = object.__new__(Volume)
+        c.B, c.N, c.ramp_ms, c.device = j - i, self.N, self.ramp_ms, self.device
+        c.db, c.tok_db = (None if v is None else v[i:j] for v in (self.db, self.tok_db))
+        return c
+
+    def options(self):
+        """The one time of this Volume, as its constructor takes it (what a copy over other rows is made with)."""
+        return dict(ramp_ms=self.ramp_ms)
+
+
+# What an engine does for SSML's <emphasis level=>: (speaking rate, pitch scale, pitch range, gain in dB) on the span.  Defaults of
+# taste, not measurements: `emphasis_tables(presets=)` takes a replacement.
+EMPHASIS_PRESETS = {"strong": (0.90, 1.06, 1.3, 3.0), "moderate": (0.95, 1.03, 1.15, 1.5), "none": (1.0, 1.0, 1.0, 0.0),
+                    "reduced": (1.05, 0.98, 0.8, -3.0)}
+
+
+def emphasis_tables(B, N, spans, presets=None):
+    """SSML's `<emphasis>` as the per-token tables of a batch of B rows of N tokens (host only).  `spans`:
+    a list of (row, first_token, last_token, level), both tokens included, `level` one of "strong", "moderate", "none" and
+    "reduced"; where spans overlap the later one wins ("none" puts its tokens back to neutral).  -> a dict of float32 [B, N] numpy
+    arrays, neutral outside the spans: `tok_speed` and `tok_f0_scale` for `Controls`, `tok_range` for `Intonation`, `tok_db` for
+    `Volume`.  `presets`: level -> (speed, pitch scale, range, dB) instead of `EMPHASIS_PRESETS`, whose numbers are defaults of
+    taste, not measurements -- a voice may want others."""
+    import numpy as np
+    presets = EMPHASIS_PRESETS if presets is None else presets
+    B, N = int(B), int(N)
+    if B <= 0 or N <= 0:
+        raise ValueError("emphasis_tables: B and N must be positive, got %r and %r" % (B, N))
+    names = ("tok_speed", "tok_f0_scale", "tok_range", "tok_db")
+    out = {name: np.full((B, N), neutral, dtype=np.float32) for name, neutral in zip(names, (1.0, 1.0, 1.0, 0.0))}
+    for span in spans:
+        if not isinstance(span, (list, tuple)) or len(span) != 4:
+            raise ValueError("emphasis_tables: a span is (row, first_token, last_token, level), got %r" % (span,))
+        b, first, last, level = span
+        if level not in presets:
+            raise ValueError("emphasis_tables: level must be one of %s, got %r" % (sorted(presets), level))
+        b, first, last = int(b), int(first), int(last)
+        if not (0 <= b < B and 0 <= first <= last < N):
+            raise ValueError("emphasis_tables: span %r lies outside %d rows of %d tokens" % (span, B, N))
+        values = presets[level]
+        if len(values) != 4:
+            raise ValueError("emphasis_tables: a preset is (speed, pitch scale, range, dB), got %r" % (values,))
+        for name, v in zip(names, values):
+            out[name][b, first:last + 1] = v
+    return out
+
+
 class Intonation:
     """A request's intonation (include/st2.h `st2_pitch_shape`): SSML's `<prosody range= contour=>`, applied
     on the device to the prosody predictor's F0 curve around every row's own voiced mean, in front of the flat pitch scales of
@@ -1295,6 +1423,8 @@ class SynthesisResult:
       dynamics (with `dynamics=`) float32 [B, 2]: {the deepest gain reduction in dB, the number of 64-sample
                blocks that were reduced}; {0, 0} for a row left alone.  Kept in the same allocation: `to_host(dynamics=True)` is
                still one copy.
+      volume   (with `volume=`) float32 [B, 2]: {the peak of the row behind the gains, the number of
+               64-sample blocks whose gain is not 1}.  Kept in the same allocation: `to_host(volume=True)` is still one copy.
       fit      (with `fit_frames=`) int32 [B, 4]: {the row's frames before the fit, its frames after,
                flag, the number of tokens whose duration changed}; flag 0 = the target was met, 1 = it was infeasible and the
                nearest feasible total was taken, 2 = nothing to stretch (no token, or every token held), 3 = the row was left
@@ -1324,8 +1454,10 @@ class SynthesisResult:
         self.edges = None if ho is None or ho.edges is None else ho.edges.view(-1, 2)
         self.breaks = None if ho is None or ho.breaks is None else ho.breaks.view(-1, 2)
         self.dynamics = None if ho is None or ho.dynamics is None else ho.dynamics.view(-1, 2)
+        self.volume = None if ho is None or ho.volume is None else ho.volume.view(-1, 2)
 
-    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False, breaks=False, dynamics=False):
+    def to_host(self, marks=False, passage=False, level=False, limit=False, edges=False, breaks=False, dynamics=False,
+                volume=False):
         """The list of per-utterance 1-D numpy arrays (int16 for "s16", uint8 for "ulaw" / "alaw", else float32; `trim` applied,
         at `sample_rate`): ONE device -> host copy
         into pinned memory of the offsets and the samples together, then one wait for it, then `ops.check_status()` -- the
@@ -1344,7 +1476,10 @@ class SynthesisResult:
         array, out of the same copy, behind those.  `breaks=True` (a result made with `breaks=`): {the row's samples with its pauses,
         the silence inserted} at the model rate as an int32 [B, 2] numpy array, out of the same copy, behind those.  `dynamics=True` (a
         result made with `dynamics=`): {deepest reduction in dB, blocks reduced} per row as a float32 [B, 2] numpy array, out of the
-        same copy, last."""
+        same copy, behind those.  `volume=True` (a result made with `volume=`): {peak, blocks with a gain} per row as a float32 [B, 2]
+        numpy array, out of the same copy, last."""
+        if volume and self.volume is None:
+            raise ValueError("this result carries no volume table: ask for it with inference(..., volume=Volume(...))")
         if dynamics and self.dynamics is None:
             raise ValueError("this result carries no dynamics table: ask for it with inference(..., dynamics=Dynamics(...))")
         if breaks and self.breaks is None:
@@ -1385,6 +1520,8 @@ class SynthesisResult:
             more += (self._ho.breaks_view(self._host).numpy().reshape(B, 2),)
         if dynamics:
             more += (self._ho.dynamics_view(self._host).numpy().reshape(B, 2),)
+        if volume:
+            more += (self._ho.volume_view(self._host).numpy().reshape(B, 2),)
         return (rows,) + more if more else rows
 
 
@@ -1444,16 +1581,17 @@ class _HandOver:
     """The layout of the ONE allocation of the hand-over, stated here and nowhere else:
 
         [offsets int64 [B + 1] | marks int32 [n_marks] | gaps int32 [B] | level float32 [4 B] | limit float32 [2 B] |
-         edges int32 [2 B] | breaks int32 [2 B] | dynamics float32 [2 B] | pad to 16 bytes | samples of `fmt`]
+         edges int32 [2 B] | breaks int32 [2 B] | dynamics float32 [2 B] | volume float32 [2 B] | pad to 16 bytes |
+         samples of `fmt`]
 
-    with `n_marks` = 0 / no gaps / no level / no limit / no edges / no breaks / no dynamics the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
-    nine parts (`samples_at` is the header's size); `views(buf)` gives the first four parts and the samples of a byte buffer of
-    this layout, on the device or its pinned mirror, `limit_view`, `edges_view`, `breaks_view` and `dynamics_view` the later
+    with `n_marks` = 0 / no gaps / no level / no limit / no edges / no breaks / no dynamics / no volume the layout is the one without them, byte for byte.  `*_at` are the byte offsets of the
+    ten parts (`samples_at` is the header's size); `views(buf)` gives the first four parts and the samples of a byte buffer of
+    this layout, on the device or its pinned mirror, `limit_view`, `edges_view`, `breaks_view`, `dynamics_view` and `volume_view` the later
     ones; `allocate` makes the device buffer, after which `buf`, `offsets`, `marks`, `gaps`, `level`, `limit`, `edges`, `breaks`,
-    `dynamics` and `packed` are the buffer and its views (None for a part the layout does not have)."""
+    `dynamics`, `volume` and `packed` are the buffer and its views (None for a part the layout does not have)."""
 
     def __init__(self, B, fmt, n_marks=0, with_gaps=False, with_level=False, with_limit=False, with_edges=False, with_breaks=False,
-                 with_dynamics=False):
+                 with_dynamics=False, with_volume=False):
         self.B, self.n_marks, self.with_gaps, self.dtype = int(B), int(n_marks), bool(with_gaps), ops.OUTPUT_FORMATS[fmt][1]
         self.with_level, self.with_limit, self.with_edges = bool(with_level), bool(with_limit), bool(with_edges)
         self.with_breaks = bool(with_breaks)
@@ -1466,9 +1604,11 @@ class _HandOver:
         self.breaks_at = self.edges_at + (8 * self.B if self.with_edges else 0)
         self.with_dynamics = bool(with_dynamics)
         self.dynamics_at = self.breaks_at + (8 * self.B if self.with_breaks else 0)
-        self.samples_at = (self.dynamics_at + (8 * self.B if self.with_dynamics else 0) + 15) // 16 * 16
+        self.with_volume = bool(with_volume)
+        self.volume_at = self.dynamics_at + (8 * self.B if self.with_dynamics else 0)
+        self.samples_at = (self.volume_at + (8 * self.B if self.with_volume else 0) + 15) // 16 * 16
         self.buf = self.offsets = self.marks = self.gaps = self.packed = self.level = self.limit = self.edges = self.breaks = None
-        self.dynamics = None
+        self.dynamics = self.volume = None
 
     def limit_view(self, buf):
         """The sixth part, float32 [2 B] (`ops.wave_limit`'s {g', min q} per row), of a uint8 buffer of this
@@ -1490,6 +1630,11 @@ class _HandOver:
         of a uint8 buffer of this layout, or None.  Apart from `views`, as `limit_view` is."""
         return buf[self.dynamics_at:self.dynamics_at + 8 * self.B].view(torch.float32) if self.with_dynamics else None
 
+    def volume_view(self, buf):
+        """The tenth part, float32 [2 B] (`ops.wave_volume`'s {peak, blocks with a gain} per row), of a uint8
+        buffer of this layout, or None.  Apart from `views`, as `limit_view` is."""
+        return buf[self.volume_at:self.volume_at + 8 * self.B].view(torch.float32) if self.with_volume else None
+
     def views(self, buf):
         """-> (offsets int64 [B + 1], marks int32 [n_marks] or None, gaps int32 [B] or None, samples, level float32 [4 B] or
         None) of a uint8 buffer: the parts the layout began with.  The later parts have a view function each."""
@@ -1505,6 +1650,7 @@ class _HandOver:
         self.edges = self.edges_view(self.buf)
         self.breaks = self.breaks_view(self.buf)
         self.dynamics = self.dynamics_view(self.buf)
+        self.volume = self.volume_view(self.buf)
         return self
 
 
@@ -1526,7 +1672,8 @@ def _capacity_only(names, *given):
 
 
 def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=False, gaps=None, max_gap=None, level=None, graph=False,
-                 passage=None, front_groups=1, edges=None, breaks=None, N=None, dynamics=None):
+                 passage=None, front_groups=1, edges=None, breaks=None, N=None, dynamics=None, volume=None,
+                 device=None):
     """The seven output options of a call of B rows -> (`_Output`, `gaps` as an int32 [B] tensor, host or device as given), and
     every refusal about them, for `inference`, `synthesize_long(max_frames=)` and `GraphedSynthesis` alike, before anything is
     launched: `pack` one of `ops.OUTPUT_FORMATS` or None; `sample_rate` one of `resample.RATES` or None; `level` a `Level` of the
@@ -1537,7 +1684,8 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
     call's `passage`, and `front_groups`: the front calls `synthesize_long` cuts the passage into -- what a `Level` of
     scope "passage" is judged by, and looked at for nothing else.  `edges`: an `Edges` of the B rows, judged here and handed on by
     the caller (the spec does not carry it, as it does not carry `level`).  `breaks`: a `Breaks` of the B rows and of the call's `N`
-    tokens (None: the caller has no token count to judge by), likewise.  `dynamics`: a `Dynamics` of the B rows, likewise."""
+    tokens (None: the caller has no token count to judge by), likewise.  `dynamics`: a `Dynamics` of the B rows, likewise.  `volume`: a `Volume` of the B rows, of the
+    call's `N` tokens where it holds a per-token table and on the call's `device` (None: the caller has none to judge by), likewise."""
     if pack is not None and pack not in ops.OUTPUT_FORMATS:
         raise ValueError("pack must be None or one of %s, got %r" % (sorted(ops.OUTPUT_FORMATS), pack))
     if sample_rate is not None and pack is None:
@@ -1565,6 +1713,12 @@ def _output_spec(B, capacity, pack=None, trim=None, sample_rate=None, marks=Fals
         raise ValueError("dynamics compress the packed samples of the capacity-bound path: pass max_frames and pack")
     if dynamics is not None and (not isinstance(dynamics, Dynamics) or dynamics.B != B):
         raise ValueError("dynamics must be a pipeline.Dynamics of %d rows" % B)
+    if volume is not None and (pack is None or not capacity):
+        raise ValueError("volume is a gain in the packed samples of the capacity-bound path: pass max_frames and pack")
+    if volume is not None and (not isinstance(volume, Volume) or volume.B != B or (N is not None and volume.N not in (None, N))):
+        raise ValueError("volume must be a pipeline.Volume of %d rows%s" % (B, "" if N is None else " of %d tokens" % N))
+    if volume is not None and device is not None and volume.device != torch.empty(0, device=device).device:
+        raise ValueError("volume holds its tables on %s, the batch is on %s" % (volume.device, device))
     if not capacity:
         _capacity_only("passage / gaps / max_gap / s_prev", gaps, max_gap)
     if pack is None and (gaps is not None or max_gap is not None):
@@ -1602,7 +1756,7 @@ def _hand_over(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_m
 
 
 def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=None, n_marks=0, gaps=None, max_gap=0, level=None,
-                     starts=None, edges=None, breaks=None, tokens=None, dynamics=None):
+                     starts=None, edges=None, breaks=None, tokens=None, dynamics=None, volume=None):
     """The packing step into ONE device allocation (`_HandOver`, returned with its views), the samples at capacity -- ceil(L U /
     D) per row, and `max_gap` more with `gaps` -- so that a single copy brings all of it to the host.  Which wrapper packs:
     with `gaps` (int32 [B], host or device) `ops.wave_pack_gaps`, which reads them from the header they
@@ -1624,7 +1778,11 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     The boundaries and the inserted silence stay with the hand-over (`pos`, `ins`) for the marks.  With `dynamics` (a `Dynamics`;
     DESIGN.md section 30) `ops.wave_dynamics` runs behind the breaks and in front of the level, into a buffer of the caching
     allocator with {deepest reduction, blocks reduced} into the header's dynamics part: sample counts do not change, so frames,
-    trim and samples_per_frame go on as they came, and the loudness target holds on the compressed programme."""
+    trim and samples_per_frame go on as they came, and the loudness target holds on the compressed programme.  With `volume` (a
+    `Volume`) `ops.wave_volume` runs behind the compressor and in front of the level, in the same manner, with
+    {peak, blocks with a gain} into the header's volume part.  The tokens' boundaries it reads are those of the rows as they are
+    by then, from ONE marks launch without a rate over `tokens`: `ops.token_marks_breaks` over the `pos` and `ins` the breaks left
+    where there are breaks, else the `ops.token_marks` / `ops.token_marks_edges` launch the breaks would have taken."""
     B, L = wave.shape[0], wave.shape[-1]
     rate = None if not _resamples(fmt, sample_rate) else (resample.MODEL_RATE if sample_rate is None else sample_rate)
     U, D = (1, 1) if rate is None else resample.table(rate, wave.device)[:2]
@@ -1634,15 +1792,19 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     limiting = level is not None and level.limiter
     ho = _HandOver(B, fmt, n_marks, gaps is not None, with_level=level is not None, with_limit=limiting,
                    with_edges=edges is not None, **({} if breaks is None else {"with_breaks": True}),
-                   **({} if dynamics is None else {"with_dynamics": True})).allocate(B * room, wave.device)
+                   **({} if dynamics is None else {"with_dynamics": True}),
+                   **({} if volume is None else {"with_volume": True})).allocate(B * room, wave.device)
+
+    def boundaries():  # in the decoder's geometry (`tokens`), moved by the trim below where there is one
+        marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
+        return marks_of(tokens["dur"], tokens["frames"], tokens["T_cap"], lengths=tokens["lengths"], shift=tokens["shift"],
+                        trim=tokens["trim"], samples_per_frame=tokens["samples_per_frame"])
     if edges is not None:
         wave, _ = ops.wave_edges(wave, frames, edges.top_db, edges.keep, resample.edge_ramp(edges.F, wave.device) if edges.F else None,
                                  trim=trim, samples_per_frame=samples_per_frame, edges=ho.edges)
         frames, trim, samples_per_frame = ho.edges.view(B, 2)[:, 1].contiguous(), 0, 1  # the counts as a row of their own
-    if breaks is not None:  # the boundaries in the decoder's geometry (`tokens`), moved by the trim above where there is one
-        marks_of = ops.token_marks if edges is None else functools.partial(ops.token_marks_edges, edges=ho.edges)
-        ho.pos = marks_of(tokens["dur"], tokens["frames"], tokens["T_cap"], lengths=tokens["lengths"], shift=tokens["shift"],
-                          trim=tokens["trim"], samples_per_frame=tokens["samples_per_frame"])
+    if breaks is not None:
+        ho.pos = boundaries()
         wave, ho.ins, _, _ = ops.wave_breaks(wave, frames, ho.pos, breaks.samples, breaks.max_break,
                                              resample.edge_ramp(breaks.F, wave.device) if breaks.F else None, trim=trim,
                                              samples_per_frame=samples_per_frame, breaks=ho.breaks)
@@ -1651,6 +1813,11 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
         A = dynamics.A
         wave, _ = ops.wave_dynamics(wave, frames, dynamics.params, resample.limit_window(A, wave.device) if A else None, A=A,
                                     rho=dynamics.rho, trim=trim, samples_per_frame=samples_per_frame, dynamics=ho.dynamics)
+    if volume is not None:
+        A = volume.A
+        pos = boundaries() if breaks is None else ops.token_marks_breaks(ho.pos, ho.ins)
+        wave, _ = ops.wave_volume(wave, frames, pos, volume.db, volume.tok_db, resample.limit_window(A, wave.device) if A else None,
+                                  A=A, lengths=tokens["lengths"], trim=trim, samples_per_frame=samples_per_frame, volume=ho.volume)
     into = dict(trim=trim, fmt=fmt, out=ho.packed, offsets=ho.offsets, samples_per_frame=samples_per_frame)
     if gaps is not None:
         ho.gaps.copy_(gaps.reshape(B), non_blocking=True)
@@ -1680,13 +1847,13 @@ def _hand_over_edges(wave, frames, trim, fmt, samples_per_frame, sample_rate=Non
     return ho
 
 
-def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None, breaks=None, dynamics=None):
+def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges=None, breaks=None, dynamics=None, volume=None):
     """ONE ragged decoder call at the capacity of prepare(max_frames=) and, with `spec.fmt`, the packed samples: nothing is read
     back, nothing is sliced on the host.  `spec.marks`: one `ops.token_marks` launch behind the packing writes the timing marks
     into the hand-over allocation.  `gaps`: the breaks behind the rows, `level`: their loudness normalisation, `starts`: the call's `passage`
     for a level of scope "passage" (`_hand_over`), `edges`: their trim (`_hand_over_edges`; the marks are then `ops.token_marks_edges`'),
     `breaks`: the pauses inside them (`_hand_over_edges`; the marks are then `ops.token_marks_breaks`'), `dynamics`: their compressor
-    (`_hand_over_edges`; it moves no sample, so the marks are what they are without it)."""
+    (`_hand_over_edges`; it moves no sample, so the marks are what they are without it), `volume`: their gains, likewise."""
     T_cap = p["max_frames"]
     w = _decode_frames(model, p, sine_noise, strict=True)  # the noise as a view or not at all: nothing is copied here
     hifigan = model.decoder.kind == "hifigan"
@@ -1698,13 +1865,19 @@ def _decode_capacity(model, p, sine_noise, spec, gaps, level, starts=None, edges
     B, N = dur.shape
     spf = w.shape[-1] // T_cap
     more = {} if edges is None else {"edges": edges}  # the optional stages of the hand-over; none: `_hand_over` as ever
+    if breaks is not None and breaks.N != N:
+        raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (B, N))
+    if volume is not None and volume.N not in (None, N):
+        raise ValueError("volume must be a pipeline.Volume of %d rows of %d tokens" % (B, N))
+    if breaks is not None or volume is not None:  # the stages that read the tokens' boundaries
+        more.update(tokens=dict(dur=dur, frames=p["frames"], T_cap=T_cap, lengths=p.get("token_lengths"), shift=hifigan,
+                                trim=spec.trim, samples_per_frame=spf))
     if breaks is not None:
-        if breaks.N != N:
-            raise ValueError("breaks must be a pipeline.Breaks of %d rows of %d tokens" % (B, N))
-        more.update(breaks=breaks, tokens=dict(dur=dur, frames=p["frames"], T_cap=T_cap, lengths=p.get("token_lengths"), shift=hifigan,
-                                               trim=spec.trim, samples_per_frame=spf))
+        more.update(breaks=breaks)
     if dynamics is not None:
         more.update(dynamics=dynamics)
+    if volume is not None:
+        more.update(volume=volume)
     hand_over = functools.partial(_hand_over_edges, **more) if more else _hand_over
     ho = hand_over(w, p["frames"], spec.trim, spec.fmt, spf, spec.sample_rate, B * (N + 1) if spec.marks else 0, gaps, spec.max_gap,
                    level, starts)
@@ -1792,13 +1965,21 @@ class GraphedSynthesis:
     neutral: range 1, no contour point, and -- with `token_controls` or `marks` -- token ranges of 1): `__call__(intonation=)`
     copies the caller's tables in, a table it lacks and a call without the argument reset to neutral, so one graph serves any
     ranges and contours; `K` and `voiced_hz` are the graph's own.  The result carries `pitch`.  Without it the graph records
-    exactly what it recorded before and refuses the argument."""
+    exactly what it recorded before and refuses the argument.
+
+    `volume=True` (or a `Volume`, whose `ramp_ms` is taken; needs `pack`): the graph records the gain stage
+    over one more static object, `static["volume"]` (a `Volume` with both tables present and 0 dB): `__call__(volume=)` copies the
+    caller's tables in, a table it lacks and a call without the argument reset to 0 dB, so one graph serves any gains; `ramp_ms`
+    is the graph's own.  The result carries `volume`.  Without it the graph records exactly what it recorded before and refuses
+    the argument."""
 
     def __init__(self, model, sampler, B, N, max_frames, diffusion_steps, ref_s=None, pack=None, trim=None,
                  embedding_scale=1.0, alpha=0.3, beta=0.7, lj_tail=None, device=None, sample_rate=None, marks=False,
                  token_controls=None, passage=False, max_gap=None, t=0.7, level=None, seeds=False, fit=False, edges=None,
-                 breaks=None, max_break_ms=None, dynamics=None, intonation=None):
+                 breaks=None, max_break_ms=None, dynamics=None, intonation=None, volume=None):
         from .diffusion import GraphedSampler
+        if volume is not None and not isinstance(volume, (bool, Volume)):
+            raise ValueError("volume must be True or a pipeline.Volume, got %s" % type(volume).__name__)
         if intonation is not None and not isinstance(intonation, (bool, Intonation)):
             raise ValueError("intonation must be True or a pipeline.Intonation, got %s" % type(intonation).__name__)
         if isinstance(intonation, Intonation) and intonation.B != B:
@@ -1821,12 +2002,18 @@ class GraphedSynthesis:
         elif isinstance(breaks, Breaks) and max_break_ms is not None and Edges.samples(max_break_ms) != breaks.max_break:
             raise ValueError("max_break_ms=%r is not the cap of the Breaks given (%r ms)" % (max_break_ms, breaks.max_ms))
         dynamics = Dynamics(B, device=dev) if dynamics is True else None if dynamics is False else dynamics
+        if volume is False:
+            volume = None
+        elif volume is not None:  # recorded over tables of its own, 0 dB everywhere: only the ramp of a `Volume` given is taken
+            volume = Volume.neutral(B, N, device=dev, **({} if volume is True else volume.options()))
         # the output as `inference` will judge it at every recording, over the static gaps: device gaps with `max_gap`
         gaps = None if max_gap is None else torch.zeros((B,), device=dev, dtype=torch.int32)
         spec, _ = _output_spec(B, True, pack, trim, sample_rate, marks, gaps, max_gap, level, graph=True, passage=self.passage,
                                **({} if edges is None else {"edges": edges}),
-                               **({} if breaks is None else {"breaks": breaks, "N": N}),
-                               **({} if dynamics is None else {"dynamics": dynamics}))
+                               **({} if breaks is None else {"breaks": breaks}),
+                               **({} if dynamics is None else {"dynamics": dynamics}),
+                               **({} if volume is None else {"volume": volume, "device": dev}),
+                               **({} if breaks is None and volume is None else {"N": N}))
         if spec.rate is not None:
             resample.table(spec.rate, dev)
         if level is not None and level.true_peak:
@@ -1839,6 +2026,8 @@ class GraphedSynthesis:
             resample.edge_ramp(breaks.F, dev)  # and that of a pause's two sides
         if dynamics is not None and dynamics.A:
             resample.limit_window(dynamics.A, dev)  # and the compressor's look-ahead window
+        if volume is not None and volume.A:
+            resample.limit_window(volume.A, dev)  # and the ramp of the gains
         self.kw = dict(diffusion_steps=self.steps, embedding_scale=embedding_scale, alpha=alpha, beta=beta, lj_tail=lj_tail,
                        max_frames=self.max_frames, pack=pack, trim=trim, sample_rate=sample_rate, marks=bool(marks),
                        max_gap=self.max_gap, t=t)
@@ -1878,6 +2067,8 @@ class GraphedSynthesis:
         if dynamics is not None:
             own = self.static["dynamics"] = dynamics.slice(0, B)
             own.params = dynamics.params.to(dev).clone()
+        if volume is not None:
+            self.static["volume"] = volume
         self._g = None
 
     def _run(self):
@@ -1890,7 +2081,8 @@ class GraphedSynthesis:
                          **({"edges": st["edges"]} if "edges" in st else {}),
                          **({"breaks": st["breaks"]} if "breaks" in st else {}),
                          **({"dynamics": st["dynamics"]} if "dynamics" in st else {}),
-                         **({"intonation": st["intonation"]} if "intonation" in st else {}))
+                         **({"intonation": st["intonation"]} if "intonation" in st else {}),
+                         **({"volume": st["volume"]} if "volume" in st else {}))
 
     def _engines(self):
         engs = model_engines(self.model, self.device)
@@ -1904,8 +2096,17 @@ class GraphedSynthesis:
     @torch.no_grad()
     def __call__(self, tokens=None, lengths=None, noise=None, step_noise=None, sine_noise=None, ref_s=None, controls=None,
                  starts=None, s_prev=None, gaps=None, level=None, seeds=None, fit_frames=None, fit_hold=None, edges=None,
-                 breaks=None, dynamics=None, intonation=None):
+                 breaks=None, dynamics=None, intonation=None, volume=None):
         st = self.static
+        if volume is not None and "volume" not in st:
+            raise ValueError("this graph was built without volume: pass volume=True")
+        if "volume" in st:
+            own = st["volume"]
+            if volume is not None:
+                if not isinstance(volume, Volume) or volume.B != own.B or volume.N not in (None, own.N):
+                    raise ValueError("volume must be a pipeline.Volume of %d rows of %d tokens" % (own.B, own.N))
+                if volume.options() != own.options():
+                    raise ValueError("ramp_ms is the graph's own (%r); the Volume given has %r" % (own.options(), volume.options()))
         if intonation is not None and "intonation" not in st:
             raise ValueError("this graph was built without intonation: pass intonation=True")
         if "intonation" in st:
@@ -2000,6 +2201,10 @@ class GraphedSynthesis:
         if self._neutral_tok is not None:
             has_tok = controls is not None and controls.tok_buf is not None
             st["controls"].tok_buf.copy_(controls.tok_buf if has_tok else self._neutral_tok, non_blocking=True)
+        if "volume" in st:  # judged at the top; written here, behind every refusal of the call
+            for name in ("db", "tok_db"):
+                given = None if volume is None else getattr(volume, name)
+                getattr(st["volume"], name).zero_() if given is None else getattr(st["volume"], name).copy_(given, non_blocking=True)
         g = self._g
         if g is not None and (g["gen"] != _sampler_generation(self.sampler)
                               or any(_engine_changed(e, rec, gen) for e, (rec, gen) in zip(self._engines(), g["engines"]))):
@@ -2160,7 +2365,7 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
               taps=None, front_stream=None, inputs_on_main=False, total_frames=None, front=None, decode_streams=None,
               ragged_decode=False, max_frames=None, pack=None, trim=None, lengths_dev=None, controls=None,
               sample_rate=None, marks=False, passage=None, gaps=None, max_gap=None, s_prev=None, t=0.7, level=None,
-              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None, dynamics=None, intonation=None):
+              seeds=None, fit_frames=None, fit_hold=None, edges=None, breaks=None, dynamics=None, intonation=None, volume=None):
     """tokens [B, N] int64 (id 0 prepended, ipynb:277) -> waveform [B, 1, 600*T] on the device.
 
     Single-speaker (LJSpeech) when `ref_s` is None, else the multi-speaker flow with style mixing
@@ -2263,13 +2468,23 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     `intonation` (an `Intonation` of B rows; with and without `max_frames`): per-row pitch range, per-token
     range and pitch contour on the device, see `prepare`; on the capacity-bound path the result carries the report as `pitch`.
     Without it the call issues exactly the launches it always did.
+
+    `volume` (a `Volume` of B rows, with `max_frames` and `pack`): SSML's `<prosody volume=>` -- one gain in
+    dB per row and one per token, ramped over `ramp_ms`, on the device (`ops.wave_volume`, behind `dynamics` and in front of
+    `level`, over the tokens' boundaries as `edges` and `breaks` left them).  No sample moves: marks, gaps, resampling and G.711
+    run unchanged; a stretch at 0 dB keeps its bits.  The result carries {peak, blocks with a gain} as `volume`.  Under a
+    `Level` of scope "row" the row's own `db` is cancelled by the normalisation and the differences between tokens survive;
+    under scope "passage" a quiet sentence stays quiet beside its neighbours.  `emphasis_tables` makes the per-token tables of
+    `<emphasis>`.  Without it the call issues exactly the launches it always did.
     """
     if intonation is not None:
         _check_intonation(intonation, tokens.device, tokens.shape[0], taps, front, tokens.shape[1])
     spec, gaps = _output_spec(tokens.shape[0], max_frames is not None, pack, trim, sample_rate, marks, gaps, max_gap, level,
                               passage=passage, **({} if edges is None else {"edges": edges}),
-                              **({} if breaks is None else {"breaks": breaks, "N": tokens.shape[1]}),
-                              **({} if dynamics is None else {"dynamics": dynamics}))
+                              **({} if breaks is None else {"breaks": breaks}),
+                              **({} if dynamics is None else {"dynamics": dynamics}),
+                              **({} if volume is None else {"volume": volume, "device": tokens.device}),
+                              **({} if breaks is None and volume is None else {"N": tokens.shape[1]}))
     carry, controls = _check_capacity_args(tokens, max_frames, lengths_dev, passage, s_prev, controls, taps, front, durations,
                                            decode_streams)
     if seeds is not None:
@@ -2308,7 +2523,8 @@ def inference(model, sampler, tokens, input_lengths=None, noise=None, diffusion_
     if max_frames is not None:
         return _decode_capacity(model, p, sine_noise, spec, gaps, level, passage, **({} if edges is None else {"edges": edges}),
                                 **({} if breaks is None else {"breaks": breaks}),
-                                **({} if dynamics is None else {"dynamics": dynamics}))
+                                **({} if dynamics is None else {"dynamics": dynamics}),
+                                **({} if volume is None else {"volume": volume}))
     if "frames" in p:
         return _decode_ragged(model, p, sine_noise)
     if "groups" not in p:
@@ -2378,7 +2594,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
                     overlap=True, on_chunk=None, bucket=0, front=None, side_stream=None, front_batch=1, decode_streams=1,
                     ragged_decode=False, controls=None, max_frames=None, pack=None, sample_rate=None, marks=False, gaps=None,
                     max_gap=None, level=None, seeds=None, fit_frames=None, edges=None, breaks=None, dynamics=None,
-                    intonation=None):
+                    intonation=None, volume=None):
     """Long-form synthesis (BASELINE.json configs[4]; Demo/Inference_LibriTTS.ipynb LFinference + its driver loop,
     Demo/Inference_LJSpeech.ipynb "Long-form generation"): `sentences` is a list of token tensors [N_i] (id 0
     prepended); each sentence is synthesised with the previous sentence's mixed style carried over
@@ -2449,6 +2665,8 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
     `intonation` (with and without `max_frames`): an `Intonation` of one row per SENTENCE, sliced per front
     group: every sentence's own pitch range and contour (`prepare(intonation=)`).  Its per-token ranges are served with
     `max_frames` only, under the rule of the per-token controls: N is the longest sentence's token count.
+    `volume` (needs `max_frames` and `pack`): a `Volume` of one row per SENTENCE, sliced per front group: every
+    sentence's own gain and its tokens' (`inference(volume=)`); a per-token table is as wide as the longest sentence.
     """
     dev = sentences[0].device
     if intonation is not None and (not isinstance(intonation, Intonation) or intonation.B != len(sentences)):
@@ -2461,11 +2679,13 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
             embedding_scale=embedding_scale, noises=noises, step_noises=step_noises, sine_noises=sine_noises, durations=durations,
             trim=trim, on_chunk=on_chunk, bucket=bucket, front=front, front_batch=front_batch, decode_streams=decode_streams,
             controls=controls, max_frames=max_frames, pack=pack, sample_rate=sample_rate, marks=marks, gaps=gaps, max_gap=max_gap,
-            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks, dynamics=dynamics, intonation=intonation)
+            level=level, seeds=seeds, fit_frames=fit_frames, edges=edges, breaks=breaks, dynamics=dynamics, intonation=intonation,
+            volume=volume)
     _capacity_only("pack / sample_rate / marks / gaps / max_gap / level", pack, sample_rate, marks or None, gaps, max_gap, level)
     _capacity_only("edges", edges)
     _capacity_only("breaks", breaks)
     _capacity_only("dynamics", dynamics)
+    _capacity_only("volume", volume)
     _capacity_only("seeds", seeds)
     _capacity_only("fit_frames / fit_hold", fit_frames)
     if controls is not None and controls.tok_present:
@@ -2552,7 +2772,7 @@ def synthesize_long(model, sampler, sentences, ref_s=None, alpha=0.3, beta=0.7, 
 def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, t, diffusion_steps, embedding_scale, noises,
                               step_noises, sine_noises, durations, trim, on_chunk, bucket, front, front_batch, decode_streams,
                               controls, max_frames, pack, sample_rate, marks, gaps, max_gap, level, seeds, fit_frames, edges=None,
-                              breaks=None, dynamics=None, intonation=None):
+                              breaks=None, dynamics=None, intonation=None, volume=None):
     """`synthesize_long(max_frames=)`: see there.  Everything a group needs is stacked before the first group is issued."""
     dev = sentences[0].device
     K = len(sentences)
@@ -2571,6 +2791,7 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
         trim = 100 if ref_s is not None else 0
     ns_all = [s.numel() for s in sentences]
     tok_ctl = controls is not None and controls.tok_buf is not None or breaks is not None  # rows as wide as the longest sentence
+    tok_ctl = tok_ctl or volume is not None and getattr(volume, "tok_db", None) is not None
     if intonation is not None:
         _check_intonation(intonation, dev, K, None, front, max(ns_all) if intonation.tok_range is not None else None)
         tok_ctl = tok_ctl or intonation.tok_range is not None
@@ -2580,8 +2801,10 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
     chunks = _front_chunks(front_batch, K)
     spec, gaps = _output_spec(K, True, pack, trim, sample_rate, marks, gaps, None if gaps is None else max_gap, level, passage=True,
                               front_groups=len(chunks), **({} if edges is None else {"edges": edges}),
-                              **({} if breaks is None else {"breaks": breaks, "N": max(ns_all)}),
-                              **({} if dynamics is None else {"dynamics": dynamics}))
+                              **({} if breaks is None else {"breaks": breaks}),
+                              **({} if dynamics is None else {"dynamics": dynamics}),
+                              **({} if volume is None else {"volume": volume, "device": dev}),
+                              **({} if breaks is None and volume is None else {"N": max(ns_all)}))
     prepped = []
     for i, i_end in chunks:
         ids = list(range(i, i_end))
@@ -2608,6 +2831,8 @@ def _synthesize_long_capacity(model, sampler, sentences, *, ref_s, alpha, beta, 
             more.update(dynamics=dynamics.slice(i, j))
         if intonation is not None:
             more.update(intonation=intonation.slice(i, j))
+        if volume is not None:
+            more.update(volume=volume.slice(i, j))
         res = inference(model, sampler, q["tokens"], input_lengths=q["lengths"], lengths_dev=q["lens_dev"], noise=q["noise"],
                         diffusion_steps=diffusion_steps, embedding_scale=embedding_scale, ref_s=q["ref_s"], alpha=alpha, beta=beta,
                         lj_tail=False, step_noise=q["step_noise"], sine_noise=q["sine"], durations=q["dur"], max_frames=T_cap,
