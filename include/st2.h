@@ -1517,7 +1517,11 @@ int st2_conv_tune_read(double* rows, int32_t cap_rows);
  *       every element's lo normal: ~4e-8)
  *   [9] share of the operand's energy carried by elements whose lo half is subnormal or zero
  *   [10] conv site (st2_calibration_read index) when an engine plan issued the launch, else -1   [11] that engine (identity)
- * in launch order and returns their number.  tools/headroom_report.py prints the table for a checkpoint. */
+ * in launch order and returns their number.  tools/headroom_report.py prints the table for a checkpoint.
+ * A ragged launch (st2_act_split_len's len, st2_conv_desc.x_len) is measured over each row's valid columns on both routes: the
+ * columns at and past a row's end are the conv's zero padding, so what memory holds there (a longer earlier batch, a NaN) enters
+ * neither the maximum nor a sum and raises no status bit; [4] stays the launch's L.  Elements with hi = lo = 0 enter no sum, and a
+ * launch without any other element reports [8] = [9] = 0.  Launches under stream capture are not recorded. */
 #define ST2_HEADROOM_COLS 12
 int st2_debug_headroom(int enable);
 int st2_debug_headroom_read(double* rows, int32_t cap_rows);
@@ -1546,7 +1550,12 @@ int st2_debug_headroom_read(double* rows, int32_t cap_rows);
  * st2_calibrate ACCUMULATES: a site's maximum is the largest over every recorded call since the table was last cleared, and sites whose
  * operand does not come out of a normalising prologue (free-ranging: F0 in Hz, stage outputs, FFN intermediates) get two more bits
  * of headroom than margin_bits (ABI v22).  st2_finalize_weights CLEARS the table (ABI v22; v20-21 kept it for an unchanged conv
- * layout): scales belong to the weights they were measured on. */
+ * layout): scales belong to the weights they were measured on.
+ * Accumulation NEVER NARROWS a site: where a non-zero scale is already there, st2_calibrate keeps min(that scale, the scale computed
+ * from the accumulated maximum).  This is the rule chosen for tables installed by st2_calibration_write, which carry scales only
+ * (the maxima behind them do not travel: column 4 restarts at 0 and then reports what was seen SINCE the write): the installed scale
+ * is itself the record of what the site must hold, so calibrating further on a quieter input leaves it alone and a louder one
+ * lowers it, exactly as on the process that measured the table.  To start over, clear first (st2_calibration_write with n = 0). */
 #define ST2_CALIBRATION_COLS 5
 int st2_calibrate(st2_engine* e, int32_t margin_bits, int32_t* n_clamped);
 int st2_calibration_read(st2_engine* e, double* rows, int32_t cap_rows);

@@ -240,10 +240,14 @@ extern "C" int st2_act_split(const float* x, int64_t x_bs, int32_t x_cs, int32_t
                            xs, xs_cg, Lp, halo, nullptr, stream);
 }
 
-extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L, int32_t pro,
-                                 float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
-                                 int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale, void* xs,
-                                 int32_t xs_cg, int32_t Lp, int32_t halo, const int32_t* len, void* stream) {
+namespace {
+// The launch behind st2_act_split / st2_act_split_len and the fused conv's telemetry.  `kind` is the headroom record's: 0 = a
+// caller's activation pass, 1 = the fused conv's probe, which may carry per-row lengths under ST2_PRO_COLNORM because the conv it
+// mirrors does (st2_conv1d_f16s zero-pads every prologue at x_len[b]; the columns past it are selected away, never multiplied).
+int act_split_launch(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L, int32_t pro, float slope,
+                     const float* stats, const float* gamma, const float* beta, int64_t gb_bs, int32_t gb_seg,
+                     int32_t gamma_plus_one, const float* alpha, float x_scale, void* xs, int32_t xs_cg, int32_t Lp, int32_t halo,
+                     const int32_t* len, int kind, void* stream) {
   ST2_REQUIRE(x && xs && B > 0 && C > 0 && L > 0, "st2_act_split: bad arguments");
   ST2_REQUIRE(B <= 65535 && xs_cg <= 65535, "st2_act_split: grid too large");
   ST2_REQUIRE(xs_cg * 8 >= C, "st2_act_split: xs_cg=%d groups cannot hold C=%d channels", xs_cg, C);
@@ -260,7 +264,8 @@ extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int
   a.alpha = alpha; a.x_scale = x_scale;
   a.xs = reinterpret_cast<st2_h8*>(xs); a.xs_cg = xs_cg; a.Lp = Lp; a.halo = halo;
   a.len = len;
-  ST2_REQUIRE(!len || pro != ST2_PRO_COLNORM, "st2_act_split_len: per-row lengths are not defined for ST2_PRO_COLNORM");
+  ST2_REQUIRE(!len || pro != ST2_PRO_COLNORM || kind == 1,
+              "st2_act_split_len: per-row lengths are not defined for ST2_PRO_COLNORM");
   a.status = st2_status_device_ptr();
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   st2_dispatch_pro(pro, [&](auto tag) {
@@ -268,13 +273,25 @@ extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int
   });
   ST2_CHECK_LAUNCH("st2_act_split");
   if (g_headroom) {
-    headroom_record(0, a, B, s);
-    if (!g_hr.empty()) g_hr.back().pro = pro;
+    const size_t before = g_hr.size();
+    headroom_record(kind, a, B, s);
+    if (g_hr.size() == before + 1) g_hr.back().pro = pro;
   }
   return 0;
 }
+}  // namespace
 
-// Telemetry for the fused conv (st2_conv1d_f16s.hip calls this in debug mode): the same prologue into scratch planes.
+extern "C" int st2_act_split_len(const float* x, int64_t x_bs, int32_t x_cs, int32_t B, int32_t C, int32_t L, int32_t pro,
+                                 float slope, const float* stats, const float* gamma, const float* beta, int64_t gb_bs,
+                                 int32_t gb_seg, int32_t gamma_plus_one, const float* alpha, float x_scale, void* xs,
+                                 int32_t xs_cg, int32_t Lp, int32_t halo, const int32_t* len, void* stream) {
+  return act_split_launch(x, x_bs, x_cs, B, C, L, pro, slope, stats, gamma, beta, gb_bs, gb_seg, gamma_plus_one, alpha, x_scale, xs,
+                          xs_cg, Lp, halo, len, 0, stream);
+}
+
+// Telemetry for the fused conv (st2_conv1d_f16s.hip calls this in debug mode): the same prologue into scratch planes, each row
+// ending where the conv ends it (d.x_len: what lies past a row's end is the conv's zero padding, not operand).  The record's L
+// stays L_in.
 int st2_headroom_of_fused_conv(const st2_conv_desc& d, hipStream_t s) {
   if (!g_headroom || !d.x) return 0;
   {
@@ -297,11 +314,8 @@ int st2_headroom_of_fused_conv(const st2_conv_desc& d, hipStream_t s) {
     }
     g_hr_scratch_bytes = bytes;
   }
-  const size_t before = g_hr.size();
-  const int rc = st2_act_split(d.x, d.x_bs, d.x_cs, d.B, d.C_in, d.L_in, d.pro, d.slope, d.stats, d.gamma, d.beta, d.gb_bs, 0,
-                               d.gamma_plus_one, d.alpha, d.x_scale, g_hr_scratch, cg, Lp, halo, s);
-  if (rc == 0 && g_hr.size() == before + 1) g_hr.back().kind = 1;
-  return rc;
+  return act_split_launch(d.x, d.x_bs, d.x_cs, d.B, d.C_in, d.L_in, d.pro, d.slope, d.stats, d.gamma, d.beta, d.gb_bs, 0,
+                          d.gamma_plus_one, d.alpha, d.x_scale, g_hr_scratch, cg, Lp, halo, d.x_len, 1, s);
 }
 
 extern "C" int st2_debug_headroom(int enable) {

@@ -1195,7 +1195,14 @@ extern "C" int st2_calibrate(st2_engine* e, int32_t margin_bits, int32_t* n_clam
     // the affine's gain whatever the utterance), two bits more where the operand is free-ranging -- the F0 curve in Hz, generator
     // stage outputs, FFN intermediates differ between utterances far more than between passes of one (advisor, round 5: 8 x over
     // ONE synthetic step is thin for those; the lo half stays a normal f16 down to 2^-14 / x_scale, two bits cost nothing there).
-    e->site_scale[i] = st2_calibration_scale(e->site_seen[i], margin_bits + (free_range[i] ? 2 : 0));
+    const float computed = st2_calibration_scale(e->site_seen[i], margin_bits + (free_range[i] ? 2 : 0));
+    // ... and never narrow a scale that is already there.  A table installed by st2_calibration_write (another rank's, or one saved
+    // beside the checkpoint) arrives without the maxima it was computed from -- site_seen restarts at 0 -- so the scale itself is
+    // the record of what the site has to hold: a larger scale than the installed one would clamp inputs the table covered.  Where
+    // site_seen was kept this changes nothing at one margin (its maximum only grows, the scale it gives only shrinks).  Clearing the table
+    // (st2_calibration_write(n = 0), st2_finalize_weights) is how a calibration starts over.
+    const float had = e->site_scale[i];
+    e->site_scale[i] = had > 0.f && computed > 0.f ? std::min(had, computed) : computed;
     ++set;
   }
   if (n_clamped) *n_clamped = clamped;

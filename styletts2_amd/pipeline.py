@@ -2862,13 +2862,15 @@ def calibrate(run, margin_bits=3, max_passes=3, engines=None, accumulate=False):
     spread of the traffic (several utterances, several reference styles): a site keeps 8 x headroom over the largest operand seen
     after a normalising prologue and 32 x where its input is free-ranging (F0 in Hz, stage outputs, FFN intermediates); beyond that
     the clamp + ST2_STATUS_F16_RANGE stay as the net.  `accumulate=True` widens the existing table with what this call sees instead
-    of starting over (more utterances later, same checkpoint).  Returns
+    of starting over (more utterances later, same checkpoint): no site's scale grows by it, whether the table was calibrated here
+    or installed by `load_calibration_state`.  Starting over clears the tables of `engines` when given, else of the engines that
+    `run()` launched -- another model loaded in the same process keeps its calibration.  Returns
     {"passes", "sites_set", "clamped_last_pass", "headroom": rows of the last pass (ops.headroom)}."""
     from . import _lib, engine
     rows, nset, clamped, passes = [], 0, 0, 0
     ops.check_status()  # whatever earlier calls raised is theirs: reported now, not swallowed by the passes below
-    if not accumulate:
-        for eng in (engines if engines is not None else engine.live_engines()):
+    if not accumulate and engines is not None:
+        for eng in engines:
             eng.set_calibration(None)  # st2_calibrate accumulates maxima: a fresh calibration starts from the rule
     for _ in range(max(1, int(max_passes))):
         with ops.headroom() as h:
@@ -2876,7 +2878,14 @@ def calibrate(run, margin_bits=3, max_passes=3, engines=None, accumulate=False):
         ops.check_status(ignore=_lib.STATUS_F16_RANGE)  # a clamp during calibration is what the pass is there to find
         rows, passes = h.rows, passes + 1
         nset = clamped = 0
+        launched = {r["engine"] for r in rows if r["site"] >= 0}
         for eng in (engines if engines is not None else engine.live_engines()):
+            if engines is None and not accumulate and passes == 1 and eng.h.value in launched:
+                # Without `engines=` the calibration belongs to the engines `run()` launches, and only the first pass says which:
+                # they start over here (their first pass ran at whatever scales they had: a site's maximum is max |hi| / x_scale,
+                # the same f16 value at any power of two that does not clamp -- and a clamp repeats the pass).  Every other
+                # engine of the process -- another loaded model -- keeps its table and its calib_gen.
+                eng.set_calibration(None)
             n, c = eng.calibrate(margin_bits)
             nset, clamped = nset + n, clamped + c
         if clamped == 0:

@@ -5,6 +5,7 @@ handed, so the plan output must not move beyond the contract tolerance).  The me
 folded by st2_calibrate on the device -- is tests/test_calibration_gpu.py."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -28,6 +29,32 @@ def test_scale_formula():
             assert top / 2 <= v * s < top, (v, s, margin)  # the largest scaled operand sits in the top octave below 2^(16-m)
     assert lib.st2_calibration_scale(0.0, 3) == 0.0 and lib.st2_calibration_scale(-1.0, 3) == 0.0
     assert lib.st2_calibration_scale(float("nan"), 3) == 0.0 and lib.st2_calibration_scale(float("inf"), 3) == 0.0
+    # The grid against an fp64 restatement: every power of two from 2^-40 to 2^20 and its fp32 neighbours one ulp either side (where
+    # floor(log2) steps), every margin.  v = f 2^ex with f in [0.5, 1) gives scale = 2^(16 - m - ex), exponent clamped to +-60;
+    # v * scale is exact in fp64 (24 bits times a power of two), so the octave invariant is tested without rounding.
+    f32 = np.float32
+    values = []
+    for k in range(-40, 21):
+        p = f32(2.0 ** k)
+        values += [float(np.nextafter(p, f32(0))), float(p), float(np.nextafter(p, f32(np.inf)))]
+    values += [2.0 ** -100, 2.0 ** -60, float(f32(1e30)), float(np.finfo(f32).max), float(np.finfo(f32).tiny), 2.0 ** -149]
+    unclamped = 0
+    for margin in range(0, 11):
+        for v in values:
+            _, ex = math.frexp(v)
+            e = 16 - margin - ex
+            want = 2.0 ** min(max(e, -60), 60)
+            s = lib.st2_calibration_scale(v, margin)
+            assert s == want, (v, margin, s, want)
+            if -60 <= e <= 60:
+                unclamped += 1
+                assert 2.0 ** (15 - margin) <= v * s < 2.0 ** (16 - margin), (v, s, margin)
+        for v in (0.0, -0.0, -1.0, -2.0 ** -40, float("inf"), float("-inf"), float("nan")):
+            assert lib.st2_calibration_scale(v, margin) == 0.0, (v, margin)
+    assert unclamped >= 11 * 3 * 61  # the whole power-of-two grid lies inside the exponent clamp
+    # margins outside 0 .. 10 are clamped to the ends
+    assert lib.st2_calibration_scale(1.0, -4) == lib.st2_calibration_scale(1.0, 0) == 2.0 ** 15
+    assert lib.st2_calibration_scale(1.0, 99) == lib.st2_calibration_scale(1.0, 10) == 2.0 ** 5
 
 
 @pytest.fixture

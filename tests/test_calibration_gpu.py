@@ -118,6 +118,142 @@ def test_calibrated_decoder_meets_the_tap_bars_at_small_magnitudes(tag, f):
     assert [r["x_scale"] for r in h2.rows] == [r["x_scale"] for r in before.rows]
 
 
+T_SMALL = 8  # frames: every conv site of the decoder launches at any frame count; 8 keeps a ragged batch of (T, T / 2, 3) distinct
+
+
+def _decoder_rows(frames, f, seed=3, poison=float("nan")):
+    """Per-row decoder inputs drawn at each row's own length (what its solo run sees) and the same rows padded to max(frames),
+    with `poison` in asr / F0 / N past each row's end (the noise stays zero-padded)."""
+    B, T = len(frames), max(frames)
+    asr, F0, N = torch.full((B, 512, T), poison), torch.full((B, 2 * T), poison), torch.full((B, 2 * T), poison)
+    noise, s, rows = torch.zeros(B, 600 * T, 9), torch.zeros(B, 128), []
+    for b, Tb in enumerate(frames):
+        a, f0, n, st, nz = synth.decoder_inputs(1, Tb, seed + b)
+        a = a * f  # asr_res and the encode block's 1x1 shortcut read it un-normalised
+        asr[b, :, :Tb], F0[b, :2 * Tb], N[b, :2 * Tb], s[b], noise[b, :600 * Tb] = a[0], f0[0], n[0], st[0], nz[0]
+        rows.append((a, f0, n, st, nz))
+    return (asr, F0, N, s, noise), rows
+
+
+def test_ragged_calibration_equals_the_per_row_maximum():
+    """A ragged batch of (T, T / 2, 3) frames through `pipeline.calibrate`, NaN in asr / F0 / N past every row's end: each site's
+    maximum must be the largest of the three rows calibrated alone -- exactly, both are maxima of the same f16 values: what lies
+    past a row's end is the convs' zero padding, not operand -- and so must its scale (the smallest of the per-row scales)."""
+    f = 1e-2
+    dc, dec = _small_decoder("ljspeech", f)
+    dec = dec.to(DEV)
+    frames = [T_SMALL, T_SMALL // 2, 3]
+    (asr, F0, N, s, noise), rows = _decoder_rows(frames, f)
+    batch = [t.to(DEV) for t in (asr, F0, N, s)]
+    fr = torch.tensor(frames, dtype=torch.int32, device=DEV)
+    nz = noise.to(DEV)
+    ops.status(clear=True)
+    rep = pipeline.calibrate(lambda: dec(*batch, noise=nz, frames=fr))
+    eng = dec._eng
+    assert rep["sites_set"] > 60 and rep["clamped_last_pass"] == 0
+    ragged = eng.calibration()
+    assert all(r["x_scale"] < 1e6 for r in ragged), "a NaN or a sentinel past a row's end reached a site's maximum"
+    solo = []
+    for a, f0, n, st, z in rows:
+        one = [t.to(DEV) for t in (a, f0, n, st)]
+        zd = z.to(DEV)
+        rb = pipeline.calibrate(lambda: dec(*one, noise=zd), engines=[eng])  # cleared first: every first pass runs by rule
+        assert rb["clamped_last_pass"] == 0 and dec._eng is eng
+        solo.append(eng.calibration())
+    torch.cuda.synchronize()
+    assert ops.status(clear=True) == 0
+    bad = []
+    for i, r in enumerate(ragged):
+        seen = max(t[i]["seen"] for t in solo)
+        scales = [t[i]["x_scale"] for t in solo if t[i]["x_scale"] > 0]
+        scale = min(scales) if scales else 0.0
+        if (r["seen"], r["x_scale"]) != (seen, scale):
+            bad.append((r["name"], r["seen"], seen, r["x_scale"], scale))
+    print("RAGGED CALIBRATION: %d sites, %d launched, %d differ" % (len(ragged), rep["sites_set"], len(bad)))
+    assert not bad, bad[:8]
+    assert sum(r["seen"] > 0 for r in ragged) == rep["sites_set"] > 60
+
+
+def test_accumulate_never_narrows_an_installed_table():
+    """Calibrated on a loud input, saved (`calibration_state`) and restored (`load_calibration_state`: how rank 0's table reaches
+    the other ranks and how a table saved beside a checkpoint comes back), then widened with a quiet input
+    (`calibrate(accumulate=True)`): no site's scale may grow -- the installed table covers the loud input and must keep doing so
+    -- sites the quiet run never launched keep theirs, and the table is the one the same two calls give without the save /
+    restore in between."""
+    man, model, sds = _whole_model("ljspeech")
+    dev = torch.device(DEV, torch.cuda.current_device())
+    for k in KEYS:
+        model[k].to(DEV)
+    dec = model.decoder
+    asr, F0, N, s, noise = (t.to(DEV) for t in synth.decoder_inputs(1, T_SMALL, 3))
+    loud = lambda: dec(asr, F0, N, s, noise=noise)
+    quiet = lambda: dec(asr * 1e-2, F0 * 0.5, N * 1e-2, s * 0.1, noise=noise)
+    ops.status(clear=True)
+    pipeline.calibrate(loud)
+    state = pipeline.calibration_state(model, dev)
+    A = list(state["decoder"])
+    assert sum(x > 0 for x in A) > 60
+    # the front engine is never launched by these calls: give it a table to keep
+    state["front"] = [2.0 ** (i % 5) for i in range(len(state["front"]))]
+    pipeline.load_calibration_state(model, dev, state)
+    engs = pipeline.model_engines(model, dev)
+    assert engs["decoder"].calibration_scales() == A and all(r["seen"] == 0 for r in engs["decoder"].calibration())
+    pipeline.calibrate(quiet, accumulate=True)
+    restored = pipeline.calibration_state(model, dev)
+    assert restored["front"] == state["front"], "sites that were not launched keep their scales"
+    grown = [(i, a, b) for i, (a, b) in enumerate(zip(A, restored["decoder"])) if b > a]
+    assert not grown, "accumulate=True raised %d scales above the installed table: %s" % (len(grown), grown[:8])
+    # the same two calls without the save / restore: the identical table (engines=: cleared first, so that this first pass
+    # runs by rule as the one above did on the fresh engine)
+    pipeline.calibrate(loud, engines=[engs["decoder"]])
+    assert pipeline.calibration_state(model, dev)["decoder"] == A
+    pipeline.calibrate(quiet, accumulate=True)
+    again = pipeline.calibration_state(model, dev)
+    assert again["decoder"] == restored["decoder"] and again["front"] == state["front"]
+    # ... and the quiet input alone would have asked for larger scales: the rule above was tested, not vacuous
+    pipeline.calibrate(quiet)
+    alone = pipeline.calibration_state(model, dev)["decoder"]
+    assert sum(q > a for q, a in zip(alone, A)) > 10
+    torch.cuda.synchronize()
+    assert ops.status(clear=True) == 0
+
+
+def test_calibrating_one_model_leaves_another_engine_alone():
+    """Two loaded models; `calibrate(run)` where run() launches only the first.  The second engine's table and its calib_gen (a
+    bump re-records its graphs) must not move: a start-over clears the engines that produced rows, no others.  The explicit
+    `engines=` argument keeps its meaning: exactly those engines start over and are folded."""
+    f = 1e-2
+    (_, dec1), (_, dec2) = _small_decoder("ljspeech", f), _small_decoder("ljspeech", f)
+    dec1, dec2 = dec1.to(DEV), dec2.to(DEV)
+    a1 = [t.to(DEV) for t in synth.decoder_inputs(1, T_SMALL, 3)]
+    a2 = [t.to(DEV) for t in synth.decoder_inputs(1, T_SMALL, 4)]
+    run1 = lambda: dec1(*a1[:4], noise=a1[4])
+    run2 = lambda: dec2(*a2[:4], noise=a2[4])
+    ops.status(clear=True)
+    rep2 = pipeline.calibrate(run2)
+    eng2 = dec2._eng
+    t2, gen2 = eng2.calibration(), eng2.calib_gen
+    assert rep2["sites_set"] > 60
+    rep1 = pipeline.calibrate(run1)
+    eng1 = dec1._eng
+    assert eng1 is not eng2 and rep1["sites_set"] > 60
+    t1 = eng1.calibration()
+    assert sum(r["x_scale"] > 0 for r in t1) == rep1["sites_set"]
+    assert eng2.calibration() == t2 and eng2.calib_gen == gen2, "calibrating one model moved another's table"
+    # calibrating the first again starts IT over: a quiet input now gives larger scales than accumulation would keep
+    quiet = lambda: dec1(a1[0] * 1e-2, a1[1] * 0.5, a1[2] * 1e-2, a1[3] * 0.1, noise=a1[4])
+    pipeline.calibrate(quiet)
+    assert sum(q["x_scale"] > r["x_scale"] for q, r in zip(eng1.calibration(), t1)) > 10
+    assert eng2.calibration() == t2 and eng2.calib_gen == gen2
+    # engines=: those engines and no others
+    pipeline.calibrate(run1, engines=[eng1])
+    assert eng1.calibration() == t1 and eng2.calibration() == t2 and eng2.calib_gen == gen2
+    pipeline.calibrate(run1, engines=[eng1, eng2])  # eng2 named and never launched: cleared, as before
+    assert eng1.calibration() == t1 and eng2.calibration_scales() == [0.0] * len(t2) and eng2.calib_gen > gen2
+    torch.cuda.synchronize()
+    assert ops.status(clear=True) == 0
+
+
 def _whole_model(tag):
     man = manifest(tag)
     args = models.recursive_munch(man["config"])
